@@ -12,10 +12,15 @@ contiguously across ranks (weak scaling: every rank scans its own reads); the
 only exchange is the final reduction of the count tables, inside the timed region.
 Rank 0 prints ONE JSON line.
 
-N = 1 (default): the BASELINE metric on config 2 (10 M x 150 bp).  The same run then
-times config 3 (50 M pairs of 2 x 150 bp) and config 4 (1 M ONT-like reads) and
-attaches them as `other_configs`, each with its own oracle check.
+N = 1 (default): the BASELINE metric on config 2 (10 M x 150 bp).
 N > 1: every rank scans config 5's per-GPU share (1 B reads / 8 = 125 M reads).
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.
+--full adds what takes work of its own: the kernels timed alone on one stream
+(roofline.serial_launch_ms), the CPU oracle's baseline and parity check, and at N = 1
+config 3 (50 M pairs of 2 x 150 bp) and config 4 (1 M ONT-like reads) as
+`other_configs`, each with its own oracle check, and the `trew` binary end to end.
+--dump-outputs DIR writes the count tables of the timed steps as DIR/table_rows.npy.
 """
 import argparse
 import csv
@@ -220,11 +225,12 @@ def timed_run(w, args, steps, warmup, world, barrier, reduce_fn):
             except w.T.TrewHipError:
                 pass
         t.collect_rows()  # first collect allocates its device scratch: part of warm-up, not of the timed job
-    # per-kernel durations with the device to themselves: two passes on ONE stream (not part of the timed region)
-    t.submit(w.batch, 0)
-    t.submit(w.batch, 0)
-    t.wait(0)
-    serial = t.last_timing(0, want_flagged=False)[:2]
+    if args.full:
+        # per-kernel durations with the device to themselves: two passes on ONE stream (not part of the timed region)
+        t.submit(w.batch, 0)
+        t.submit(w.batch, 0)
+        t.wait(0)
+        serial = t.last_timing(0, want_flagged=False)[:2]
     t.reset_tables()
     barrier()
     t0 = time.perf_counter()
@@ -248,6 +254,28 @@ def timed_run(w, args, steps, warmup, world, barrier, reduce_fn):
         a, b, nf = t.last_timing(s)
         fs, es, cnt, nflag = fs + a * k, es + b * k, cnt + k, nf
     return {"dt": dt, "host_ms": host_ms, "filter_ms": fs / cnt, "exact_ms": es / cnt, "serial_ms": serial, "nflag": int(nflag), "rows": merged, "exchange_ms": exchange_ms}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, rows):
+    """The count tables the timed steps left (what a caller of the path collects; counts add up over the steps) as
+    d/table_rows.npy, float64 [n, 7]: table, k, word_lo bits 0-31 and 32-63, word_hi bits 0-31 and 32-63, count -- every
+    field exact in float64.  Rows sorted by (table, k, word) so the file does not depend on hash-slot order; above 64 MB
+    a seeded sample of the sorted rows."""
+    import numpy as np
+
+    rows = rows[np.lexsort((rows["word_lo"], rows["word_hi"], rows["k"], rows["table"]))]
+    lo32 = np.uint64(0xFFFFFFFF)
+    cols = [rows["table"], rows["k"], rows["word_lo"] & lo32, rows["word_lo"] >> np.uint64(32),
+            rows["word_hi"] & lo32, rows["word_hi"] >> np.uint64(32), rows["count"]]
+    out = np.stack([c.astype(np.float64) for c in cols], axis=1) if len(rows) else np.zeros((0, len(cols)))
+    cap = DUMP_MAX_BYTES // out[:1].nbytes if len(out) else 0
+    if len(out) > cap:
+        out = out[np.sort(np.random.default_rng(SEED).choice(len(out), cap, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "table_rows.npy"), out)
 
 
 def oracle_check(w, args, O, cores):
@@ -407,6 +435,10 @@ def main():
     ap.add_argument("--flags", type=int, default=0, help="TREW_FLAG_* (debug experiments only)")
     ap.add_argument("--mode", default="short", choices=["short", "pair", "long"],
                     help="short = the BASELINE metric (config 2); pair / long = configs 3 / 4 as the primary line")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernels alone on one stream (roofline.serial_launch_ms), the CPU baseline and oracle parity, "
+                         "configs 3 and 4 (N = 1, --mode short) and the end-to-end `trew` run; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the count tables of the timed steps as DIR/table_rows.npy (float64)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse on one GPU)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "device", "host"],
                     help="table reduction: device = collect_device -> all_gather of device tensors -> add_rows_device (what nccl runs use); "
@@ -500,7 +532,7 @@ def main():
             traffic_all, valu, prof_round = committed_profile(n, L)
         # counter traffic of one STEP (both kernels of a slot; FETCH_SIZE x 2 + WRITE_SIZE per MI355X_MICROARCH.md), with the split
         traffic = round(sum(traffic_all.values())) if traffic_all else None
-        s_f, s_e = m["serial_ms"]
+        s_f, s_e = m["serial_ms"] or (None, None)
         s_dom = s_f if dom == "filter_kernel" else s_e
         workload = workload_name(args.mode, n, w.bases_per_step)
         if world > 1 and args.mode == "short" and n == CONFIG5_READS_PER_GPU:
@@ -540,13 +572,13 @@ def main():
                 "traffic_over_algorithmic": round(traffic / alg_bytes, 3) if traffic else None,
                 "avg_launch_ms": {"filter_kernel": round(f_avg, 4), "exact_kernel": round(e_avg, 4)},
                 "slot_cycle_ms": round(f_avg + e_avg, 4),  # one slot runs its prefilter then its exact kernel: with S slots a step takes >= slot_cycle_ms / S
-                "serial_launch_ms": {"filter_kernel": round(s_f, 4), "exact_kernel": round(s_e, 4)},
-                "frac_serial": round(alg_bytes / (s_dom * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                "serial_launch_ms": {"filter_kernel": round(s_f, 4), "exact_kernel": round(s_e, 4)} if s_dom is not None else None,
+                "frac_serial": round(alg_bytes / (s_dom * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if s_dom is not None else None,
                 "valu": valu,
                 # MODELLED, not a counter: SQ_INSTS_VALU of the committed profile x the measured cost of its instruction classes
                 "valu_issue_modelled": ((valu or {}).get(dom, {}).get("class_weighted") or {}).get("valu_issue"),
                 "note": "integer-issue bound, not HBM bound (SURVEY 8(d)). avg_launch_ms: HIP events over the timed region, where the %d slots overlap "
-                        "(a kernel shares the SIMDs with the other slot's kernel, so its own launch is longer than alone); serial_launch_ms: the same "
+                        "(a kernel shares the SIMDs with the other slot's kernel, so its own launch is longer than alone); serial_launch_ms (--full): the same "
                         "kernels alone on one stream, measured in this run outside the timed region.  traffic: HBM bytes of one step from the committed PMC runs "
                         "(both kernels; achieved / frac use the ALGORITHMIC bytes).  valu: SQ counters of the committed rocprofv3 PMC "
                         "runs of this command (profiles/%s): issue_frac_2cyc = SQ_INSTS_VALU x 2 / SIMD cycles, class_weighted = the same with the measured cost of full-rate and half-rate instructions (profiles/valu_rate.json) -- the prefilter's mix is the static one of its dominant loop, the exact kernel's the dynamic one of tools/region_mix.py; see bench.py::committed_profile.  %.3g (window,k) "
@@ -562,9 +594,11 @@ def main():
         if world > 1:
             # rank 0's wall time of the one exchange of the job (compaction -> all_gather -> merge kernel -> final rows), part of dt
             out["exchange_ms"] = round(m["exchange_ms"], 3)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, m["rows"])
 
-    # CPU baseline + parity on a bounded sample of the same workload (rank 0, N = 1 only)
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu
+    # CPU baseline + parity on a bounded sample of the same workload (rank 0, N = 1 only, --full)
+    do_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu
     O = None
     if do_cpu:
         import oracle as O
@@ -583,8 +617,8 @@ def main():
         out["parity_note"] = "GPU tables vs CPU oracle on the sample: %s" % ("bit-exact" if ok else "MISMATCH")
     w.close()
 
-    # configs 3 and 4 at BASELINE size in the same run (N = 1, default invocation), each checked against the oracle
-    if rank == 0 and world == 1 and args.mode == "short" and not args.no_other_configs:
+    # configs 3 and 4 at BASELINE size in the same run (N = 1, --mode short, --full), each checked against the oracle
+    if args.full and rank == 0 and world == 1 and args.mode == "short" and not args.no_other_configs:
         others = []
         osteps = args.other_steps or max(1, min(args.steps, 10))
         for mode in ("pair", "long"):
@@ -616,7 +650,7 @@ def main():
             others.append(entry)
         out["other_configs"] = others
 
-    if rank == 0 and world == 1 and args.mode == "short" and not args.no_e2e and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and args.mode == "short" and not args.no_e2e and not args.no_cpu:
         try:
             out["e2e"] = end_to_end(capi, args, usable_cores())
         except Exception as ex:  # the end-to-end leg must never take the bench line down

@@ -16,7 +16,7 @@ for v in tree w5; do
   lib=$R/tools/proflib/$v/libtrew_hip.so
   [ "$v" = tree ] && lib=$R/trew_amd/lib/libtrew_hip.so
   for mode in pair long; do
-    out=$(TREW_HIP_LIB=$lib python3 $R/bench.py --mode $mode --steps 10 --warmup 2 --no-cpu 2>/dev/null | tail -1)
+    out=$(TREW_HIP_LIB=$lib python3 $R/bench.py --full --mode $mode --steps 10 --warmup 2 --no-cpu 2>/dev/null | tail -1)
     echo "$v mode=$mode $(echo "$out" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("value", d["value"], "ms/step", d["ms_per_step"], "timed", d["roofline"]["avg_launch_ms"], "serial", d["roofline"]["serial_launch_ms"])')"
   done
 done

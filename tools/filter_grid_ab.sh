@@ -8,7 +8,7 @@ for v in f64 f256; do
     if [ "$v" = f64 ] && [ $bpc -gt 0 ] && [ $bpc -lt 12 ]; then continue; fi
     if [ $bpc -eq 0 ]; then unset TREW_FILTER_BLOCKS_PER_CU; else export TREW_FILTER_BLOCKS_PER_CU=$bpc; fi
     for st in 1 2; do
-      out=$(TREW_HIP_LIB=$R/tools/proflib/$v/libtrew_hip.so python3 $R/bench.py --steps 30 --warmup 3 --no-cpu --no-other-configs --streams $st 2>/dev/null | tail -1)
+      out=$(TREW_HIP_LIB=$R/tools/proflib/$v/libtrew_hip.so python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu --no-other-configs --streams $st 2>/dev/null | tail -1)
       echo "$v bpc=$bpc streams=$st $(echo "$out" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("value", d["value"], "ms/step", d["ms_per_step"], "serial", d["roofline"]["serial_launch_ms"], "timed", d["roofline"]["avg_launch_ms"])')"
     done
   done
