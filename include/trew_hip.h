@@ -68,6 +68,9 @@ enum {
     TREW_FLAG_DEBUG_NO_JOINT = 2048, /* tests: the prefilter's uniform path judges every segment in a k loop of its own instead of both
                                 halves of a read in one (filter_halves_uni); the flagged reads may differ by a few (odd lengths use a
                                 joint threshold), the tables never */
+    TREW_FLAG_DEBUG_NO_UNI_DRAIN = 4096, /* tests and A/B runs: the prefilter judges the reads its uniform path set aside with the
+                                general per-segment path (filter_segment) instead of the joint loop of filter_deferred_uni; the
+                                flagged reads may differ only where a segment's [kmin, kmax] is narrower than the k loop, the tables never */
     TREW_FLAG_DEBUG_NO_GROUP = 1024, /* tests and A/B runs: the exact kernel gives every segment a wave of its own (decide()) instead
                                 of deciding four segments in lock step, 16 lanes each (decide_group); results are identical */
     TREW_FLAG_TRACK_PRESSURE = 256 /* every batch ends with a copy of the table's fill counters into pinned host memory, and

@@ -21,6 +21,7 @@ FLAG_NO_TIMING = 64  # no HIP events per submit (last_timing unavailable)
 FLAG_COMPAT_G1 = 512  # pair mode, one slot: the reference's 64-bit pair branch as written (un-cleared temp_result_left)
 FLAG_TRACK_PRESSURE = 256  # the fill counters come back with every batch; table_pressure asks no device
 FLAG_DEBUG_NO_JOINT = 2048  # tests: the prefilter's uniform path without the joint k loop of both halves
+FLAG_DEBUG_NO_UNI_DRAIN = 4096  # tests / A-B: the prefilter's set-aside reads judged by the general path (not filter_deferred_uni)
 FLAG_DEBUG_NO_GROUP = 1024  # tests / A-B: every segment decided by a wave of its own (no decide_group)
 FLAG_DEBUG_WIDE_NO_WAIT = 128  # tests: the wide table never waits for a slot's ready bit (forces its time-out path)
 TABLE_NAMES = ("forward_high", "forward_low", "backward_high", "backward_low", "both_high", "both_low")

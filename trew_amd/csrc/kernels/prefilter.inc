@@ -100,7 +100,11 @@ __device__ __forceinline__ void filter_k(const u32 (&P1)[NW], const u32 (&P2)[NW
     const bool pass4 = (float) m4 > thr;
     bool pass = pass4;
     const bool first = (cand_lo | cand_hi) == 0;
+#ifdef TREW_AB_SKIP_DRAIN8  // A/B builds (instruction attribution, profiles/r05): the 8-bucket block left out
+    if (false) {
+#else
     if (__any(pass4 && first)) {
+#endif
         u32 c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0;
 #pragma unroll
         for (int j = 0; j < NWW; j++) {
@@ -649,6 +653,206 @@ __device__ __forceinline__ u64 filter_halves_uni(const HalvesP &A, const HalvesP
     return trig;
 }
 
+// ---- the reads the uniform path set aside, judged in one joint k loop (3-word kernel) ----
+// The fast path sets aside every read with an N in a half (7 % of the synthetic reads) and every read some k of which passes
+// its 4-bucket test (3 %: the telomeric ones and a few near misses).  filter_deferred_uni gives them the verdict the general
+// path (filter_segment, a call per half) gives when the k loop is the halves' own [kmin, kmax]: a read is flagged exactly when
+// some half has some k whose 8-bucket maximum over the windows without an N reaches ithr(COUNT) -- the general path's first
+// candidate of a segment is always an 8-bucket pass, and m8 <= m4.  Written like the fast loop, with per-lane window masks:
+//   - both halves in one k loop, wave-uniform loop control;
+//   - V_k (windows of length k with no N, bit i = window i) per lane: V_{k+1} = V_k & (V_k >> 1) from V_1 = the valid bases, for
+//     any number of Ns; it goes into the xor_and that builds each parity word, so masking a word costs nothing;
+//   - COUNT = popc(V_k) per lane, its thresholds from an LDS table indexed by COUNT (cnt_thr, the general path's float
+//     expression, so exact by construction): the popcount chains start from them and the 4-bucket test is a sign test;
+//   - the 8-bucket stage runs per half only when some lane not flagged yet passes that half's 4-bucket test, and a lane once
+//     flagged is done (the loop ends when every lane is);
+//   - k with more than 64 windows in some half: three words and funnel shifts; the rest: one 64-bit container shift per parity.
+constexpr int kCntThr = 97;  // COUNT = 0 .. 96: segments of at most 95 bases
+// cnt_thr[c] = {-2 ithr, -ithr, 4 ithr - c - 1, ithr}, ithr = floor((float) c * lowf) + 1: (float) m > (float) c * lowf  <=>  m >= ithr
+__device__ __forceinline__ int4 count_thresholds(int c, float lowf) {
+    const float prod = __fmul_rn((float) c, lowf);  // the general path's (float) count * lowf
+    const int ithr = (int) floorf(prod) + 1;
+    return make_int4(-2 * ithr, -ithr, 4 * ithr - c - 1, ithr);
+}
+
+struct DrainHalf {
+    u32 P1[3], P2[3], P3[3];  // prefix parities of the lo, hi and lo & hi planes
+    u32 V[3];                 // V_k
+};
+__device__ __forceinline__ void drain_half_init(const u32 (&lo)[3], const u32 (&hi)[3], const u32 (&nm)[3], int L, bool active, DrainHalf &h) {
+    u32 f1[3], f2[3], f3[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int bits = L - 32 * j;
+        const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+        h.V[j] = active ? ~nm[j] & lm : 0u;  // V_1: bases inside the half that are A/C/G/T (an inactive lane has no window)
+        f1[j] = lo[j] & lm;
+        f2[j] = hi[j] & lm;
+        f3[j] = f1[j] & f2[j];
+    }
+    prefix_parity<3>(f1, h.P1);
+    prefix_parity<3>(f2, h.P2);
+    prefix_parity<3>(f3, h.P3);
+}
+__device__ __forceinline__ void drain_v_step3(u32 (&V)[3]) {  // V_{k+1} = V_k & (V_k >> 1)
+    V[0] &= alignbit(V[1], V[0], 1u);
+    V[1] &= alignbit(V[2], V[1], 1u);
+    V[2] &= V[2] >> 1;
+}
+// 4-bucket test of one half from its N window-parity words (already masked by V_k), thresholds th = cnt_thr[COUNT]:
+// the result is >= 0 (as int) iff some bucket reaches ithr (halves_signs with per-lane constants)
+template <int N>
+__device__ __forceinline__ int drain_signs(const u32 (&F1)[N], const u32 (&F2)[N], const int4 th) {
+    u32 a = (u32) th.x, b = (u32) th.x, c = (u32) th.y;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        a = bcnt_acc(F1[j], a);
+        b = bcnt_acc(F2[j], b);
+        c = bcnt_acc(F1[j] & F2[j], c);
+    }
+    const u32 p = a - c, q = b - c;
+    const u32 t = a + q + (u32) th.z;
+    return (int) __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(p, q, c, 0x80), t, t, 0x30);  // p & q & c & ~t
+}
+// 8-bucket maximum of one half reaches ithr (the rare stage: only for lanes not flagged yet that pass the 4-bucket test)
+template <int N>
+__device__ __forceinline__ bool drain_pass8(const u32 (&F1)[N], const u32 (&F2)[N], const u32 (&F3)[N], const u32 (&V)[N], u32 count, int ithr) {
+    u32 c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const u32 a11 = F1[j] & F2[j], a10 = F1[j] & ~F2[j], a01 = ~F1[j] & F2[j], a00 = V[j] & ~(F1[j] | F2[j]);
+        const u32 b111 = a11 & F3[j], b101 = a10 & F3[j], b011 = a01 & F3[j], b001 = a00 & F3[j];
+        c111 += __popc(b111);
+        c110 += __popc(a11 ^ b111);
+        c101 += __popc(b101);
+        c100 += __popc(a10 ^ b101);
+        c011 += __popc(b011);
+        c010 += __popc(a01 ^ b011);
+        c001 += __popc(b001);
+    }
+    const u32 c000 = count - c001 - c010 - c011 - c100 - c101 - c110 - c111;
+    const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+    return (int) m8 >= ithr;
+}
+
+// Geometry the drain needs (block-uniform, from the batch's uniform length): the valid segments are exactly the 2 (short) or 4
+// (pair) halves, pairing up as (0, 1) and (2, 3) with the same [kmin, kmax], at most 95 bases and one base apart, k <= length.
+__device__ __forceinline__ bool drain_uni_applies(const DevParams &P, u32 UL, int gmax_run) {
+    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : (P.mode == TREW_MODE_SHORT ? 2 : 0);
+    if (n_halves == 0) return false;
+    for (int slot = n_halves; slot < mode_slots(P.mode); slot++)
+        if (get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len).valid) return false;
+    for (int p = 0; p < n_halves; p += 2) {
+        const Segment a = get_segment(P.mode, p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const Segment b = get_segment(P.mode, p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const int la = (int) a.len, lb = (int) b.len, lmin = la < lb ? la : lb, lmax = la < lb ? lb : la;
+        const int khi = a.kmax < gmax_run ? a.kmax : gmax_run;
+        if (!(a.valid && b.valid && a.kmin == b.kmin && a.kmax == b.kmax && lmax <= 95 && lmax - lmin <= 1 && a.kmin >= 1 && khi <= lmin)) return false;
+    }
+    return true;
+}
+
+// Verdict of one unit (short: a read, pair: two mates) set aside by the uniform path; cnt_thr: LDS, kCntThr entries.
+__device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const DevBatch &B, u64 unit, bool active, int gmax_run,
+                                                    const int4 *cnt_thr) {
+    const u32 UL = B.uniform_length;
+    ReadRef rd[2];
+    rd[0].w = B.words;
+    rd[0].len = 0;
+    rd[0].nw = 0;
+    rd[1] = rd[0];
+    if (active) {
+        if (P.mode == TREW_MODE_PAIR) {
+            rd[0] = get_read(B, 2 * unit);
+            rd[1] = get_read(B, 2 * unit + 1);
+        } else {
+            rd[0] = get_read(B, unit);
+        }
+    }
+    const u64 actm = __ballot(active);
+    u64 flag = 0;
+    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : 2;
+    for (int p = 0; p < n_halves && flag != actm; p += 2) {
+        const Segment sA = get_segment(P.mode, p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const Segment sB = get_segment(P.mode, p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const int LA = rfl_i((int) sA.len), LB = rfl_i((int) sB.len), Lmax = LA < LB ? LB : LA;
+        const int klo = rfl_i(sA.kmin > P.min_mer ? sA.kmin : P.min_mer), khi = rfl_i(sA.kmax < gmax_run ? sA.kmax : gmax_run);
+        DrainHalf A, Bh;
+        {
+            u32 lo[3], hi[3], nm[3];
+            load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, lo, hi, nm);
+            drain_half_init(lo, hi, nm, LA, active, A);
+            load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, lo, hi, nm);
+            drain_half_init(lo, hi, nm, LB, active, Bh);
+        }
+        for (int t = 1; t < klo; t++) {  // V_klo
+            drain_v_step3(A.V);
+            drain_v_step3(Bh.V);
+        }
+        int k = klo;
+        // (b) k with more than 64 windows in some half (k <= Lmax - 64 <= 31): three words, funnel shifts
+        {
+            const int b = khi < Lmax - 64 ? khi : Lmax - 64;
+            auto half3 = [&](const DrainHalf &h, u32 bs) __attribute__((always_inline)) -> u64 {
+                const u32 cnt = bcnt_acc(h.V[2], bcnt_acc(h.V[1], __popc(h.V[0])));
+                const int4 th = cnt_thr[cnt];
+                u32 F1[3], F2[3];
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+                    F1[j] = xor_and(h.P1[j], alignbit(j < 2 ? h.P1[j < 2 ? j + 1 : 0] : 0u, h.P1[j], bs), h.V[j]);
+                    F2[j] = xor_and(h.P2[j], alignbit(j < 2 ? h.P2[j < 2 ? j + 1 : 0] : 0u, h.P2[j], bs), h.V[j]);
+                }
+                const u64 p4 = __ballot(drain_signs<3>(F1, F2, th) >= 0);
+                u64 p8 = 0;
+                if (p4 & ~flag) {
+                    u32 F3[3];
+#pragma unroll
+                    for (int j = 0; j < 3; j++) F3[j] = h.P3[j] ^ alignbit(j < 2 ? h.P3[j < 2 ? j + 1 : 0] : 0u, h.P3[j], bs);
+                    p8 = __ballot(drain_pass8<3>(F1, F2, F3, h.V, cnt, th.w));
+                }
+                return p8;
+            };
+            for (; k <= b && flag != actm; k++) {
+                flag |= half3(A, (u32) k);
+                flag |= half3(Bh, (u32) k);
+                drain_v_step3(A.V);
+                drain_v_step3(Bh.V);
+            }
+        }
+        // (c) at most 64 windows in either half: windows 0..63 of P >> k from one 64-bit shift of the container Q = P[s .. s + 64)
+        if (k <= khi && flag != actm) {
+            const int oA = LA > 63 ? LA - 63 : 0, oB = LB > 63 ? LB - 63 : 0;  // container offsets
+            const u64 QA1 = container64(A.P1, oA), QA2 = container64(A.P2, oA), QB1 = container64(Bh.P1, oB), QB2 = container64(Bh.P2, oB);
+            u64 VA = ((u64) A.V[1] << 32) | A.V[0], VB = ((u64) Bh.V[1] << 32) | Bh.V[0];  // V[2] is empty from here on
+            auto half2 = [&](const DrainHalf &h, u64 Q1, u64 Q2, u64 V, int s) __attribute__((always_inline)) -> u64 {
+                const u32 v0 = (u32) V, v1 = (u32) (V >> 32);
+                const u32 cnt = bcnt_acc(v1, __popc(v0));
+                const int4 th = cnt_thr[cnt];
+                const u32 sh = (u32) (k - s);
+                const u64 S1 = Q1 >> sh, S2 = Q2 >> sh;
+                const u32 F1[2] = {xor_and(h.P1[0], (u32) S1, v0), xor_and(h.P1[1], (u32) (S1 >> 32), v1)};
+                const u32 F2[2] = {xor_and(h.P2[0], (u32) S2, v0), xor_and(h.P2[1], (u32) (S2 >> 32), v1)};
+                const u64 p4 = __ballot(drain_signs<2>(F1, F2, th) >= 0);
+                u64 p8 = 0;
+                if (p4 & ~flag) {
+                    const u64 S3 = container64(h.P3, s) >> sh;
+                    const u32 F3[2] = {h.P3[0] ^ (u32) S3, h.P3[1] ^ (u32) (S3 >> 32)};
+                    const u32 Vw[2] = {v0, v1};
+                    p8 = __ballot(drain_pass8<2>(F1, F2, F3, Vw, cnt, th.w));
+                }
+                return p8;
+            };
+            for (; k <= khi && flag != actm; k++) {
+                flag |= half2(A, QA1, QA2, VA, oA);
+                flag |= half2(Bh, QB1, QB2, VB, oB);
+                VA &= VA >> 1;
+                VB &= VB >> 1;
+            }
+        }
+    }
+    return (flag >> lane_id()) & 1ull;
+}
+
 // Block size of the prefilter.  Measured on MI355X (tools/filter_grid_ab.sh, profiles/r02/README.md): 64-thread blocks
 // (no block-level barrier at all) and 256-thread blocks run the same 0.70-0.72 ms on 10 M reads, and a variant with
 // wave-private staging lists was slower (95 VGPRs, 5 waves per SIMD) -- the kernel is bound by VALU issue, not by
@@ -782,10 +986,14 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
     __shared__ unsigned char defer_kind[kDefer];  // 1: set aside because of an N
     __shared__ u32 wm_tab[34];  // all ones >> i: the joint loop's window masks (filter_halves_uni)
     if (threadIdx.x < 34) wm_tab[threadIdx.x] = threadIdx.x < 32 ? 0xffffffffu >> threadIdx.x : 0u;
+    __shared__ int4 cnt_thr[kCntThr];  // thresholds by window count (filter_deferred_uni)
+    for (u32 i = threadIdx.x; i < (u32) kCntThr; i += blockDim.x) cnt_thr[i] = count_thresholds((int) i, P.lowf);
     // thr_tab[slot * kThrRow + k - 1] = pass thresholds of (slot, k) for this batch's uniform geometry (fill_thresholds, below): read-only
     // global memory at a wave-uniform address, i.e. scalar loads into SGPRs -- the k loops spend no vector instruction on them
     const u32 UL = B.uniform_length;
     const bool uni = NW <= 5 && UL != 0 && thr_tab != nullptr && P.mode != TREW_MODE_LONG && !(P.flags & TREW_FLAG_NO_FILTER);
+    // the reads set aside by the uniform path are judged by filter_deferred_uni, or by the general path (any NW, dbg_masks, A/B)
+    const bool uni_drain = NW == 3 && uni && !dbg_masks && !(P.flags & TREW_FLAG_DEBUG_NO_UNI_DRAIN) && drain_uni_applies(P, UL, gmax_run);
     if (threadIdx.x == 0) defer_n = 0;
     __syncthreads();
     __shared__ u32 next_chunk[2];  // written by thread 0 in round r (slot r & 1), read by all after that round's barrier
@@ -946,7 +1154,14 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             const bool n2 = active2 && defer_kind[at + threadIdx.x] != 0;
             __syncthreads();
             if (threadIdx.x == 0) defer_n = at;
-            const u64 any2 = general(unit2, active2);
+#ifndef TREW_AB_SKIP_DRAIN
+            const u64 any2 = uni_drain ? (u64) filter_deferred_uni(P, B, unit2, active2, gmax_run, cnt_thr) : general(unit2, active2);
+#else  // A/B builds (instruction attribution, profiles/r05): the drain computes nothing; its inputs are kept alive
+            u64 any2 = 0;
+            u32 keep = unit2;
+            asm volatile("" : "+v"(keep), "+v"(any2));
+            (void) keep;
+#endif
             // The reads with an N go to the worklist behind the others of this block-full, next to each other: the exact kernel
             // decides two consecutive reads of the worklist in one pass and runs the N variant of its bounds when either holds
             // an N (mixed at random, 12 % of its passes did; exact kernel 0.408 against 0.399 ms with the same reads).
