@@ -28,6 +28,8 @@
 extern "C" {
 #endif
 
+/* Still 4 with the annotation entry points (trew_motif_parse, trew_hip_annotate, trew_hip_annotate_results,
+ * trew_annotate_host): they are purely additive -- no existing structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
 /* scan modes: which per-read driver of the reference is reproduced */
@@ -73,6 +75,8 @@ enum {
                                 flagged reads may differ only where a segment's [kmin, kmax] is narrower than the k loop, the tables never */
     TREW_FLAG_DEBUG_NO_GROUP = 1024, /* tests and A/B runs: the exact kernel gives every segment a wave of its own (decide()) instead
                                 of deciding four segments in lock step, 16 lanes each (decide_group); results are identical */
+    TREW_FLAG_DEBUG_ANNOT_GENERAL = 8192, /* tests: trew_hip_annotate gives every batch a wave per read, also where its reads are
+                                short enough for the lane-per-read kernel; results are identical */
     TREW_FLAG_TRACK_PRESSURE = 256 /* every batch ends with a copy of the table's fill counters into pinned host memory, and
                                 trew_hip_table_pressure answers from those copies (and from what collect / add_rows /
                                 reset read since) instead of asking the device: for hosts that ask before every batch.
@@ -261,6 +265,44 @@ int trew_hip_filter_masks(trew_hip_ctx *ctx, const trew_hip_batch *batch, uint64
  * slot's own stream, at most the last 128 submits), milliseconds; n_flagged (optional) = reads
  * the prefilter passed to the exact kernel in the last submit. */
 int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filter, float *ms_exact, uint64_t *n_flagged);
+
+/* ---- per-read annotation against given motifs (no counterpart in the reference, which only sums over reads) ----
+ * For a read of n bases and a motif M of k bases (3 <= k <= 32): window i (0 <= i <= n - k) is valid when none of its k
+ * bases has its nmask bit set; it matches strand fwd when it is valid and a rotation of M (its smallest rotation as a 2k-bit
+ * word, get_rot_seq kmer.cpp:1815-1823, equals that of M), strand rev when it is a rotation of the reverse complement of M.
+ *   windows_s      number of matching windows of strand s
+ *   tract_start_s  first window of the longest run of consecutive matching windows (the earliest run on a tie)
+ *   tract_len_s    that run's length in BASES: its number of windows + k - 1; no run: start = len = 0
+ * A self-reverse-complementary class reports the same numbers on both strands; non-primitive motifs and homopolymers follow
+ * the same definition; n < k gives zeros. */
+typedef struct {
+    int32_t k;        /* 3 .. 32 */
+    int32_t reserved; /* 0 */
+    uint64_t word;    /* any rotation of the motif, packed like trew_hip_row.word_lo: first base most significant, no bits above 2k */
+} trew_hip_motif;
+typedef struct {
+    uint32_t windows_fwd, windows_rev, tract_start_fwd, tract_len_fwd, tract_start_rev, tract_len_rev;
+} trew_hip_annot;
+#define TREW_ANNOT_MAX_MOTIFS 8
+
+/* "TTAGGG" (upper or lower case A, C, G, T only) -> motif; host only.  Non-zero for any other character or a k outside [3, 32]
+ * (text through trew_hip_last_error with a NULL context). */
+int trew_motif_parse(const char *text, trew_hip_motif *out);
+/* Annotates every read of the batch against n_motifs (1 .. 8) motifs.  Behaves like trew_hip_submit: the same batch shapes,
+ * copied the same way, queued on the slot's stream, asynchronous; the caller keeps the batch until trew_hip_wait(slot).  Works
+ * on a context of any mode (in pair mode the mates are two reads) and is independent of the scan: it neither reads nor writes
+ * the count tables and may be interleaved with submits on any slot.  max_batch_words / max_batch_reads apply, the scan's
+ * read-length rules do not.  Batches whose longest read has at most 256 bases (uniform_length, the lengths of a host batch,
+ * max_length of a device-resident one; 0 = unknown) run one lane per read, all others one wave per read. */
+int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs);
+/* Waits for the slot and copies the records of its last trew_hip_annotate: out[r * n_motifs + m], n_reads * n_motifs of them;
+ * *n receives that number even when it exceeds cap (then cap records are copied).  ms_kernel (may be NULL): kernel time from
+ * HIP events on the slot's stream. */
+int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_annot *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same records computed on the host, window by window, over packed planes (words / offsets / lengths as trew_pack_reads
+ * writes them): what tests compare the device with where the inputs are large. */
+int trew_annotate_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                       const trew_hip_motif *motifs, int n_motifs, trew_hip_annot *out);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -7,6 +7,7 @@ only binds the C ABI for tests and benchmarks.
 from . import capi  # noqa: F401
 from .capi import (  # noqa: F401
     FLAG_NO_FILTER,
+    FLAG_DEBUG_ANNOT_GENERAL,
     FLAG_DEBUG_POISON_LDS,
     FLAG_NO_TIMING,
     FLAG_TRACK_PRESSURE,
@@ -22,6 +23,7 @@ from .capi import (  # noqa: F401
     TABLE_NAMES,
     TrewHip,
     TrewHipError,
+    annotate,
     k_mer_check,
     pack_reads,
 )

@@ -23,6 +23,7 @@ FLAG_TRACK_PRESSURE = 256  # the fill counters come back with every batch; table
 FLAG_DEBUG_NO_JOINT = 2048  # tests: the prefilter's uniform path without the joint k loop of both halves
 FLAG_DEBUG_NO_UNI_DRAIN = 4096  # tests / A-B: the prefilter's set-aside reads judged by the general path (not filter_deferred_uni)
 FLAG_DEBUG_NO_GROUP = 1024  # tests / A-B: every segment decided by a wave of its own (no decide_group)
+FLAG_DEBUG_ANNOT_GENERAL = 8192  # tests: annotate gives every batch a wave per read (the lane-per-read kernel is never picked)
 FLAG_DEBUG_WIDE_NO_WAIT = 128  # tests: the wide table never waits for a slot's ready bit (forces its time-out path)
 TABLE_NAMES = ("forward_high", "forward_low", "backward_high", "backward_low", "both_high", "both_low")
 
@@ -37,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "trew_synth_long_lengths", "trew_synth_long_ascii", "trew_synth_long_device",
     "trew_hip_collect_device", "trew_hip_add_rows_device", "trew_hip_merge", "trew_hip_table_pressure",
     "trew_hip_add_gathered_device", "trew_hip_collect_slice_device", "trew_hip_debug_counters", "trew_hip_debug_worklist", "trew_hip_submit_ascii", "trew_hip_pack_ascii",
+    "trew_motif_parse", "trew_hip_annotate", "trew_hip_annotate_results", "trew_annotate_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target")
 
@@ -73,6 +75,19 @@ class Row(C.Structure):
     _fields_ = [("k", C.c_int32), ("table", C.c_int32), ("word_lo", C.c_uint64), ("word_hi", C.c_uint64),
                 ("count", C.c_uint64)]
 
+
+class Motif(C.Structure):
+    _fields_ = [("k", C.c_int32), ("reserved", C.c_int32), ("word", C.c_uint64)]
+
+
+class Annot(C.Structure):
+    _fields_ = [("windows_fwd", C.c_uint32), ("windows_rev", C.c_uint32), ("tract_start_fwd", C.c_uint32),
+                ("tract_len_fwd", C.c_uint32), ("tract_start_rev", C.c_uint32), ("tract_len_rev", C.c_uint32)]
+
+
+ANNOT_DTYPE = np.dtype([(name, "<u4") for name, _ in Annot._fields_])
+assert ANNOT_DTYPE.itemsize == C.sizeof(Annot)
+MAX_MOTIFS = 8
 
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
@@ -130,6 +145,10 @@ def load():
     lib.trew_hip_segment_results.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, u64]
     lib.trew_hip_filter_masks.argtypes = [vp, C.POINTER(Batch), vp, i32]
     lib.trew_hip_last_timing.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(u64)]
+    lib.trew_motif_parse.argtypes = [C.c_char_p, C.POINTER(Motif)]
+    lib.trew_hip_annotate.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32]
+    lib.trew_hip_annotate_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_float)]
+    lib.trew_annotate_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -175,6 +194,41 @@ def pack_reads(reads):
     if w == 2 ** 64 - 1:
         raise TrewHipError("trew_pack_reads: buffer too small")
     return words[: int(w)], offsets[:n], lengths[:n]
+
+
+def motif(text):
+    """'TTAGGG' (str or bytes, either case) -> Motif; raises TrewHipError for other characters or a length outside [3, 32]."""
+    lib = load()
+    if isinstance(text, Motif):
+        return text
+    m = Motif()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    if lib.trew_motif_parse(raw, C.byref(m)) != 0:
+        raise TrewHipError("trew_motif_parse failed: %s" % lib.trew_hip_last_error(None).decode())
+    return m
+
+
+def _motif_array(motifs):
+    ms = [motif(m) for m in motifs]
+    return (Motif * max(len(ms), 1))(*ms), len(ms)
+
+
+def annotate_host(reads_or_packed, motifs):
+    """trew_annotate_host: the annotation computed on the host, window by window.  reads_or_packed: a list of reads (bytes /
+    str) or the (words, offsets, lengths) of pack_reads.  Returns ANNOT_DTYPE records of shape (n_reads, n_motifs)."""
+    lib = load()
+    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
+        words, offsets, lengths = reads_or_packed
+    else:
+        words, offsets, lengths = pack_reads(reads_or_packed)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    arr, nm = _motif_array(motifs)
+    out = np.zeros((len(offsets), max(nm, 1)), dtype=ANNOT_DTYPE)
+    if lib.trew_annotate_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, out.ctypes.data) != 0:
+        raise TrewHipError("trew_annotate_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out[:, :nm]
 
 
 def synth_short_ascii(seed, first_read, n_reads, read_len):
@@ -313,6 +367,26 @@ class TrewHip:
 
     def wait(self, slot=0):
         self._chk(self.lib.trew_hip_wait(self.ctx, slot), "trew_hip_wait")
+
+    def annotate(self, batch, motifs, slot=0):
+        """Queue the annotation of every read of `batch` against `motifs` (texts or Motif, at most 8) on the slot's stream."""
+        arr, nm = _motif_array(motifs)
+        self._keep[("annot", slot)] = (batch, arr)
+        self._annot_shape = getattr(self, "_annot_shape", {})
+        self._annot_shape[slot] = (int(batch.n_reads), nm)
+        self._chk(self.lib.trew_hip_annotate(self.ctx, C.byref(batch), slot, arr, nm), "trew_hip_annotate")
+
+    def annotate_results(self, slot=0, want_ms=False):
+        """Records of the slot's last annotate: ANNOT_DTYPE array of shape (n_reads, n_motifs) [, kernel ms]."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm = getattr(self, "_annot_shape", {}).get(slot, (0, 1))
+        out = np.zeros((n_reads, nm), dtype=ANNOT_DTYPE)
+        self._chk(self.lib.trew_hip_annotate_results(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), C.byref(ms) if want_ms else None),
+                  "trew_hip_annotate_results")
+        if int(n.value) != n_reads * nm:
+            raise TrewHipError("trew_hip_annotate_results: %d records, expected %d" % (n.value, n_reads * nm))
+        return (out, ms.value) if want_ms else out
 
     def submit_reads(self, reads, slot=0):
         b = self.host_batch(*pack_reads(reads))
@@ -480,3 +554,13 @@ def k_mer_check(seq, min_mer=5, max_mer=32, low=0.5, high=0.8, flags=0, device=0
         tabs = t.collect()
     return dict(k_high=int(kh[0]), k_low=int(kl[0]), seq_high=int(sh[0]), seq_low=int(sl[0]),
                 hist_high=tabs["forward_high"], hist_low=tabs["forward_low"])
+
+
+def annotate(reads, motifs, device=0):
+    """Per-read motif annotation on the GPU: for every read (bytes / str) and motif (text) the matching windows and the
+    longest tract on each strand, as ANNOT_DTYPE records of shape (n_reads, n_motifs)."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        t.annotate(t.host_batch(words, offsets, lengths), motifs)
+        return t.annotate_results()

@@ -1186,4 +1186,166 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
+// ---------------------------------------------------------------- trew annotate
+// Per-read motif annotation of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
+// 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, runs trew_hip_annotate on a slot of its own
+// and keeps the records that reach MIN_TRACT.  The ordinal of a read is the index of its sequence line among the file's
+// sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
+// rows come out the same for any number of workers once they are sorted.
+struct Annotator {
+    std::vector<trew_hip_ctx *> ctx;
+    struct Worker {
+        int dev_index = 0, slot = 0;
+        uint32_t *h_buf = nullptr;  // pinned: [offsets n][lengths n][words]
+        std::vector<trew_hip_annot> recs;
+        AnnotFileResult part;
+        std::vector<uint32_t> nl;
+        std::vector<int64_t> st, nd;
+    };
+    std::vector<Worker> workers;
+    uint64_t words_cap = 0, reads_cap = 0;
+};
+
+Annotator *annotator_create(const Config &cfg) {
+    Annotator *a = new Annotator();
+    const int n_workers = std::max(1, cfg.NUM_THREAD - 1);  // the caller's thread is the reader
+    const int ndev = (int) cfg.devices.size();
+    a->reads_cap = 1ull << 20;                                               // a 4 MiB chunk holds fewer FASTQ records than this
+    a->words_cap = 3ull * ((uint64_t) LENGTH / 32 + a->reads_cap) + 64;      // every read may waste up to one triple of padding
+    std::vector<int> slots_on_dev((size_t) ndev, 0);
+    for (int w = 0; w < n_workers; w++) slots_on_dev[(size_t) (w % ndev)]++;
+    for (int d = 0; d < ndev; d++) {
+        trew_hip_params p;
+        memset(&p, 0, sizeof(p));
+        p.min_mer = 5;  // the scan's parameters only shape the scan; the annotation does not read them
+        p.max_mer = 32;
+        p.low_baseline = 0.5;
+        p.high_baseline = 0.8;
+        p.slice_length = 150;
+        p.mode = TREW_MODE_SHORT;
+        p.device = cfg.devices[(size_t) d];
+        p.n_slots = std::max(1, slots_on_dev[(size_t) d]);
+        p.max_batch_words = a->words_cap;
+        p.max_batch_reads = a->reads_cap;
+        p.table_log2_slots = 12;  // no scan: the smallest table there is
+        p.flags = TREW_FLAG_NO_TIMING;
+        trew_hip_ctx *c = nullptr;
+        if (trew_hip_init(&p, &c) != 0) die(trew_hip_last_error(nullptr));
+        a->ctx.push_back(c);
+    }
+    std::vector<int> next_slot((size_t) ndev, 0);
+    a->workers.resize((size_t) n_workers);
+    for (int w = 0; w < n_workers; w++) {
+        Annotator::Worker &wk = a->workers[(size_t) w];
+        wk.dev_index = w % ndev;
+        wk.slot = next_slot[(size_t) wk.dev_index]++;
+        trew_hip_ctx *c = a->ctx[(size_t) wk.dev_index];
+        if (trew_hip_host_alloc(c, (a->words_cap + 2 * a->reads_cap) * 4, (void **) &wk.h_buf)) hip_die(c, "pinned allocation");
+    }
+    return a;
+}
+
+void annotator_destroy(Annotator *a) {
+    if (!a) return;
+    for (auto &w : a->workers) trew_hip_host_free(a->ctx[(size_t) w.dev_index], w.h_buf);
+    for (auto c : a->ctx) trew_hip_destroy(c);
+    delete a;
+}
+
+static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
+    trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
+    const int nm = rq->n_motifs;
+    for (;;) {
+        Chunk *ch = q->pop();
+        if (ch->sentinel) {
+            delete ch;
+            break;
+        }
+        // the newline that makes num & 3 == 2 closes a sequence line (see worker_loop); no length limit here
+        if (w->nl.size() < (size_t) LENGTH + 2) w->nl.resize((size_t) LENGTH + 2);
+        const size_t cnt = scan_newlines(ch->buffer1, (size_t) ch->total, w->nl.data());
+        const size_t j0 = (size_t) ((1 - ch->num_before) & 3);
+        const uint64_t first_read = (uint64_t) (ch->num_before + (int64_t) j0) >> 2;
+        w->st.clear();
+        w->nd.clear();
+        for (size_t j = j0; j < cnt; j += 4) {
+            const int64_t start = j > 0 ? (int64_t) w->nl[j - 1] + 1 : 0, len = (int64_t) w->nl[j] - start;
+            w->st.push_back(start);
+            w->nd.push_back(start + len - 1);
+        }
+        const uint64_t n = w->st.size();
+        if (n > a->reads_cap) die("internal error: a chunk holds more reads than the slot");
+        if (n) {
+            uint32_t *offsets = w->h_buf, *lengths = w->h_buf + n, *words = w->h_buf + 2 * n;
+            const uint64_t nw = trew_pack_reads(ch->buffer1, w->st.data(), w->nd.data(), n, words, a->words_cap, offsets, lengths);
+            if (nw == (uint64_t) -1) die("internal error: packed chunk exceeds the slot buffer");
+            trew_hip_batch b;
+            memset(&b, 0, sizeof(b));
+            b.words = words;
+            b.n_words = nw;
+            b.offsets = offsets;
+            b.lengths = lengths;
+            b.n_reads = n;
+            if (trew_hip_annotate(c, &b, w->slot, rq->motifs, nm)) hip_die(c, "trew_hip_annotate");
+            if (w->recs.size() < n * (size_t) nm) w->recs.resize(n * (size_t) nm);
+            uint64_t got = 0;
+            if (trew_hip_annotate_results(c, w->slot, w->recs.data(), n * (uint64_t) nm, &got, nullptr)) hip_die(c, "trew_hip_annotate_results");
+            AnnotFileResult &p = w->part;
+            p.reads += n;
+            for (uint64_t r = 0; r < n; r++) {
+                p.bases += lengths[r];
+                for (int m = 0; m < nm; m++) {
+                    const trew_hip_annot &x = w->recs[r * (size_t) nm + (size_t) m];
+                    const uint32_t longest = std::max(x.tract_len_fwd, x.tract_len_rev);
+                    p.windows_fwd[m] += x.windows_fwd;
+                    p.windows_rev[m] += x.windows_rev;
+                    p.longest[m] = std::max(p.longest[m], longest);
+                    if (longest >= rq->min_tract[m]) {
+                        p.reported[m]++;
+                        p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, x});
+                    }
+                }
+            }
+        }
+        free(ch->buffer1);
+        delete ch;
+    }
+}
+
+AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (auto &w : a->workers) w.part = AnnotFileResult();
+    ChunkQueue q(256);
+    std::vector<std::thread> th;
+    for (auto &w : a->workers) th.emplace_back(annotate_worker_loop, a, &w, &q, &rq);
+    FileReader f = open_reader(file_name, is_gz, cfg.NUM_THREAD);
+    read_fastq_thread(f, &q);
+    f.close();
+    for (size_t i = 0; i < a->workers.size(); i++) {
+        Chunk *c = new Chunk();
+        c->sentinel = true;
+        q.push(c);
+    }
+    for (auto &t : th) t.join();
+    AnnotFileResult out;
+    for (auto &w : a->workers) {
+        out.reads += w.part.reads;
+        out.bases += w.part.bases;
+        for (int m = 0; m < TREW_ANNOT_MAX_MOTIFS; m++) {
+            out.windows_fwd[m] += w.part.windows_fwd[m];
+            out.windows_rev[m] += w.part.windows_rev[m];
+            out.reported[m] += w.part.reported[m];
+            out.longest[m] = std::max(out.longest[m], w.part.longest[m]);
+        }
+        out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
+    }
+    std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
+    if (cfg.stats) {
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + annotate; serial reader, %d worker(s))\n", file_name,
+                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, (int) a->workers.size());
+    }
+    return out;
+}
+
 }  // namespace trew_host

@@ -91,6 +91,30 @@ FinalFastqOutput process_output(const char *file_name, const ResultMapData &resu
 void final_process_output(FinalFastqData &total_result_high, FinalFastqData &total_result_low, FILE *out);
 std::map<KmerSeq, uint32_t> get_score_map(const FinalFastqData &total_result);
 
+// ---- trew annotate MOTIF[,MOTIF...] FASTQ...: per-read motif tracts (host/annotate.cpp, process.cpp) ----
+struct AnnotRequest {
+    trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
+    uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];  // a (read, motif) is reported when its longer tract has at least this many bases
+    int n_motifs = 0;
+};
+struct AnnotRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    int motif;        // index in command-line order
+    trew_hip_annot a;
+};
+struct AnnotFileResult {
+    std::vector<AnnotRow> rows;  // sorted by read, then motif
+    uint64_t reads = 0, bases = 0;
+    uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
+    uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {};
+};
+struct Annotator;  // device contexts and one slot per worker
+Annotator *annotator_create(const Config &cfg);
+void annotator_destroy(Annotator *a);
+AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq);
+int annotate_main(int argc, char **argv);  // the subcommand: arguments, output
+
 struct RunStats {
     uint64_t reads = 0, bases = 0;
     double seconds = 0;

@@ -1,4 +1,5 @@
-// trew_main.cpp -- the `trew short|long MIN_MER MAX_MER` command line of the MI355X-native build.
+// trew_main.cpp -- the `trew short|long MIN_MER MAX_MER` command line of the MI355X-native build
+// (and `trew annotate MOTIF[,MOTIF...] FASTQ...`, which has no counterpart in the reference: host/annotate.cpp).
 //
 // Same sub-commands, positional arguments, options, limits and messages as the reference CLI
 // (trew.cpp:22-478): stdout carries the CSV sections, stderr errors/usage, exit code 1 on error.
@@ -31,8 +32,9 @@ static void usage(const char *mode) {
                 "             [--batch_mib N] [--host_pack] [--compat_g1] MIN_MER MAX_MER [SHORT_FASTQ]...\n\n"
                 "Estimate TRM from short-read sequencing data.\n");
     } else {
-        fprintf(stderr, "Usage: trew [--help] [--version] {long,short}\n\nSubcommands:\n  long          Estimate TRM from long-read sequencing data.\n"
-                        "  short         Estimate TRM from short-read sequencing data.\n");
+        fprintf(stderr, "Usage: trew [--help] [--version] {long,short,annotate}\n\nSubcommands:\n  long          Estimate TRM from long-read sequencing data.\n"
+                        "  short         Estimate TRM from short-read sequencing data.\n"
+                        "  annotate      Report the reads that carry given repeat motifs and their longest tracts.\n");
     }
 }
 
@@ -84,6 +86,7 @@ int main(int argc, char **argv) {
         usage(nullptr);
         return 0;
     }
+    if (mode == "annotate") return annotate_main(argc, argv);
     if (mode != "short" && mode != "long") {
         usage(nullptr);
         return 1;

@@ -45,6 +45,15 @@ struct Slot {
     u64 n_submits = 0;   // submits since init
     u64 n_reported = 0;  // submits already averaged by trew_hip_last_timing
     u64 n_units = 0;
+    // trew_hip_annotate: everything below is created by the first annotate call on the slot (a context that never annotates
+    // allocates nothing of it)
+    trew_hip_annot *d_annot = nullptr;  // records of the last annotate, grown on demand
+    u64 annot_cap = 0;                  // records d_annot holds
+    AnnotMotifDev *d_motifs = nullptr, *h_motifs = nullptr;  // kAnnotMaxMotifs pattern tables: device copy and pinned staging
+    int annot_motifs_staged = 0;        // motifs of h_motifs that d_motifs holds (or will, in stream order)
+    hipEvent_t ev_annot[2] = {nullptr, nullptr};
+    bool annot_valid = false, annot_timed = false;  // an annotate was queued / its kernel was launched between the events
+    u64 annot_n = 0;                    // records of the last annotate
 };
 
 thread_local std::string g_init_error;  // trew_hip_init failures before a context exists (read back on the same thread)
@@ -355,6 +364,11 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         for (int i = 0; i < Slot::kRing; i++)
             for (int j = 0; j < 3; j++)
                 if (s.ev[i][j]) (void) hipEventDestroy(s.ev[i][j]);
+        if (s.d_annot) (void) hipFree(s.d_annot);
+        if (s.d_motifs) (void) hipFree(s.d_motifs);
+        if (s.h_motifs) (void) hipHostFree(s.h_motifs);
+        for (auto e : s.ev_annot)
+            if (e) (void) hipEventDestroy(e);
         if (s.ev_tail) (void) hipEventDestroy(s.ev_tail);
         if (s.ev_copied) (void) hipEventDestroy(s.ev_copied);
         if (s.stream) (void) hipStreamDestroy(s.stream);
@@ -1161,6 +1175,220 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
         u32 c = 0;
         if (s.n_launches) HIPCHK(ctx, hipMemcpy(&c, s.d_wl_count + ((s.n_launches - 1) & 1) * kWlCountWords, 4, hipMemcpyDeviceToHost));
         *n_flagged = c;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- per-read annotation against given motifs
+namespace {
+
+// T=0 G=1 C=2 A=3: the complement is 3 - code
+u64 motif_revcomp(u64 w, int k) {
+    u64 r = 0;
+    for (int i = 0; i < k; i++) {
+        r = (r << 2) | (3u - (w & 3u));
+        w >>= 2;
+    }
+    return r;
+}
+
+u64 motif_mask(int k) { return k >= 32 ? ~0ull : (1ull << (2 * k)) - 1ull; }
+
+const char *motif_error(const trew_hip_motif &m) {
+    if (m.k < 3 || m.k > 32) return "motif: k must be in [3, 32]";
+    if (m.word & ~motif_mask(m.k)) return "motif: word has bits above 2k";
+    return nullptr;
+}
+
+const char *motifs_error(const trew_hip_motif *motifs, int n_motifs) {
+    if (n_motifs < 1 || n_motifs > kAnnotMaxMotifs) return "n_motifs must be in [1, 8]";
+    if (!motifs) return "motifs is NULL";
+    for (int m = 0; m < n_motifs; m++)
+        if (const char *e = motif_error(motifs[m])) return e;
+    return nullptr;
+}
+
+// the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
+void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
+    memset(d, 0, sizeof(*d));
+    d->k = (u32) m.k;
+    const u64 target[2] = {m.word, motif_revcomp(m.word, m.k)};
+    for (int s = 0; s < 2; s++)
+        for (int q = 0; q < m.k; q++) {
+            u32 lo = 0, hi = 0;
+            for (int i = 0; i < 32; i++) {
+                const int j = (i + q) % m.k;  // base j of the target, first base most significant
+                const u32 c = (u32) (target[s] >> (2 * (m.k - 1 - j))) & 3u;
+                lo |= (c & 1u) << i;
+                hi |= (c >> 1) << i;
+            }
+            d->plo[s][q] = lo;
+            d->phi[s][q] = hi;
+        }
+}
+
+}  // namespace
+
+extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
+    auto bad = [](const std::string &msg) {
+        g_thread_error = g_init_error = msg;
+        return -1;
+    };
+    if (!text || !out) return bad("trew_motif_parse: null argument");
+    const size_t k = strlen(text);
+    u64 w = 0;
+    for (size_t i = 0; i < k; i++) {
+        u32 c;
+        switch (text[i]) {
+        case 'T': case 't': c = 0; break;
+        case 'G': case 'g': c = 1; break;
+        case 'C': case 'c': c = 2; break;
+        case 'A': case 'a': c = 3; break;
+        default: return bad(std::string("motif '") + text + "': only A, C, G and T are allowed");
+        }
+        if (i < 32) w = (w << 2) | c;
+    }
+    if (k < 3 || k > 32) return bad(std::string("motif '") + text + "': the length must be in [3, 32]");
+    out->k = (int32_t) k;
+    out->reserved = 0;
+    out->word = w;
+    return 0;
+}
+
+extern "C" int trew_annotate_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                  const trew_hip_motif *motifs, int n_motifs, trew_hip_annot *out) {
+    if (const char *e = motifs_error(motifs, n_motifs)) {
+        g_thread_error = g_init_error = e;
+        return -1;
+    }
+    if (n_reads && (!words || !offsets || !lengths || !out)) {
+        g_thread_error = g_init_error = "trew_annotate_host: null argument";
+        return -1;
+    }
+    // a window matches a strand when its word is one of the k rotations of the strand's target
+    struct Strand {
+        u64 rot[32];
+    };
+    std::vector<Strand> rots((size_t) n_motifs * 2);
+    for (int m = 0; m < n_motifs; m++) {
+        const int k = motifs[m].k;
+        const u64 mask = motif_mask(k);
+        u64 t[2] = {motifs[m].word, motif_revcomp(motifs[m].word, k)};
+        for (int s = 0; s < 2; s++)
+            for (int i = 0; i < k; i++) {
+                rots[(size_t) m * 2 + s].rot[i] = t[s];
+                t[s] = ((t[s] << 2) | (t[s] >> (2 * (k - 1)))) & mask;
+            }
+    }
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        for (int m = 0; m < n_motifs; m++) {
+            const int k = motifs[m].k;
+            const u64 mask = motif_mask(k);
+            u32 cnt[2] = {0, 0}, best_len[2] = {0, 0}, best_start[2] = {0, 0}, run[2] = {0, 0};
+            u64 word = 0;
+            u32 clean = 0;  // bases since the last one with its nmask bit set
+            for (u32 i = 0; i < n; i++) {
+                const u32 j = i >> 5, b = i & 31u;
+                const u32 c = ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
+                clean = ((w[3 * j + 2] >> b) & 1u) ? 0 : clean + 1;
+                word = ((word << 2) | c) & mask;
+                if (i + 1 < (u32) k) continue;
+                const u32 start = i + 1 - (u32) k;  // the window that ends with base i
+                for (int s = 0; s < 2; s++) {
+                    bool hit = false;
+                    if (clean >= (u32) k)
+                        for (int x = 0; x < k && !hit; x++) hit = word == rots[(size_t) m * 2 + s].rot[x];
+                    if (hit) {
+                        cnt[s]++;
+                        if (++run[s] > best_len[s]) {  // strictly longer: the earliest run wins a tie
+                            best_len[s] = run[s];
+                            best_start[s] = start + 1 - run[s];
+                        }
+                    } else {
+                        run[s] = 0;
+                    }
+                }
+            }
+            trew_hip_annot &o = out[r * (u64) n_motifs + (u64) m];
+            o.windows_fwd = cnt[0];
+            o.windows_rev = cnt[1];
+            o.tract_start_fwd = best_len[0] ? best_start[0] : 0;
+            o.tract_len_fwd = best_len[0] ? best_len[0] + (u32) k - 1 : 0;
+            o.tract_start_rev = best_len[1] ? best_start[1] : 0;
+            o.tract_len_rev = best_len[1] ? best_len[1] + (u32) k - 1 : 0;
+        }
+    }
+    return 0;
+}
+
+extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
+    if (!ctx || !batch) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
+    HIPCHK(ctx, hipSetDevice(ctx->p.device));
+    Slot &s = ctx->slots[(size_t) slot];
+    // the longest read picks the kernel; none of the scan's read-length rules applies (no batch_geometry)
+    u32 max_len = 0;
+    bool general = (ctx->p.flags & TREW_FLAG_DEBUG_ANNOT_GENERAL) != 0;
+    if (!batch->lengths) {
+        max_len = batch->uniform_length;
+    } else if (!batch->on_device) {
+        for (u64 i = 0; i < batch->n_reads; i++) max_len = std::max(max_len, batch->lengths[i]);
+    } else if (batch->max_length > 0) {
+        max_len = (u32) batch->max_length;
+    } else {
+        general = true;  // unknown
+    }
+    DevBatch db;
+    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
+    // first annotate on this slot (each piece on its own, so that a failed call can simply be repeated)
+    if (!s.d_motifs) HIPCHK(ctx, hipMalloc((void **) &s.d_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs));
+    if (!s.h_motifs) HIPCHK(ctx, hipHostMalloc((void **) &s.h_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs, hipHostMallocDefault));
+    for (auto &e : s.ev_annot)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    // the pattern tables travel on the slot's stream in front of the kernel, and only when they changed
+    AnnotMotifDev tab[kAnnotMaxMotifs];
+    for (int m = 0; m < n_motifs; m++) fill_motif(motifs[m], &tab[m]);
+    if (s.annot_motifs_staged < n_motifs || memcmp(tab, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs) != 0) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // an earlier copy may still be reading the staging buffer
+        memcpy(s.h_motifs, tab, sizeof(AnnotMotifDev) * (size_t) n_motifs);
+        HIPCHK(ctx, hipMemcpyAsync(s.d_motifs, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs, hipMemcpyHostToDevice, s.stream));
+        s.annot_motifs_staged = n_motifs;
+    }
+    const u64 need = db.n_reads * (u64) n_motifs;
+    if (need > s.annot_cap) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
+        if (s.d_annot) HIPCHK(ctx, hipFree(s.d_annot));
+        s.d_annot = nullptr;
+        s.annot_cap = 0;
+        HIPCHK(ctx, hipMalloc((void **) &s.d_annot, need * sizeof(trew_hip_annot)));
+        s.annot_cap = need;
+    }
+    s.annot_valid = true;
+    s.annot_timed = false;
+    s.annot_n = need;
+    if (need == 0) return 0;
+    HIPCHK(ctx, hipEventRecord(s.ev_annot[0], s.stream));
+    HIPCHK(ctx, launch_annotate(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, max_len, general, s.d_annot));
+    HIPCHK(ctx, hipEventRecord(s.ev_annot[1], s.stream));
+    s.annot_timed = true;
+    return 0;
+}
+
+extern "C" int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_annot *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    if (!ctx) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    Slot &s = ctx->slots[(size_t) slot];
+    if (!s.annot_valid) return fail(ctx, "no trew_hip_annotate on this slot yet");
+    if (int rc = trew_hip_wait(ctx, slot)) return rc;
+    if (n) *n = s.annot_n;
+    const u64 take = std::min<u64>(s.annot_n, cap);
+    if (out && take) HIPCHK(ctx, hipMemcpy(out, s.d_annot, take * sizeof(trew_hip_annot), hipMemcpyDeviceToHost));
+    if (ms_kernel) {
+        *ms_kernel = 0.0f;
+        if (s.annot_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_annot[0], s.ev_annot[1]));
     }
     return 0;
 }

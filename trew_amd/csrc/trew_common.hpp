@@ -128,6 +128,17 @@ struct SegResults {
     u64 *seq_low_hi;
 };
 
+// one motif of trew_hip_annotate as the kernels read it (kernels/annotate.inc): for strand s (0 = the motif, 1 = its reverse
+// complement) and phase q < k, plo/phi[s][q] are the lo / hi plane bits of 32 bases of the endless repetition of the strand's
+// target, starting at its base q.  A slot keeps kAnnotMaxMotifs of them in device memory.
+constexpr int kAnnotMaxMotifs = TREW_ANNOT_MAX_MOTIFS;
+struct AnnotMotifDev {
+    u32 k;
+    u32 pad[3];
+    u32 plo[2][32];
+    u32 phi[2][32];
+};
+
 struct Segment {
     u32 mate;   // 0 = first read of the unit, 1 = second (pair mode)
     u32 start;  // first base

@@ -34,6 +34,7 @@
 //   driver_long.inc    run_long        driver_pair.inc   run_pair
 //   exact_kernel.inc   exact_kernel<NW, MODE, WT>
 //   table_kernels.inc  add-rows / compaction kernels      synth_kernels.inc  workload generators
+//   annotate.inc       annotate_lane_kernel<NW> / annotate_wave_kernel (per-read motif tracts, beside the scan)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -63,6 +64,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/g1_compat.inc"
 #include "kernels/table_kernels.inc"
 #include "kernels/synth_kernels.inc"
+#include "kernels/annotate.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -291,6 +293,25 @@ hipError_t launch_compact(hipStream_t st, const DevTable &T, u64 n_slots, u32 wi
 hipError_t launch_slice_finish(hipStream_t st, trew_hip_row *d_slice, u64 slice_rows, const unsigned long long *d_n, const trew_hip_row *d_spill_rows,
                                const u32 *d_spill_n, u32 spill_cap) {
     hipLaunchKernelGGL(table_slice_finish_kernel, dim3((spill_cap + 255u) / 256u), dim3(256), 0, st, d_slice, slice_rows, d_n, d_spill_rows, d_spill_n, spill_cap);
+    return hipGetLastError();
+}
+
+// Per-read annotation.  Reads of up to 160 bases keep their planes in 15 registers (NW = 5), up to 256 in 24 (NW = 8); anything
+// longer, or of unknown length, gets a wave per read.
+hipError_t launch_annotate(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, u32 max_len, bool general,
+                           trew_hip_annot *d_out) {
+    if (B.n_reads == 0) return hipSuccess;
+    if (general || max_len > 256u) {
+        // persistent waves, grid-strided over the reads; four waves a block, up to eight blocks a CU
+        const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+        hipLaunchKernelGGL(annotate_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, (u32 *) d_out);
+    } else {
+        const dim3 grid((u32) ((B.n_reads + 255ull) / 256ull));
+        if (max_len <= 160u)
+            hipLaunchKernelGGL(annotate_lane_kernel<5>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
+        else
+            hipLaunchKernelGGL(annotate_lane_kernel<8>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
+    }
     return hipGetLastError();
 }
 
