@@ -155,8 +155,7 @@ __device__ __forceinline__ RowCount<WT> eval_row(ExactSmem sm, const u32 (&lo)[N
     u32 V[NW];
 #pragma unroll
     for (int w = 0; w < NW; w++) {
-        const int bits = W - 32 * w;
-        V[w] = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+        V[w] = low_mask(W - 32 * w);
     }
     // ... without those that hold an N (kmer.cpp:2190): an N at base p spoils the windows p-k+1 .. p.  Segments with an N are one
     // in five of those that reach this point and carry one N as a rule, so the N are taken one at a time (more than four: the
@@ -168,9 +167,7 @@ __device__ __forceinline__ RowCount<WT> eval_row(ExactSmem sm, const u32 (&lo)[N
         u32 nn[NW], left = 0;
 #pragma unroll
         for (int w = 0; w < NW; w++) {
-            const int bits = W + k - 1 - 32 * w;
-            const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-            nn[w] = (ev & has_n) ? (~v1[w] & lm) : 0u;
+            nn[w] = (ev & has_n) ? (~v1[w] & low_mask(W + k - 1 - 32 * w)) : 0u;
             left += __popc(nn[w]);
         }
         many_n = left > 4u ? 1u : 0u;
@@ -188,10 +185,7 @@ __device__ __forceinline__ RowCount<WT> eval_row(ExactSmem sm, const u32 (&lo)[N
             const int a = left ? ((int) p - k + 1 > 0 ? (int) p - k + 1 : 0) : 0, b = left ? (int) p + 1 : 0;  // windows [a, b) go
 #pragma unroll
             for (int w = 0; w < NW; w++) {
-                const int hb = b - 32 * w, la = a - 32 * w;
-                const u32 upto = hb >= 32 ? 0xffffffffu : (hb <= 0 ? 0u : ((1u << hb) - 1u));
-                const u32 below = la >= 32 ? 0xffffffffu : (la <= 0 ? 0u : ((1u << la) - 1u));
-                V[w] &= ~(upto & ~below);
+                V[w] &= ~(low_mask(b - 32 * w) & ~low_mask(a - 32 * w));
             }
             left = left ? left - 1u : 0u;
         }
@@ -307,16 +301,9 @@ __device__ __forceinline__ void row_prepare(ExactSmem sm, const ReadRef &rd, con
         else
             load_planes<1>(rd, sg.start + 32u * w, lo1, hi1, nm1);  // (long reads stay in global memory)
     }
-    const int bits = (int) sg.len - 32 * (int) w;
-    const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-    const u32 v1 = ~nm1[0] & lm;  // base is A/C/G/T and inside the segment
+    const u32 v1 = ~nm1[0] & low_mask((int) sg.len - 32 * (int) w);  // base is A/C/G/T and inside the segment
     const u32 f1 = lo1[0] & v1, f2 = hi1[0] & v1;
-    u32 x = p == 0u ? f1 : (p == 1u ? f2 : (f1 & f2));
-    x ^= x << 1;
-    x ^= x << 2;
-    x ^= x << 4;
-    x ^= x << 8;
-    x ^= x << 16;  // bit i = parity of the word's bits 0..i
+    const u32 x = word_parity(p == 0u ? f1 : (p == 1u ? f2 : (f1 & f2)));  // bit i = parity of the word's bits 0..i
     const u32 top = mine ? x >> 31 : 0u;  // parity of the whole word
     u32 carry = 0;   // parity of the feature's words below w
 #pragma unroll
@@ -349,9 +336,7 @@ __device__ __forceinline__ void row_load(ExactSmem sm, int L, RowSeg<NW> &r) {
         r.P1[w] = prep[3 * NW + w];
         r.P2[w] = prep[4 * NW + w];
         r.P3[w] = prep[5 * NW + w];
-        const int bits = L - 32 * w;
-        const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-        anyn |= ~r.v1[w] & lm;
+        anyn |= ~r.v1[w] & low_mask(L - 32 * w);
     }
     r.has_n = anyn != 0u ? 1u : 0u;
 }
@@ -368,67 +353,17 @@ template <int NW, bool SMALLK = false>
 __device__ __forceinline__ u32 bound_at_k(const RowSeg<NW> &r, int L, int k, int gmax, const DevParams &P) {
     const u32 ku = (u32) k;
     u32 V[NW];
-    if (r.has_n == 0u) {  // row-uniform
-        const int wbits = L - k + 1;
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            const int bits = wbits - 32 * w;
-            V[w] = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-        }
-    } else {
-        // V_k[i] = AND_{t<k} v1[i+t] by binary decomposition of k over A_b = AND of b consecutive bases
-        u32 A[NW];
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            V[w] = 0xffffffffu;
-            A[w] = r.v1[w];
-        }
-        u32 off = 0;
-#pragma unroll
-        for (int b = 1; b <= 32; b <<= 1) {
-            if (b > 1) {
-                u32 T2[NW];
-#pragma unroll
-                for (int w = 0; w < NW; w++) T2[w] = A[w] & shr_var_word<NW>(A, w, (u32) (b / 2));
-#pragma unroll
-                for (int w = 0; w < NW; w++) A[w] = T2[w];
-            }
-            const bool take = (ku & (u32) b) != 0;
-#pragma unroll
-            for (int w = 0; w < NW; w++) {
-                const u32 sh = shr_var_word<NW>(A, w, off);
-                V[w] &= take ? sh : 0xffffffffu;
-            }
-            off += take ? (u32) b : 0u;
-        }
-    }
-    u32 c000 = 0, c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0, count = 0, links = 0;
+    windows_without_n<NW>(r.v1, r.has_n != 0u /* row-uniform */, L, k, 32, V);
+    Buckets8<false, false> b8;
     u32 Ew[NW];
 #pragma unroll
     for (int w = 0; w < NW; w++) {
         const u32 F1 = r.P1[w] ^ shr_k_word<NW, SMALLK>(r.P1, w, ku), F2 = r.P2[w] ^ shr_k_word<NW, SMALLK>(r.P2, w, ku);
         const u32 F3 = r.P3[w] ^ shr_k_word<NW, SMALLK>(r.P3, w, ku);
-        const u32 v = V[w];
         Ew[w] = ~((r.lo[w] ^ shr_k_word<NW, SMALLK>(r.lo, w, ku)) | (r.hi[w] ^ shr_k_word<NW, SMALLK>(r.hi, w, ku)));
-        const u32 a1 = v & F1, a0 = v ^ a1;
-        const u32 a11 = a1 & F2, a10 = a1 ^ a11, a01 = a0 & F2, a00 = a0 ^ a01;
-        const u32 b111 = a11 & F3, b101 = a10 & F3, b011 = a01 & F3, b001 = a00 & F3;
-        count += __popc(v);
-        c111 += __popc(b111);
-        c110 += __popc(a11 ^ b111);
-        c101 += __popc(b101);
-        c100 += __popc(a10 ^ b101);
-        c011 += __popc(b011);
-        c010 += __popc(a01 ^ b011);
-        c001 += __popc(b001);
-        c000 += __popc(a00 ^ b001);
+        b8.add(F1, F2, F3, V[w]);
     }
-#pragma unroll
-    for (int w = 0; w < NW; w++) {  // valid windows i, i+1 that share a class
-        const u32 vn = w + 1 < NW ? V[w + 1 < NW ? w + 1 : 0] : 0u;
-        links += __popc(V[w] & Ew[w] & alignbit(vn, V[w], 1u));
-    }
-    const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+    const u32 m8 = b8.largest(), count = b8.count, links = class_links<NW>(V, Ew);
     const u32 runs = count - links < 127u ? count - links : 127u;
     // m8 / COUNT >= baseline as the reference's doubles say it (MAX <= m8 and IEEE division is monotone in the numerator).  The
     // division itself is only needed within rounding distance of the threshold: baseline * COUNT lies within 2e-13 of its double.
@@ -625,9 +560,7 @@ __device__ __forceinline__ void stage_two(ExactSmem sm, const ReadRef &rdA, cons
             if (l < nwords) {
                 u32 lo1[1], hi1[1], nm1[1];
                 load_planes_lds<1>(rr, 32u * l, lo1, hi1, nm1);
-                const int bits = (int) L - 32 * (int) l;
-                const u32 lm = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
-                nmv = nm1[0] | ~lm;
+                nmv = nm1[0] | ~low_mask<true>((int) L - 32 * (int) l);
                 const u32 lq = lo1[0] & ~nmv, hq = hi1[0] & ~nmv;
                 sq = spread32(__brev(lq)) | (spread32(__brev(hq)) << 1);
             }
@@ -780,7 +713,7 @@ __device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, co
                 const u32 *nmk = sm_nmask(sm) + r * segwords;
                 const u32 wi = (u32) i >> 5;
                 const u32 nb = alignbit(wi + 1u < segwords ? nmk[wi + 1u] : 0xffffffffu, nmk[wi], (u32) i & 31u);  // N flags of bases i .. i + 31
-                if ((nb & (tk >= 32 ? 0xffffffffu : (1u << tk) - 1u)) == 0u) {
+                if ((nb & low_mask<true>(tk)) == 0u) {
                     sv = 1u;
                     cs = min_rotation<WT>(window_word_at(sm, range_base(sm, r) + (u32) i, tk), tk);
                 }
@@ -819,8 +752,7 @@ __device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, co
             load_planes_lds<NWW>(r, 0, wlo, whi, nm);
 #pragma unroll
             for (int w = 0; w < NWW; w++) {
-                const int bits = (int) rd.len - 32 * w;
-                const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+                const u32 lm = low_mask((int) rd.len - 32 * w);
                 wv1[w] = ~nm[w] & lm;
                 w_n |= nm[w] & lm;
             }

@@ -273,9 +273,7 @@ __device__ void run_long_groups(ExactSmem sm, const DevParams &P, const DevBatch
                     if (l < nwords) {
                         u32 lo1[1], hi1[1], nm1[1];
                         load_planes_lds<1>(rd, sst + 32u * l, lo1, hi1, nm1);
-                        const int bits = (int) sl - 32 * (int) l;
-                        const u32 lm = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
-                        nmv = nm1[0] | ~lm;
+                        nmv = nm1[0] | ~low_mask<true>((int) sl - 32 * (int) l);
                         const u32 lq = lo1[0] & ~nmv, hq = hi1[0] & ~nmv;
                         sq = spread32(__brev(lq)) | (spread32(__brev(hq)) << 1);
                     }

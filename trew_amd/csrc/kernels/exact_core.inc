@@ -192,9 +192,7 @@ __attribute__((noinline)) __device__ void stage_bases(ExactSmem sm, ReadRef rd, 
         if (lane < nwords) {
             u32 lo[1], hi[1], nm[1];
             load_planes<1>(rd, s + 32u * lane, lo, hi, nm);
-            const int bits = (int) L - 32 * (int) lane;
-            const u32 lm = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
-            nmv = nm[0] | ~lm;
+            nmv = nm[0] | ~low_mask<true>((int) L - 32 * (int) lane);
             const u32 l = lo[0] & ~nmv, h = hi[0] & ~nmv;
             sq = spread32(__brev(l)) | (spread32(__brev(h)) << 1);
         }
@@ -250,7 +248,7 @@ __device__ __forceinline__ WT min_rotation(WT w, int k) {
         const u32 w32 = (u32) w;
         const u64 dup = ((u64) w32 << (2 * k)) | w32;
         const u32 dlo = (u32) dup, dhi = (u32) (dup >> 32);
-        const u32 km = 2 * k >= 32 ? 0xffffffffu : ((1u << (2 * k)) - 1u);
+        const u32 km = low_mask<true>(2 * k);
         u32 ans = w32;
         if (k <= 8) {  // the doubled word fits 32 bits: one bit-field extract per rotation
             for (int i = 1; i < k; i++) ans = min(ans, __builtin_amdgcn_ubfe(dlo, 2u * (u32) i, 2u * (u32) k));
@@ -477,16 +475,13 @@ __attribute__((noinline)) __device__ KStat<WT> eval_k(ExactSmem sm, int L, int k
         rr.len = 0;
         u32 lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, nm[3] = {0, 0, 0};
         if (lane < segw) load_planes<3>(rr, sm.rs + 32u * lane, lo, hi, nm);
-        const int lbits = L - 32 * (int) lane;
-        const u32 lm = lbits >= 32 ? 0xffffffffu : (lbits <= 0 ? 0u : ((1u << lbits) - 1u));
-        if (!__any((nm[0] & lm) != 0u)) {
+        if (!__any((nm[0] & low_mask(L - 32 * (int) lane)) != 0u)) {
             const bool big = k >= 32;
             const u32 ks = (u32) k & 31u;
             const u32 slo = alignbit(big ? lo[2] : lo[1], big ? lo[1] : lo[0], ks);
             const u32 shi = alignbit(big ? hi[2] : hi[1], big ? hi[1] : hi[0], ks);
             const u32 e = ~((lo[0] ^ slo) | (hi[0] ^ shi));
-            const int wbits = W - 32 * (int) lane;
-            const u32 v = wbits >= 32 ? 0xffffffffu : (wbits <= 0 ? 0u : ((1u << wbits) - 1u));
+            const u32 v = low_mask(W - 32 * (int) lane);
             if (lane < 2u * ((u32) rounds + 1u)) {  // including the terminating zero word
                 ((u32 *) sm_vmask(sm))[lane] = v;
                 ((u32 *) sm_emask(sm))[lane] = e & v;
@@ -797,14 +792,6 @@ __attribute__((noinline)) __device__ void emit_k(ExactSmem sm, TableRef Tp, u32 
     PH_ADD(PH_EMIT, t_ph);
 }
 
-// per-lane variable right shift of a multiword mask by off in [0, 63]
-template <int NW>
-__device__ __forceinline__ u32 shr_var_word(const u32 (&x)[NW], int j, u32 off) {
-    const bool big = off >= 32u;
-    const u32 x0 = x[j], x1 = j + 1 < NW ? x[j + 1 < NW ? j + 1 : 0] : 0u, x2 = j + 2 < NW ? x[j + 2 < NW ? j + 2 : 0] : 0u;
-    return alignbit(big ? x2 : x1, big ? x1 : x0, off & 31u);
-}
-
 // Upper bound of MAX/COUNT for EVERY k of one segment at once: lane l handles
 // k = gmin + l with the same bit-parallel parity-bucket bound as the prefilter
 // (filter_segment), the shift amounts simply differ per lane.  Used by decide()
@@ -842,37 +829,19 @@ __device__ __forceinline__ void lane_bounds_at(const ReadRef &rd, u32 s, int L, 
     u32 lo[NW], hi[NW], nm[NW];
     load_planes<NW>(rd, s, lo, hi, nm);  // the lanes of one segment read the same (LDS-staged) words
     u32 v1[NW], P1[NW], P2[NW], P3[NW];
-    {
-        u32 f1[NW], f2[NW], f3[NW];
-#pragma unroll
-        for (int j = 0; j < NW; j++) {
-            int bits = L - 32 * j;
-            u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-            v1[j] = ~nm[j] & lm;
-            f1[j] = lo[j] & v1[j];
-            f2[j] = hi[j] & v1[j];
-            f3[j] = f1[j] & f2[j];
-        }
-        prefix_parity<NW>(f1, P1);
-        prefix_parity<NW>(f2, P2);
-        prefix_parity<NW>(f3, P3);
-    }
+    segment_setup<NW, true>(lo, hi, nm, L, v1, P1, P2, P3);
     const u32 ku = (u32) k;
     u32 V[NW];
-    u32 anyn = 0;
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        int bits = L - 32 * j;
-        u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-        anyn |= nm[j] & lm;
-    }
+    const u32 anyn = segment_has_n<NW>(nm, L);
+    // V = windows_without_n<NW>(v1, anyn != 0, L, k, gmax) (bound.inc, which bound_at_k calls), written out: through the call --
+    // by reference, by value or with a local copy -- the spills of up to twenty exact kernels change
+    // (profiles/bound_refactor/README.md).  A change to one of the two is a change to both.
     if (anyn == 0) {
         // no N in the segment (wave-uniform: every lane sees the same segment): V_k = the L-k+1 lowest bits
         const int wbits = L - k + 1;
 #pragma unroll
         for (int j = 0; j < NW; j++) {
-            const int bits = wbits - 32 * j;
-            V[j] = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+            V[j] = low_mask(wbits - 32 * j);
         }
     } else {
         // V_k[i] = AND_{t<k} v1[i+t] by binary decomposition of k over A_b = AND of b consecutive bases
@@ -903,7 +872,7 @@ __device__ __forceinline__ void lane_bounds_at(const ReadRef &rd, u32 s, int L, 
             }
         }
     }
-    u32 c000 = 0, c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0, count = 0;
+    Buckets8<false, false> b8;
 #pragma unroll
     for (int j = 0; j < NW; j++) {
         const u32 F1 = P1[j] ^ shr_var_word<NW>(P1, j, ku), F2 = P2[j] ^ shr_var_word<NW>(P2, j, ku);
@@ -911,34 +880,15 @@ __device__ __forceinline__ void lane_bounds_at(const ReadRef &rd, u32 s, int L, 
         const u32 v = V[j];
         out.V[j] = v;
         out.E[j] = ~((lo[j] ^ shr_var_word<NW>(lo, j, ku)) | (hi[j] ^ shr_var_word<NW>(hi, j, ku)));
-        const u32 a1 = v & F1, a0 = v ^ a1;
-        const u32 a11 = a1 & F2, a10 = a1 ^ a11, a01 = a0 & F2, a00 = a0 ^ a01;
-        const u32 b111 = a11 & F3, b101 = a10 & F3, b011 = a01 & F3, b001 = a00 & F3;
-        count += __popc(v);
-        c111 += __popc(b111);
-        c110 += __popc(a11 ^ b111);
-        c101 += __popc(b101);
-        c100 += __popc(a10 ^ b101);
-        c011 += __popc(b011);
-        c010 += __popc(a01 ^ b011);
-        c001 += __popc(b001);
-        c000 += __popc(a00 ^ b001);
+        b8.add(F1, F2, F3, v);
     }
-    const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+    const u32 m8 = b8.largest(), count = b8.count;
     // k = 64 is not bounded here (shift amounts stay below 64): never prune it
     out.ub = (k > gmax || k >= 64 || count == 0) ? ((k >= 64 && k <= gmax) ? 2.0 : 0.0) : (double) m8 / (double) count;
     out.m8 = (k > gmax || k >= 64) ? 0u : m8;
     out.cnt = (k > gmax || k >= 64) ? 0u : count;
     out.has_n = anyn != 0u;
-    {
-        u32 links = 0;  // valid windows i, i+1 that share a class
-#pragma unroll
-        for (int j = 0; j < NW; j++) {
-            const u32 vn = j + 1 < NW ? out.V[j + 1 < NW ? j + 1 : 0] : 0u;
-            links += __popc(out.V[j] & out.E[j] & alignbit(vn, out.V[j], 1u));
-        }
-        out.runs = count - links;
-    }
+    out.runs = count - class_links<NW>(out.V, out.E);
     PH_ADD(PH_BOUNDS, t_ph);
 }
 

@@ -1,5 +1,5 @@
 // kernels/helpers.inc -- part of trew_kernels.hip (included there, inside namespace trew; not a translation unit of its own).
-// Small device helpers shared by both kernels: funnel shifts, wave reductions (DPP), read descriptors, plane loads.
+// Small device helpers shared by both kernels: funnel shifts, wave reductions (DPP), read descriptors, plane loads, LDS list append.
 
 // ------------------------------------------------------------------ helpers
 __device__ u32 g_fallback[kFallbackWords];  // see kFallback* (trew_common.hpp); read by fallback_counters_read()
@@ -97,43 +97,29 @@ __device__ __forceinline__ ReadRef get_read(const DevBatch &b, u64 r) {
     return x;
 }
 
-// 32*NW plane bits starting at base s of a read: lo/hi/nmask, bit i = base s+i.
-template <int NW>
-__device__ __forceinline__ void load_planes(const ReadRef &rd, u32 s, u32 (&lo)[NW], u32 (&hi)[NW], u32 (&nm)[NW]) {
-    const u32 ws = s >> 5, bs = s & 31u;
-    u32 c0 = 0, c1 = 0, c2 = 0;
-    if (ws < rd.nw) {
-        c0 = rd.w[3 * ws + 0];
-        c1 = rd.w[3 * ws + 1];
-        c2 = rd.w[3 * ws + 2];
-    }
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        u32 n0 = 0, n1 = 0, n2 = 0;
-        const u32 idx = ws + (u32) j + 1u;
-        if (idx < rd.nw) {
-            n0 = rd.w[3 * idx + 0];
-            n1 = rd.w[3 * idx + 1];
-            n2 = rd.w[3 * idx + 2];
+// the one or two reads of a unit (pair mode: the two mates); an inactive lane gets empty descriptors
+__device__ __forceinline__ void unit_reads(const DevParams &P, const DevBatch &B, u64 unit, bool active, ReadRef (&rd)[2]) {
+    rd[0].w = B.words;
+    rd[0].len = 0;
+    rd[0].nw = 0;
+    rd[1] = rd[0];
+    if (active) {
+        if (P.mode == TREW_MODE_PAIR) {
+            rd[0] = get_read(B, 2 * unit);
+            rd[1] = get_read(B, 2 * unit + 1);
+        } else {
+            rd[0] = get_read(B, unit);
         }
-        lo[j] = alignbit(n0, c0, bs);
-        hi[j] = alignbit(n1, c1, bs);
-        nm[j] = alignbit(n2, c2, bs);
-        c0 = n0;
-        c1 = n1;
-        c2 = n2;
     }
 }
 
-// the same for a read whose triples are staged in LDS: ds_read instead of flat loads (a flat load counts as a vector-memory
-// operation, and waiting for one waits for everything the load unit was given before it -- the exact kernel's chunk prefetch)
-typedef const __attribute__((address_space(3))) u32 *lds_u32;
-template <int NW>
-__device__ __forceinline__ void load_planes_lds(const ReadRef &rd, u32 s, u32 (&lo)[NW], u32 (&hi)[NW], u32 (&nm)[NW]) {
-    const lds_u32 w = (lds_u32) rd.w;
+// 32*NW plane bits starting at base s of a read of nw triples at w: lo/hi/nmask, bit i = base s+i.  Ptr: the pointer's address
+// space decides the load instruction (load_planes / load_planes_lds below).
+template <int NW, typename Ptr>
+__device__ __forceinline__ void load_planes_from(const Ptr w, u32 nw, u32 s, u32 (&lo)[NW], u32 (&hi)[NW], u32 (&nm)[NW]) {
     const u32 ws = s >> 5, bs = s & 31u;
     u32 c0 = 0, c1 = 0, c2 = 0;
-    if (ws < rd.nw) {
+    if (ws < nw) {
         c0 = w[3 * ws + 0];
         c1 = w[3 * ws + 1];
         c2 = w[3 * ws + 2];
@@ -142,7 +128,7 @@ __device__ __forceinline__ void load_planes_lds(const ReadRef &rd, u32 s, u32 (&
     for (int j = 0; j < NW; j++) {
         u32 n0 = 0, n1 = 0, n2 = 0;
         const u32 idx = ws + (u32) j + 1u;
-        if (idx < rd.nw) {
+        if (idx < nw) {
             n0 = w[3 * idx + 0];
             n1 = w[3 * idx + 1];
             n2 = w[3 * idx + 2];
@@ -153,5 +139,33 @@ __device__ __forceinline__ void load_planes_lds(const ReadRef &rd, u32 s, u32 (&
         c0 = n0;
         c1 = n1;
         c2 = n2;
+    }
+}
+template <int NW>
+__device__ __forceinline__ void load_planes(const ReadRef &rd, u32 s, u32 (&lo)[NW], u32 (&hi)[NW], u32 (&nm)[NW]) {
+    load_planes_from<NW>(rd.w, rd.nw, s, lo, hi, nm);
+}
+
+// the same for a read whose triples are staged in LDS: ds_read instead of flat loads (a flat load counts as a vector-memory
+// operation, and waiting for one waits for everything the load unit was given before it -- the exact kernel's chunk prefetch)
+typedef const __attribute__((address_space(3))) u32 *lds_u32;
+template <int NW>
+__device__ __forceinline__ void load_planes_lds(const ReadRef &rd, u32 s, u32 (&lo)[NW], u32 (&hi)[NW], u32 (&nm)[NW]) {
+    load_planes_from<NW>((lds_u32) rd.w, rd.nw, s, lo, hi, nm);
+}
+
+// Wave-aggregated append to a list in LDS: one atomic on its counter per wave (the first flagged lane's); every flagged lane then
+// calls put(index of its entry).  (A callback, not a return value: the store stays inside the two conditions, as the generated
+// code has it; a capture by value where the callback reads variables the caller goes on using.)
+template <typename Put>
+__device__ __forceinline__ void wave_append(u32 *counter, bool flag, Put put) {
+    const u64 bal = __ballot(flag);
+    if (bal) {
+        const u32 lane = lane_id();
+        const int leader = __ffsll((long long) bal) - 1;
+        u32 sb = 0;
+        if ((int) lane == leader) sb = atomicAdd(counter, (u32) __popcll(bal));
+        sb = __shfl(sb, leader);
+        if (flag) put(sb + (u32) __popcll(bal & ((1ull << lane) - 1ull)));
     }
 }

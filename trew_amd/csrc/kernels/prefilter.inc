@@ -3,50 +3,6 @@
 
 // ------------------------------------------------------------------ prefilter
 
-// exclusive prefix parity of f over bits 0..32*NW-1: P[i] = XOR_{t<i} f[t]
-template <int NW>
-__device__ __forceinline__ void prefix_parity(const u32 (&f)[NW], u32 (&P)[NW]) {
-    u32 carry = 0, prev_top = 0;
-#pragma unroll
-    for (int j = 0; j < NW; j++) {
-        u32 x = f[j];
-        x ^= x << 1;
-        x ^= x << 2;
-        x ^= x << 4;
-        x ^= x << 8;
-        x ^= x << 16;
-        x ^= carry;  // carry = all-ones when the parity of all lower words is odd
-        P[j] = (x << 1) | prev_top;
-        prev_top = x >> 31;
-        carry = 0u - prev_top;
-    }
-}
-
-// the same for 3 words with the first two as one 64-bit value: six 64-bit shift + xor steps instead of ten 32-bit ones
-// (v_lshlrev_b64 costs what a 32-bit shift costs, tools/valu_rate.hip)
-template <>
-__device__ __forceinline__ void prefix_parity<3>(const u32 (&f)[3], u32 (&P)[3]) {
-    u64 x = ((u64) f[1] << 32) | f[0];
-    x ^= x << 1;
-    x ^= x << 2;
-    x ^= x << 4;
-    x ^= x << 8;
-    x ^= x << 16;
-    x ^= x << 32;  // bit i = parity of f bits 0..i
-    u32 y = f[2];
-    y ^= y << 1;
-    y ^= y << 2;
-    y ^= y << 4;
-    y ^= y << 8;
-    y ^= y << 16;
-    const u32 top = (u32) (x >> 63);
-    y ^= 0u - top;  // the parity of the 64 lower bits carries into every bit of the third word
-    const u64 e = x << 1;  // exclusive prefix of the first two words
-    P[0] = (u32) e;
-    P[1] = (u32) (e >> 32);
-    P[2] = (y << 1) | top;
-}
-
 // (x ^ y) & m as ONE instruction (v_bitop3_b32, truth table 0x28 = (0xF0 ^ 0xCC) & 0xAA)
 __device__ __forceinline__ u32 xor_and(u32 x, u32 y, u32 m) { return __builtin_amdgcn_bitop3_b32(x, y, m, 0x28); }
 
@@ -105,25 +61,14 @@ __device__ __forceinline__ void filter_k(const u32 (&P1)[NW], const u32 (&P2)[NW
 #else
     if (__any(pass4 && first)) {
 #endif
-        u32 c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0;
+        Buckets8<false, true> b8;
 #pragma unroll
         for (int j = 0; j < NWW; j++) {
             const u32 F1 = P1[j] ^ shr_word<NW, WS>(P1, j, bs), F2 = P2[j] ^ shr_word<NW, WS>(P2, j, bs);
             const u32 F3 = P3[j] ^ shr_word<NW, WS>(P3, j, bs);
-            const u32 v = V[j];
-            const u32 a1 = v & F1, a0 = v ^ a1;
-            const u32 a11 = a1 & F2, a10 = a1 ^ a11, a01 = a0 & F2, a00 = a0 ^ a01;
-            const u32 b111 = a11 & F3, b101 = a10 & F3, b011 = a01 & F3, b001 = a00 & F3;
-            c111 += __popc(b111);
-            c110 += __popc(a11 ^ b111);
-            c101 += __popc(b101);
-            c100 += __popc(a10 ^ b101);
-            c011 += __popc(b011);
-            c010 += __popc(a01 ^ b011);
-            c001 += __popc(b001);
+            b8.add(F1, F2, F3, V[j]);
         }
-        const u32 c000 = count - c001 - c010 - c011 - c100 - c101 - c110 - c111;
-        const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+        const u32 m8 = b8.largest(count);
         pass = first ? ((float) m8 > thr) : pass4;
     }
     if (k <= 32)
@@ -171,11 +116,13 @@ __device__ __forceinline__ u64 filter_segment(const u32 (&lo)[NW], const u32 (&h
                                               int kmin, int kmax, int gmin, int gmax, int max_seg, float lowf) {
     u32 v1[NW], P1[NW], P2[NW], P3[NW], V[NW];
     {
+        // segment_setup<NW, true> (bound.inc) written out, with V = v1 in the same loop: calling it here changes the register
+        // allocation of filter_kernel<32> (profiles/bound_refactor/README.md)
         u32 f1[NW], f2[NW], f3[NW];
 #pragma unroll
         for (int j = 0; j < NW; j++) {
             int bits = L - 32 * j;
-            u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+            u32 lm = low_mask(bits);
             v1[j] = ~nm[j] & lm;  // base is A/C/G/T and inside the segment
             f1[j] = lo[j] & v1[j];
             f2[j] = hi[j] & v1[j];
@@ -260,23 +207,13 @@ __device__ __forceinline__ u64 filter_k_uni(const u32 (&P1)[NW], const u32 (&P2)
     const u64 p4 = __ballot(m3 >= (u32) th.x) | __ballot(t <= th.y);  // two compares straight into SGPR masks
     u64 pm = p4;
     if (p4 & ~hasm) {  // third parity, as in filter_k: only for a lane's first candidate
-        u32 c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0;
+        u32 F3[NWW], Vw[NWW];
 #pragma unroll
         for (int j = 0; j < NWW; j++) {
-            const u32 F3 = P3[j] ^ shr_word<NW, WS>(P3, j, bs);
-            const u32 v = j == NWW - 1 ? wm : 0xffffffffu;
-            const u32 a11 = F1[j] & F2[j], a10 = F1[j] & ~F2[j], a01 = ~F1[j] & F2[j], a00 = v & ~(F1[j] | F2[j]);
-            const u32 b111 = a11 & F3, b101 = a10 & F3, b011 = a01 & F3, b001 = a00 & F3;
-            c111 += __popc(b111);
-            c110 += __popc(a11 ^ b111);
-            c101 += __popc(b101);
-            c100 += __popc(a10 ^ b101);
-            c011 += __popc(b011);
-            c010 += __popc(a01 ^ b011);
-            c001 += __popc(b001);
+            F3[j] = P3[j] ^ shr_word<NW, WS>(P3, j, bs);
+            Vw[j] = j == NWW - 1 ? wm : 0xffffffffu;
         }
-        const u32 c000 = (u32) W - c001 - c010 - c011 - c100 - c101 - c110 - c111;
-        const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+        const u32 m8 = max_bucket8<NWW>(F1, F2, F3, Vw, (u32) W);
         const u64 p8 = __ballot(m8 >= (u32) th.x);
         pm = (p4 & hasm) | (p8 & ~hasm);
     }
@@ -299,16 +236,7 @@ __device__ __forceinline__ u64 filter_k_uni_q(const u32 (&P1)[3], const u32 (&P2
                                               const int2 th, u64 hasm) {
     const int W = L - k + 1;  // COUNT: 32..64
     const u32 sh = (u32) (k - s);
-#ifndef TREW_AB_NO_Q
     const u64 S1 = Q1 >> sh, S2 = Q2 >> sh;
-#else  // A/B builds: the same words by funnel shifts
-    (void) Q1;
-    (void) Q2;
-    const bool kb = k >= 32;
-    const u32 kbs = (u32) k & 31u;
-    const u64 S1 = ((u64) alignbit(kb ? 0u : P1[2], kb ? P1[2] : P1[1], kbs) << 32) | alignbit(kb ? P1[2] : P1[1], kb ? P1[1] : P1[0], kbs);
-    const u64 S2 = ((u64) alignbit(kb ? 0u : P2[2], kb ? P2[2] : P2[1], kbs) << 32) | alignbit(kb ? P2[2] : P2[1], kb ? P2[1] : P2[0], kbs);
-#endif
     const u32 wm = W >= 64 ? 0xffffffffu : ((1u << ((W - 32) & 31)) - 1u);  // scalar: windows 32 .. COUNT-1
     const u32 F1a = P1[0] ^ (u32) S1, F2a = P2[0] ^ (u32) S2;
     const u32 F1b = xor_and(P1[1], (u32) (S1 >> 32), wm), F2b = xor_and(P2[1], (u32) (S2 >> 32), wm);  // one v_bitop3_b32 each
@@ -326,23 +254,8 @@ __device__ __forceinline__ u64 filter_k_uni_q(const u32 (&P1)[3], const u32 (&P2
     u64 pm = p4;
     if (p4 & ~hasm) {  // third parity, only for a lane's first candidate (rare: its shifted words are rebuilt here)
         const u64 S3 = container64(P3, s) >> sh;
-        const u32 F3a = P3[0] ^ (u32) S3, F3b = P3[1] ^ (u32) (S3 >> 32);
-        u32 c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const u32 F1 = j ? F1b : F1a, F2 = j ? F2b : F2a, F3 = j ? F3b : F3a, v = j ? wm : 0xffffffffu;
-            const u32 a11 = F1 & F2, a10 = F1 & ~F2, a01 = ~F1 & F2, a00 = v & ~(F1 | F2);
-            const u32 b111 = a11 & F3, b101 = a10 & F3, b011 = a01 & F3, b001 = a00 & F3;
-            c111 += __popc(b111);
-            c110 += __popc(a11 ^ b111);
-            c101 += __popc(b101);
-            c100 += __popc(a10 ^ b101);
-            c011 += __popc(b011);
-            c010 += __popc(a01 ^ b011);
-            c001 += __popc(b001);
-        }
-        const u32 c000 = (u32) W - c001 - c010 - c011 - c100 - c101 - c110 - c111;
-        const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+        const u32 F1[2] = {F1a, F1b}, F2[2] = {F2a, F2b}, F3[2] = {P3[0] ^ (u32) S3, P3[1] ^ (u32) (S3 >> 32)}, Vw[2] = {0xffffffffu, wm};
+        const u32 m8 = max_bucket8<2>(F1, F2, F3, Vw, (u32) W);
         const u64 p8 = __ballot(m8 >= (u32) th.x);
         pm = (p4 & hasm) | (p8 & ~hasm);
     }
@@ -355,6 +268,21 @@ struct UniVerdict {
     u64 flagm;  // wave mask: lanes with a candidate inside the segment's own [kmin, kmax]
     u32 clo, chi;  // this lane's candidate mask (only maintained when `dbg`)
 };
+
+// the verdict mask pm of one k goes into the segment's.  slow: see FilterRangeUni
+__device__ __forceinline__ void uni_note(UniVerdict &vd, u64 pm, int k, bool slow, int kmin, int kmax, bool dbg) {
+    vd.hasm |= pm;
+    if (slow) {
+        if (k >= kmin && k <= kmax) vd.flagm |= pm;
+        if (dbg) {  // wave-uniform
+            const bool mine = (pm >> lane_id()) & 1ull;
+            if (k <= 32)
+                vd.clo |= mine ? (1u << ((k - 1) & 31)) : 0u;
+            else
+                vd.chi |= mine ? (1u << ((k - 33) & 31)) : 0u;
+        }
+    }
+}
 
 // as FilterRange, with the word count taken from the segment's own (uniform) length.
 // SLOW: some k of the loop lie outside the segment's [kmin, kmax], or the per-lane masks are wanted
@@ -373,18 +301,7 @@ struct FilterRangeUni {
             for (int k = a; k <= b; k++) {
                 const int2 th = th_next;
                 th_next = thr_row[k];  // entry 64 exists (padding)
-                const u64 pm = filter_k_uni<NW, WS, NWW>(P1, P2, P3, L, k, th, vd.hasm);
-                vd.hasm |= pm;
-                if (SLOW) {
-                    if (k >= kmin && k <= kmax) vd.flagm |= pm;
-                    if (dbg) {  // wave-uniform
-                        const bool mine = (pm >> lane_id()) & 1ull;
-                        if (k <= 32)
-                            vd.clo |= mine ? (1u << ((k - 1) & 31)) : 0u;
-                        else
-                            vd.chi |= mine ? (1u << ((k - 33) & 31)) : 0u;
-                    }
-                }
+                uni_note(vd, filter_k_uni<NW, WS, NWW>(P1, P2, P3, L, k, th, vd.hasm), k, SLOW, kmin, kmax, dbg);
             }
         }
         FilterRangeUni<NW, WS, NWW - 1, SLOW>::run(P1, P2, P3, klo, khi, L, kmin, kmax, thr_row, dbg, vd);
@@ -401,57 +318,26 @@ struct FilterRangeUni<NW, WS, 0, SLOW> {
 template <int NW>
 __device__ __forceinline__ void filter_segment_uni(const u32 (&lo)[NW], const u32 (&hi)[NW], int L, int kmin, int kmax, int gmin, int gmax,
                                                    const int2 *__restrict__ thr_row, bool dbg, UniVerdict &vd) {
-    u32 P1[NW], P2[NW], P3[NW];
-    {
-        u32 f1[NW], f2[NW], f3[NW];
-#pragma unroll
-        for (int j = 0; j < NW; j++) {
-            const int bits = L - 32 * j;
-            const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-            f1[j] = lo[j] & lm;
-            f2[j] = hi[j] & lm;
-            f3[j] = f1[j] & f2[j];
-        }
-        prefix_parity<NW>(f1, P1);
-        prefix_parity<NW>(f2, P2);
-        prefix_parity<NW>(f3, P3);
-    }
+    u32 P1[NW], P2[NW], P3[NW], none[NW];
+    segment_setup<NW, false>(lo, hi, /* N plane: not read */ lo, L, /* v1: not written */ none, P1, P2, P3);
     vd.hasm = vd.flagm = 0;
     vd.clo = vd.chi = 0;
     const int g31 = gmax < 31 ? gmax : 31;
     const bool slow = dbg || kmin > gmin || kmax < gmax;  // wave-uniform
-#ifndef TREW_AB_NO_CONTAINER
-    constexpr bool kSplit3 = NW == 3;
-#else
-    constexpr bool kSplit3 = false;  // A/B builds (tools/build_variant.sh): the round-2 k loops
-#endif
-    if constexpr (kSplit3) {
+    if constexpr (NW == 3) {
         // The 3-word kernel (segments of up to 95 bases: the halves of 150-bp reads) splits the k range by COUNT = L-k+1:
         //   COUNT >= 73         three mask words, funnel shifts                  (FilterRangeUni, NWW = 3)
         //   65 <= COUNT <= 72   the first 64 windows only, two full words        (filter_k_uni<.., SUBSET>)
         //   32 <= COUNT <= 64   two words from one 64-bit container shift        (filter_k_uni_q)
         //   COUNT <= 31         one word                                         (FilterRangeUni, NWW = 1)
         // kUniSubsetMax (trew_common.hpp) is shared with fill_thresholds: both sides must agree on the windows counted.
-        auto note = [&](u64 pm, int k) __attribute__((always_inline)) {
-            vd.hasm |= pm;
-            if (slow) {
-                if (k >= kmin && k <= kmax) vd.flagm |= pm;
-                if (dbg) {
-                    const bool mine = (pm >> lane_id()) & 1ull;
-                    if (k <= 32)
-                        vd.clo |= mine ? (1u << ((k - 1) & 31)) : 0u;
-                    else
-                        vd.chi |= mine ? (1u << ((k - 33) & 31)) : 0u;
-                }
-            }
-        };
         // (a) COUNT >= 73: k <= L - 72 (always below 32 since L <= 95)
         {
             const int hi = (L - kUniSubsetMax) < g31 ? (L - kUniSubsetMax) : g31;
             if (slow)
                 FilterRangeUni<NW, 0, NW, true>::run(P1, P2, P3, gmin, hi, L, kmin, kmax, thr_row, dbg, vd);
             else
-                FilterRangeUni<NW, 0, NW, false>::run(P1, P2, P3, gmin, hi, L, kmin, kmax, thr_row, false, vd);
+                FilterRangeUni<NW, 0, NW, false>::run(P1, P2, P3, gmin, hi, L, kmin, kmax, thr_row, dbg, vd);
         }
         // (b) 65 <= COUNT <= 72: k in [L-71, L-64] (k <= 31)
         {
@@ -463,7 +349,7 @@ __device__ __forceinline__ void filter_segment_uni(const u32 (&lo)[NW], const u3
                 for (int k = a; k <= b; k++) {
                     const int2 th = th_next;
                     th_next = thr_row[k];
-                    note(filter_k_uni<NW, 0, 2, true>(P1, P2, P3, L, k, th, vd.hasm), k);
+                    uni_note(vd, filter_k_uni<NW, 0, 2, true>(P1, P2, P3, L, k, th, vd.hasm), k, slow, kmin, kmax, dbg);
                 }
             }
         }
@@ -479,11 +365,13 @@ __device__ __forceinline__ void filter_segment_uni(const u32 (&lo)[NW], const u3
                 for (int k = a; k <= b; k++) {
                     const int2 th = th_next;
                     th_next = thr_row[k];
-                    note(filter_k_uni_q(P1, P2, P3, Q1, Q2, s, L, k, th, vd.hasm), k);
+                    uni_note(vd, filter_k_uni_q(P1, P2, P3, Q1, Q2, s, L, k, th, vd.hasm), k, slow, kmin, kmax, dbg);
                 }
             }
         }
         // (d) COUNT <= 31: one word, k >= L - 30
+        // (the three word offsets of a range are spelled out here and below: a helper that runs them costs filter_kernel<5>
+        // fourteen instructions, profiles/bound_refactor/README.md)
         if (slow) {
             FilterRangeUni<NW, 0, 1, true>::run(P1, P2, P3, gmin, g31, L, kmin, kmax, thr_row, dbg, vd);
             FilterRangeUni<NW, 1, 1, true>::run(P1, P2, P3, gmin > 32 ? gmin : 32, gmax < 63 ? gmax : 63, L, kmin, kmax, thr_row, dbg, vd);
@@ -522,16 +410,8 @@ struct HalvesP {
     u32 P1[3], P2[3];  // prefix parities of the lo plane and the hi plane of one half
 };
 __device__ __forceinline__ void halves_prefix(const u32 (&lo)[3], const u32 (&hi)[3], int L, HalvesP &o) {
-    u32 f1[3], f2[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int bits = L - 32 * j;
-        const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-        f1[j] = lo[j] & lm;
-        f2[j] = hi[j] & lm;
-    }
-    prefix_parity<3>(f1, o.P1);
-    prefix_parity<3>(f2, o.P2);
+    u32 none[3];
+    segment_setup<3, false, false>(lo, hi, /* N plane: not read */ lo, L, /* v1, P3: not written */ none, o.P1, o.P2, none);
 }
 // 4-bucket statistics of one half at one k from its two window-parity words (second word already masked to the windows that
 // exist), as SIGNS: with the popcount chains started at -2 ithr (c1x, cx1) and -ithr (c11),
@@ -680,19 +560,9 @@ struct DrainHalf {
     u32 V[3];                 // V_k
 };
 __device__ __forceinline__ void drain_half_init(const u32 (&lo)[3], const u32 (&hi)[3], const u32 (&nm)[3], int L, bool active, DrainHalf &h) {
-    u32 f1[3], f2[3], f3[3];
+    segment_setup<3, false, true, true>(lo, hi, nm, L, h.V, h.P1, h.P2, h.P3);  // V_1: bases inside the half that are A/C/G/T
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int bits = L - 32 * j;
-        const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-        h.V[j] = active ? ~nm[j] & lm : 0u;  // V_1: bases inside the half that are A/C/G/T (an inactive lane has no window)
-        f1[j] = lo[j] & lm;
-        f2[j] = hi[j] & lm;
-        f3[j] = f1[j] & f2[j];
-    }
-    prefix_parity<3>(f1, h.P1);
-    prefix_parity<3>(f2, h.P2);
-    prefix_parity<3>(f3, h.P3);
+    for (int j = 0; j < 3; j++) h.V[j] = active ? h.V[j] : 0u;  // an inactive lane has no window
 }
 __device__ __forceinline__ void drain_v_step3(u32 (&V)[3]) {  // V_{k+1} = V_k & (V_k >> 1)
     V[0] &= alignbit(V[1], V[0], 1u);
@@ -717,21 +587,7 @@ __device__ __forceinline__ int drain_signs(const u32 (&F1)[N], const u32 (&F2)[N
 // 8-bucket maximum of one half reaches ithr (the rare stage: only for lanes not flagged yet that pass the 4-bucket test)
 template <int N>
 __device__ __forceinline__ bool drain_pass8(const u32 (&F1)[N], const u32 (&F2)[N], const u32 (&F3)[N], const u32 (&V)[N], u32 count, int ithr) {
-    u32 c001 = 0, c010 = 0, c011 = 0, c100 = 0, c101 = 0, c110 = 0, c111 = 0;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const u32 a11 = F1[j] & F2[j], a10 = F1[j] & ~F2[j], a01 = ~F1[j] & F2[j], a00 = V[j] & ~(F1[j] | F2[j]);
-        const u32 b111 = a11 & F3[j], b101 = a10 & F3[j], b011 = a01 & F3[j], b001 = a00 & F3[j];
-        c111 += __popc(b111);
-        c110 += __popc(a11 ^ b111);
-        c101 += __popc(b101);
-        c100 += __popc(a10 ^ b101);
-        c011 += __popc(b011);
-        c010 += __popc(a01 ^ b011);
-        c001 += __popc(b001);
-    }
-    const u32 c000 = count - c001 - c010 - c011 - c100 - c101 - c110 - c111;
-    const u32 m8 = max(max(max(c000, c001), max(c010, c011)), max(max(c100, c101), max(c110, c111)));
+    const u32 m8 = max_bucket8<N>(F1, F2, F3, V, count);
     return (int) m8 >= ithr;
 }
 
@@ -757,18 +613,7 @@ __device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const De
                                                     const int4 *cnt_thr) {
     const u32 UL = B.uniform_length;
     ReadRef rd[2];
-    rd[0].w = B.words;
-    rd[0].len = 0;
-    rd[0].nw = 0;
-    rd[1] = rd[0];
-    if (active) {
-        if (P.mode == TREW_MODE_PAIR) {
-            rd[0] = get_read(B, 2 * unit);
-            rd[1] = get_read(B, 2 * unit + 1);
-        } else {
-            rd[0] = get_read(B, unit);
-        }
-    }
+    unit_reads(P, B, unit, active, rd);
     const u64 actm = __ballot(active);
     u64 flag = 0;
     const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : 2;
@@ -907,15 +752,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
     };
     // wave-aggregated append of the flagged units to the block's LDS stage (block-uniform call)
     auto append = [&](bool flag, u32 unit) __attribute__((always_inline)) {
-        const u64 bal = __ballot(flag);
-        if (bal) {
-            const u32 lane = lane_id();
-            const int leader = __ffsll((long long) bal) - 1;
-            u32 sb = 0;
-            if ((int) lane == leader) sb = atomicAdd(&stage_n, (u32) __popcll(bal));
-            sb = __shfl(sb, leader);
-            if (flag) stage[sb + (u32) __popcll(bal & ((1ull << lane) - 1ull))] = unit;  // < kStage: flushed below when > kStage - block size
-        }
+        wave_append(&stage_n, flag, [&](u32 at) __attribute__((always_inline)) { stage[at] = unit; });  // < kStage: flushed below when > kStage - block size
         __syncthreads();
         // Every thread reads the fill level before any thread goes on: a wave that ran ahead into the NEXT append (the general path
         // makes two in a row) would add to stage_n while a slower wave still looked at it, and the block would disagree about
@@ -931,18 +768,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
     // general path: any read length, N anywhere
     auto general = [&](u64 unit, bool active) __attribute__((always_inline)) -> u64 {
         ReadRef rd[2];
-        rd[0].w = B.words;
-        rd[0].len = 0;
-        rd[0].nw = 0;
-        rd[1] = rd[0];
-        if (active) {
-            if (P.mode == TREW_MODE_PAIR) {
-                rd[0] = get_read(B, 2 * unit);
-                rd[1] = get_read(B, 2 * unit + 1);
-            } else {
-                rd[0] = get_read(B, unit);
-            }
-        }
+        unit_reads(P, B, unit, active, rd);
         u64 any = 0;
 #pragma unroll
         for (int slot = 0; slot < kMaxSlots; slot++) {
@@ -1013,31 +839,15 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             // thread 0 asks for the next chunk FIRST: memory operations complete in order, so the round trip of this atomic
             // (L2, ~1-2 us) lies under the HBM latency of the read loads below, which have to be waited for anyway
             u32 nxt = 0;
-#ifndef TREW_AB_STATIC_CHUNKS
             if (threadIdx.x == 0) nxt = gridDim.x + kChunkShards * atomicAdd(shard_ctr(my_shard), 1u) + my_shard;
-#else
-            nxt = (u32) chunk + gridDim.x;  // A/B builds: the round-2 static grid stride
-#endif
             u64 any = 0;
             bool dfr = active, dfr_n = false;  // dfr_n: set aside because of an N
             if constexpr (NW <= 5) {
                 if (uni) {
                     ReadRef rd[2];
-                    rd[0].w = B.words;
-                    rd[0].len = 0;
-                    rd[0].nw = 0;
-                    rd[1] = rd[0];
-                    if (active) {
-                        if (P.mode == TREW_MODE_PAIR) {
-                            rd[0] = get_read(B, 2 * unit);
-                            rd[1] = get_read(B, 2 * unit + 1);
-                        } else {
-                            rd[0] = get_read(B, unit);
-                        }
-                    }
+                    unit_reads(P, B, unit, active, rd);
                     dfr = false;
                     int slot0 = 0;
-#ifndef TREW_AB_NO_JOINT
                     if constexpr (NW == 3) {
                         // halves of equal length whose whole k range has 32..72 windows (150-bp reads at 5..32: 44..71): both
                         // halves of a read in one k loop (filter_halves_uni); anything else takes the per-segment loops below
@@ -1056,14 +866,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                             u32 loA[3], hiA[3], nmA[3], loB[3], hiB[3], nmB[3];
                             load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, loA, hiA, nmA);
                             load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, loB, hiB, nmB);
-                            u32 anyn = 0;
-#pragma unroll
-                            for (int j = 0; j < 3; j++) {
-                                const int bits = L - 32 * j, bitsB = (int) sB.len - 32 * j;  // an N in the right half's extra base counts
-                                const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
-                                const u32 lmB = bitsB >= 32 ? 0xffffffffu : (bitsB <= 0 ? 0u : ((1u << bitsB) - 1u));
-                                anyn |= (nmA[j] & lm) | (nmB[j] & lmB);
-                            }
+                            const u32 anyn = segment_has_n<3>(nmA, L) | segment_has_n<3>(nmB, (int) sB.len);  // an N in the right half's extra base counts
                             dfr = dfr || (active && anyn != 0);  // a half with an N does not fit the model: the read is set aside
                             dfr_n = dfr_n || (active && anyn != 0);
                             HalvesP hA, hB;
@@ -1077,7 +880,6 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                             dfr = dfr || (active && any == 0 && ((trig >> lane_id()) & 1ull) != 0);
                         }
                     }
-#endif
                     for (int slot = slot0; slot < nslots; slot++) {  // wave-uniform geometry: no need to unroll
                         const Segment sg = get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len);
                         if (!sg.valid) continue;
@@ -1088,11 +890,11 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                         u32 lo[NW], hi[NW], nm[NW];
                         const ReadRef r = sg.mate ? rd[1] : rd[0];
                         load_planes<NW>(r, sg.start, lo, hi, nm);
-                        u32 anyn = 0;
+                        u32 anyn = 0;  // segment_has_n<NW> written out: the call costs filter_kernel<5> two instructions (profiles/bound_refactor/README.md)
 #pragma unroll
                         for (int j = 0; j < NW; j++) {
                             const int bits = (int) sg.len - 32 * j;
-                            const u32 lm = bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u));
+                            const u32 lm = low_mask(bits);
                             anyn |= nm[j] & lm;
                         }
                         UniVerdict vd;
@@ -1106,24 +908,14 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                 }
             }
             {
-                const u64 bal = __ballot(dfr);
-                if (bal) {
-                    const u32 lane = lane_id();
-                    const int leader = __ffsll((long long) bal) - 1;
-                    u32 sb = 0;
-                    if ((int) lane == leader) sb = atomicAdd(&defer_n, (u32) __popcll(bal));
-                    sb = __shfl(sb, leader);
-                    if (dfr) {  // < kDefer: drained below at one block-full
-                        const u32 at = sb + (u32) __popcll(bal & ((1ull << lane) - 1ull));
-                        defer[at] = (u32) unit;
-                        defer_kind[at] = dfr_n ? 1 : 0;
-                    }
-                }
+                wave_append(&defer_n, dfr, [=](u32 at) __attribute__((always_inline)) {  // < kDefer: drained below at one block-full
+                    defer[at] = (u32) unit;
+                    defer_kind[at] = dfr_n ? 1 : 0;
+                });
             }
             if (threadIdx.x == 0) next_chunk[round & 1u] = nxt;
             append(active && !dfr && any != 0, (u32) unit);  // syncs the block
             chunk = next_chunk[round & 1u];
-#ifndef TREW_AB_STATIC_CHUNKS
             if (chunk * kFilterThreads >= B.n_units) {  // block-uniform; end of the input only: look at the other shards, synchronously
                 __syncthreads();  // every thread has read the dry id above before thread 0 replaces it (else a late wave would skip this branch and its barriers)
                 if (threadIdx.x == 0) {
@@ -1138,7 +930,6 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                 chunk = next_chunk[round & 1u];
                 __syncthreads();  // the next round may write this slot's twin only after everybody has read this one
             }
-#endif
             round++;
         }
         // block-uniform: the length as every thread read it inside the last append() -- every add of this round happened before

@@ -168,7 +168,7 @@ __global__ void pack_ascii_kernel(const unsigned char *__restrict__ bases, const
         hi |= gather4(c | a) << (4 * d);
         nm |= gather4(~(a | c | g | tt) & 0x80808080u) << (4 * d);
     }
-    const u32 keep = m >= 32u ? 0xffffffffu : ((1u << m) - 1u);
+    const u32 keep = low_mask<true>((int) m);
     const u64 w = word_offsets ? (u64) word_offsets[r] + 3ull * j : 3ull * t;
     words[w + 0] = lo & keep;
     words[w + 1] = hi & keep;

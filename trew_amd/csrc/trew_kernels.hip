@@ -26,8 +26,10 @@
 // No CUDA shims, no dual paths: HIP for gfx950 only.
 //
 // One translation unit; the device code lives in kernels/*.inc, included below in dependency order:
-//   helpers.inc        funnel shifts, DPP wave reductions, read descriptors, plane loads
-//   prefilter.inc      filter_kernel<NW> (general path + uniform-geometry fast path)
+//   helpers.inc        funnel shifts, DPP wave reductions, read descriptors (unit_reads), plane loads, wave_append
+//   bound.inc          the parity-bucket bound's building blocks, shared by the prefilter and the exact kernel: low_mask,
+//                      prefix_parity, segment_setup, segment_has_n, windows_without_n, max_bucket8, class_links
+//   prefilter.inc      filter_kernel<NW> (general path + uniform-geometry fast path + joint halves loop + uniform drain)
 //   count_table.inc    table_add / table_add_wide / spill log
 //   exact_core.inc     LDS working set, eval_k / eval_runs (Lemma A), lane_bounds, decide, emit_k, run_short, run_segment
 //   decide_group.inc   decide_group (four segments in lock step, 16 lanes each), run_short_group
@@ -54,6 +56,7 @@ namespace trew {
 typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_128, kmer.cpp:2346-2547)
 
 #include "kernels/helpers.inc"
+#include "kernels/bound.inc"
 #include "kernels/prefilter.inc"
 #include "kernels/count_table.inc"
 #include "kernels/exact_core.inc"
@@ -194,7 +197,8 @@ hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &
     // long mode: the kernel is built for the regular slice (SLICE_LENGTH bases); its driver decides the one longer middle slice
     // without lane bounds (run_long), so that slice does not set the register budget
     const u32 bound_len = P.mode == TREW_MODE_LONG ? (u32) P.slice_len : max_seg_len;
-    const int nw = (P.flags & TREW_FLAG_NO_FILTER) ? 0 : (bound_len <= 95 ? 3 : bound_len <= 159 ? 5 : bound_len <= 319 ? 10 : 0);
+    // 0: no lane bounds -- NO_FILTER, and segments above 319 bases (pick_nw's 32, which the switches below map to 0)
+    const int nw = (P.flags & TREW_FLAG_NO_FILTER) ? 0 : pick_nw(bound_len);
     // one block = one wave; fill the chip exactly once (persistent, self-scheduling waves)
     typedef void (*kern_t)(DevParams, DevBatch, DevTableG1, const u32 *, u32 *, u32 *, u32, SegResults, u32, u32);
     kern_t fn = nullptr;
