@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 /* Still 4 with the annotation entry points (trew_motif_parse, trew_hip_annotate, trew_hip_annotate_results,
- * trew_annotate_host): they are purely additive -- no existing structure, enumerator or function changed. */
+ * trew_annotate_host) and the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host): they are purely additive -- no existing structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
 /* scan modes: which per-read driver of the reference is reproduced */
@@ -303,6 +303,31 @@ int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_annot *out, 
  * writes them): what tests compare the device with where the inputs are large. */
 int trew_annotate_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                        const trew_hip_motif *motifs, int n_motifs, trew_hip_annot *out);
+
+/* ---- error-tolerant terminal tracts per read (how long is the telomere at the end of this read?) ----
+ * match_s[i] as above.  cov_s[p] (0 <= p < n) = 1 when some matching window of strand s contains base p, else 0: one
+ * substitution inside a perfect repeat removes k windows but leaves only that base uncovered.  score(p) = +1 when covered,
+ * else -penalty (1 <= penalty <= 64); S(e) = sum of score(p) over p < e, S(0) = 0.
+ *   covered_s   number of covered bases
+ *   head_len_s  the smallest e in [0, n] at which S(e) is largest (0 when the maximum is 0): the tract at the 5' end
+ *   head_cov_s  covered bases among the first head_len_s
+ *   tail_len_s  n - b, b the largest position in [0, n] at which S(b) is smallest: the best-scoring suffix, the 3' tract
+ *   tail_cov_s  covered bases among the last tail_len_s
+ * On ties the shorter tract wins at both ends; n < k gives zeros; a self-reverse-complementary class reports the same numbers
+ * on both strands.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t covered_fwd, head_len_fwd, head_cov_fwd, tail_len_fwd, tail_cov_fwd;
+    uint32_t covered_rev, head_len_rev, head_cov_rev, tail_len_rev, tail_cov_rev;
+} trew_hip_tract;
+/* Like trew_hip_annotate (batch shapes, staging, asynchronous on the slot's stream, independent of the scan and of the
+ * annotation), with a result buffer of its own that the slot's first call allocates.  One kernel, a wave per read, for every
+ * read length. */
+int trew_hip_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty);
+/* Waits for the slot and copies the records of its last trew_hip_tracts; arguments as trew_hip_annotate_results. */
+int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tract *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same records on the host, base by base from the definition, over packed planes. */
+int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                     const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_tract *out);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

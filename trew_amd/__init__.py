@@ -26,4 +26,5 @@ from .capi import (  # noqa: F401
     annotate,
     k_mer_check,
     pack_reads,
+    tracts,
 )

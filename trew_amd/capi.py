@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_collect_device", "trew_hip_add_rows_device", "trew_hip_merge", "trew_hip_table_pressure",
     "trew_hip_add_gathered_device", "trew_hip_collect_slice_device", "trew_hip_debug_counters", "trew_hip_debug_worklist", "trew_hip_submit_ascii", "trew_hip_pack_ascii",
     "trew_motif_parse", "trew_hip_annotate", "trew_hip_annotate_results", "trew_annotate_host",
+    "trew_hip_tracts", "trew_hip_tracts_results", "trew_tracts_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target")
 
@@ -88,6 +89,15 @@ class Annot(C.Structure):
 ANNOT_DTYPE = np.dtype([(name, "<u4") for name, _ in Annot._fields_])
 assert ANNOT_DTYPE.itemsize == C.sizeof(Annot)
 MAX_MOTIFS = 8
+
+
+class Tract(C.Structure):
+    _fields_ = [(name + sfx, C.c_uint32) for sfx in ("_fwd", "_rev")
+                for name in ("covered", "head_len", "head_cov", "tail_len", "tail_cov")]
+
+
+TRACT_DTYPE = np.dtype([(name, "<u4") for name, _ in Tract._fields_])
+assert TRACT_DTYPE.itemsize == C.sizeof(Tract) == 40
 
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
@@ -149,6 +159,9 @@ def load():
     lib.trew_hip_annotate.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32]
     lib.trew_hip_annotate_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_float)]
     lib.trew_annotate_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, vp]
+    lib.trew_hip_tracts.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, i32]
+    lib.trew_hip_tracts_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_float)]
+    lib.trew_tracts_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, i32, vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -228,6 +241,24 @@ def annotate_host(reads_or_packed, motifs):
     out = np.zeros((len(offsets), max(nm, 1)), dtype=ANNOT_DTYPE)
     if lib.trew_annotate_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, out.ctypes.data) != 0:
         raise TrewHipError("trew_annotate_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out[:, :nm]
+
+
+def tracts_host(reads_or_packed, motifs, penalty=3):
+    """trew_tracts_host: the error-tolerant terminal tracts computed on the host, base by base from the definition.
+    reads_or_packed as for annotate_host.  Returns TRACT_DTYPE records of shape (n_reads, n_motifs)."""
+    lib = load()
+    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
+        words, offsets, lengths = reads_or_packed
+    else:
+        words, offsets, lengths = pack_reads(reads_or_packed)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    arr, nm = _motif_array(motifs)
+    out = np.zeros((len(offsets), max(nm, 1)), dtype=TRACT_DTYPE)
+    if lib.trew_tracts_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
+        raise TrewHipError("trew_tracts_host failed: %s" % lib.trew_hip_last_error(None).decode())
     return out[:, :nm]
 
 
@@ -386,6 +417,27 @@ class TrewHip:
                   "trew_hip_annotate_results")
         if int(n.value) != n_reads * nm:
             raise TrewHipError("trew_hip_annotate_results: %d records, expected %d" % (n.value, n_reads * nm))
+        return (out, ms.value) if want_ms else out
+
+    def tracts(self, batch, motifs, penalty=3, slot=0):
+        """Queue the error-tolerant terminal tracts of every read of `batch` for `motifs` (texts or Motif, at most 8) on the
+        slot's stream."""
+        arr, nm = _motif_array(motifs)
+        self._keep[("tract", slot)] = (batch, arr)
+        self._tract_shape = getattr(self, "_tract_shape", {})
+        self._tract_shape[slot] = (int(batch.n_reads), nm)
+        self._chk(self.lib.trew_hip_tracts(self.ctx, C.byref(batch), slot, arr, nm, int(penalty)), "trew_hip_tracts")
+
+    def tracts_results(self, slot=0, want_ms=False):
+        """Records of the slot's last tracts: TRACT_DTYPE array of shape (n_reads, n_motifs) [, kernel ms]."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm = getattr(self, "_tract_shape", {}).get(slot, (0, 1))
+        out = np.zeros((n_reads, nm), dtype=TRACT_DTYPE)
+        self._chk(self.lib.trew_hip_tracts_results(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), C.byref(ms) if want_ms else None),
+                  "trew_hip_tracts_results")
+        if int(n.value) != n_reads * nm:
+            raise TrewHipError("trew_hip_tracts_results: %d records, expected %d" % (n.value, n_reads * nm))
         return (out, ms.value) if want_ms else out
 
     def submit_reads(self, reads, slot=0):
@@ -564,3 +616,13 @@ def annotate(reads, motifs, device=0):
                  max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
         t.annotate(t.host_batch(words, offsets, lengths), motifs)
         return t.annotate_results()
+
+
+def tracts(reads, motifs, penalty=3, device=0):
+    """Error-tolerant terminal motif tracts on the GPU: for every read (bytes / str) and motif (text) the covered bases and
+    the head (5') and tail (3') tract on each strand, as TRACT_DTYPE records of shape (n_reads, n_motifs)."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        t.tracts(t.host_batch(words, offsets, lengths), motifs, penalty)
+        return t.tracts_results()

@@ -1189,8 +1189,8 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
 // ---------------------------------------------------------------- trew annotate
 // Per-read motif annotation of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, runs trew_hip_annotate on a slot of its own
-// and keeps the records that reach MIN_TRACT.  The ordinal of a read is the index of its sequence line among the file's
-// sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
+// (for `trew tracts`: trew_hip_tracts; AnnotRequest::penalty picks the record type) and keeps the records that reach
+// MIN_TRACT.  The ordinal of a read is the index of its sequence line among the file's sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
 // rows come out the same for any number of workers once they are sorted.
 struct Annotator {
     std::vector<trew_hip_ctx *> ctx;
@@ -1198,6 +1198,7 @@ struct Annotator {
         int dev_index = 0, slot = 0;
         uint32_t *h_buf = nullptr;  // pinned: [offsets n][lengths n][words]
         std::vector<trew_hip_annot> recs;
+        std::vector<trew_hip_tract> trecs;  // trew tracts
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1286,23 +1287,45 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             b.offsets = offsets;
             b.lengths = lengths;
             b.n_reads = n;
-            if (trew_hip_annotate(c, &b, w->slot, rq->motifs, nm)) hip_die(c, "trew_hip_annotate");
-            if (w->recs.size() < n * (size_t) nm) w->recs.resize(n * (size_t) nm);
-            uint64_t got = 0;
-            if (trew_hip_annotate_results(c, w->slot, w->recs.data(), n * (uint64_t) nm, &got, nullptr)) hip_die(c, "trew_hip_annotate_results");
             AnnotFileResult &p = w->part;
             p.reads += n;
-            for (uint64_t r = 0; r < n; r++) {
-                p.bases += lengths[r];
-                for (int m = 0; m < nm; m++) {
-                    const trew_hip_annot &x = w->recs[r * (size_t) nm + (size_t) m];
-                    const uint32_t longest = std::max(x.tract_len_fwd, x.tract_len_rev);
-                    p.windows_fwd[m] += x.windows_fwd;
-                    p.windows_rev[m] += x.windows_rev;
-                    p.longest[m] = std::max(p.longest[m], longest);
-                    if (longest >= rq->min_tract[m]) {
-                        p.reported[m]++;
-                        p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, x});
+            if (rq->penalty) {  // trew tracts
+                if (trew_hip_tracts(c, &b, w->slot, rq->motifs, nm, rq->penalty)) hip_die(c, "trew_hip_tracts");
+                if (w->trecs.size() < n * (size_t) nm) w->trecs.resize(n * (size_t) nm);
+                uint64_t got = 0;
+                if (trew_hip_tracts_results(c, w->slot, w->trecs.data(), n * (uint64_t) nm, &got, nullptr)) hip_die(c, "trew_hip_tracts_results");
+                for (uint64_t r = 0; r < n; r++) {
+                    p.bases += lengths[r];
+                    for (int m = 0; m < nm; m++) {
+                        const trew_hip_tract &x = w->trecs[r * (size_t) nm + (size_t) m];
+                        const uint32_t head = std::max(x.head_len_fwd, x.head_len_rev), tail = std::max(x.tail_len_fwd, x.tail_len_rev);
+                        p.windows_fwd[m] += x.covered_fwd;
+                        p.windows_rev[m] += x.covered_rev;
+                        p.longest[m] = std::max(p.longest[m], head);
+                        p.longest_tail[m] = std::max(p.longest_tail[m], tail);
+                        if (std::max(head, tail) >= rq->min_tract[m]) {
+                            p.reported[m]++;
+                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, trew_hip_annot(), x});
+                        }
+                    }
+                }
+            } else {
+                if (trew_hip_annotate(c, &b, w->slot, rq->motifs, nm)) hip_die(c, "trew_hip_annotate");
+                if (w->recs.size() < n * (size_t) nm) w->recs.resize(n * (size_t) nm);
+                uint64_t got = 0;
+                if (trew_hip_annotate_results(c, w->slot, w->recs.data(), n * (uint64_t) nm, &got, nullptr)) hip_die(c, "trew_hip_annotate_results");
+                for (uint64_t r = 0; r < n; r++) {
+                    p.bases += lengths[r];
+                    for (int m = 0; m < nm; m++) {
+                        const trew_hip_annot &x = w->recs[r * (size_t) nm + (size_t) m];
+                        const uint32_t longest = std::max(x.tract_len_fwd, x.tract_len_rev);
+                        p.windows_fwd[m] += x.windows_fwd;
+                        p.windows_rev[m] += x.windows_rev;
+                        p.longest[m] = std::max(p.longest[m], longest);
+                        if (longest >= rq->min_tract[m]) {
+                            p.reported[m]++;
+                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, x, trew_hip_tract()});
+                        }
                     }
                 }
             }
@@ -1336,14 +1359,15 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
             out.windows_rev[m] += w.part.windows_rev[m];
             out.reported[m] += w.part.reported[m];
             out.longest[m] = std::max(out.longest[m], w.part.longest[m]);
+            out.longest_tail[m] = std::max(out.longest_tail[m], w.part.longest_tail[m]);
         }
         out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
     }
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + annotate; serial reader, %d worker(s))\n", file_name,
-                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, (int) a->workers.size());
+        fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + %s; serial reader, %d worker(s))\n", file_name,
+                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, rq.penalty ? "tracts" : "annotate", (int) a->workers.size());
     }
     return out;
 }

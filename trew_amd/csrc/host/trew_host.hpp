@@ -96,24 +96,30 @@ struct AnnotRequest {
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];  // a (read, motif) is reported when its longer tract has at least this many bases
     int n_motifs = 0;
+    int penalty = 0;  // 0: annotate (trew_hip_annot records); 1 .. 64: tracts (trew_hip_tract records) at this penalty
 };
 struct AnnotRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
     uint32_t length;  // bases
     int motif;        // index in command-line order
-    trew_hip_annot a;
+    trew_hip_annot a;  // annotate
+    trew_hip_tract t;  // tracts
 };
 struct AnnotFileResult {
     std::vector<AnnotRow> rows;  // sorted by read, then motif
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {};
+    // tracts: windows_fwd / windows_rev hold the covered bases of each strand, longest the longest head tract
+    uint32_t longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
 };
 struct Annotator;  // device contexts and one slot per worker
 Annotator *annotator_create(const Config &cfg);
 void annotator_destroy(Annotator *a);
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq);
 int annotate_main(int argc, char **argv);  // the subcommand: arguments, output
+// ---- trew tracts MOTIF[,MOTIF...] FASTQ...: error-tolerant terminal tracts (host/tracts.cpp); the same Annotator path ----
+int tracts_main(int argc, char **argv);
 
 struct RunStats {
     uint64_t reads = 0, bases = 0;

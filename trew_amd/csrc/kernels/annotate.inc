@@ -184,41 +184,49 @@ __device__ __forceinline__ AnnotRun annot_word_run(u32 m) {
 // longer run first, earlier start on a tie: one u64 whose maximum is the answer
 __device__ __forceinline__ u64 annot_key(u32 len, u32 start) { return ((u64) len << 32) | (u64) (0xffffffffu - start); }
 
+// match word of 32-base word w of a read, one strand of one motif: bit i = window 32 w + i is a rotation of the target.  The
+// next word is the look-ahead (k - 1 <= 31 bases); a word at or past the end of the read has no match.  Shared with
+// kernels/tracts.inc, so the k-phase match exists once.
+__device__ __forceinline__ u32 annot_wave_match(const ReadRef &rd, const AnnotMotifDev *mm, int strand, u32 k, u32 w) {
+    const u32 step = 32u % k;
+    u32 c0 = 0, c1 = 0, c2 = 0xffffffffu, n0 = 0, n1 = 0, n2 = 0xffffffffu;
+    if (w < rd.nw) {
+        c0 = rd.w[3ull * w + 0];
+        c1 = rd.w[3ull * w + 1];
+        c2 = rd.w[3ull * w + 2];
+        const long long left = (long long) rd.len - 32ll * (long long) w;  // >= 1
+        if (left < 32) c2 |= 0xffffffffu << (u32) left;
+    }
+    if (w + 1u < rd.nw) {
+        n0 = rd.w[3ull * (w + 1u) + 0];
+        n1 = rd.w[3ull * (w + 1u) + 1];
+        n2 = rd.w[3ull * (w + 1u) + 2];
+        const long long left = (long long) rd.len - 32ll * (long long) (w + 1u);
+        if (left < 32) n2 |= 0xffffffffu << (u32) left;
+    }
+    u32 m = 0;
+    for (u32 q = 0; q < k; q++) {
+        u32 q1 = q + step;
+        q1 = q1 >= k ? q1 - k : q1;
+        const u32 z0 = ~((c0 ^ mm->plo[strand][q]) | (c1 ^ mm->phi[strand][q]) | c2);
+        const u32 z1 = ~((n0 ^ mm->plo[strand][q1]) | (n1 ^ mm->phi[strand][q1]) | n2);
+        u64 z = ((u64) z1 << 32) | z0;  // window i <= 31 needs bits i .. i + k - 1 <= 62
+        u32 L = 1;
+        for (; 2 * L <= k; L *= 2) z &= z >> L;
+        if (L < k) z &= z >> (k - L);
+        m |= (u32) z;
+    }
+    return m;
+}
+
 __device__ __forceinline__ void annot_wave_strand(const ReadRef &rd, const AnnotMotifDev *mm, int strand, u32 k, u32 &windows, u32 &start, u32 &len) {
     const u32 lane = lane_id();
-    const u32 step = 32u % k;
     u32 wsum = 0;
     u64 best = 0;
     u32 carry_len = 0, carry_start = 0;  // wave-uniform: the run of ones that ends with the previous iteration's last bit
     for (u32 t0 = 0; t0 < rd.nw; t0 += 64u) {
         const u32 w = t0 + lane;
-        u32 c0 = 0, c1 = 0, c2 = 0xffffffffu, n0 = 0, n1 = 0, n2 = 0xffffffffu;
-        if (w < rd.nw) {
-            c0 = rd.w[3ull * w + 0];
-            c1 = rd.w[3ull * w + 1];
-            c2 = rd.w[3ull * w + 2];
-            const long long left = (long long) rd.len - 32ll * (long long) w;  // >= 1
-            if (left < 32) c2 |= 0xffffffffu << (u32) left;
-        }
-        if (w + 1u < rd.nw) {
-            n0 = rd.w[3ull * (w + 1u) + 0];
-            n1 = rd.w[3ull * (w + 1u) + 1];
-            n2 = rd.w[3ull * (w + 1u) + 2];
-            const long long left = (long long) rd.len - 32ll * (long long) (w + 1u);
-            if (left < 32) n2 |= 0xffffffffu << (u32) left;
-        }
-        u32 m = 0;
-        for (u32 q = 0; q < k; q++) {
-            u32 q1 = q + step;
-            q1 = q1 >= k ? q1 - k : q1;
-            const u32 z0 = ~((c0 ^ mm->plo[strand][q]) | (c1 ^ mm->phi[strand][q]) | c2);
-            const u32 z1 = ~((n0 ^ mm->plo[strand][q1]) | (n1 ^ mm->phi[strand][q1]) | n2);
-            u64 z = ((u64) z1 << 32) | z0;  // window i <= 31 needs bits i .. i + k - 1 <= 62
-            u32 L = 1;
-            for (; 2 * L <= k; L *= 2) z &= z >> L;
-            if (L < k) z &= z >> (k - L);
-            m |= (u32) z;
-        }
+        const u32 m = annot_wave_match(rd, mm, strand, k, w);
         wsum = bcnt_acc(m, wsum);
         // this lane's word: ones at its low end, ones at its high end, the best run inside
         const bool full = m == 0xffffffffu;

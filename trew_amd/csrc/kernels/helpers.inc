@@ -75,6 +75,18 @@ __device__ __forceinline__ u32 wave_sum_u32(u32 v) {
     return (u32) __builtin_amdgcn_readlane((int) v, 63);
 }
 
+// inclusive prefix sum of a u32 across the wave (the same steps as wave_sum_u32, whose lane 63 is the last prefix): lane l
+// gets v[0] + ... + v[l]; two's complement, so signed values sum as well
+__device__ __forceinline__ u32 wave_scan_u32(u32 v) {
+    v += (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);
+    v += (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);
+    v += (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);
+    v += (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);
+    v += (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+    v += (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
 struct ReadRef {
     const u32 *w;  // first triple
     u32 len;       // bases

@@ -54,6 +54,12 @@ struct Slot {
     hipEvent_t ev_annot[2] = {nullptr, nullptr};
     bool annot_valid = false, annot_timed = false;  // an annotate was queued / its kernel was launched between the events
     u64 annot_n = 0;                    // records of the last annotate
+    // trew_hip_tracts: a result buffer of its own, created by the slot's first tracts call; the pattern tables above are shared
+    trew_hip_tract *d_tract = nullptr;
+    u64 tract_cap = 0;
+    hipEvent_t ev_tract[2] = {nullptr, nullptr};
+    bool tract_valid = false, tract_timed = false;
+    u64 tract_n = 0;
 };
 
 thread_local std::string g_init_error;  // trew_hip_init failures before a context exists (read back on the same thread)
@@ -368,6 +374,9 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         if (s.d_motifs) (void) hipFree(s.d_motifs);
         if (s.h_motifs) (void) hipHostFree(s.h_motifs);
         for (auto e : s.ev_annot)
+            if (e) (void) hipEventDestroy(e);
+        if (s.d_tract) (void) hipFree(s.d_tract);
+        for (auto e : s.ev_tract)
             if (e) (void) hipEventDestroy(e);
         if (s.ev_tail) (void) hipEventDestroy(s.ev_tail);
         if (s.ev_copied) (void) hipEventDestroy(s.ev_copied);
@@ -1323,6 +1332,23 @@ extern "C" int trew_annotate_host(const uint32_t *words, const uint32_t *offsets
     return 0;
 }
 
+// The pattern tables of a slot, shared by trew_hip_annotate and trew_hip_tracts: created by the first call that needs them
+// (each piece on its own, so that a failed call can simply be repeated); they travel on the slot's stream in front of the
+// kernel, and only when they changed.
+static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs, int n_motifs) {
+    if (!s.d_motifs) HIPCHK(ctx, hipMalloc((void **) &s.d_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs));
+    if (!s.h_motifs) HIPCHK(ctx, hipHostMalloc((void **) &s.h_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs, hipHostMallocDefault));
+    AnnotMotifDev tab[kAnnotMaxMotifs];
+    for (int m = 0; m < n_motifs; m++) fill_motif(motifs[m], &tab[m]);
+    if (s.annot_motifs_staged < n_motifs || memcmp(tab, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs) != 0) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // an earlier copy may still be reading the staging buffer
+        memcpy(s.h_motifs, tab, sizeof(AnnotMotifDev) * (size_t) n_motifs);
+        HIPCHK(ctx, hipMemcpyAsync(s.d_motifs, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs, hipMemcpyHostToDevice, s.stream));
+        s.annot_motifs_staged = n_motifs;
+    }
+    return 0;
+}
+
 extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
     if (!ctx || !batch) return -1;
     if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
@@ -1343,20 +1369,9 @@ extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch,
     }
     DevBatch db;
     if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
-    // first annotate on this slot (each piece on its own, so that a failed call can simply be repeated)
-    if (!s.d_motifs) HIPCHK(ctx, hipMalloc((void **) &s.d_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs));
-    if (!s.h_motifs) HIPCHK(ctx, hipHostMalloc((void **) &s.h_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs, hipHostMallocDefault));
+    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
     for (auto &e : s.ev_annot)
         if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    // the pattern tables travel on the slot's stream in front of the kernel, and only when they changed
-    AnnotMotifDev tab[kAnnotMaxMotifs];
-    for (int m = 0; m < n_motifs; m++) fill_motif(motifs[m], &tab[m]);
-    if (s.annot_motifs_staged < n_motifs || memcmp(tab, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs) != 0) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // an earlier copy may still be reading the staging buffer
-        memcpy(s.h_motifs, tab, sizeof(AnnotMotifDev) * (size_t) n_motifs);
-        HIPCHK(ctx, hipMemcpyAsync(s.d_motifs, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs, hipMemcpyHostToDevice, s.stream));
-        s.annot_motifs_staged = n_motifs;
-    }
     const u64 need = db.n_reads * (u64) n_motifs;
     if (need > s.annot_cap) {
         HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
@@ -1389,6 +1404,132 @@ extern "C" int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_a
     if (ms_kernel) {
         *ms_kernel = 0.0f;
         if (s.annot_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_annot[0], s.ev_annot[1]));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- per-read error-tolerant terminal tracts
+extern "C" int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_tract *out) {
+    const char *e = motifs_error(motifs, n_motifs);
+    if (!e && (penalty < 1 || penalty > 64)) e = "penalty must be in [1, 64]";
+    if (!e && n_reads && (!words || !offsets || !lengths || !out)) e = "trew_tracts_host: null argument";
+    if (e) {
+        g_thread_error = g_init_error = e;
+        return -1;
+    }
+    std::vector<unsigned char> cov;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        for (int m = 0; m < n_motifs; m++) {
+            const int k = motifs[m].k;
+            const u64 mask = motif_mask(k);
+            u32 res[2][5];
+            for (int s = 0; s < 2; s++) {
+                u64 rot[32], t = s ? motif_revcomp(motifs[m].word, k) : motifs[m].word;
+                for (int i = 0; i < k; i++) {
+                    rot[i] = t;
+                    t = ((t << 2) | (t >> (2 * (k - 1)))) & mask;
+                }
+                // cov[p]: some matching window contains base p
+                cov.assign((size_t) n, 0);
+                u64 word = 0;
+                u32 clean = 0;  // bases since the last one with its nmask bit set
+                for (u32 i = 0; i < n; i++) {
+                    const u32 j = i >> 5, b = i & 31u;
+                    const u32 c = ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
+                    clean = ((w[3 * j + 2] >> b) & 1u) ? 0 : clean + 1;
+                    word = ((word << 2) | c) & mask;
+                    if (clean < (u32) k) continue;  // also: fewer than k bases so far
+                    bool hit = false;
+                    for (int x = 0; x < k && !hit; x++) hit = word == rot[x];
+                    if (hit)
+                        for (u32 p = i + 1 - (u32) k; p <= i; p++) cov[p] = 1;
+                }
+                // S(e), e = 0 .. n: the earliest largest value and the latest smallest value; covered counts alongside
+                long long S = 0, hi = 0, lo = 0;
+                u32 e_hi = 0, e_lo = 0, c = 0, c_hi = 0, c_lo = 0;
+                for (u32 p = 0; p < n; p++) {
+                    S += cov[p] ? 1 : -(long long) penalty;
+                    c += cov[p];
+                    if (S > hi) {
+                        hi = S;
+                        e_hi = p + 1;
+                        c_hi = c;
+                    }
+                    if (S <= lo) {
+                        lo = S;
+                        e_lo = p + 1;
+                        c_lo = c;
+                    }
+                }
+                res[s][0] = c;
+                res[s][1] = e_hi;
+                res[s][2] = c_hi;
+                res[s][3] = n - e_lo;
+                res[s][4] = c - c_lo;
+            }
+            trew_hip_tract &o = out[r * (u64) n_motifs + (u64) m];
+            o.covered_fwd = res[0][0];
+            o.head_len_fwd = res[0][1];
+            o.head_cov_fwd = res[0][2];
+            o.tail_len_fwd = res[0][3];
+            o.tail_cov_fwd = res[0][4];
+            o.covered_rev = res[1][0];
+            o.head_len_rev = res[1][1];
+            o.head_cov_rev = res[1][2];
+            o.tail_len_rev = res[1][3];
+            o.tail_cov_rev = res[1][4];
+        }
+    }
+    return 0;
+}
+
+extern "C" int trew_hip_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty) {
+    if (!ctx || !batch) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
+    if (penalty < 1 || penalty > 64) return fail(ctx, "penalty must be in [1, 64]");
+    HIPCHK(ctx, hipSetDevice(ctx->p.device));
+    Slot &s = ctx->slots[(size_t) slot];
+    DevBatch db;
+    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
+    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
+    for (auto &e : s.ev_tract)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    const u64 need = db.n_reads * (u64) n_motifs;
+    if (need > s.tract_cap) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
+        if (s.d_tract) HIPCHK(ctx, hipFree(s.d_tract));
+        s.d_tract = nullptr;
+        s.tract_cap = 0;
+        HIPCHK(ctx, hipMalloc((void **) &s.d_tract, need * sizeof(trew_hip_tract)));
+        s.tract_cap = need;
+    }
+    s.tract_valid = true;
+    s.tract_timed = false;
+    s.tract_n = need;
+    if (need == 0) return 0;
+    HIPCHK(ctx, hipEventRecord(s.ev_tract[0], s.stream));
+    HIPCHK(ctx, launch_tracts(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, s.d_tract));
+    HIPCHK(ctx, hipEventRecord(s.ev_tract[1], s.stream));
+    s.tract_timed = true;
+    return 0;
+}
+
+extern "C" int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tract *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    if (!ctx) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    Slot &s = ctx->slots[(size_t) slot];
+    if (!s.tract_valid) return fail(ctx, "no trew_hip_tracts on this slot yet");
+    if (int rc = trew_hip_wait(ctx, slot)) return rc;
+    if (n) *n = s.tract_n;
+    const u64 take = std::min<u64>(s.tract_n, cap);
+    if (out && take) HIPCHK(ctx, hipMemcpy(out, s.d_tract, take * sizeof(trew_hip_tract), hipMemcpyDeviceToHost));
+    if (ms_kernel) {
+        *ms_kernel = 0.0f;
+        if (s.tract_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_tract[0], s.ev_tract[1]));
     }
     return 0;
 }

@@ -37,6 +37,7 @@
 //   exact_kernel.inc   exact_kernel<NW, MODE, WT>
 //   table_kernels.inc  add-rows / compaction kernels      synth_kernels.inc  workload generators
 //   annotate.inc       annotate_lane_kernel<NW> / annotate_wave_kernel (per-read motif tracts, beside the scan)
+//   tracts.inc         tracts_wave_kernel (per-read error-tolerant terminal tracts; shares annotate.inc's match word)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -68,6 +69,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/table_kernels.inc"
 #include "kernels/synth_kernels.inc"
 #include "kernels/annotate.inc"
+#include "kernels/tracts.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -316,6 +318,14 @@ hipError_t launch_annotate(hipStream_t st, u32 n_cu, const DevBatch &B, const An
         else
             hipLaunchKernelGGL(annotate_lane_kernel<8>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
     }
+    return hipGetLastError();
+}
+
+// Per-read terminal tracts: one kernel, a wave per read, for every read length (same grid as the annotation's wave kernel).
+hipError_t launch_tracts(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_tract *d_out) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(tracts_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, (u32 *) d_out);
     return hipGetLastError();
 }
 

@@ -30,6 +30,8 @@ hipError_t launch_slice_finish(hipStream_t st, trew_hip_row *d_slice, u64 slice_
 // trew_hip_annotate: general = the wave-per-read kernel, else the lane-per-read one (max_len <= 256)
 hipError_t launch_annotate(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, u32 max_len, bool general,
                            trew_hip_annot *d_out);
+// trew_hip_tracts: the wave-per-read kernel of kernels/tracts.inc, whatever the read lengths
+hipError_t launch_tracts(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_tract *d_out);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
