@@ -29,7 +29,9 @@ extern "C" {
 #endif
 
 /* Still 4 with the annotation entry points (trew_motif_parse, trew_hip_annotate, trew_hip_annotate_results,
- * trew_annotate_host) and the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host): they are purely additive -- no existing structure, enumerator or function changed. */
+ * trew_annotate_host), the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host) and the interval
+ * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host): they are purely additive -- no existing
+ * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
 /* scan modes: which per-read driver of the reference is reproduced */
@@ -328,6 +330,41 @@ int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tract *out, ui
 /* The same records on the host, base by base from the definition, over packed planes. */
 int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                      const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_tract *out);
+
+/* ---- gap-tolerant motif intervals anywhere in a read (where in this read does the repeat lie, and how many tracts are there?) ----
+ * cov_s[p] as above.  Every motif m has a rule {max_gap, min_len}: max_gap is any u32, min_len >= 1.  With the covered
+ * positions of strand s p_1 < p_2 < ..., an interval is a maximal group of consecutive covered positions in which every two
+ * neighbours satisfy p_(j+1) - p_j - 1 <= max_gap.  Its record:
+ *   start    its first covered position (0-based)
+ *   end      its last covered position + 1
+ *   covered  the number of covered bases in [start, end)
+ * An interval is kept when end - start >= min_len.  n < k or no covered base gives no interval; start and end - 1 are always
+ * covered; the intervals of one (read, motif, strand) are disjoint and more than max_gap uncovered bases apart; a
+ * self-reverse-complementary class yields the same intervals on both strands, reported under both.  strand: 0 = the motif,
+ * 1 = its reverse complement.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t max_gap, min_len;
+} trew_hip_interval_rule; /* one per motif */
+typedef struct {
+    uint32_t read, motif, strand, start, end, covered;
+} trew_hip_interval;
+/* Like trew_hip_tracts (batch shapes, staging, asynchronous on the slot's stream, a context of any mode, independent of the
+ * scan, the annotation and the tracts), with buffers of its own that the slot's first call allocates: a log of max_intervals
+ * records (>= 1; the log grows when a call asks for more) to which the kernel appends every kept interval, and one count per
+ * (read, motif, strand).  A batch holds at most 2^32 - 1 reads.  One kernel, a wave per read, for every read length. */
+int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, const trew_hip_interval_rule *rules,
+                       int n_motifs, uint64_t max_intervals);
+/* Waits for the slot.  *n = the number of kept intervals found, also when that exceeds max_intervals or cap.  Copies
+ * min(cap, *n, max_intervals) records sorted by (read, motif, strand, start), so the output does not depend on device
+ * scheduling.  counts (n_reads * n_motifs * 2 values, [read][motif][strand]; may be NULL) = the kept intervals of every key,
+ * whether or not they fitted in the log.  When *n > max_intervals the records are an unspecified subset while counts and *n
+ * are still exact: repeat trew_hip_intervals with max_intervals >= *n -- one retry always suffices.  That case is no error
+ * (the call returns 0), like trew_hip_collect with too small a buffer. */
+int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel);
+/* The same on the host, base by base from the definition, over packed planes: *n = intervals found, min(cap, *n) records
+ * (the first ones of the sorted order), counts as above (may be NULL). */
+int trew_intervals_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                        const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_add_gathered_device", "trew_hip_collect_slice_device", "trew_hip_debug_counters", "trew_hip_debug_worklist", "trew_hip_submit_ascii", "trew_hip_pack_ascii",
     "trew_motif_parse", "trew_hip_annotate", "trew_hip_annotate_results", "trew_annotate_host",
     "trew_hip_tracts", "trew_hip_tracts_results", "trew_tracts_host",
+    "trew_hip_intervals", "trew_hip_intervals_results", "trew_intervals_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target")
 
@@ -98,6 +99,18 @@ class Tract(C.Structure):
 
 TRACT_DTYPE = np.dtype([(name, "<u4") for name, _ in Tract._fields_])
 assert TRACT_DTYPE.itemsize == C.sizeof(Tract) == 40
+
+
+class IntervalRule(C.Structure):
+    _fields_ = [("max_gap", C.c_uint32), ("min_len", C.c_uint32)]
+
+
+class Interval(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("read", "motif", "strand", "start", "end", "covered")]
+
+
+INTERVAL_DTYPE = np.dtype([(name, "<u4") for name, _ in Interval._fields_])
+assert INTERVAL_DTYPE.itemsize == C.sizeof(Interval) == 24 and C.sizeof(IntervalRule) == 8
 
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
@@ -162,6 +175,9 @@ def load():
     lib.trew_hip_tracts.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, i32]
     lib.trew_hip_tracts_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_float)]
     lib.trew_tracts_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, i32, vp]
+    lib.trew_hip_intervals.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), C.POINTER(IntervalRule), i32, u64]
+    lib.trew_hip_intervals_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), vp, C.POINTER(C.c_float)]
+    lib.trew_intervals_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), C.POINTER(IntervalRule), i32, vp, u64, C.POINTER(u64), vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -260,6 +276,56 @@ def tracts_host(reads_or_packed, motifs, penalty=3):
     if lib.trew_tracts_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
         raise TrewHipError("trew_tracts_host failed: %s" % lib.trew_hip_last_error(None).decode())
     return out[:, :nm]
+
+
+def _rule_array(arr, nm, max_gap, min_len):
+    """(IntervalRule * 8): max_gap / min_len are an int, a per-motif list or None (the defaults 3 k and 4 k of each motif)."""
+    def per_motif(v, name, factor):
+        if v is None:
+            return [factor * int(arr[m].k) for m in range(nm)]
+        if isinstance(v, (int, np.integer)):
+            return [int(v)] * nm
+        v = [int(x) for x in v]
+        if len(v) != nm:
+            raise TrewHipError("%s: %d values for %d motifs" % (name, len(v), nm))
+        return v
+    gaps, lens = per_motif(max_gap, "max_gap", 3), per_motif(min_len, "min_len", 4)
+    rules = (IntervalRule * MAX_MOTIFS)()
+    for m in range(min(nm, MAX_MOTIFS)):
+        if not (0 <= gaps[m] < 1 << 32 and 0 <= lens[m] < 1 << 32):
+            raise TrewHipError("max_gap and min_len must fit in 32 bits")
+        rules[m] = IntervalRule(gaps[m], lens[m])
+    return rules
+
+
+def intervals_host(reads_or_packed, motifs, max_gap=None, min_len=None, cap=None):
+    """trew_intervals_host: the gap-tolerant motif intervals computed on the host, base by base from the definition.
+    reads_or_packed as for annotate_host; max_gap / min_len as for TrewHip.intervals.  Returns (INTERVAL_DTYPE records sorted
+    by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2), found); with `cap` at most that many records."""
+    lib = load()
+    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
+        words, offsets, lengths = reads_or_packed
+    else:
+        words, offsets, lengths = pack_reads(reads_or_packed)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    arr, nm = _motif_array(motifs)
+    rules = _rule_array(arr, min(max(nm, 0), MAX_MOTIFS), max_gap, min_len)
+    counts = np.zeros((len(offsets), max(nm, 1), 2), dtype=np.uint32)
+    n = C.c_uint64(0)
+
+    def call(out):
+        if lib.trew_intervals_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, rules, nm,
+                                   out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
+            raise TrewHipError("trew_intervals_host failed: %s" % lib.trew_hip_last_error(None).decode())
+
+    out = np.zeros(0 if cap is None else int(cap), dtype=INTERVAL_DTYPE)
+    call(out)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=INTERVAL_DTYPE)
+        call(out)
+    return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
 
 
 def synth_short_ascii(seed, first_read, n_reads, read_len):
@@ -439,6 +505,36 @@ class TrewHip:
         if int(n.value) != n_reads * nm:
             raise TrewHipError("trew_hip_tracts_results: %d records, expected %d" % (n.value, n_reads * nm))
         return (out, ms.value) if want_ms else out
+
+    def intervals(self, batch, motifs, max_gap=None, min_len=None, max_intervals=None, slot=0):
+        """Queue the gap-tolerant motif intervals of every read of `batch` for `motifs` (texts or Motif, at most 8) on the
+        slot's stream.  max_gap / min_len: an int, a per-motif list, or None for the defaults 3 k and 4 k of each motif;
+        max_intervals: the capacity of the log for this call (default: the batch's read count, at least 1)."""
+        arr, nm = _motif_array(motifs)
+        rules = _rule_array(arr, min(max(nm, 0), MAX_MOTIFS), max_gap, min_len)
+        if max_intervals is None:
+            max_intervals = max(int(batch.n_reads), 1)
+        self._keep[("ival", slot)] = (batch, arr, rules)
+        self._ival_shape = getattr(self, "_ival_shape", {})
+        self._ival_shape[slot] = (int(batch.n_reads), nm, int(max_intervals))
+        self._chk(self.lib.trew_hip_intervals(self.ctx, C.byref(batch), slot, arr, rules, nm, int(max_intervals)), "trew_hip_intervals")
+
+    def intervals_results(self, slot=0, want_ms=False):
+        """Results of the slot's last intervals: (INTERVAL_DTYPE records sorted by (read, motif, strand, start), counts of
+        shape (n_reads, n_motifs, 2), found [, kernel ms]).  found > max_intervals: the records are a subset (as many as the
+        log held), counts and found are exact; repeat the call with max_intervals >= found."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm, cap = getattr(self, "_ival_shape", {}).get(slot, (0, 1, 0))
+        counts = np.zeros((n_reads, nm, 2), dtype=np.uint32)
+        # the log is read once, into a buffer of its capacity or of the sum of the counts, whichever is smaller
+        self._chk(self.lib.trew_hip_intervals_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
+                  "trew_hip_intervals_results")
+        found = int(n.value)
+        out = np.zeros(min(found, cap), dtype=INTERVAL_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_intervals_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_intervals_results")
+        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
 
     def submit_reads(self, reads, slot=0):
         b = self.host_batch(*pack_reads(reads))
@@ -626,3 +722,22 @@ def tracts(reads, motifs, penalty=3, device=0):
                  max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
         t.tracts(t.host_batch(words, offsets, lengths), motifs, penalty)
         return t.tracts_results()
+
+
+def intervals(reads, motifs, max_gap=None, min_len=None, device=0, max_intervals=None):
+    """Gap-tolerant motif intervals on the GPU: for every read (bytes / str) and motif (text) the intervals of covered bases
+    whose gaps are at most max_gap bases and whose length is at least min_len (defaults: 3 k and 4 k of each motif), on each
+    strand.  Returns (INTERVAL_DTYPE records sorted by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2)).
+    The first call's log holds max_intervals records (default: one per read); when more are found the call is repeated once
+    with the exact number."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        b = t.host_batch(words, offsets, lengths)
+        cap = max(len(offsets), 1) if max_intervals is None else int(max_intervals)
+        t.intervals(b, motifs, max_gap, min_len, cap)
+        out, counts, found = t.intervals_results()
+        if found > cap:
+            t.intervals(b, motifs, max_gap, min_len, found)
+            out, counts, found = t.intervals_results()
+        return out, counts

@@ -1189,8 +1189,9 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
 // ---------------------------------------------------------------- trew annotate
 // Per-read motif annotation of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, runs trew_hip_annotate on a slot of its own
-// (for `trew tracts`: trew_hip_tracts; AnnotRequest::penalty picks the record type) and keeps the records that reach
-// MIN_TRACT.  The ordinal of a read is the index of its sequence line among the file's sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
+// (for `trew tracts`: trew_hip_tracts, for `trew intervals`: trew_hip_intervals; AnnotRequest::intervals and ::penalty pick
+// the record type) and keeps the records that reach MIN_TRACT (intervals: every record; min_len is part of the kernel's
+// rule, and a batch whose log overflows is resubmitted once with the exact number).  The ordinal of a read is the index of its sequence line among the file's sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
 // rows come out the same for any number of workers once they are sorted.
 struct Annotator {
     std::vector<trew_hip_ctx *> ctx;
@@ -1199,6 +1200,8 @@ struct Annotator {
         uint32_t *h_buf = nullptr;  // pinned: [offsets n][lengths n][words]
         std::vector<trew_hip_annot> recs;
         std::vector<trew_hip_tract> trecs;  // trew tracts
+        std::vector<trew_hip_interval> irecs;  // trew intervals
+        std::vector<uint32_t> icounts;
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1289,7 +1292,39 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             b.n_reads = n;
             AnnotFileResult &p = w->part;
             p.reads += n;
-            if (rq->penalty) {  // trew tracts
+            if (rq->intervals) {  // trew intervals: a variable number of records; the log starts at one per read
+                uint64_t cap = n, found = 0;
+                for (int attempt = 0;; attempt++) {
+                    if (trew_hip_intervals(c, &b, w->slot, rq->motifs, rq->rules, nm, cap)) hip_die(c, "trew_hip_intervals");
+                    if (w->irecs.size() < cap) w->irecs.resize(cap);
+                    if (w->icounts.size() < n * (size_t) nm * 2) w->icounts.resize(n * (size_t) nm * 2);
+                    if (trew_hip_intervals_results(c, w->slot, w->irecs.data(), cap, &found, w->icounts.data(), nullptr)) hip_die(c, "trew_hip_intervals_results");
+                    if (found <= cap) break;
+                    if (attempt) die("internal error: the interval log overflowed twice");
+                    cap = found;  // the exact number: one retry always suffices
+                    p.interval_retries++;
+                }
+                for (uint64_t r = 0; r < n; r++) {
+                    p.bases += lengths[r];
+                    for (int m = 0; m < nm; m++)
+                        if (w->icounts[(r * (size_t) nm + (size_t) m) * 2] + w->icounts[(r * (size_t) nm + (size_t) m) * 2 + 1]) p.reported[m]++;
+                }
+                for (uint64_t i = 0; i < found; i++) {
+                    const trew_hip_interval &x = w->irecs[i];
+                    const uint32_t len = lengths[x.read];
+                    const bool terminal = x.start == 0 || x.end == len;
+                    if (x.strand) {
+                        p.windows_rev[x.motif]++;
+                        p.longest_tail[x.motif] = std::max(p.longest_tail[x.motif], x.end - x.start);
+                        p.terminal_rev[x.motif] += terminal;
+                    } else {
+                        p.windows_fwd[x.motif]++;
+                        p.longest[x.motif] = std::max(p.longest[x.motif], x.end - x.start);
+                        p.terminal_fwd[x.motif] += terminal;
+                    }
+                    p.irows.push_back(IntervalRow{first_read + x.read, len, x});
+                }
+            } else if (rq->penalty) {  // trew tracts
                 if (trew_hip_tracts(c, &b, w->slot, rq->motifs, nm, rq->penalty)) hip_die(c, "trew_hip_tracts");
                 if (w->trecs.size() < n * (size_t) nm) w->trecs.resize(n * (size_t) nm);
                 uint64_t got = 0;
@@ -1360,14 +1395,26 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
             out.reported[m] += w.part.reported[m];
             out.longest[m] = std::max(out.longest[m], w.part.longest[m]);
             out.longest_tail[m] = std::max(out.longest_tail[m], w.part.longest_tail[m]);
+            out.terminal_fwd[m] += w.part.terminal_fwd[m];
+            out.terminal_rev[m] += w.part.terminal_rev[m];
         }
+        out.interval_retries += w.part.interval_retries;
         out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
+        out.irows.insert(out.irows.end(), w.part.irows.begin(), w.part.irows.end());
     }
+    std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
+        if (x.read != y.read) return x.read < y.read;
+        if (x.iv.motif != y.iv.motif) return x.iv.motif < y.iv.motif;
+        if (x.iv.strand != y.iv.strand) return x.iv.strand < y.iv.strand;
+        return x.iv.start < y.iv.start;
+    });
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + %s; serial reader, %d worker(s))\n", file_name,
-                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, rq.penalty ? "tracts" : "annotate", (int) a->workers.size());
+                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, rq.intervals ? "intervals" : rq.penalty ? "tracts" : "annotate", (int) a->workers.size());
+        if (rq.intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
+                                  (unsigned long long) out.irows.size(), (unsigned long long) out.interval_retries);
     }
     return out;
 }

@@ -97,6 +97,8 @@ struct AnnotRequest {
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];  // a (read, motif) is reported when its longer tract has at least this many bases
     int n_motifs = 0;
     int penalty = 0;  // 0: annotate (trew_hip_annot records); 1 .. 64: tracts (trew_hip_tract records) at this penalty
+    bool intervals = false;  // true: intervals (trew_hip_interval records, any number per read) under `rules`; penalty is not read
+    trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];
 };
 struct AnnotRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
@@ -105,13 +107,23 @@ struct AnnotRow {
     trew_hip_annot a;  // annotate
     trew_hip_tract t;  // tracts
 };
+struct IntervalRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_interval iv;  // iv.read is the index inside its batch; iv.motif the index in command-line order
+};
 struct AnnotFileResult {
     std::vector<AnnotRow> rows;  // sorted by read, then motif
+    std::vector<IntervalRow> irows;  // intervals: sorted by read, motif, strand, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {};
     // tracts: windows_fwd / windows_rev hold the covered bases of each strand, longest the longest head tract
     uint32_t longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
+    // intervals: windows_fwd / windows_rev hold the kept intervals of each strand, longest / longest_tail the longest one of
+    // the forward / reverse strand, reported the reads with at least one; terminal_s = intervals that touch an end of their read
+    uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
+    uint64_t interval_retries = 0;  // batches resubmitted because their log overflowed
 };
 struct Annotator;  // device contexts and one slot per worker
 Annotator *annotator_create(const Config &cfg);
@@ -120,6 +132,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
 int annotate_main(int argc, char **argv);  // the subcommand: arguments, output
 // ---- trew tracts MOTIF[,MOTIF...] FASTQ...: error-tolerant terminal tracts (host/tracts.cpp); the same Annotator path ----
 int tracts_main(int argc, char **argv);
+// ---- trew intervals MOTIF[,MOTIF...] FASTQ...: gap-tolerant intervals anywhere in a read (host/intervals.cpp); the same path ----
+int intervals_main(int argc, char **argv);
 
 struct RunStats {
     uint64_t reads = 0, bases = 0;

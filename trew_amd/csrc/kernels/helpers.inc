@@ -87,6 +87,22 @@ __device__ __forceinline__ u32 wave_scan_u32(u32 v) {
     return v;
 }
 
+// inclusive prefix maximum of a u32 across the wave (0 for idle lanes), the steps of wave_scan_u32: lane l gets
+// max(v[0], ..., v[l])
+__device__ __forceinline__ u32 wave_scan_max_u32(u32 v) {
+    v = max(v, (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true));
+    v = max(v, (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true));
+    v = max(v, (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true));
+    v = max(v, (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true));
+    v = max(v, (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false));  // row_bcast:15 into rows 1 and 3
+    v = max(v, (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false));  // row_bcast:31 into rows 2 and 3
+    return v;
+}
+// the value of the lane below (wave_shr:1); lane 0 gets 0: turns an inclusive scan into an exclusive one
+__device__ __forceinline__ u32 wave_prev_lane_u32(u32 v) {
+    return (u32) __builtin_amdgcn_update_dpp(0, (int) v, 0x138, 0xf, 0xf, false);
+}
+
 struct ReadRef {
     const u32 *w;  // first triple
     u32 len;       // bases

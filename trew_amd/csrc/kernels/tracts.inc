@@ -10,15 +10,34 @@
 // With c covered bases among len, score = c - penalty (len - c), so c = (score + penalty len) / (1 + penalty): no second pass.
 //
 // Wave per read, for every length: lane l takes 32-base word 64 t + l in iteration t (annot_wave_match).  Its coverage word
-// is its match word dilated by k together with the top k - 1 bits of the word before it: one DPP read from lane l - 1, and
-// lane 63's match word carried (wave-uniform) into lane 0 of the next iteration.  Every lane walks its word for the word's
-// total, its best prefix (earliest position) and its lowest prefix (latest position); a DPP prefix sum of the totals places
+// is its match word dilated by k together with the top k - 1 bits of the word before it (wave_cov_word, shared with
+// kernels/intervals.inc).  Every lane walks its word for the word's total, its best prefix (earliest position) and its lowest prefix (latest position); a DPP prefix sum of the totals places
 // the words, two DPP maxima over packed {value, position} keys give the iteration's arg-max and arg-min, and those are
 // compared with the wave-uniform best so far.  The running sum travels between iterations in 64 bits; inside an iteration
 // |S| <= 64 words * 32 bases * 64 = 2^17.
 
 // numerator / (1 + penalty), both wave-uniform; the 64-bit division only where a read is long enough to need it
 __device__ __forceinline__ u32 tract_div(u64 num, u32 p1) { return (num >> 32) ? (u32) (num / (u64) p1) : (u32) num / p1; }
+
+// coverage word of 32-base word w of a read, one strand of one motif, every lane of the wave calling it for w = 64 t + lane:
+// bit i = some matching window contains base 32 w + i.  Base p is covered by the windows p - k + 1 .. p, up to k - 1 of
+// which start in the word before: the match word dilated by k together with the top bits of the previous lane's match word
+// (one DPP read), lane 63's match word carried (wave-uniform, carry_m; 0 in front of the first iteration) into lane 0 of the
+// next iteration.  nv = bases of the read inside the word; bits at and past the end of the read are not covered (no window
+// reaches there).  Shared with kernels/intervals.inc, so the dilation exists once.
+__device__ __forceinline__ u32 wave_cov_word(const ReadRef &rd, const AnnotMotifDev *mm, int strand, u32 k, u32 w, u32 &carry_m, u32 &nv) {
+    const u32 m = annot_wave_match(rd, mm, strand, k, w);
+    const u32 pm = (u32) __builtin_amdgcn_update_dpp((int) carry_m, (int) m, 0x138, 0xf, 0xf, false);  // wave_shr:1; lane 0 keeps carry_m
+    carry_m = (u32) __builtin_amdgcn_readlane((int) m, 63);
+    u64 y = ((u64) m << 32) | pm;
+    u32 L = 1;
+    for (; 2 * L <= k; L *= 2) y |= y << L;
+    if (L < k) y |= y << (k - L);
+    const long long left = (long long) rd.len - 32ll * (long long) w;
+    nv = left >= 32 ? 32u : left > 0 ? (u32) left : 0u;
+    const u32 valid = nv >= 32u ? 0xffffffffu : (1u << nv) - 1u;
+    return (u32) (y >> 32) & valid;
+}
 
 // one strand of one motif: o = {covered, head_len, head_cov, tail_len, tail_cov}
 __device__ __forceinline__ void tract_wave_strand(const ReadRef &rd, const AnnotMotifDev *mm, int strand, u32 k, int P, u32 (&o)[5]) {
@@ -30,19 +49,10 @@ __device__ __forceinline__ void tract_wave_strand(const ReadRef &rd, const Annot
     u32 carry_m = 0;                     // match word of the word in front of this iteration
     for (u32 t0 = 0; t0 < rd.nw; t0 += 64u) {
         const u32 w = t0 + lane;
-        const u32 m = annot_wave_match(rd, mm, strand, k, w);
-        // coverage: base p is covered by the windows p - k + 1 .. p, up to k - 1 of which start in the word before
-        const u32 pm = (u32) __builtin_amdgcn_update_dpp((int) carry_m, (int) m, 0x138, 0xf, 0xf, false);  // wave_shr:1; lane 0 keeps carry_m
-        carry_m = (u32) __builtin_amdgcn_readlane((int) m, 63);
-        u64 y = ((u64) m << 32) | pm;
-        u32 L = 1;
-        for (; 2 * L <= k; L *= 2) y |= y << L;
-        if (L < k) y |= y << (k - L);
-        // bits at and past the end of the read are neither covered nor scored (no window reaches there: cov is inside valid)
-        const long long left = (long long) rd.len - 32ll * (long long) w;
-        const u32 nv = left >= 32 ? 32u : left > 0 ? (u32) left : 0u;
+        u32 nv;
+        const u32 cov = wave_cov_word(rd, mm, strand, k, w, carry_m, nv);
         const u32 valid = nv >= 32u ? 0xffffffffu : (1u << nv) - 1u;
-        const u32 cov = (u32) (y >> 32) & valid, unc = valid & ~cov;
+        const u32 unc = valid & ~cov;
         // in-word walk over the prefixes e = 1 .. 32 (e = 0: value 0).  Keys: the largest value with the smallest e, the
         // smallest value with the largest e.  A bit past the end scores 0, which can only tie: towards the smaller e in kmx,
         // and in kmn the position is clamped to nv afterwards (the value there is the same).

@@ -60,6 +60,15 @@ struct Slot {
     hipEvent_t ev_tract[2] = {nullptr, nullptr};
     bool tract_valid = false, tract_timed = false;
     u64 tract_n = 0;
+    // trew_hip_intervals: an append log with its counter and one count per (read, motif, strand), created (and grown) by the
+    // slot's intervals calls; the pattern tables above are shared
+    u32 *d_ival_log = nullptr;                 // ival_log_cap records of six u32
+    unsigned long long *d_ival_counter = nullptr;
+    u32 *d_ival_counts = nullptr;
+    u64 ival_log_cap = 0, ival_counts_cap = 0;
+    hipEvent_t ev_ival[2] = {nullptr, nullptr};
+    bool ival_valid = false, ival_timed = false;
+    u64 ival_max = 0, ival_keys = 0;           // max_intervals and n_reads * n_motifs * 2 of the last call
 };
 
 thread_local std::string g_init_error;  // trew_hip_init failures before a context exists (read back on the same thread)
@@ -377,6 +386,11 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
             if (e) (void) hipEventDestroy(e);
         if (s.d_tract) (void) hipFree(s.d_tract);
         for (auto e : s.ev_tract)
+            if (e) (void) hipEventDestroy(e);
+        if (s.d_ival_log) (void) hipFree(s.d_ival_log);
+        if (s.d_ival_counter) (void) hipFree(s.d_ival_counter);
+        if (s.d_ival_counts) (void) hipFree(s.d_ival_counts);
+        for (auto e : s.ev_ival)
             if (e) (void) hipEventDestroy(e);
         if (s.ev_tail) (void) hipEventDestroy(s.ev_tail);
         if (s.ev_copied) (void) hipEventDestroy(s.ev_copied);
@@ -1409,6 +1423,32 @@ extern "C" int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_a
 }
 
 // ---------------------------------------------------------------- per-read error-tolerant terminal tracts
+// cov[p] (p < n) = some matching window of strand s of the motif contains base p: the definition, base by base over the
+// packed planes of one read.  Shared by trew_tracts_host and trew_intervals_host.
+static void host_coverage(const u32 *w, u32 n, const trew_hip_motif &motif, int s, std::vector<unsigned char> &cov) {
+    const int k = motif.k;
+    const u64 mask = motif_mask(k);
+    u64 rot[32], t = s ? motif_revcomp(motif.word, k) : motif.word;
+    for (int i = 0; i < k; i++) {
+        rot[i] = t;
+        t = ((t << 2) | (t >> (2 * (k - 1)))) & mask;
+    }
+    cov.assign((size_t) n, 0);
+    u64 word = 0;
+    u32 clean = 0;  // bases since the last one with its nmask bit set
+    for (u32 i = 0; i < n; i++) {
+        const u32 j = i >> 5, b = i & 31u;
+        const u32 c = ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
+        clean = ((w[3 * j + 2] >> b) & 1u) ? 0 : clean + 1;
+        word = ((word << 2) | c) & mask;
+        if (clean < (u32) k) continue;  // also: fewer than k bases so far
+        bool hit = false;
+        for (int x = 0; x < k && !hit; x++) hit = word == rot[x];
+        if (hit)
+            for (u32 p = i + 1 - (u32) k; p <= i; p++) cov[p] = 1;
+    }
+}
+
 extern "C" int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                                 const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_tract *out) {
     const char *e = motifs_error(motifs, n_motifs);
@@ -1423,30 +1463,9 @@ extern "C" int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, 
         const u32 *w = words + offsets[r];
         const u32 n = lengths[r];
         for (int m = 0; m < n_motifs; m++) {
-            const int k = motifs[m].k;
-            const u64 mask = motif_mask(k);
             u32 res[2][5];
             for (int s = 0; s < 2; s++) {
-                u64 rot[32], t = s ? motif_revcomp(motifs[m].word, k) : motifs[m].word;
-                for (int i = 0; i < k; i++) {
-                    rot[i] = t;
-                    t = ((t << 2) | (t >> (2 * (k - 1)))) & mask;
-                }
-                // cov[p]: some matching window contains base p
-                cov.assign((size_t) n, 0);
-                u64 word = 0;
-                u32 clean = 0;  // bases since the last one with its nmask bit set
-                for (u32 i = 0; i < n; i++) {
-                    const u32 j = i >> 5, b = i & 31u;
-                    const u32 c = ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
-                    clean = ((w[3 * j + 2] >> b) & 1u) ? 0 : clean + 1;
-                    word = ((word << 2) | c) & mask;
-                    if (clean < (u32) k) continue;  // also: fewer than k bases so far
-                    bool hit = false;
-                    for (int x = 0; x < k && !hit; x++) hit = word == rot[x];
-                    if (hit)
-                        for (u32 p = i + 1 - (u32) k; p <= i; p++) cov[p] = 1;
-                }
+                host_coverage(w, n, motifs[m], s, cov);
                 // S(e), e = 0 .. n: the earliest largest value and the latest smallest value; covered counts alongside
                 long long S = 0, hi = 0, lo = 0;
                 u32 e_hi = 0, e_lo = 0, c = 0, c_hi = 0, c_lo = 0;
@@ -1530,6 +1549,165 @@ extern "C" int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tra
     if (ms_kernel) {
         *ms_kernel = 0.0f;
         if (s.tract_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_tract[0], s.ev_tract[1]));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- gap-tolerant motif intervals anywhere in a read
+static const char *rules_error(const trew_hip_interval_rule *rules, int n_motifs) {
+    if (!rules) return "rules must not be null";
+    for (int m = 0; m < n_motifs; m++)
+        if (rules[m].min_len < 1) return "min_len must be at least 1";
+    return nullptr;
+}
+static void sort_intervals(trew_hip_interval *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_interval &a, const trew_hip_interval &b) {
+        if (a.read != b.read) return a.read < b.read;
+        if (a.motif != b.motif) return a.motif < b.motif;
+        if (a.strand != b.strand) return a.strand < b.strand;
+        return a.start < b.start;
+    });
+}
+
+extern "C" int trew_intervals_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                   const trew_hip_motif *motifs, const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out,
+                                   uint64_t cap, uint64_t *n, uint32_t *counts) {
+    const char *e = motifs_error(motifs, n_motifs);
+    if (!e) e = rules_error(rules, n_motifs);
+    if (!e && (!n || (cap && !out))) e = "trew_intervals_host: null argument";
+    if (!e && n_reads && (!words || !offsets || !lengths)) e = "trew_intervals_host: null argument";
+    if (!e && n_reads > 0xffffffffull) e = "trew_intervals_host: more than 2^32 - 1 reads";
+    if (e) {
+        g_thread_error = g_init_error = e;
+        return -1;
+    }
+    std::vector<unsigned char> cov;
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 len = lengths[r];
+        for (int m = 0; m < n_motifs; m++) {
+            for (int s = 0; s < 2; s++) {
+                host_coverage(w, len, motifs[m], s, cov);
+                u32 kept = 0;
+                bool open = false;
+                u32 start = 0, last = 0, c = 0;  // of the open interval: first and last covered position, covered bases
+                auto close = [&]() {
+                    if (open && last + 1 - start >= rules[m].min_len) {
+                        if (found < cap) out[found] = trew_hip_interval{(u32) r, (u32) m, (u32) s, start, last + 1, c};
+                        found++;
+                        kept++;
+                    }
+                };
+                for (u32 p = 0; p < len; p++) {
+                    if (!cov[p]) continue;
+                    if (open && p - last - 1 > rules[m].max_gap) {
+                        close();
+                        open = false;
+                    }
+                    if (!open) {
+                        open = true;
+                        start = p;
+                        c = 0;
+                    }
+                    last = p;
+                    c++;
+                }
+                close();
+                if (counts) counts[(r * (u64) n_motifs + (u64) m) * 2ull + (u64) s] = kept;
+            }
+        }
+    }
+    *n = found;
+    sort_intervals(out, std::min<u64>(found, cap));  // already in this order: reads, motifs, strands and positions ascend
+    return 0;
+}
+
+extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs,
+                                  const trew_hip_interval_rule *rules, int n_motifs, uint64_t max_intervals) {
+    if (!ctx || !batch) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
+    if (const char *e = rules_error(rules, n_motifs)) return fail(ctx, e);
+    if (max_intervals < 1) return fail(ctx, "max_intervals must be at least 1");
+    HIPCHK(ctx, hipSetDevice(ctx->p.device));
+    Slot &s = ctx->slots[(size_t) slot];
+    DevBatch db;
+    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;  // also: the read index fits the record's u32
+    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
+    for (auto &e : s.ev_ival)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    if (!s.d_ival_counter) HIPCHK(ctx, hipMalloc((void **) &s.d_ival_counter, sizeof(unsigned long long)));
+    const u64 keys = db.n_reads * (u64) n_motifs * 2ull;
+    if (keys > s.ival_counts_cap || max_intervals > s.ival_log_cap) HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffers
+    if (keys > s.ival_counts_cap) {
+        if (s.d_ival_counts) HIPCHK(ctx, hipFree(s.d_ival_counts));
+        s.d_ival_counts = nullptr;
+        s.ival_counts_cap = 0;
+        HIPCHK(ctx, hipMalloc((void **) &s.d_ival_counts, keys * sizeof(u32)));
+        s.ival_counts_cap = keys;
+    }
+    if (max_intervals > s.ival_log_cap) {
+        if (s.d_ival_log) HIPCHK(ctx, hipFree(s.d_ival_log));
+        s.d_ival_log = nullptr;
+        s.ival_log_cap = 0;
+        HIPCHK(ctx, hipMalloc((void **) &s.d_ival_log, max_intervals * sizeof(trew_hip_interval)));
+        s.ival_log_cap = max_intervals;
+    }
+    s.ival_valid = true;
+    s.ival_timed = false;
+    s.ival_max = max_intervals;
+    s.ival_keys = keys;
+    // the counter starts every call at zero, also a call without reads (its results then report no interval)
+    HIPCHK(ctx, hipMemsetAsync(s.d_ival_counter, 0, sizeof(unsigned long long), s.stream));
+    if (keys == 0) return 0;
+    IntervalRulesDev rd;
+    memset(&rd, 0, sizeof(rd));
+    for (int m = 0; m < n_motifs; m++) {
+        rd.max_gap[m] = rules[m].max_gap;
+        rd.min_len[m] = rules[m].min_len;
+    }
+    IntervalLog lg;
+    lg.counter = s.d_ival_counter;
+    lg.recs = s.d_ival_log;
+    lg.cap = max_intervals;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
+    HIPCHK(ctx, hipEventRecord(s.ev_ival[0], s.stream));
+    HIPCHK(ctx, launch_intervals(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, rd, lg, s.d_ival_counts));
+    HIPCHK(ctx, hipEventRecord(s.ev_ival[1], s.stream));
+    s.ival_timed = true;
+    return 0;
+}
+
+extern "C" int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts,
+                                          float *ms_kernel) {
+    if (!ctx) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (!n) return fail(ctx, "trew_hip_intervals_results: n must not be null");
+    if (cap && !out) return fail(ctx, "trew_hip_intervals_results: out must not be null");
+    Slot &s = ctx->slots[(size_t) slot];
+    if (!s.ival_valid) return fail(ctx, "no trew_hip_intervals on this slot yet");
+    if (int rc = trew_hip_wait(ctx, slot)) return rc;
+    unsigned long long found = 0;
+    HIPCHK(ctx, hipMemcpy(&found, s.d_ival_counter, sizeof(found), hipMemcpyDeviceToHost));
+    *n = found;
+    if (counts && s.ival_keys) HIPCHK(ctx, hipMemcpy(counts, s.d_ival_counts, s.ival_keys * sizeof(u32), hipMemcpyDeviceToHost));
+    const u64 in_log = std::min<u64>(found, s.ival_max);
+    const u64 take = std::min<u64>(in_log, cap);
+    if (take) {
+        // sorted on the host, so the records do not depend on the order in which the waves appended them
+        if (take == in_log) {
+            HIPCHK(ctx, hipMemcpy(out, s.d_ival_log, take * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
+            sort_intervals(out, take);
+        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
+            std::vector<trew_hip_interval> all((size_t) in_log);
+            HIPCHK(ctx, hipMemcpy(all.data(), s.d_ival_log, in_log * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
+            sort_intervals(all.data(), in_log);
+            memcpy(out, all.data(), take * sizeof(trew_hip_interval));
+        }
+    }
+    if (ms_kernel) {
+        *ms_kernel = 0.0f;
+        if (s.ival_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_ival[0], s.ev_ival[1]));
     }
     return 0;
 }

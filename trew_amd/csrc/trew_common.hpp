@@ -139,6 +139,17 @@ struct AnnotMotifDev {
     u32 phi[2][32];
 };
 
+// trew_hip_intervals as its kernel reads it (kernels/intervals.inc): the rule of every motif, by value in the kernel's
+// arguments, and the slot's append log.
+struct IntervalRulesDev {
+    u32 max_gap[kAnnotMaxMotifs], min_len[kAnnotMaxMotifs];
+};
+struct IntervalLog {
+    unsigned long long *counter;  // kept intervals found; keeps counting past cap
+    u32 *recs;                    // cap records of six u32 (trew_hip_interval)
+    u64 cap;
+};
+
 struct Segment {
     u32 mate;   // 0 = first read of the unit, 1 = second (pair mode)
     u32 start;  // first base

@@ -38,6 +38,7 @@
 //   table_kernels.inc  add-rows / compaction kernels      synth_kernels.inc  workload generators
 //   annotate.inc       annotate_lane_kernel<NW> / annotate_wave_kernel (per-read motif tracts, beside the scan)
 //   tracts.inc         tracts_wave_kernel (per-read error-tolerant terminal tracts; shares annotate.inc's match word)
+//   intervals.inc      intervals_wave_kernel (gap-tolerant motif intervals anywhere in a read; shares tracts.inc's coverage word)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -70,6 +71,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/synth_kernels.inc"
 #include "kernels/annotate.inc"
 #include "kernels/tracts.inc"
+#include "kernels/intervals.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -326,6 +328,15 @@ hipError_t launch_tracts(hipStream_t st, u32 n_cu, const DevBatch &B, const Anno
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(tracts_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, (u32 *) d_out);
+    return hipGetLastError();
+}
+
+// Gap-tolerant intervals: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_intervals(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const IntervalRulesDev &rules,
+                            const IntervalLog &lg, u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(intervals_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, rules, lg, d_counts);
     return hipGetLastError();
 }
 

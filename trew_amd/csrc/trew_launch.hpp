@@ -32,6 +32,10 @@ hipError_t launch_annotate(hipStream_t st, u32 n_cu, const DevBatch &B, const An
                            trew_hip_annot *d_out);
 // trew_hip_tracts: the wave-per-read kernel of kernels/tracts.inc, whatever the read lengths
 hipError_t launch_tracts(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_tract *d_out);
+// trew_hip_intervals: the wave-per-read kernel of kernels/intervals.inc on the grid of launch_tracts; the counter of `lg` is zero
+// when the kernel starts (the caller's memset on the same stream)
+hipError_t launch_intervals(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const IntervalRulesDev &rules,
+                            const IntervalLog &lg, u32 *d_counts);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
