@@ -1143,7 +1143,8 @@ def test_joint_halves_loop_is_sound(n):
     by its first L bases against a joint threshold row) is switched off whenever per-k masks are asked for, so
     test_uniform_fast_path_is_sound never sees it.  Here its verdict is observed where it lands: the worklist.  Every read for
     which the oracle records anything -- i.e. some (segment, k) passes k_mer_check -- must be among the flagged units, with the
-    joint loop (default) and without it (TREW_FLAG_DEBUG_NO_JOINT); the tables of both runs equal the oracle's."""
+    joint loop (default) and without it (TREW_FLAG_DEBUG_NO_JOINT); the tables of both runs equal the oracle's.
+    test_gpu_prefilter_edges.py does the same in pair and long mode and at other parameters, at reads on the pass/fail edge."""
     import random
 
     rnd = random.Random(7700 + n)
@@ -1176,7 +1177,8 @@ def test_uniform_fast_path_is_sound(n):
     whose MAX/COUNT reaches LOW must be a candidate.  The lengths pick every k-range of the 3-word kernel (halves of 75:
     first-64-windows subset bound for k < 12, one 64-bit container shift for 12 <= k <= 32; halves of 95: three mask words as
     well; halves of 33/48: container and one-word ranges) and the 5-word kernel (n = 190 has halves of 95 -> 3 words, n = 126
-    a whole-read segment of 126 bases -> 5 words)."""
+    a whole-read segment of 126 bases -> 5 words).  test_gpu_prefilter_edges.py checks the masks in pair mode and at other
+    parameters, at reads on the pass/fail edge."""
     import random
 
     rnd = random.Random(900 + n)
