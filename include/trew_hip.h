@@ -29,9 +29,10 @@ extern "C" {
 #endif
 
 /* Still 4 with the annotation entry points (trew_motif_parse, trew_hip_annotate, trew_hip_annotate_results,
- * trew_annotate_host), the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host) and the interval
- * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host): they are purely additive -- no existing
- * structure, enumerator or function changed. */
+ * trew_annotate_host), the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host), the interval
+ * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host) and the variant entry points
+ * (trew_hip_variants, trew_hip_variants_results, trew_variants_host): they are purely additive -- no existing structure,
+ * enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
 /* scan modes: which per-read driver of the reference is reproduced */
@@ -365,6 +366,49 @@ int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_interval *o
  * (the first ones of the sorted order), counts as above (may be NULL). */
 int trew_intervals_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                         const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+
+/* ---- telomere variant repeats: in-phase variant units per read, batch histogram (what is the repeat made of?) ----
+ * Base codes as in trew_motif_parse: T = 0, G = 1, C = 2, A = 3; the complement of code c is 3 - c.  The motif M of k bases is
+ * taken AS TYPED (trew_hip_motif.word keeps the typed rotation) and variants are named relative to that rotation.  Target of
+ * strand fwd: T_0 = M; of strand rev: T_1 = revcomp(M), T_1[j] = 3 - M[k-1-j].  Window i (0 <= i <= n - k) is valid when none
+ * of its k bases has its nmask bit set.  Per strand s:
+ *   exact_s[i]  window i is valid and equals T_s base for base (this rotation, not any rotation)
+ *   var_s[i]    window i is valid and differs from T_s in exactly one position j, where the read has base c
+ * A variant window is ANCHORED when its in-phase neighbour is exact: (i >= k and exact_s[i-k]) or (i + k <= n - k and
+ * exact_s[i+k]).  Phase is local: an indel shifts it, nothing global is assumed.  The bin of an anchored variant window is in
+ * motif coordinates on both strands: fwd 4 j + c, rev 4 (k-1-j) + (3-c), so TCAGGG on the forward strand and CCCTGA on the
+ * reverse strand both land in bin (1, C) of TTAGGG.  A bin whose base equals M[j] is always 0.
+ *   units_s      number of windows with exact_s, anchored or not
+ *   variants_s   number of anchored variant windows
+ *   distinct_s   number of non-zero bins of this read and strand
+ *   top_s        the bin with the largest count, the smallest such bin on a tie; TREW_VARIANT_NONE when variants_s = 0
+ *   top_count_s  the count of that bin, 0 when there is none
+ * n < k: everything 0, top_s = TREW_VARIANT_NONE.  Per batch two arrays of u64, each [motif][strand][bin]:
+ *   hist = sum over reads of the read's bin count;  reads_with = number of reads whose bin count is non-zero.
+ * Consequences: the bins of a read's histogram sum to variants_s; units_s <= trew_hip_annot.windows_s; a read that is an exact
+ * periodic repeat of M has variants = 0; the rev record of a read equals the fwd record of its reverse complement and vice
+ * versa, the histograms likewise; for a self-reverse-complementary motif strand rev is strand fwd under (j, c) ->
+ * (k-1-j, 3-c).  Only substitutions are variants: a unit with an inserted or deleted base is out of scope (it shifts the
+ * phase and is seen by no window).  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+#define TREW_VARIANT_BINS 128
+#define TREW_VARIANT_NONE 0xffffffffu
+typedef struct {
+    uint32_t units_fwd, variants_fwd, distinct_fwd, top_fwd, top_count_fwd;
+    uint32_t units_rev, variants_rev, distinct_rev, top_rev, top_count_rev;
+} trew_hip_variant;
+/* Like trew_hip_tracts (batch shapes, staging, asynchronous on the slot's stream, a context of any mode, independent of the
+ * scan and of the other three kernels), with buffers of its own that the slot's first call allocates: the records and the
+ * two batch histograms, which are zeroed on the slot's stream in front of every launch.  One kernel, a wave per read, for
+ * every read length. */
+int trew_hip_variants(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs);
+/* Waits for the slot and copies the records of its last trew_hip_variants: out[r * n_motifs + m]; *n receives their number
+ * even when it exceeds cap (then cap records are copied).  hist / reads_with: n_motifs * 2 * TREW_VARIANT_BINS values each,
+ * [motif][strand][bin]; either may be NULL.  ms_kernel (may be NULL): kernel time from HIP events on the slot's stream. */
+int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_variant *out, uint64_t cap, uint64_t *n, uint64_t *hist, uint64_t *reads_with,
+                              float *ms_kernel);
+/* The same on the host, window by window from the definition, over packed planes; hist / reads_with may be NULL. */
+int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                       int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

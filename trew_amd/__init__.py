@@ -28,4 +28,5 @@ from .capi import (  # noqa: F401
     k_mer_check,
     pack_reads,
     tracts,
+    variants,
 )

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "trew_motif_parse", "trew_hip_annotate", "trew_hip_annotate_results", "trew_annotate_host",
     "trew_hip_tracts", "trew_hip_tracts_results", "trew_tracts_host",
     "trew_hip_intervals", "trew_hip_intervals_results", "trew_intervals_host",
+    "trew_hip_variants", "trew_hip_variants_results", "trew_variants_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target")
 
@@ -112,6 +113,16 @@ class Interval(C.Structure):
 INTERVAL_DTYPE = np.dtype([(name, "<u4") for name, _ in Interval._fields_])
 assert INTERVAL_DTYPE.itemsize == C.sizeof(Interval) == 24 and C.sizeof(IntervalRule) == 8
 
+
+class Variant(C.Structure):
+    _fields_ = [(name + s, C.c_uint32) for s in ("_fwd", "_rev") for name in ("units", "variants", "distinct", "top", "top_count")]
+
+
+VARIANT_DTYPE = np.dtype([(name, "<u4") for name, _ in Variant._fields_])
+assert VARIANT_DTYPE.itemsize == C.sizeof(Variant) == 40
+VARIANT_BINS = 128
+VARIANT_NONE = 0xFFFFFFFF
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -178,6 +189,9 @@ def load():
     lib.trew_hip_intervals.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), C.POINTER(IntervalRule), i32, u64]
     lib.trew_hip_intervals_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), vp, C.POINTER(C.c_float)]
     lib.trew_intervals_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), C.POINTER(IntervalRule), i32, vp, u64, C.POINTER(u64), vp]
+    lib.trew_hip_variants.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32]
+    lib.trew_hip_variants_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), vp, vp, C.POINTER(C.c_float)]
+    lib.trew_variants_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, vp, vp, vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -276,6 +290,28 @@ def tracts_host(reads_or_packed, motifs, penalty=3):
     if lib.trew_tracts_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
         raise TrewHipError("trew_tracts_host failed: %s" % lib.trew_hip_last_error(None).decode())
     return out[:, :nm]
+
+
+def variants_host(reads_or_packed, motifs):
+    """trew_variants_host: the in-phase variant units computed on the host, window by window from the definition.
+    reads_or_packed as for annotate_host.  Returns (VARIANT_DTYPE records of shape (n_reads, n_motifs), hist, reads_with),
+    the two histograms uint64 of shape (n_motifs, 2, VARIANT_BINS)."""
+    lib = load()
+    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
+        words, offsets, lengths = reads_or_packed
+    else:
+        words, offsets, lengths = pack_reads(reads_or_packed)
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    arr, nm = _motif_array(motifs)
+    out = np.zeros((len(offsets), max(nm, 1)), dtype=VARIANT_DTYPE)
+    hist = np.zeros((max(nm, 1), 2, VARIANT_BINS), dtype=np.uint64)
+    reads_with = np.zeros_like(hist)
+    if lib.trew_variants_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, out.ctypes.data,
+                              hist.ctypes.data, reads_with.ctypes.data) != 0:
+        raise TrewHipError("trew_variants_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out[:, :nm], hist[:nm], reads_with[:nm]
 
 
 def _rule_array(arr, nm, max_gap, min_len):
@@ -506,6 +542,30 @@ class TrewHip:
             raise TrewHipError("trew_hip_tracts_results: %d records, expected %d" % (n.value, n_reads * nm))
         return (out, ms.value) if want_ms else out
 
+    def variants(self, batch, motifs, slot=0):
+        """Queue the in-phase variant units of every read of `batch` for `motifs` (texts or Motif, at most 8, taken as typed)
+        on the slot's stream."""
+        arr, nm = _motif_array(motifs)
+        self._keep[("var", slot)] = (batch, arr)
+        self._var_shape = getattr(self, "_var_shape", {})
+        self._var_shape[slot] = (int(batch.n_reads), nm)
+        self._chk(self.lib.trew_hip_variants(self.ctx, C.byref(batch), slot, arr, nm), "trew_hip_variants")
+
+    def variants_results(self, slot=0, want_ms=False):
+        """Results of the slot's last variants: (VARIANT_DTYPE records of shape (n_reads, n_motifs), hist, reads_with
+        [, kernel ms]); the two batch histograms are uint64 of shape (n_motifs, 2, VARIANT_BINS)."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm = getattr(self, "_var_shape", {}).get(slot, (0, 1))
+        out = np.zeros((n_reads, nm), dtype=VARIANT_DTYPE)
+        hist = np.zeros((nm, 2, VARIANT_BINS), dtype=np.uint64)
+        reads_with = np.zeros_like(hist)
+        self._chk(self.lib.trew_hip_variants_results(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), hist.ctypes.data, reads_with.ctypes.data,
+                                                     C.byref(ms) if want_ms else None), "trew_hip_variants_results")
+        if int(n.value) != n_reads * nm:
+            raise TrewHipError("trew_hip_variants_results: %d records, expected %d" % (n.value, n_reads * nm))
+        return (out, hist, reads_with, ms.value) if want_ms else (out, hist, reads_with)
+
     def intervals(self, batch, motifs, max_gap=None, min_len=None, max_intervals=None, slot=0):
         """Queue the gap-tolerant motif intervals of every read of `batch` for `motifs` (texts or Motif, at most 8) on the
         slot's stream.  max_gap / min_len: an int, a per-motif list, or None for the defaults 3 k and 4 k of each motif;
@@ -722,6 +782,17 @@ def tracts(reads, motifs, penalty=3, device=0):
                  max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
         t.tracts(t.host_batch(words, offsets, lengths), motifs, penalty)
         return t.tracts_results()
+
+
+def variants(reads, motifs, device=0):
+    """In-phase variant units on the GPU: for every read (bytes / str) and motif (text, taken as typed) the exact units, the
+    anchored units with one substituted base and the commonest substitution on each strand, and the histogram of the
+    substitutions over all reads.  Returns (VARIANT_DTYPE records of shape (n_reads, n_motifs), hist, reads_with)."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        t.variants(t.host_batch(words, offsets, lengths), motifs)
+        return t.variants_results()
 
 
 def intervals(reads, motifs, max_gap=None, min_len=None, device=0, max_intervals=None):

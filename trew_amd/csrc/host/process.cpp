@@ -1189,8 +1189,8 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
 // ---------------------------------------------------------------- trew annotate
 // Per-read motif annotation of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, runs trew_hip_annotate on a slot of its own
-// (for `trew tracts`: trew_hip_tracts, for `trew intervals`: trew_hip_intervals; AnnotRequest::intervals and ::penalty pick
-// the record type) and keeps the records that reach MIN_TRACT (intervals: every record; min_len is part of the kernel's
+// (for `trew tracts`: trew_hip_tracts, for `trew intervals`: trew_hip_intervals, for `trew variants`: trew_hip_variants;
+// AnnotRequest::variants, ::intervals and ::penalty pick the record type) and keeps the records that reach MIN_TRACT (intervals: every record; min_len is part of the kernel's
 // rule, and a batch whose log overflows is resubmitted once with the exact number).  The ordinal of a read is the index of its sequence line among the file's sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
 // rows come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1202,6 +1202,8 @@ struct Annotator {
         std::vector<trew_hip_tract> trecs;  // trew tracts
         std::vector<trew_hip_interval> irecs;  // trew intervals
         std::vector<uint32_t> icounts;
+        std::vector<trew_hip_variant> vrecs;  // trew variants
+        std::vector<uint64_t> vhist;          // hist, then reads_with, of one batch
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1292,7 +1294,36 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             b.n_reads = n;
             AnnotFileResult &p = w->part;
             p.reads += n;
-            if (rq->intervals) {  // trew intervals: a variable number of records; the log starts at one per read
+            if (rq->variants) {  // trew variants: one record per (read, motif) and the batch's two histograms
+                const size_t hl = (size_t) nm * 2 * TREW_VARIANT_BINS;
+                if (trew_hip_variants(c, &b, w->slot, rq->motifs, nm)) hip_die(c, "trew_hip_variants");
+                if (w->vrecs.size() < n * (size_t) nm) w->vrecs.resize(n * (size_t) nm);
+                w->vhist.resize(2 * hl);
+                uint64_t got = 0;
+                if (trew_hip_variants_results(c, w->slot, w->vrecs.data(), n * (uint64_t) nm, &got, w->vhist.data(), w->vhist.data() + hl, nullptr))
+                    hip_die(c, "trew_hip_variants_results");
+                p.var_hist.resize(hl);
+                p.var_reads_with.resize(hl);
+                for (size_t i = 0; i < hl; i++) {
+                    p.var_hist[i] += w->vhist[i];
+                    p.var_reads_with[i] += w->vhist[hl + i];
+                }
+                for (uint64_t r = 0; r < n; r++) {
+                    p.bases += lengths[r];
+                    for (int m = 0; m < nm; m++) {
+                        const trew_hip_variant &x = w->vrecs[r * (size_t) nm + (size_t) m];
+                        p.windows_fwd[m] += x.units_fwd;
+                        p.windows_rev[m] += x.units_rev;
+                        p.variants_fwd[m] += x.variants_fwd;
+                        p.variants_rev[m] += x.variants_rev;
+                        const uint64_t most = std::max((uint64_t) x.units_fwd + x.variants_fwd, (uint64_t) x.units_rev + x.variants_rev);
+                        if (most >= rq->min_tract[m]) {
+                            p.reported[m]++;
+                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, trew_hip_annot(), trew_hip_tract(), x});
+                        }
+                    }
+                }
+            } else if (rq->intervals) {  // trew intervals: a variable number of records; the log starts at one per read
                 uint64_t cap = n, found = 0;
                 for (int attempt = 0;; attempt++) {
                     if (trew_hip_intervals(c, &b, w->slot, rq->motifs, rq->rules, nm, cap)) hip_die(c, "trew_hip_intervals");
@@ -1340,7 +1371,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
                         p.longest_tail[m] = std::max(p.longest_tail[m], tail);
                         if (std::max(head, tail) >= rq->min_tract[m]) {
                             p.reported[m]++;
-                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, trew_hip_annot(), x});
+                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, trew_hip_annot(), x, trew_hip_variant()});
                         }
                     }
                 }
@@ -1359,7 +1390,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
                         p.longest[m] = std::max(p.longest[m], longest);
                         if (longest >= rq->min_tract[m]) {
                             p.reported[m]++;
-                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, x, trew_hip_tract()});
+                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, x, trew_hip_tract(), trew_hip_variant()});
                         }
                     }
                 }
@@ -1397,6 +1428,16 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
             out.longest_tail[m] = std::max(out.longest_tail[m], w.part.longest_tail[m]);
             out.terminal_fwd[m] += w.part.terminal_fwd[m];
             out.terminal_rev[m] += w.part.terminal_rev[m];
+            out.variants_fwd[m] += w.part.variants_fwd[m];
+            out.variants_rev[m] += w.part.variants_rev[m];
+        }
+        if (out.var_hist.size() < w.part.var_hist.size()) {
+            out.var_hist.resize(w.part.var_hist.size());
+            out.var_reads_with.resize(w.part.var_hist.size());
+        }
+        for (size_t i = 0; i < w.part.var_hist.size(); i++) {
+            out.var_hist[i] += w.part.var_hist[i];
+            out.var_reads_with[i] += w.part.var_reads_with[i];
         }
         out.interval_retries += w.part.interval_retries;
         out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
@@ -1412,7 +1453,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + %s; serial reader, %d worker(s))\n", file_name,
-                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, rq.intervals ? "intervals" : rq.penalty ? "tracts" : "annotate", (int) a->workers.size());
+                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, rq.variants ? "variants" : rq.intervals ? "intervals" : rq.penalty ? "tracts" : "annotate", (int) a->workers.size());
         if (rq.intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.irows.size(), (unsigned long long) out.interval_retries);
     }

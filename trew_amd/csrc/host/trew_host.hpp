@@ -99,6 +99,7 @@ struct AnnotRequest {
     int penalty = 0;  // 0: annotate (trew_hip_annot records); 1 .. 64: tracts (trew_hip_tract records) at this penalty
     bool intervals = false;  // true: intervals (trew_hip_interval records, any number per read) under `rules`; penalty is not read
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];
+    bool variants = false;  // true: variants (trew_hip_variant records and the two batch histograms); min_tract holds MIN_UNITS
 };
 struct AnnotRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
@@ -106,6 +107,7 @@ struct AnnotRow {
     int motif;        // index in command-line order
     trew_hip_annot a;  // annotate
     trew_hip_tract t;  // tracts
+    trew_hip_variant v;  // variants
 };
 struct IntervalRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
@@ -124,6 +126,11 @@ struct AnnotFileResult {
     // the forward / reverse strand, reported the reads with at least one; terminal_s = intervals that touch an end of their read
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t interval_retries = 0;  // batches resubmitted because their log overflowed
+    // variants: windows_fwd / windows_rev hold the exact units of each strand, variants_s the anchored variant units; the two
+    // histograms ([motif][strand][bin], n_motifs * 2 * TREW_VARIANT_BINS values; empty for the other record kinds) are summed
+    // over the batches of the file, over all reads and not only the reported ones
+    uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
+    std::vector<uint64_t> var_hist, var_reads_with;
 };
 struct Annotator;  // device contexts and one slot per worker
 Annotator *annotator_create(const Config &cfg);
@@ -134,6 +141,8 @@ int annotate_main(int argc, char **argv);  // the subcommand: arguments, output
 int tracts_main(int argc, char **argv);
 // ---- trew intervals MOTIF[,MOTIF...] FASTQ...: gap-tolerant intervals anywhere in a read (host/intervals.cpp); the same path ----
 int intervals_main(int argc, char **argv);
+// ---- trew variants MOTIF[,MOTIF...] FASTQ...: in-phase variant units and their histogram (host/variants.cpp); the same path ----
+int variants_main(int argc, char **argv);
 
 struct RunStats {
     uint64_t reads = 0, bases = 0;

@@ -69,6 +69,14 @@ struct Slot {
     hipEvent_t ev_ival[2] = {nullptr, nullptr};
     bool ival_valid = false, ival_timed = false;
     u64 ival_max = 0, ival_keys = 0;           // max_intervals and n_reads * n_motifs * 2 of the last call
+    // trew_hip_variants: the records and, in one allocation, the two batch histograms (hist, then reads_with; each
+    // kAnnotMaxMotifs * 2 * TREW_VARIANT_BINS u64), created by the slot's first variants call; the pattern tables are shared
+    trew_hip_variant *d_var = nullptr;
+    unsigned long long *d_var_hist = nullptr;
+    u64 var_cap = 0, var_n = 0;
+    int var_motifs = 0;
+    hipEvent_t ev_var[2] = {nullptr, nullptr};
+    bool var_valid = false, var_timed = false;
 };
 
 thread_local std::string g_init_error;  // trew_hip_init failures before a context exists (read back on the same thread)
@@ -391,6 +399,10 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         if (s.d_ival_counter) (void) hipFree(s.d_ival_counter);
         if (s.d_ival_counts) (void) hipFree(s.d_ival_counts);
         for (auto e : s.ev_ival)
+            if (e) (void) hipEventDestroy(e);
+        if (s.d_var) (void) hipFree(s.d_var);
+        if (s.d_var_hist) (void) hipFree(s.d_var_hist);
+        for (auto e : s.ev_var)
             if (e) (void) hipEventDestroy(e);
         if (s.ev_tail) (void) hipEventDestroy(s.ev_tail);
         if (s.ev_copied) (void) hipEventDestroy(s.ev_copied);
@@ -1708,6 +1720,145 @@ extern "C" int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_
     if (ms_kernel) {
         *ms_kernel = 0.0f;
         if (s.ival_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_ival[0], s.ev_ival[1]));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- telomere variant repeats
+constexpr u64 kVarHistLen = (u64) kAnnotMaxMotifs * 2ull * TREW_VARIANT_BINS;  // values of one histogram of a slot
+
+extern "C" int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                  const trew_hip_motif *motifs, int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with) {
+    const char *e = motifs_error(motifs, n_motifs);
+    if (!e && n_reads && (!words || !offsets || !lengths || !out)) e = "trew_variants_host: null argument";
+    if (e) {
+        g_thread_error = g_init_error = e;
+        return -1;
+    }
+    const size_t hl = (size_t) n_motifs * 2 * TREW_VARIANT_BINS;
+    if (hist) memset(hist, 0, hl * sizeof(uint64_t));
+    if (reads_with) memset(reads_with, 0, hl * sizeof(uint64_t));
+    std::vector<unsigned char> base, state;  // per base: code, or 4 with its nmask bit set; per window: 1 exact, 2 variant
+    std::vector<u32> bin_of;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        base.resize(n);
+        for (u32 i = 0; i < n; i++) {
+            const u32 j = i >> 5, b = i & 31u;
+            base[i] = ((w[3 * j + 2] >> b) & 1u) ? 4 : (unsigned char) (((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1));
+        }
+        for (int m = 0; m < n_motifs; m++) {
+            const u32 k = (u32) motifs[m].k;
+            u32 res[2][5];
+            for (int s = 0; s < 2; s++) {
+                const u64 t = s ? motif_revcomp(motifs[m].word, (int) k) : motifs[m].word;
+                u32 *o = res[s];
+                o[0] = o[1] = o[2] = o[4] = 0;
+                o[3] = TREW_VARIANT_NONE;
+                if (n < k) continue;
+                const u32 nwin = n - k + 1;
+                state.assign(nwin, 0);
+                bin_of.assign(nwin, 0);
+                for (u32 i = 0; i < nwin; i++) {
+                    u32 mism = 0, jj = 0, cc = 0;
+                    bool valid = true;
+                    for (u32 j = 0; j < k && valid; j++) {
+                        const u32 c = base[i + j];
+                        if (c > 3) valid = false;
+                        else if (c != ((u32) (t >> (2 * (k - 1 - j))) & 3u)) {
+                            mism++;
+                            jj = j;
+                            cc = c;
+                        }
+                    }
+                    if (!valid) continue;
+                    if (mism == 0) state[i] = 1;
+                    if (mism == 1) {
+                        state[i] = 2;
+                        bin_of[i] = s ? 4u * (k - 1u - jj) + (3u - cc) : 4u * jj + cc;
+                    }
+                }
+                u32 bins[TREW_VARIANT_BINS] = {};
+                for (u32 i = 0; i < nwin; i++) {
+                    if (state[i] == 1) o[0]++;
+                    if (state[i] != 2) continue;
+                    const bool anchored = (i >= k && state[i - k] == 1) || ((u64) i + k < nwin && state[i + k] == 1);
+                    if (anchored) {
+                        o[1]++;
+                        bins[bin_of[i]]++;
+                    }
+                }
+                for (u32 b = 0; b < TREW_VARIANT_BINS; b++) {
+                    if (!bins[b]) continue;
+                    o[2]++;
+                    if (bins[b] > o[4]) {  // strictly: the smallest bin keeps a tie
+                        o[4] = bins[b];
+                        o[3] = b;
+                    }
+                    const size_t at = ((size_t) m * 2 + (size_t) s) * TREW_VARIANT_BINS + b;
+                    if (hist) hist[at] += bins[b];
+                    if (reads_with) reads_with[at]++;
+                }
+            }
+            memcpy(&out[r * (u64) n_motifs + (u64) m], res, sizeof(trew_hip_variant));
+        }
+    }
+    return 0;
+}
+
+extern "C" int trew_hip_variants(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
+    if (!ctx || !batch) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
+    HIPCHK(ctx, hipSetDevice(ctx->p.device));
+    Slot &s = ctx->slots[(size_t) slot];
+    DevBatch db;
+    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
+    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
+    for (auto &e : s.ev_var)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    if (!s.d_var_hist) HIPCHK(ctx, hipMalloc((void **) &s.d_var_hist, 2ull * kVarHistLen * sizeof(unsigned long long)));
+    const u64 need = db.n_reads * (u64) n_motifs;
+    if (need > s.var_cap) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
+        if (s.d_var) HIPCHK(ctx, hipFree(s.d_var));
+        s.d_var = nullptr;
+        s.var_cap = 0;
+        HIPCHK(ctx, hipMalloc((void **) &s.d_var, need * sizeof(trew_hip_variant)));
+        s.var_cap = need;
+    }
+    s.var_valid = true;
+    s.var_timed = false;
+    s.var_n = need;
+    s.var_motifs = n_motifs;
+    // both histograms start every call at zero, also a call without reads
+    HIPCHK(ctx, hipMemsetAsync(s.d_var_hist, 0, 2ull * kVarHistLen * sizeof(unsigned long long), s.stream));
+    if (need == 0) return 0;
+    HIPCHK(ctx, hipEventRecord(s.ev_var[0], s.stream));
+    HIPCHK(ctx, launch_variants(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, s.d_var, s.d_var_hist, s.d_var_hist + kVarHistLen));
+    HIPCHK(ctx, hipEventRecord(s.ev_var[1], s.stream));
+    s.var_timed = true;
+    return 0;
+}
+
+extern "C" int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_variant *out, uint64_t cap, uint64_t *n, uint64_t *hist,
+                                         uint64_t *reads_with, float *ms_kernel) {
+    if (!ctx) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (cap && !out) return fail(ctx, "trew_hip_variants_results: out must not be null");
+    Slot &s = ctx->slots[(size_t) slot];
+    if (!s.var_valid) return fail(ctx, "no trew_hip_variants on this slot yet");
+    if (int rc = trew_hip_wait(ctx, slot)) return rc;
+    if (n) *n = s.var_n;
+    const u64 take = std::min<u64>(s.var_n, cap);
+    if (out && take) HIPCHK(ctx, hipMemcpy(out, s.d_var, take * sizeof(trew_hip_variant), hipMemcpyDeviceToHost));
+    const size_t hb = (size_t) s.var_motifs * 2 * TREW_VARIANT_BINS * sizeof(uint64_t);
+    if (hist && hb) HIPCHK(ctx, hipMemcpy(hist, s.d_var_hist, hb, hipMemcpyDeviceToHost));
+    if (reads_with && hb) HIPCHK(ctx, hipMemcpy(reads_with, s.d_var_hist + kVarHistLen, hb, hipMemcpyDeviceToHost));
+    if (ms_kernel) {
+        *ms_kernel = 0.0f;
+        if (s.var_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_var[0], s.ev_var[1]));
     }
     return 0;
 }

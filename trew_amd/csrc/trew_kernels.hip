@@ -39,6 +39,7 @@
 //   annotate.inc       annotate_lane_kernel<NW> / annotate_wave_kernel (per-read motif tracts, beside the scan)
 //   tracts.inc         tracts_wave_kernel (per-read error-tolerant terminal tracts; shares annotate.inc's match word)
 //   intervals.inc      intervals_wave_kernel (gap-tolerant motif intervals anywhere in a read; shares tracts.inc's coverage word)
+//   variants.inc       variants_wave_kernel (in-phase variant units per read and their batch histogram; Hamming distance 1)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -72,6 +73,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/annotate.inc"
 #include "kernels/tracts.inc"
 #include "kernels/intervals.inc"
+#include "kernels/variants.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -337,6 +339,15 @@ hipError_t launch_intervals(hipStream_t st, u32 n_cu, const DevBatch &B, const A
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(intervals_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, rules, lg, d_counts);
+    return hipGetLastError();
+}
+
+// Variant repeats: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_variants(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, trew_hip_variant *d_out,
+                           unsigned long long *d_hist, unsigned long long *d_reads_with) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(variants_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, (u32 *) d_out, d_hist, d_reads_with);
     return hipGetLastError();
 }
 

@@ -36,6 +36,10 @@ hipError_t launch_tracts(hipStream_t st, u32 n_cu, const DevBatch &B, const Anno
 // when the kernel starts (the caller's memset on the same stream)
 hipError_t launch_intervals(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const IntervalRulesDev &rules,
                             const IntervalLog &lg, u32 *d_counts);
+// trew_hip_variants: the wave-per-read kernel of kernels/variants.inc on the grid of launch_tracts; hist and reads_with are zero
+// when the kernel starts (the caller's memsets on the same stream)
+hipError_t launch_variants(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, trew_hip_variant *d_out,
+                           unsigned long long *d_hist, unsigned long long *d_reads_with);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
