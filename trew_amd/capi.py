@@ -256,17 +256,20 @@ def _motif_array(motifs):
     return (Motif * max(len(ms), 1))(*ms), len(ms)
 
 
-def annotate_host(reads_or_packed, motifs):
-    """trew_annotate_host: the annotation computed on the host, window by window.  reads_or_packed: a list of reads (bytes /
-    str) or the (words, offsets, lengths) of pack_reads.  Returns ANNOT_DTYPE records of shape (n_reads, n_motifs)."""
-    lib = load()
+def _packed(reads_or_packed):
+    """A list of reads (bytes / str), or the (words, offsets, lengths) of pack_reads -> the three arrays, contiguous uint32."""
     if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
         words, offsets, lengths = reads_or_packed
     else:
         words, offsets, lengths = pack_reads(reads_or_packed)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    return tuple(np.ascontiguousarray(a, dtype=np.uint32) for a in (words, offsets, lengths))
+
+
+def annotate_host(reads_or_packed, motifs):
+    """trew_annotate_host: the annotation computed on the host, window by window.  reads_or_packed: a list of reads (bytes /
+    str) or the (words, offsets, lengths) of pack_reads.  Returns ANNOT_DTYPE records of shape (n_reads, n_motifs)."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
     arr, nm = _motif_array(motifs)
     out = np.zeros((len(offsets), max(nm, 1)), dtype=ANNOT_DTYPE)
     if lib.trew_annotate_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, out.ctypes.data) != 0:
@@ -278,13 +281,7 @@ def tracts_host(reads_or_packed, motifs, penalty=3):
     """trew_tracts_host: the error-tolerant terminal tracts computed on the host, base by base from the definition.
     reads_or_packed as for annotate_host.  Returns TRACT_DTYPE records of shape (n_reads, n_motifs)."""
     lib = load()
-    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
-        words, offsets, lengths = reads_or_packed
-    else:
-        words, offsets, lengths = pack_reads(reads_or_packed)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    words, offsets, lengths = _packed(reads_or_packed)
     arr, nm = _motif_array(motifs)
     out = np.zeros((len(offsets), max(nm, 1)), dtype=TRACT_DTYPE)
     if lib.trew_tracts_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
@@ -297,13 +294,7 @@ def variants_host(reads_or_packed, motifs):
     reads_or_packed as for annotate_host.  Returns (VARIANT_DTYPE records of shape (n_reads, n_motifs), hist, reads_with),
     the two histograms uint64 of shape (n_motifs, 2, VARIANT_BINS)."""
     lib = load()
-    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
-        words, offsets, lengths = reads_or_packed
-    else:
-        words, offsets, lengths = pack_reads(reads_or_packed)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    words, offsets, lengths = _packed(reads_or_packed)
     arr, nm = _motif_array(motifs)
     out = np.zeros((len(offsets), max(nm, 1)), dtype=VARIANT_DTYPE)
     hist = np.zeros((max(nm, 1), 2, VARIANT_BINS), dtype=np.uint64)
@@ -339,13 +330,7 @@ def intervals_host(reads_or_packed, motifs, max_gap=None, min_len=None, cap=None
     reads_or_packed as for annotate_host; max_gap / min_len as for TrewHip.intervals.  Returns (INTERVAL_DTYPE records sorted
     by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2), found); with `cap` at most that many records."""
     lib = load()
-    if isinstance(reads_or_packed, tuple) and len(reads_or_packed) == 3 and isinstance(reads_or_packed[0], np.ndarray):
-        words, offsets, lengths = reads_or_packed
-    else:
-        words, offsets, lengths = pack_reads(reads_or_packed)
-    words = np.ascontiguousarray(words, dtype=np.uint32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    words, offsets, lengths = _packed(reads_or_packed)
     arr, nm = _motif_array(motifs)
     rules = _rule_array(arr, min(max(nm, 0), MAX_MOTIFS), max_gap, min_len)
     counts = np.zeros((len(offsets), max(nm, 1), 2), dtype=np.uint32)
@@ -418,6 +403,7 @@ class TrewHip:
             raise TrewHipError("trew_hip_init failed (%d): %s" % (rc, self.lib.trew_hip_last_error(None).decode()))
         self.mode = mode
         self._keep = {}
+        self._queued = {}  # (measure, slot) -> the shape of what the measure queued last on the slot
 
     def close(self):
         if self.ctx:
@@ -501,70 +487,62 @@ class TrewHip:
     def wait(self, slot=0):
         self._chk(self.lib.trew_hip_wait(self.ctx, slot), "trew_hip_wait")
 
+    def _queue(self, measure, slot, batch, arr, nm, keep=(), shape=()):
+        """Before a measure's queue call: keeps the batch and the argument arrays (`arr`, `keep`) alive, remembers
+        (n_reads, n_motifs) + shape."""
+        self._keep[(measure, slot)] = (batch, arr) + keep
+        self._queued[(measure, slot)] = (int(batch.n_reads), nm) + shape
+
+    def _fetch_records(self, measure, slot, dtype, want_ms, *extra):
+        """The fixed-size records of the slot's last `measure`: (out of shape (n_reads, n_motifs),) + extra [+ (kernel ms,)];
+        `extra` are arrays the results call fills between the count and the time."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm = self._queued.get((measure, slot), (0, 1))
+        out = np.zeros((n_reads, nm), dtype=dtype)
+        what = "trew_hip_%s_results" % measure
+        self._chk(getattr(self.lib, what)(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), *[x.ctypes.data for x in extra],
+                                          C.byref(ms) if want_ms else None), what)
+        if int(n.value) != n_reads * nm:
+            raise TrewHipError("%s: %d records, expected %d" % (what, n.value, n_reads * nm))
+        return (out,) + extra + ((ms.value,) if want_ms else ())
+
     def annotate(self, batch, motifs, slot=0):
         """Queue the annotation of every read of `batch` against `motifs` (texts or Motif, at most 8) on the slot's stream."""
         arr, nm = _motif_array(motifs)
-        self._keep[("annot", slot)] = (batch, arr)
-        self._annot_shape = getattr(self, "_annot_shape", {})
-        self._annot_shape[slot] = (int(batch.n_reads), nm)
+        self._queue("annotate", slot, batch, arr, nm)
         self._chk(self.lib.trew_hip_annotate(self.ctx, C.byref(batch), slot, arr, nm), "trew_hip_annotate")
 
     def annotate_results(self, slot=0, want_ms=False):
         """Records of the slot's last annotate: ANNOT_DTYPE array of shape (n_reads, n_motifs) [, kernel ms]."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, nm = getattr(self, "_annot_shape", {}).get(slot, (0, 1))
-        out = np.zeros((n_reads, nm), dtype=ANNOT_DTYPE)
-        self._chk(self.lib.trew_hip_annotate_results(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), C.byref(ms) if want_ms else None),
-                  "trew_hip_annotate_results")
-        if int(n.value) != n_reads * nm:
-            raise TrewHipError("trew_hip_annotate_results: %d records, expected %d" % (n.value, n_reads * nm))
-        return (out, ms.value) if want_ms else out
+        res = self._fetch_records("annotate", slot, ANNOT_DTYPE, want_ms)
+        return res if want_ms else res[0]
 
     def tracts(self, batch, motifs, penalty=3, slot=0):
         """Queue the error-tolerant terminal tracts of every read of `batch` for `motifs` (texts or Motif, at most 8) on the
         slot's stream."""
         arr, nm = _motif_array(motifs)
-        self._keep[("tract", slot)] = (batch, arr)
-        self._tract_shape = getattr(self, "_tract_shape", {})
-        self._tract_shape[slot] = (int(batch.n_reads), nm)
+        self._queue("tracts", slot, batch, arr, nm)
         self._chk(self.lib.trew_hip_tracts(self.ctx, C.byref(batch), slot, arr, nm, int(penalty)), "trew_hip_tracts")
 
     def tracts_results(self, slot=0, want_ms=False):
         """Records of the slot's last tracts: TRACT_DTYPE array of shape (n_reads, n_motifs) [, kernel ms]."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, nm = getattr(self, "_tract_shape", {}).get(slot, (0, 1))
-        out = np.zeros((n_reads, nm), dtype=TRACT_DTYPE)
-        self._chk(self.lib.trew_hip_tracts_results(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), C.byref(ms) if want_ms else None),
-                  "trew_hip_tracts_results")
-        if int(n.value) != n_reads * nm:
-            raise TrewHipError("trew_hip_tracts_results: %d records, expected %d" % (n.value, n_reads * nm))
-        return (out, ms.value) if want_ms else out
+        res = self._fetch_records("tracts", slot, TRACT_DTYPE, want_ms)
+        return res if want_ms else res[0]
 
     def variants(self, batch, motifs, slot=0):
         """Queue the in-phase variant units of every read of `batch` for `motifs` (texts or Motif, at most 8, taken as typed)
         on the slot's stream."""
         arr, nm = _motif_array(motifs)
-        self._keep[("var", slot)] = (batch, arr)
-        self._var_shape = getattr(self, "_var_shape", {})
-        self._var_shape[slot] = (int(batch.n_reads), nm)
+        self._queue("variants", slot, batch, arr, nm)
         self._chk(self.lib.trew_hip_variants(self.ctx, C.byref(batch), slot, arr, nm), "trew_hip_variants")
 
     def variants_results(self, slot=0, want_ms=False):
         """Results of the slot's last variants: (VARIANT_DTYPE records of shape (n_reads, n_motifs), hist, reads_with
         [, kernel ms]); the two batch histograms are uint64 of shape (n_motifs, 2, VARIANT_BINS)."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, nm = getattr(self, "_var_shape", {}).get(slot, (0, 1))
-        out = np.zeros((n_reads, nm), dtype=VARIANT_DTYPE)
+        nm = self._queued.get(("variants", slot), (0, 1))[1]
         hist = np.zeros((nm, 2, VARIANT_BINS), dtype=np.uint64)
-        reads_with = np.zeros_like(hist)
-        self._chk(self.lib.trew_hip_variants_results(self.ctx, slot, out.ctypes.data, n_reads * nm, C.byref(n), hist.ctypes.data, reads_with.ctypes.data,
-                                                     C.byref(ms) if want_ms else None), "trew_hip_variants_results")
-        if int(n.value) != n_reads * nm:
-            raise TrewHipError("trew_hip_variants_results: %d records, expected %d" % (n.value, n_reads * nm))
-        return (out, hist, reads_with, ms.value) if want_ms else (out, hist, reads_with)
+        return self._fetch_records("variants", slot, VARIANT_DTYPE, want_ms, hist, np.zeros_like(hist))
 
     def intervals(self, batch, motifs, max_gap=None, min_len=None, max_intervals=None, slot=0):
         """Queue the gap-tolerant motif intervals of every read of `batch` for `motifs` (texts or Motif, at most 8) on the
@@ -574,9 +552,7 @@ class TrewHip:
         rules = _rule_array(arr, min(max(nm, 0), MAX_MOTIFS), max_gap, min_len)
         if max_intervals is None:
             max_intervals = max(int(batch.n_reads), 1)
-        self._keep[("ival", slot)] = (batch, arr, rules)
-        self._ival_shape = getattr(self, "_ival_shape", {})
-        self._ival_shape[slot] = (int(batch.n_reads), nm, int(max_intervals))
+        self._queue("intervals", slot, batch, arr, nm, keep=(rules,), shape=(int(max_intervals),))
         self._chk(self.lib.trew_hip_intervals(self.ctx, C.byref(batch), slot, arr, rules, nm, int(max_intervals)), "trew_hip_intervals")
 
     def intervals_results(self, slot=0, want_ms=False):
@@ -585,7 +561,7 @@ class TrewHip:
         log held), counts and found are exact; repeat the call with max_intervals >= found."""
         n = C.c_uint64(0)
         ms = C.c_float(0)
-        n_reads, nm, cap = getattr(self, "_ival_shape", {}).get(slot, (0, 1, 0))
+        n_reads, nm, cap = self._queued.get(("intervals", slot), (0, 1, 0))
         counts = np.zeros((n_reads, nm, 2), dtype=np.uint32)
         # the log is read once, into a buffer of its capacity or of the sum of the counts, whichever is smaller
         self._chk(self.lib.trew_hip_intervals_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),

@@ -1,0 +1,142 @@
+// motif_cli.cpp -- what the command lines share: the argument helpers of every subcommand, and the front end of the four
+// per-read motif subcommands `trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ...` (motif_cli_main).  A
+// subcommand's own file (annotate.cpp, ...) holds its usage text, its options and their defaults, its rows and its summary.
+// The conventions are those of `short` and `long`: CSV on stdout, messages on stderr, exit status 1 and an empty stdout on an
+// argument error.
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+#include <sys/stat.h>
+
+#include "trew_host.hpp"
+
+namespace trew_host {
+
+bool is_regular_file(const std::string &p) {
+    struct stat st;
+    return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+}
+
+bool parse_int(const char *s, int *out) {
+    char *end = nullptr;
+    long v = strtol(s, &end, 10);
+    if (!s[0] || *end || v < INT_MIN || v > INT_MAX) return false;
+    *out = (int) v;
+    return true;
+}
+
+bool parse_devices(const std::string &list, std::vector<int> *devices) {
+    devices->clear();
+    bool ok = true;
+    size_t pos = 0;
+    while (pos <= list.size()) {
+        size_t comma = list.find(',', pos);
+        if (comma == std::string::npos) comma = list.size();
+        int d;
+        if (!parse_int(list.substr(pos, comma - pos).c_str(), &d) || d < 0) ok = false;
+        else devices->push_back(d);
+        pos = comma + 1;
+    }
+    return ok && !devices->empty();
+}
+
+bool has_gz_ext(const std::string &p) {  // trew.cpp:407,422-433
+    const size_t dot = p.find_last_of('.');
+    const size_t slash = p.find_last_of('/');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return false;
+    const std::string ext = p.substr(dot);
+    return ext == ".gz" || ext == ".bgz";
+}
+
+std::string canonical(const std::string &p) {  // std::filesystem::canonical, trew.cpp:439-451
+    char buf[PATH_MAX];
+    if (realpath(p.c_str(), buf)) return std::string(buf);
+    return p;
+}
+
+int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
+    Config cfg;
+    std::vector<std::string> positional;
+    auto bad = [&](const std::string &msg) {
+        fprintf(stderr, "%s\n", msg.c_str());
+        cli.usage();
+        return 1;
+    };
+    for (int i = 2; i < argc; i++) {
+        const std::string a = argv[i];
+        auto need = [&](const char *name) -> const char * {
+            if (i + 1 >= argc) {
+                fprintf(stderr, "%s: expected 1 argument(s). 0 provided.\n", name);
+                cli.usage();
+                exit(1);
+            }
+            return argv[++i];
+        };
+        const MotifOption *own = nullptr;
+        for (const auto &o : cli.options)
+            if (a == o.name) own = &o;
+        if (a == "-h" || a == "--help") {
+            cli.usage();
+            return 0;
+        } else if (a == "-t" || a == "--thread") {
+            if (!parse_int(need("--thread"), &cfg.NUM_THREAD)) return bad("THREAD must be a number.");
+        } else if (own) {
+            if (!own->parse(need(own->name))) return bad(own->error);
+        } else if (a == "--stats") {
+            cfg.stats = true;
+        } else if (a == "--devices") {
+            if (!parse_devices(need("--devices"), &cfg.devices)) return bad("DEVICES must be a comma-separated list of device ordinals.");
+        } else if (a.size() > 1 && a[0] == '-') {
+            return bad("Unknown argument: " + a);
+        } else {
+            positional.push_back(a);
+        }
+    }
+    if (positional.empty()) return bad("MOTIF is required.");
+    if (cfg.NUM_THREAD <= 0) return bad("number of threads must be positive.");
+    if (const char *e = cli.check()) return bad(e);
+
+    // MOTIF[,MOTIF...], printed as given
+    std::vector<std::string> names;
+    {
+        const std::string &list = positional[0];
+        size_t pos = 0;
+        while (pos <= list.size()) {
+            size_t comma = list.find(',', pos);
+            if (comma == std::string::npos) comma = list.size();
+            names.push_back(list.substr(pos, comma - pos));
+            pos = comma + 1;
+        }
+    }
+    if (names.size() > TREW_ANNOT_MAX_MOTIFS) return bad("At most 8 motifs can be given.");
+    AnnotRequest rq;
+    rq.kind = kind;
+    for (const auto &name : names) {
+        for (char ch : name)
+            if (!strchr("ACGTacgt", ch) || !ch) return bad("MOTIF '" + name + "' must consist of A, C, G and T.");
+        if (name.size() < 3 || name.size() > 32) return bad("MOTIF '" + name + "': the length must be in range 3 to 32.");
+        if (trew_motif_parse(name.c_str(), &rq.motifs[rq.n_motifs])) return bad(trew_hip_last_error(nullptr));
+        cli.per_motif(rq, rq.n_motifs, (uint32_t) name.size());
+        rq.n_motifs++;
+    }
+    if (positional.size() < 2) return bad("FASTQ is required.");
+    std::vector<std::string> files(positional.begin() + 1, positional.end());
+    for (const auto &f : files)
+        if (!is_regular_file(f)) return bad(f + " : file not found");
+    if (cfg.NUM_THREAD - 1 > 16 * (int) cfg.devices.size()) cfg.NUM_THREAD = 16 * (int) cfg.devices.size() + 1;
+
+    Annotator *an = annotator_create(cfg);
+    AnnotFileResult total;
+    for (const auto &f : files) {
+        const std::string path = canonical(f);
+        const AnnotFileResult r = process_annotate(an, cfg, path.c_str(), has_gz_ext(f), rq);
+        printf(">%s\n", path.c_str());
+        cli.print_rows(r, names);
+        add_totals(total, r);
+    }
+    annotator_destroy(an);
+    cli.print_summary(total, names);
+    return 0;
+}
+
+}  // namespace trew_host

@@ -1186,13 +1186,13 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate
-// Per-read motif annotation of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
-// 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, runs trew_hip_annotate on a slot of its own
-// (for `trew tracts`: trew_hip_tracts, for `trew intervals`: trew_hip_intervals, for `trew variants`: trew_hip_variants;
-// AnnotRequest::variants, ::intervals and ::penalty pick the record type) and keeps the records that reach MIN_TRACT (intervals: every record; min_len is part of the kernel's
-// rule, and a batch whose log overflows is resubmitted once with the exact number).  The ordinal of a read is the index of its sequence line among the file's sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the
-// rows come out the same for any number of workers once they are sorted.
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants
+// A per-read motif measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
+// 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
+// names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
+// fold_tracts, fold_intervals, fold_variants).  The ordinal of a read is the index of its sequence line among the file's
+// sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
+// come out the same for any number of workers once they are sorted.
 struct Annotator {
     std::vector<trew_hip_ctx *> ctx;
     struct Worker {
@@ -1258,9 +1258,149 @@ void annotator_destroy(Annotator *a) {
     delete a;
 }
 
+// one packed chunk on its way through a worker's slot
+struct AnnotBatch {
+    trew_hip_ctx *c;
+    Annotator::Worker *w;
+    const AnnotRequest *rq;
+    trew_hip_batch b;
+    const uint32_t *lengths;
+    uint64_t n, first_read;  // reads of the chunk, ordinal of the first
+};
+
+static AnnotRow annot_row(const AnnotBatch &x, uint64_t r, int m) {
+    AnnotRow row;
+    row.read = x.first_read + r;
+    row.length = x.lengths[r];
+    row.motif = m;
+    return row;
+}
+
+// trew annotate.  windows_fwd / windows_rev: the matching windows of each strand; longest: the longest tract of either
+// strand; reported: the (read, motif) whose longer tract reaches MIN_TRACT, which are the rows.
+static void fold_annotate(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    if (trew_hip_annotate(x.c, &x.b, w->slot, x.rq->motifs, nm)) hip_die(x.c, "trew_hip_annotate");
+    if (w->recs.size() < x.n * (size_t) nm) w->recs.resize(x.n * (size_t) nm);
+    uint64_t got = 0;
+    if (trew_hip_annotate_results(x.c, w->slot, w->recs.data(), x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_annotate_results");
+    for (uint64_t r = 0; r < x.n; r++)
+        for (int m = 0; m < nm; m++) {
+            const trew_hip_annot &rec = w->recs[r * (size_t) nm + (size_t) m];
+            const uint32_t longest = std::max(rec.tract_len_fwd, rec.tract_len_rev);
+            p.windows_fwd[m] += rec.windows_fwd;
+            p.windows_rev[m] += rec.windows_rev;
+            p.longest[m] = std::max(p.longest[m], longest);
+            if (longest >= x.rq->min_tract[m]) {
+                p.reported[m]++;
+                p.rows.push_back(annot_row(x, r, m));
+                p.rows.back().a = rec;
+            }
+        }
+}
+
+// trew tracts.  windows_fwd / windows_rev: the covered bases of each strand; longest / longest_tail: the longest head / tail
+// tract of either strand; reported: the (read, motif) whose longest of the four tracts reaches MIN_TRACT, which are the rows.
+static void fold_tracts(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    if (trew_hip_tracts(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty)) hip_die(x.c, "trew_hip_tracts");
+    if (w->trecs.size() < x.n * (size_t) nm) w->trecs.resize(x.n * (size_t) nm);
+    uint64_t got = 0;
+    if (trew_hip_tracts_results(x.c, w->slot, w->trecs.data(), x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_tracts_results");
+    for (uint64_t r = 0; r < x.n; r++)
+        for (int m = 0; m < nm; m++) {
+            const trew_hip_tract &rec = w->trecs[r * (size_t) nm + (size_t) m];
+            const uint32_t head = std::max(rec.head_len_fwd, rec.head_len_rev), tail = std::max(rec.tail_len_fwd, rec.tail_len_rev);
+            p.windows_fwd[m] += rec.covered_fwd;
+            p.windows_rev[m] += rec.covered_rev;
+            p.longest[m] = std::max(p.longest[m], head);
+            p.longest_tail[m] = std::max(p.longest_tail[m], tail);
+            if (std::max(head, tail) >= x.rq->min_tract[m]) {
+                p.reported[m]++;
+                p.rows.push_back(annot_row(x, r, m));
+                p.rows.back().t = rec;
+            }
+        }
+}
+
+// trew intervals: a variable number of records, every one a row (min_len is part of the kernel's rule).  windows_fwd /
+// windows_rev: the kept intervals of each strand; longest / longest_tail: the longest one of the forward / reverse strand;
+// reported: the reads with at least one; terminal_s: the intervals that touch an end of their read.  The log starts at one
+// record per read; a batch whose log overflows is resubmitted once, with the exact number.
+static void fold_intervals(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    uint64_t cap = x.n, found = 0;
+    for (int attempt = 0;; attempt++) {
+        if (trew_hip_intervals(x.c, &x.b, w->slot, x.rq->motifs, x.rq->rules, nm, cap)) hip_die(x.c, "trew_hip_intervals");
+        if (w->irecs.size() < cap) w->irecs.resize(cap);
+        if (w->icounts.size() < x.n * (size_t) nm * 2) w->icounts.resize(x.n * (size_t) nm * 2);
+        if (trew_hip_intervals_results(x.c, w->slot, w->irecs.data(), cap, &found, w->icounts.data(), nullptr)) hip_die(x.c, "trew_hip_intervals_results");
+        if (found <= cap) break;
+        if (attempt) die("internal error: the interval log overflowed twice");
+        cap = found;  // the exact number: one retry always suffices
+        p.interval_retries++;
+    }
+    for (uint64_t r = 0; r < x.n; r++)
+        for (int m = 0; m < nm; m++)
+            if (w->icounts[(r * (size_t) nm + (size_t) m) * 2] + w->icounts[(r * (size_t) nm + (size_t) m) * 2 + 1]) p.reported[m]++;
+    for (uint64_t i = 0; i < found; i++) {
+        const trew_hip_interval &rec = w->irecs[i];
+        const uint32_t len = x.lengths[rec.read];
+        const bool terminal = rec.start == 0 || rec.end == len;
+        if (rec.strand) {
+            p.windows_rev[rec.motif]++;
+            p.longest_tail[rec.motif] = std::max(p.longest_tail[rec.motif], rec.end - rec.start);
+            p.terminal_rev[rec.motif] += terminal;
+        } else {
+            p.windows_fwd[rec.motif]++;
+            p.longest[rec.motif] = std::max(p.longest[rec.motif], rec.end - rec.start);
+            p.terminal_fwd[rec.motif] += terminal;
+        }
+        p.irows.push_back(IntervalRow{x.first_read + rec.read, len, rec});
+    }
+}
+
+// trew variants: one record per (read, motif) and the batch's two histograms.  windows_fwd / windows_rev: the exact units
+// of each strand; variants_s: the anchored variant units; reported: the (read, motif) whose larger units_s + variants_s
+// reaches MIN_UNITS (AnnotRequest::min_tract), which are the rows; var_hist / var_reads_with: the histograms summed over the
+// batches, over all reads and not only the reported ones.
+static void fold_variants(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    const size_t hl = (size_t) nm * 2 * TREW_VARIANT_BINS;
+    if (trew_hip_variants(x.c, &x.b, w->slot, x.rq->motifs, nm)) hip_die(x.c, "trew_hip_variants");
+    if (w->vrecs.size() < x.n * (size_t) nm) w->vrecs.resize(x.n * (size_t) nm);
+    w->vhist.resize(2 * hl);
+    uint64_t got = 0;
+    if (trew_hip_variants_results(x.c, w->slot, w->vrecs.data(), x.n * (uint64_t) nm, &got, w->vhist.data(), w->vhist.data() + hl, nullptr))
+        hip_die(x.c, "trew_hip_variants_results");
+    p.var_hist.resize(hl);
+    p.var_reads_with.resize(hl);
+    for (size_t i = 0; i < hl; i++) {
+        p.var_hist[i] += w->vhist[i];
+        p.var_reads_with[i] += w->vhist[hl + i];
+    }
+    for (uint64_t r = 0; r < x.n; r++)
+        for (int m = 0; m < nm; m++) {
+            const trew_hip_variant &rec = w->vrecs[r * (size_t) nm + (size_t) m];
+            p.windows_fwd[m] += rec.units_fwd;
+            p.windows_rev[m] += rec.units_rev;
+            p.variants_fwd[m] += rec.variants_fwd;
+            p.variants_rev[m] += rec.variants_rev;
+            const uint64_t most = std::max((uint64_t) rec.units_fwd + rec.variants_fwd, (uint64_t) rec.units_rev + rec.variants_rev);
+            if (most >= x.rq->min_tract[m]) {
+                p.reported[m]++;
+                p.rows.push_back(annot_row(x, r, m));
+                p.rows.back().v = rec;
+            }
+        }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
-    const int nm = rq->n_motifs;
     for (;;) {
         Chunk *ch = q->pop();
         if (ch->sentinel) {
@@ -1285,121 +1425,54 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             uint32_t *offsets = w->h_buf, *lengths = w->h_buf + n, *words = w->h_buf + 2 * n;
             const uint64_t nw = trew_pack_reads(ch->buffer1, w->st.data(), w->nd.data(), n, words, a->words_cap, offsets, lengths);
             if (nw == (uint64_t) -1) die("internal error: packed chunk exceeds the slot buffer");
-            trew_hip_batch b;
-            memset(&b, 0, sizeof(b));
-            b.words = words;
-            b.n_words = nw;
-            b.offsets = offsets;
-            b.lengths = lengths;
-            b.n_reads = n;
+            AnnotBatch x{c, w, rq, trew_hip_batch(), lengths, n, first_read};
+            memset(&x.b, 0, sizeof(x.b));
+            x.b.words = words;
+            x.b.n_words = nw;
+            x.b.offsets = offsets;
+            x.b.lengths = lengths;
+            x.b.n_reads = n;
             AnnotFileResult &p = w->part;
             p.reads += n;
-            if (rq->variants) {  // trew variants: one record per (read, motif) and the batch's two histograms
-                const size_t hl = (size_t) nm * 2 * TREW_VARIANT_BINS;
-                if (trew_hip_variants(c, &b, w->slot, rq->motifs, nm)) hip_die(c, "trew_hip_variants");
-                if (w->vrecs.size() < n * (size_t) nm) w->vrecs.resize(n * (size_t) nm);
-                w->vhist.resize(2 * hl);
-                uint64_t got = 0;
-                if (trew_hip_variants_results(c, w->slot, w->vrecs.data(), n * (uint64_t) nm, &got, w->vhist.data(), w->vhist.data() + hl, nullptr))
-                    hip_die(c, "trew_hip_variants_results");
-                p.var_hist.resize(hl);
-                p.var_reads_with.resize(hl);
-                for (size_t i = 0; i < hl; i++) {
-                    p.var_hist[i] += w->vhist[i];
-                    p.var_reads_with[i] += w->vhist[hl + i];
-                }
-                for (uint64_t r = 0; r < n; r++) {
-                    p.bases += lengths[r];
-                    for (int m = 0; m < nm; m++) {
-                        const trew_hip_variant &x = w->vrecs[r * (size_t) nm + (size_t) m];
-                        p.windows_fwd[m] += x.units_fwd;
-                        p.windows_rev[m] += x.units_rev;
-                        p.variants_fwd[m] += x.variants_fwd;
-                        p.variants_rev[m] += x.variants_rev;
-                        const uint64_t most = std::max((uint64_t) x.units_fwd + x.variants_fwd, (uint64_t) x.units_rev + x.variants_rev);
-                        if (most >= rq->min_tract[m]) {
-                            p.reported[m]++;
-                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, trew_hip_annot(), trew_hip_tract(), x});
-                        }
-                    }
-                }
-            } else if (rq->intervals) {  // trew intervals: a variable number of records; the log starts at one per read
-                uint64_t cap = n, found = 0;
-                for (int attempt = 0;; attempt++) {
-                    if (trew_hip_intervals(c, &b, w->slot, rq->motifs, rq->rules, nm, cap)) hip_die(c, "trew_hip_intervals");
-                    if (w->irecs.size() < cap) w->irecs.resize(cap);
-                    if (w->icounts.size() < n * (size_t) nm * 2) w->icounts.resize(n * (size_t) nm * 2);
-                    if (trew_hip_intervals_results(c, w->slot, w->irecs.data(), cap, &found, w->icounts.data(), nullptr)) hip_die(c, "trew_hip_intervals_results");
-                    if (found <= cap) break;
-                    if (attempt) die("internal error: the interval log overflowed twice");
-                    cap = found;  // the exact number: one retry always suffices
-                    p.interval_retries++;
-                }
-                for (uint64_t r = 0; r < n; r++) {
-                    p.bases += lengths[r];
-                    for (int m = 0; m < nm; m++)
-                        if (w->icounts[(r * (size_t) nm + (size_t) m) * 2] + w->icounts[(r * (size_t) nm + (size_t) m) * 2 + 1]) p.reported[m]++;
-                }
-                for (uint64_t i = 0; i < found; i++) {
-                    const trew_hip_interval &x = w->irecs[i];
-                    const uint32_t len = lengths[x.read];
-                    const bool terminal = x.start == 0 || x.end == len;
-                    if (x.strand) {
-                        p.windows_rev[x.motif]++;
-                        p.longest_tail[x.motif] = std::max(p.longest_tail[x.motif], x.end - x.start);
-                        p.terminal_rev[x.motif] += terminal;
-                    } else {
-                        p.windows_fwd[x.motif]++;
-                        p.longest[x.motif] = std::max(p.longest[x.motif], x.end - x.start);
-                        p.terminal_fwd[x.motif] += terminal;
-                    }
-                    p.irows.push_back(IntervalRow{first_read + x.read, len, x});
-                }
-            } else if (rq->penalty) {  // trew tracts
-                if (trew_hip_tracts(c, &b, w->slot, rq->motifs, nm, rq->penalty)) hip_die(c, "trew_hip_tracts");
-                if (w->trecs.size() < n * (size_t) nm) w->trecs.resize(n * (size_t) nm);
-                uint64_t got = 0;
-                if (trew_hip_tracts_results(c, w->slot, w->trecs.data(), n * (uint64_t) nm, &got, nullptr)) hip_die(c, "trew_hip_tracts_results");
-                for (uint64_t r = 0; r < n; r++) {
-                    p.bases += lengths[r];
-                    for (int m = 0; m < nm; m++) {
-                        const trew_hip_tract &x = w->trecs[r * (size_t) nm + (size_t) m];
-                        const uint32_t head = std::max(x.head_len_fwd, x.head_len_rev), tail = std::max(x.tail_len_fwd, x.tail_len_rev);
-                        p.windows_fwd[m] += x.covered_fwd;
-                        p.windows_rev[m] += x.covered_rev;
-                        p.longest[m] = std::max(p.longest[m], head);
-                        p.longest_tail[m] = std::max(p.longest_tail[m], tail);
-                        if (std::max(head, tail) >= rq->min_tract[m]) {
-                            p.reported[m]++;
-                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, trew_hip_annot(), x, trew_hip_variant()});
-                        }
-                    }
-                }
-            } else {
-                if (trew_hip_annotate(c, &b, w->slot, rq->motifs, nm)) hip_die(c, "trew_hip_annotate");
-                if (w->recs.size() < n * (size_t) nm) w->recs.resize(n * (size_t) nm);
-                uint64_t got = 0;
-                if (trew_hip_annotate_results(c, w->slot, w->recs.data(), n * (uint64_t) nm, &got, nullptr)) hip_die(c, "trew_hip_annotate_results");
-                for (uint64_t r = 0; r < n; r++) {
-                    p.bases += lengths[r];
-                    for (int m = 0; m < nm; m++) {
-                        const trew_hip_annot &x = w->recs[r * (size_t) nm + (size_t) m];
-                        const uint32_t longest = std::max(x.tract_len_fwd, x.tract_len_rev);
-                        p.windows_fwd[m] += x.windows_fwd;
-                        p.windows_rev[m] += x.windows_rev;
-                        p.longest[m] = std::max(p.longest[m], longest);
-                        if (longest >= rq->min_tract[m]) {
-                            p.reported[m]++;
-                            p.rows.push_back(AnnotRow{first_read + r, lengths[r], m, x, trew_hip_tract(), trew_hip_variant()});
-                        }
-                    }
-                }
+            for (uint64_t r = 0; r < n; r++) p.bases += lengths[r];
+            switch (rq->kind) {
+            case Measure::Annotate: fold_annotate(x, p); break;
+            case Measure::Tracts: fold_tracts(x, p); break;
+            case Measure::Intervals: fold_intervals(x, p); break;
+            case Measure::Variants: fold_variants(x, p); break;
             }
         }
         free(ch->buffer1);
         delete ch;
     }
 }
+
+void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
+    into.reads += from.reads;
+    into.bases += from.bases;
+    for (int m = 0; m < TREW_ANNOT_MAX_MOTIFS; m++) {
+        into.windows_fwd[m] += from.windows_fwd[m];
+        into.windows_rev[m] += from.windows_rev[m];
+        into.reported[m] += from.reported[m];
+        into.longest[m] = std::max(into.longest[m], from.longest[m]);
+        into.longest_tail[m] = std::max(into.longest_tail[m], from.longest_tail[m]);
+        into.terminal_fwd[m] += from.terminal_fwd[m];
+        into.terminal_rev[m] += from.terminal_rev[m];
+        into.variants_fwd[m] += from.variants_fwd[m];
+        into.variants_rev[m] += from.variants_rev[m];
+    }
+    if (into.var_hist.size() < from.var_hist.size()) {
+        into.var_hist.resize(from.var_hist.size());
+        into.var_reads_with.resize(from.var_hist.size());
+    }
+    for (size_t i = 0; i < from.var_hist.size(); i++) {
+        into.var_hist[i] += from.var_hist[i];
+        into.var_reads_with[i] += from.var_reads_with[i];
+    }
+    into.interval_retries += from.interval_retries;
+}
+
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants"};  // in the order of Measure
 
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1418,28 +1491,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     for (auto &t : th) t.join();
     AnnotFileResult out;
     for (auto &w : a->workers) {
-        out.reads += w.part.reads;
-        out.bases += w.part.bases;
-        for (int m = 0; m < TREW_ANNOT_MAX_MOTIFS; m++) {
-            out.windows_fwd[m] += w.part.windows_fwd[m];
-            out.windows_rev[m] += w.part.windows_rev[m];
-            out.reported[m] += w.part.reported[m];
-            out.longest[m] = std::max(out.longest[m], w.part.longest[m]);
-            out.longest_tail[m] = std::max(out.longest_tail[m], w.part.longest_tail[m]);
-            out.terminal_fwd[m] += w.part.terminal_fwd[m];
-            out.terminal_rev[m] += w.part.terminal_rev[m];
-            out.variants_fwd[m] += w.part.variants_fwd[m];
-            out.variants_rev[m] += w.part.variants_rev[m];
-        }
-        if (out.var_hist.size() < w.part.var_hist.size()) {
-            out.var_hist.resize(w.part.var_hist.size());
-            out.var_reads_with.resize(w.part.var_hist.size());
-        }
-        for (size_t i = 0; i < w.part.var_hist.size(); i++) {
-            out.var_hist[i] += w.part.var_hist[i];
-            out.var_reads_with[i] += w.part.var_reads_with[i];
-        }
-        out.interval_retries += w.part.interval_retries;
+        add_totals(out, w.part);
         out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
         out.irows.insert(out.irows.end(), w.part.irows.begin(), w.part.irows.end());
     }
@@ -1453,8 +1505,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + %s; serial reader, %d worker(s))\n", file_name,
-                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, rq.variants ? "variants" : rq.intervals ? "intervals" : rq.penalty ? "tracts" : "annotate", (int) a->workers.size());
-        if (rq.intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
+                (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, kMeasureNames[(int) rq.kind], (int) a->workers.size());
+        if (rq.kind == Measure::Intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.irows.size(), (unsigned long long) out.interval_retries);
     }
     return out;

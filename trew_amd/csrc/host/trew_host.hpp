@@ -12,6 +12,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <utility>
@@ -91,57 +92,78 @@ FinalFastqOutput process_output(const char *file_name, const ResultMapData &resu
 void final_process_output(FinalFastqData &total_result_high, FinalFastqData &total_result_low, FILE *out);
 std::map<KmerSeq, uint32_t> get_score_map(const FinalFastqData &total_result);
 
-// ---- trew annotate MOTIF[,MOTIF...] FASTQ...: per-read motif tracts (host/annotate.cpp, process.cpp) ----
+// ---- argument helpers of every subcommand (host/motif_cli.cpp) ----
+bool parse_int(const char *s, int *out);
+bool parse_devices(const std::string &list, std::vector<int> *devices);  // "0,2": false unless every entry is an ordinal and there is one
+bool is_regular_file(const std::string &p);
+bool has_gz_ext(const std::string &p);
+std::string canonical(const std::string &p);
+
+// ---- trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ...: the per-read motif measures.  One file path for
+// all four (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp, intervals.cpp and
+// variants.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants };
 struct AnnotRequest {
+    Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
-    uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];  // a (read, motif) is reported when its longer tract has at least this many bases
+    // a (read, motif) is reported when its longer tract has at least this many bases (variants: MIN_UNITS; intervals: not read)
+    uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
-    int penalty = 0;  // 0: annotate (trew_hip_annot records); 1 .. 64: tracts (trew_hip_tract records) at this penalty
-    bool intervals = false;  // true: intervals (trew_hip_interval records, any number per read) under `rules`; penalty is not read
-    trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];
-    bool variants = false;  // true: variants (trew_hip_variant records and the two batch histograms); min_tract holds MIN_UNITS
+    int penalty = 0;                                      // tracts
+    trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
 };
 struct AnnotRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
     uint32_t length;  // bases
     int motif;        // index in command-line order
-    trew_hip_annot a;  // annotate
-    trew_hip_tract t;  // tracts
-    trew_hip_variant v;  // variants
+    union {           // the record of the request's kind
+        trew_hip_annot a;
+        trew_hip_tract t;
+        trew_hip_variant v;
+    };
 };
 struct IntervalRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
     uint32_t length;  // bases
     trew_hip_interval iv;  // iv.read is the index inside its batch; iv.motif the index in command-line order
 };
+// What one file (or, summed, all files) came to.  What the per-motif counters count depends on the kind: see the function
+// of process.cpp that folds the kind's records into them.
 struct AnnotFileResult {
-    std::vector<AnnotRow> rows;  // sorted by read, then motif
+    std::vector<AnnotRow> rows;      // annotate, tracts, variants: sorted by read, then motif
     std::vector<IntervalRow> irows;  // intervals: sorted by read, motif, strand, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
-    uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {};
-    // tracts: windows_fwd / windows_rev hold the covered bases of each strand, longest the longest head tract
-    uint32_t longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
-    // intervals: windows_fwd / windows_rev hold the kept intervals of each strand, longest / longest_tail the longest one of
-    // the forward / reverse strand, reported the reads with at least one; terminal_s = intervals that touch an end of their read
+    uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t interval_retries = 0;  // batches resubmitted because their log overflowed
-    // variants: windows_fwd / windows_rev hold the exact units of each strand, variants_s the anchored variant units; the two
-    // histograms ([motif][strand][bin], n_motifs * 2 * TREW_VARIANT_BINS values; empty for the other record kinds) are summed
-    // over the batches of the file, over all reads and not only the reported ones
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
-    std::vector<uint64_t> var_hist, var_reads_with;
+    std::vector<uint64_t> var_hist, var_reads_with;  // variants: [motif][strand][bin]; empty for the other kinds
 };
+void add_totals(AnnotFileResult &into, const AnnotFileResult &from);  // everything but the rows: sums, and the larger of longest*
 struct Annotator;  // device contexts and one slot per worker
 Annotator *annotator_create(const Config &cfg);
 void annotator_destroy(Annotator *a);
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq);
-int annotate_main(int argc, char **argv);  // the subcommand: arguments, output
-// ---- trew tracts MOTIF[,MOTIF...] FASTQ...: error-tolerant terminal tracts (host/tracts.cpp); the same Annotator path ----
+
+// the command line of one measure: what motif_cli_main does not share
+struct MotifOption {
+    const char *name;                          // "--min_tract"; takes one argument
+    std::function<bool(const char *)> parse;   // false: the argument is refused with `error`
+    const char *error;
+};
+struct MotifCli {
+    void (*usage)();
+    std::vector<MotifOption> options;
+    std::function<const char *()> check;  // once all arguments are read: the text of the first complaint about the options, or nullptr
+    std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
+    std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
+    std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
+};
+int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
+int annotate_main(int argc, char **argv);
 int tracts_main(int argc, char **argv);
-// ---- trew intervals MOTIF[,MOTIF...] FASTQ...: gap-tolerant intervals anywhere in a read (host/intervals.cpp); the same path ----
 int intervals_main(int argc, char **argv);
-// ---- trew variants MOTIF[,MOTIF...] FASTQ...: in-phase variant units and their histogram (host/variants.cpp); the same path ----
 int variants_main(int argc, char **argv);
 
 struct RunStats {

@@ -6,11 +6,9 @@
 // (trew.cpp:22-478): stdout carries the CSV sections, stderr errors/usage, exit code 1 on error.
 // Additions (stderr only, stdout stays CSV-identical): --devices LIST, --stats, --table_log2_slots N,
 // --serial_reader, --batch_mib N, --host_pack, --compat_g1.
-#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <sys/stat.h>
 
 #include "trew_host.hpp"
 
@@ -42,38 +40,12 @@ static void usage(const char *mode) {
     }
 }
 
-static bool is_regular_file(const std::string &p) {
-    struct stat st;
-    return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-}
-
-static bool parse_int(const char *s, int *out) {
-    char *end = nullptr;
-    long v = strtol(s, &end, 10);
-    if (!s[0] || *end || v < INT_MIN || v > INT_MAX) return false;
-    *out = (int) v;
-    return true;
-}
 static bool parse_double(const char *s, double *out) {
     char *end = nullptr;
     double v = strtod(s, &end);
     if (!s[0] || *end) return false;
     *out = v;
     return true;
-}
-
-static bool has_gz_ext(const std::string &p) {  // trew.cpp:407,422-433
-    const size_t dot = p.find_last_of('.');
-    const size_t slash = p.find_last_of('/');
-    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return false;
-    const std::string ext = p.substr(dot);
-    return ext == ".gz" || ext == ".bgz";
-}
-
-static std::string canonical(const std::string &p) {  // std::filesystem::canonical, trew.cpp:439-451
-    char buf[PATH_MAX];
-    if (realpath(p.c_str(), buf)) return std::string(buf);
-    return p;
 }
 
 int main(int argc, char **argv) {
@@ -166,18 +138,7 @@ int main(int argc, char **argv) {
             ok = parse_int(need("--table_log2_slots"), &cfg.table_log2_slots);
         } else if (a == "--devices") {
             multi = nullptr;
-            std::string list = need("--devices");
-            cfg.devices.clear();
-            size_t pos = 0;
-            while (pos <= list.size()) {
-                size_t comma = list.find(',', pos);
-                if (comma == std::string::npos) comma = list.size();
-                int d;
-                if (!parse_int(list.substr(pos, comma - pos).c_str(), &d) || d < 0) ok = false;
-                else cfg.devices.push_back(d);
-                pos = comma + 1;
-            }
-            if (cfg.devices.empty()) ok = false;
+            ok = parse_devices(need("--devices"), &cfg.devices);
         } else if (a.size() > 1 && a[0] == '-' && !(a[1] >= '0' && a[1] <= '9')) {
             fprintf(stderr, "Unknown argument: %s\n", a.c_str());
             ok = false;

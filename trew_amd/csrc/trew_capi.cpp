@@ -18,11 +18,33 @@
 
 #include "trew_common.hpp"
 #include "trew_launch.hpp"
+#include "trew_measures_host.hpp"
 #include "trew_synth.hpp"
 
 using namespace trew;
 
 namespace {
+
+// The per-read motif measures (trew_hip_annotate, _tracts, _intervals, _variants) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants"};
+struct DevBuf {
+    void *p = nullptr;
+    u64 bytes = 0;  // capacity
+};
+struct MeasureState {
+    DevBuf records;                         // the records of the last call, grown on demand (intervals: its append log)
+    DevBuf counts;                          // intervals: one u32 per (read, motif, strand), grown on demand
+    unsigned long long *counter = nullptr;  // intervals: the records the kernel found, in the log or not
+    unsigned long long *hist = nullptr;     // variants: the batch histograms hist, then reads_with, kVarHistLen values each
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
+    // the numbers of the last call
+    u64 n = 0;         // annotate, tracts, variants: its records, n_reads * n_motifs
+    u64 max_log = 0;   // intervals: its max_intervals
+    u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2
+    int n_motifs = 0;  // variants
+};
 
 struct Slot {
     hipStream_t stream = nullptr;
@@ -45,38 +67,11 @@ struct Slot {
     u64 n_submits = 0;   // submits since init
     u64 n_reported = 0;  // submits already averaged by trew_hip_last_timing
     u64 n_units = 0;
-    // trew_hip_annotate: everything below is created by the first annotate call on the slot (a context that never annotates
-    // allocates nothing of it)
-    trew_hip_annot *d_annot = nullptr;  // records of the last annotate, grown on demand
-    u64 annot_cap = 0;                  // records d_annot holds
+    // the pattern tables of the per-read motif measures (stage_motifs) and the state of each measure; all of it is created by
+    // the slot's first call of a measure (a context that only scans allocates nothing of it)
     AnnotMotifDev *d_motifs = nullptr, *h_motifs = nullptr;  // kAnnotMaxMotifs pattern tables: device copy and pinned staging
-    int annot_motifs_staged = 0;        // motifs of h_motifs that d_motifs holds (or will, in stream order)
-    hipEvent_t ev_annot[2] = {nullptr, nullptr};
-    bool annot_valid = false, annot_timed = false;  // an annotate was queued / its kernel was launched between the events
-    u64 annot_n = 0;                    // records of the last annotate
-    // trew_hip_tracts: a result buffer of its own, created by the slot's first tracts call; the pattern tables above are shared
-    trew_hip_tract *d_tract = nullptr;
-    u64 tract_cap = 0;
-    hipEvent_t ev_tract[2] = {nullptr, nullptr};
-    bool tract_valid = false, tract_timed = false;
-    u64 tract_n = 0;
-    // trew_hip_intervals: an append log with its counter and one count per (read, motif, strand), created (and grown) by the
-    // slot's intervals calls; the pattern tables above are shared
-    u32 *d_ival_log = nullptr;                 // ival_log_cap records of six u32
-    unsigned long long *d_ival_counter = nullptr;
-    u32 *d_ival_counts = nullptr;
-    u64 ival_log_cap = 0, ival_counts_cap = 0;
-    hipEvent_t ev_ival[2] = {nullptr, nullptr};
-    bool ival_valid = false, ival_timed = false;
-    u64 ival_max = 0, ival_keys = 0;           // max_intervals and n_reads * n_motifs * 2 of the last call
-    // trew_hip_variants: the records and, in one allocation, the two batch histograms (hist, then reads_with; each
-    // kAnnotMaxMotifs * 2 * TREW_VARIANT_BINS u64), created by the slot's first variants call; the pattern tables are shared
-    trew_hip_variant *d_var = nullptr;
-    unsigned long long *d_var_hist = nullptr;
-    u64 var_cap = 0, var_n = 0;
-    int var_motifs = 0;
-    hipEvent_t ev_var[2] = {nullptr, nullptr};
-    bool var_valid = false, var_timed = false;
+    int motifs_staged = 0;                                   // motifs of h_motifs that d_motifs holds (or will, in stream order)
+    MeasureState measure[kMeasures];
 };
 
 thread_local std::string g_init_error;  // trew_hip_init failures before a context exists (read back on the same thread)
@@ -387,23 +382,14 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         for (int i = 0; i < Slot::kRing; i++)
             for (int j = 0; j < 3; j++)
                 if (s.ev[i][j]) (void) hipEventDestroy(s.ev[i][j]);
-        if (s.d_annot) (void) hipFree(s.d_annot);
         if (s.d_motifs) (void) hipFree(s.d_motifs);
         if (s.h_motifs) (void) hipHostFree(s.h_motifs);
-        for (auto e : s.ev_annot)
-            if (e) (void) hipEventDestroy(e);
-        if (s.d_tract) (void) hipFree(s.d_tract);
-        for (auto e : s.ev_tract)
-            if (e) (void) hipEventDestroy(e);
-        if (s.d_ival_log) (void) hipFree(s.d_ival_log);
-        if (s.d_ival_counter) (void) hipFree(s.d_ival_counter);
-        if (s.d_ival_counts) (void) hipFree(s.d_ival_counts);
-        for (auto e : s.ev_ival)
-            if (e) (void) hipEventDestroy(e);
-        if (s.d_var) (void) hipFree(s.d_var);
-        if (s.d_var_hist) (void) hipFree(s.d_var_hist);
-        for (auto e : s.ev_var)
-            if (e) (void) hipEventDestroy(e);
+        for (auto &st : s.measure) {
+            for (void *p : {st.records.p, st.counts.p, (void *) st.counter, (void *) st.hist})
+                if (p) (void) hipFree(p);
+            for (auto e : st.ev)
+                if (e) (void) hipEventDestroy(e);
+        }
         if (s.ev_tail) (void) hipEventDestroy(s.ev_tail);
         if (s.ev_copied) (void) hipEventDestroy(s.ev_copied);
         if (s.stream) (void) hipStreamDestroy(s.stream);
@@ -1214,37 +1200,45 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read annotation against given motifs
-namespace {
-
-// T=0 G=1 C=2 A=3: the complement is 3 - code
-u64 motif_revcomp(u64 w, int k) {
-    u64 r = 0;
-    for (int i = 0; i < k; i++) {
-        r = (r << 2) | (3u - (w & 3u));
-        w >>= 2;
-    }
-    return r;
+// ---------------------------------------------------------------- per-read motif measures: annotate, tracts, intervals, variants
+// The four measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
+// Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
+extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
+    const std::string e = motif_parse(text, out);
+    if (!e.empty()) g_thread_error = g_init_error = e;
+    return e.empty() ? 0 : -1;
 }
 
-u64 motif_mask(int k) { return k >= 32 ? ~0ull : (1ull << (2 * k)) - 1ull; }
-
-const char *motif_error(const trew_hip_motif &m) {
-    if (m.k < 3 || m.k > 32) return "motif: k must be in [3, 32]";
-    if (m.word & ~motif_mask(m.k)) return "motif: word has bits above 2k";
-    return nullptr;
+// result of a trew_*_host definition -> status; the text goes where trew_hip_last_error finds it with or without a context
+static int host_status(const char *e) {
+    if (e) g_thread_error = g_init_error = e;
+    return e ? -1 : 0;
 }
 
-const char *motifs_error(const trew_hip_motif *motifs, int n_motifs) {
-    if (n_motifs < 1 || n_motifs > kAnnotMaxMotifs) return "n_motifs must be in [1, 8]";
-    if (!motifs) return "motifs is NULL";
-    for (int m = 0; m < n_motifs; m++)
-        if (const char *e = motif_error(motifs[m])) return e;
-    return nullptr;
+extern "C" int trew_annotate_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                  const trew_hip_motif *motifs, int n_motifs, trew_hip_annot *out) {
+    return host_status(annotate_host(words, offsets, lengths, n_reads, motifs, n_motifs, out));
+}
+
+extern "C" int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_tract *out) {
+    return host_status(tracts_host(words, offsets, lengths, n_reads, motifs, n_motifs, penalty, out));
+}
+
+extern "C" int trew_intervals_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                   const trew_hip_motif *motifs, const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out,
+                                   uint64_t cap, uint64_t *n, uint32_t *counts) {
+    return host_status(intervals_host(words, offsets, lengths, n_reads, motifs, rules, n_motifs, out, cap, n, counts));
+}
+
+extern "C" int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                  const trew_hip_motif *motifs, int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with) {
+    return host_status(variants_host(words, offsets, lengths, n_reads, motifs, n_motifs, out, hist, reads_with));
 }
 
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
-void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
+static void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
     memset(d, 0, sizeof(*d));
     d->k = (u32) m.k;
     const u64 target[2] = {m.word, motif_revcomp(m.word, m.k)};
@@ -1262,125 +1256,97 @@ void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
         }
 }
 
-}  // namespace
-
-extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
-    auto bad = [](const std::string &msg) {
-        g_thread_error = g_init_error = msg;
-        return -1;
-    };
-    if (!text || !out) return bad("trew_motif_parse: null argument");
-    const size_t k = strlen(text);
-    u64 w = 0;
-    for (size_t i = 0; i < k; i++) {
-        u32 c;
-        switch (text[i]) {
-        case 'T': case 't': c = 0; break;
-        case 'G': case 'g': c = 1; break;
-        case 'C': case 'c': c = 2; break;
-        case 'A': case 'a': c = 3; break;
-        default: return bad(std::string("motif '") + text + "': only A, C, G and T are allowed");
-        }
-        if (i < 32) w = (w << 2) | c;
-    }
-    if (k < 3 || k > 32) return bad(std::string("motif '") + text + "': the length must be in [3, 32]");
-    out->k = (int32_t) k;
-    out->reserved = 0;
-    out->word = w;
-    return 0;
-}
-
-extern "C" int trew_annotate_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
-                                  const trew_hip_motif *motifs, int n_motifs, trew_hip_annot *out) {
-    if (const char *e = motifs_error(motifs, n_motifs)) {
-        g_thread_error = g_init_error = e;
-        return -1;
-    }
-    if (n_reads && (!words || !offsets || !lengths || !out)) {
-        g_thread_error = g_init_error = "trew_annotate_host: null argument";
-        return -1;
-    }
-    // a window matches a strand when its word is one of the k rotations of the strand's target
-    struct Strand {
-        u64 rot[32];
-    };
-    std::vector<Strand> rots((size_t) n_motifs * 2);
-    for (int m = 0; m < n_motifs; m++) {
-        const int k = motifs[m].k;
-        const u64 mask = motif_mask(k);
-        u64 t[2] = {motifs[m].word, motif_revcomp(motifs[m].word, k)};
-        for (int s = 0; s < 2; s++)
-            for (int i = 0; i < k; i++) {
-                rots[(size_t) m * 2 + s].rot[i] = t[s];
-                t[s] = ((t[s] << 2) | (t[s] >> (2 * (k - 1)))) & mask;
-            }
-    }
-    for (u64 r = 0; r < n_reads; r++) {
-        const u32 *w = words + offsets[r];
-        const u32 n = lengths[r];
-        for (int m = 0; m < n_motifs; m++) {
-            const int k = motifs[m].k;
-            const u64 mask = motif_mask(k);
-            u32 cnt[2] = {0, 0}, best_len[2] = {0, 0}, best_start[2] = {0, 0}, run[2] = {0, 0};
-            u64 word = 0;
-            u32 clean = 0;  // bases since the last one with its nmask bit set
-            for (u32 i = 0; i < n; i++) {
-                const u32 j = i >> 5, b = i & 31u;
-                const u32 c = ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
-                clean = ((w[3 * j + 2] >> b) & 1u) ? 0 : clean + 1;
-                word = ((word << 2) | c) & mask;
-                if (i + 1 < (u32) k) continue;
-                const u32 start = i + 1 - (u32) k;  // the window that ends with base i
-                for (int s = 0; s < 2; s++) {
-                    bool hit = false;
-                    if (clean >= (u32) k)
-                        for (int x = 0; x < k && !hit; x++) hit = word == rots[(size_t) m * 2 + s].rot[x];
-                    if (hit) {
-                        cnt[s]++;
-                        if (++run[s] > best_len[s]) {  // strictly longer: the earliest run wins a tie
-                            best_len[s] = run[s];
-                            best_start[s] = start + 1 - run[s];
-                        }
-                    } else {
-                        run[s] = 0;
-                    }
-                }
-            }
-            trew_hip_annot &o = out[r * (u64) n_motifs + (u64) m];
-            o.windows_fwd = cnt[0];
-            o.windows_rev = cnt[1];
-            o.tract_start_fwd = best_len[0] ? best_start[0] : 0;
-            o.tract_len_fwd = best_len[0] ? best_len[0] + (u32) k - 1 : 0;
-            o.tract_start_rev = best_len[1] ? best_start[1] : 0;
-            o.tract_len_rev = best_len[1] ? best_len[1] + (u32) k - 1 : 0;
-        }
-    }
-    return 0;
-}
-
-// The pattern tables of a slot, shared by trew_hip_annotate and trew_hip_tracts: created by the first call that needs them
-// (each piece on its own, so that a failed call can simply be repeated); they travel on the slot's stream in front of the
-// kernel, and only when they changed.
+// The pattern tables of a slot, shared by the four measures: created by the first call that needs them (each piece on its
+// own, so that a failed call can simply be repeated); they travel on the slot's stream in front of the kernel, and only when
+// they changed.
 static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs, int n_motifs) {
     if (!s.d_motifs) HIPCHK(ctx, hipMalloc((void **) &s.d_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs));
     if (!s.h_motifs) HIPCHK(ctx, hipHostMalloc((void **) &s.h_motifs, sizeof(AnnotMotifDev) * kAnnotMaxMotifs, hipHostMallocDefault));
     AnnotMotifDev tab[kAnnotMaxMotifs];
     for (int m = 0; m < n_motifs; m++) fill_motif(motifs[m], &tab[m]);
-    if (s.annot_motifs_staged < n_motifs || memcmp(tab, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs) != 0) {
+    if (s.motifs_staged < n_motifs || memcmp(tab, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs) != 0) {
         HIPCHK(ctx, hipStreamSynchronize(s.stream));  // an earlier copy may still be reading the staging buffer
         memcpy(s.h_motifs, tab, sizeof(AnnotMotifDev) * (size_t) n_motifs);
         HIPCHK(ctx, hipMemcpyAsync(s.d_motifs, s.h_motifs, sizeof(AnnotMotifDev) * (size_t) n_motifs, hipMemcpyHostToDevice, s.stream));
-        s.annot_motifs_staged = n_motifs;
+        s.motifs_staged = n_motifs;
     }
     return 0;
 }
 
-extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
+// What every queue call does before anything of its own: the argument checks in the order callers see them (`own` holds
+// the measure's own checks; it runs behind the motifs' check and in front of the first HIP call), the batch and the motifs onto the slot's stream, and the measure's two events on its first use.
+template <class Own>
+static int measure_begin(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
+                         Own own, Slot **slot_out, DevBatch *db) {
     if (!ctx || !batch) return -1;
     if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
     if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
+    if (const char *e = own()) return fail(ctx, e);
     HIPCHK(ctx, hipSetDevice(ctx->p.device));
     Slot &s = ctx->slots[(size_t) slot];
+    if (int rc = stage_batch(ctx, batch, s, db)) return rc;  // also: the read index fits a record's u32
+    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
+    for (auto &e : s.measure[which].ev)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    *slot_out = &s;
+    return 0;
+}
+static const char *no_own_checks() { return nullptr; }
+
+// A device buffer that only grows.  The fields are zeroed between free and malloc, so that a call that fails here can
+// simply be repeated.
+static int grow(trew_hip_ctx *ctx, Slot &s, DevBuf &b, u64 want) {
+    if (want <= b.bytes) return 0;
+    HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
+    if (b.p) HIPCHK(ctx, hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    HIPCHK(ctx, hipMalloc(&b.p, want));
+    b.bytes = want;
+    return 0;
+}
+
+// the measure's kernel between its two events; `launch` returns a status and sets the error text like every other step
+template <class Launch>
+static int timed_launch(trew_hip_ctx *ctx, Slot &s, MeasureState &st, Launch launch) {
+    HIPCHK(ctx, hipEventRecord(st.ev[0], s.stream));
+    if (int rc = launch()) return rc;
+    HIPCHK(ctx, hipEventRecord(st.ev[1], s.stream));
+    st.timed = true;
+    return 0;
+}
+
+// What every results call does first: the checks (`arg_error`: the text of the measure's own argument check, which comes
+// behind the slot's), then the wait for the slot's stream.
+static int fetch_begin(trew_hip_ctx *ctx, int slot, Measure which, const char *arg_error, Slot **slot_out) {
+    if (!ctx) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    if (arg_error) return fail(ctx, arg_error);
+    Slot &s = ctx->slots[(size_t) slot];
+    if (!s.measure[which].valid) return fail(ctx, std::string("no trew_hip_") + kMeasureName[which] + " on this slot yet");
+    *slot_out = &s;
+    return trew_hip_wait(ctx, slot);
+}
+
+// the fixed-size records of annotate, tracts and variants: min(n, cap) of them; without `out` none (no error)
+static int fetch_records(trew_hip_ctx *ctx, const MeasureState &st, void *out, u64 cap, size_t rec_bytes, uint64_t *n) {
+    if (n) *n = st.n;
+    const u64 take = std::min<u64>(st.n, cap);
+    if (out && take) HIPCHK(ctx, hipMemcpy(out, st.records.p, take * rec_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int fetch_end(trew_hip_ctx *ctx, const MeasureState &st, float *ms_kernel) {
+    if (ms_kernel) {
+        *ms_kernel = 0.0f;
+        if (st.timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, st.ev[0], st.ev[1]));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- per-read annotation against given motifs
+extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
+    if (!ctx || !batch) return -1;
     // the longest read picks the kernel; none of the scan's read-length rules applies (no batch_geometry)
     u32 max_len = 0;
     bool general = (ctx->p.flags & TREW_FLAG_DEBUG_ANNOT_GENERAL) != 0;
@@ -1393,285 +1359,81 @@ extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch,
     } else {
         general = true;  // unknown
     }
+    Slot *sp = nullptr;
     DevBatch db;
-    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
-    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
-    for (auto &e : s.ev_annot)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kAnnotate, no_own_checks, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kAnnotate];
     const u64 need = db.n_reads * (u64) n_motifs;
-    if (need > s.annot_cap) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
-        if (s.d_annot) HIPCHK(ctx, hipFree(s.d_annot));
-        s.d_annot = nullptr;
-        s.annot_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **) &s.d_annot, need * sizeof(trew_hip_annot)));
-        s.annot_cap = need;
-    }
-    s.annot_valid = true;
-    s.annot_timed = false;
-    s.annot_n = need;
+    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_annot))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
     if (need == 0) return 0;
-    HIPCHK(ctx, hipEventRecord(s.ev_annot[0], s.stream));
-    HIPCHK(ctx, launch_annotate(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, max_len, general, s.d_annot));
-    HIPCHK(ctx, hipEventRecord(s.ev_annot[1], s.stream));
-    s.annot_timed = true;
-    return 0;
-}
-
-extern "C" int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_annot *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    if (!ctx) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    Slot &s = ctx->slots[(size_t) slot];
-    if (!s.annot_valid) return fail(ctx, "no trew_hip_annotate on this slot yet");
-    if (int rc = trew_hip_wait(ctx, slot)) return rc;
-    if (n) *n = s.annot_n;
-    const u64 take = std::min<u64>(s.annot_n, cap);
-    if (out && take) HIPCHK(ctx, hipMemcpy(out, s.d_annot, take * sizeof(trew_hip_annot), hipMemcpyDeviceToHost));
-    if (ms_kernel) {
-        *ms_kernel = 0.0f;
-        if (s.annot_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_annot[0], s.ev_annot[1]));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------- per-read error-tolerant terminal tracts
-// cov[p] (p < n) = some matching window of strand s of the motif contains base p: the definition, base by base over the
-// packed planes of one read.  Shared by trew_tracts_host and trew_intervals_host.
-static void host_coverage(const u32 *w, u32 n, const trew_hip_motif &motif, int s, std::vector<unsigned char> &cov) {
-    const int k = motif.k;
-    const u64 mask = motif_mask(k);
-    u64 rot[32], t = s ? motif_revcomp(motif.word, k) : motif.word;
-    for (int i = 0; i < k; i++) {
-        rot[i] = t;
-        t = ((t << 2) | (t >> (2 * (k - 1)))) & mask;
-    }
-    cov.assign((size_t) n, 0);
-    u64 word = 0;
-    u32 clean = 0;  // bases since the last one with its nmask bit set
-    for (u32 i = 0; i < n; i++) {
-        const u32 j = i >> 5, b = i & 31u;
-        const u32 c = ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
-        clean = ((w[3 * j + 2] >> b) & 1u) ? 0 : clean + 1;
-        word = ((word << 2) | c) & mask;
-        if (clean < (u32) k) continue;  // also: fewer than k bases so far
-        bool hit = false;
-        for (int x = 0; x < k && !hit; x++) hit = word == rot[x];
-        if (hit)
-            for (u32 p = i + 1 - (u32) k; p <= i; p++) cov[p] = 1;
-    }
-}
-
-extern "C" int trew_tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
-                                const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_tract *out) {
-    const char *e = motifs_error(motifs, n_motifs);
-    if (!e && (penalty < 1 || penalty > 64)) e = "penalty must be in [1, 64]";
-    if (!e && n_reads && (!words || !offsets || !lengths || !out)) e = "trew_tracts_host: null argument";
-    if (e) {
-        g_thread_error = g_init_error = e;
-        return -1;
-    }
-    std::vector<unsigned char> cov;
-    for (u64 r = 0; r < n_reads; r++) {
-        const u32 *w = words + offsets[r];
-        const u32 n = lengths[r];
-        for (int m = 0; m < n_motifs; m++) {
-            u32 res[2][5];
-            for (int s = 0; s < 2; s++) {
-                host_coverage(w, n, motifs[m], s, cov);
-                // S(e), e = 0 .. n: the earliest largest value and the latest smallest value; covered counts alongside
-                long long S = 0, hi = 0, lo = 0;
-                u32 e_hi = 0, e_lo = 0, c = 0, c_hi = 0, c_lo = 0;
-                for (u32 p = 0; p < n; p++) {
-                    S += cov[p] ? 1 : -(long long) penalty;
-                    c += cov[p];
-                    if (S > hi) {
-                        hi = S;
-                        e_hi = p + 1;
-                        c_hi = c;
-                    }
-                    if (S <= lo) {
-                        lo = S;
-                        e_lo = p + 1;
-                        c_lo = c;
-                    }
-                }
-                res[s][0] = c;
-                res[s][1] = e_hi;
-                res[s][2] = c_hi;
-                res[s][3] = n - e_lo;
-                res[s][4] = c - c_lo;
-            }
-            trew_hip_tract &o = out[r * (u64) n_motifs + (u64) m];
-            o.covered_fwd = res[0][0];
-            o.head_len_fwd = res[0][1];
-            o.head_cov_fwd = res[0][2];
-            o.tail_len_fwd = res[0][3];
-            o.tail_cov_fwd = res[0][4];
-            o.covered_rev = res[1][0];
-            o.head_len_rev = res[1][1];
-            o.head_cov_rev = res[1][2];
-            o.tail_len_rev = res[1][3];
-            o.tail_cov_rev = res[1][4];
-        }
-    }
-    return 0;
-}
-
-extern "C" int trew_hip_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty) {
-    if (!ctx || !batch) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
-    if (penalty < 1 || penalty > 64) return fail(ctx, "penalty must be in [1, 64]");
-    HIPCHK(ctx, hipSetDevice(ctx->p.device));
-    Slot &s = ctx->slots[(size_t) slot];
-    DevBatch db;
-    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
-    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
-    for (auto &e : s.ev_tract)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    const u64 need = db.n_reads * (u64) n_motifs;
-    if (need > s.tract_cap) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
-        if (s.d_tract) HIPCHK(ctx, hipFree(s.d_tract));
-        s.d_tract = nullptr;
-        s.tract_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **) &s.d_tract, need * sizeof(trew_hip_tract)));
-        s.tract_cap = need;
-    }
-    s.tract_valid = true;
-    s.tract_timed = false;
-    s.tract_n = need;
-    if (need == 0) return 0;
-    HIPCHK(ctx, hipEventRecord(s.ev_tract[0], s.stream));
-    HIPCHK(ctx, launch_tracts(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, s.d_tract));
-    HIPCHK(ctx, hipEventRecord(s.ev_tract[1], s.stream));
-    s.tract_timed = true;
-    return 0;
-}
-
-extern "C" int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tract *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    if (!ctx) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    Slot &s = ctx->slots[(size_t) slot];
-    if (!s.tract_valid) return fail(ctx, "no trew_hip_tracts on this slot yet");
-    if (int rc = trew_hip_wait(ctx, slot)) return rc;
-    if (n) *n = s.tract_n;
-    const u64 take = std::min<u64>(s.tract_n, cap);
-    if (out && take) HIPCHK(ctx, hipMemcpy(out, s.d_tract, take * sizeof(trew_hip_tract), hipMemcpyDeviceToHost));
-    if (ms_kernel) {
-        *ms_kernel = 0.0f;
-        if (s.tract_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_tract[0], s.ev_tract[1]));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------- gap-tolerant motif intervals anywhere in a read
-static const char *rules_error(const trew_hip_interval_rule *rules, int n_motifs) {
-    if (!rules) return "rules must not be null";
-    for (int m = 0; m < n_motifs; m++)
-        if (rules[m].min_len < 1) return "min_len must be at least 1";
-    return nullptr;
-}
-static void sort_intervals(trew_hip_interval *v, u64 n) {
-    std::sort(v, v + n, [](const trew_hip_interval &a, const trew_hip_interval &b) {
-        if (a.read != b.read) return a.read < b.read;
-        if (a.motif != b.motif) return a.motif < b.motif;
-        if (a.strand != b.strand) return a.strand < b.strand;
-        return a.start < b.start;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_annotate(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, max_len, general, (trew_hip_annot *) st.records.p));
+        return 0;
     });
 }
 
-extern "C" int trew_intervals_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
-                                   const trew_hip_motif *motifs, const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out,
-                                   uint64_t cap, uint64_t *n, uint32_t *counts) {
-    const char *e = motifs_error(motifs, n_motifs);
-    if (!e) e = rules_error(rules, n_motifs);
-    if (!e && (!n || (cap && !out))) e = "trew_intervals_host: null argument";
-    if (!e && n_reads && (!words || !offsets || !lengths)) e = "trew_intervals_host: null argument";
-    if (!e && n_reads > 0xffffffffull) e = "trew_intervals_host: more than 2^32 - 1 reads";
-    if (e) {
-        g_thread_error = g_init_error = e;
-        return -1;
-    }
-    std::vector<unsigned char> cov;
-    u64 found = 0;
-    for (u64 r = 0; r < n_reads; r++) {
-        const u32 *w = words + offsets[r];
-        const u32 len = lengths[r];
-        for (int m = 0; m < n_motifs; m++) {
-            for (int s = 0; s < 2; s++) {
-                host_coverage(w, len, motifs[m], s, cov);
-                u32 kept = 0;
-                bool open = false;
-                u32 start = 0, last = 0, c = 0;  // of the open interval: first and last covered position, covered bases
-                auto close = [&]() {
-                    if (open && last + 1 - start >= rules[m].min_len) {
-                        if (found < cap) out[found] = trew_hip_interval{(u32) r, (u32) m, (u32) s, start, last + 1, c};
-                        found++;
-                        kept++;
-                    }
-                };
-                for (u32 p = 0; p < len; p++) {
-                    if (!cov[p]) continue;
-                    if (open && p - last - 1 > rules[m].max_gap) {
-                        close();
-                        open = false;
-                    }
-                    if (!open) {
-                        open = true;
-                        start = p;
-                        c = 0;
-                    }
-                    last = p;
-                    c++;
-                }
-                close();
-                if (counts) counts[(r * (u64) n_motifs + (u64) m) * 2ull + (u64) s] = kept;
-            }
-        }
-    }
-    *n = found;
-    sort_intervals(out, std::min<u64>(found, cap));  // already in this order: reads, motifs, strands and positions ascend
-    return 0;
+extern "C" int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_annot *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kAnnotate, nullptr, &sp)) return rc;
+    const MeasureState &st = sp->measure[kAnnotate];
+    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_annot), n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
 }
 
+// ---------------------------------------------------------------- per-read error-tolerant terminal tracts
+extern "C" int trew_hip_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * { return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr; };
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kTracts, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kTracts];
+    const u64 need = db.n_reads * (u64) n_motifs;
+    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_tract))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    if (need == 0) return 0;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_tracts(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_tract *) st.records.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tract *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kTracts, nullptr, &sp)) return rc;
+    const MeasureState &st = sp->measure[kTracts];
+    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_tract), n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- gap-tolerant motif intervals anywhere in a read
 extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs,
                                   const trew_hip_interval_rule *rules, int n_motifs, uint64_t max_intervals) {
-    if (!ctx || !batch) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
-    if (const char *e = rules_error(rules, n_motifs)) return fail(ctx, e);
-    if (max_intervals < 1) return fail(ctx, "max_intervals must be at least 1");
-    HIPCHK(ctx, hipSetDevice(ctx->p.device));
-    Slot &s = ctx->slots[(size_t) slot];
+    Slot *sp = nullptr;
     DevBatch db;
-    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;  // also: the read index fits the record's u32
-    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
-    for (auto &e : s.ev_ival)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    if (!s.d_ival_counter) HIPCHK(ctx, hipMalloc((void **) &s.d_ival_counter, sizeof(unsigned long long)));
+    auto own = [&]() -> const char * {
+        if (const char *e = rules_error(rules, n_motifs)) return e;
+        return max_intervals < 1 ? "max_intervals must be at least 1" : nullptr;
+    };
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kIntervals, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kIntervals];
     const u64 keys = db.n_reads * (u64) n_motifs * 2ull;
-    if (keys > s.ival_counts_cap || max_intervals > s.ival_log_cap) HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffers
-    if (keys > s.ival_counts_cap) {
-        if (s.d_ival_counts) HIPCHK(ctx, hipFree(s.d_ival_counts));
-        s.d_ival_counts = nullptr;
-        s.ival_counts_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **) &s.d_ival_counts, keys * sizeof(u32)));
-        s.ival_counts_cap = keys;
-    }
-    if (max_intervals > s.ival_log_cap) {
-        if (s.d_ival_log) HIPCHK(ctx, hipFree(s.d_ival_log));
-        s.d_ival_log = nullptr;
-        s.ival_log_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **) &s.d_ival_log, max_intervals * sizeof(trew_hip_interval)));
-        s.ival_log_cap = max_intervals;
-    }
-    s.ival_valid = true;
-    s.ival_timed = false;
-    s.ival_max = max_intervals;
-    s.ival_keys = keys;
+    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
+    if (int rc = grow(ctx, s, st.counts, keys * sizeof(u32))) return rc;
+    if (int rc = grow(ctx, s, st.records, max_intervals * sizeof(trew_hip_interval))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.max_log = max_intervals;
+    st.n_counts = keys;
     // the counter starts every call at zero, also a call without reads (its results then report no interval)
-    HIPCHK(ctx, hipMemsetAsync(s.d_ival_counter, 0, sizeof(unsigned long long), s.stream));
+    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
     if (keys == 0) return 0;
     IntervalRulesDev rd;
     memset(&rd, 0, sizeof(rd));
@@ -1680,187 +1442,81 @@ extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch
         rd.min_len[m] = rules[m].min_len;
     }
     IntervalLog lg;
-    lg.counter = s.d_ival_counter;
-    lg.recs = s.d_ival_log;
+    lg.counter = st.counter;
+    lg.recs = (u32 *) st.records.p;
     lg.cap = max_intervals;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
-    HIPCHK(ctx, hipEventRecord(s.ev_ival[0], s.stream));
-    HIPCHK(ctx, launch_intervals(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, rd, lg, s.d_ival_counts));
-    HIPCHK(ctx, hipEventRecord(s.ev_ival[1], s.stream));
-    s.ival_timed = true;
-    return 0;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_intervals(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, rd, lg, (u32 *) st.counts.p));
+        return 0;
+    });
 }
 
 extern "C" int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts,
                                           float *ms_kernel) {
-    if (!ctx) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    if (!n) return fail(ctx, "trew_hip_intervals_results: n must not be null");
-    if (cap && !out) return fail(ctx, "trew_hip_intervals_results: out must not be null");
-    Slot &s = ctx->slots[(size_t) slot];
-    if (!s.ival_valid) return fail(ctx, "no trew_hip_intervals on this slot yet");
-    if (int rc = trew_hip_wait(ctx, slot)) return rc;
+    // unlike the other three, this call needs `n` (the only way to learn of an overflow), and like variants it refuses a
+    // capacity without a buffer
+    const char *arg_error = !n ? "trew_hip_intervals_results: n must not be null" : cap && !out ? "trew_hip_intervals_results: out must not be null" : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kIntervals, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kIntervals];
     unsigned long long found = 0;
-    HIPCHK(ctx, hipMemcpy(&found, s.d_ival_counter, sizeof(found), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
     *n = found;
-    if (counts && s.ival_keys) HIPCHK(ctx, hipMemcpy(counts, s.d_ival_counts, s.ival_keys * sizeof(u32), hipMemcpyDeviceToHost));
-    const u64 in_log = std::min<u64>(found, s.ival_max);
+    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
+    const u64 in_log = std::min<u64>(found, st.max_log);
     const u64 take = std::min<u64>(in_log, cap);
     if (take) {
         // sorted on the host, so the records do not depend on the order in which the waves appended them
         if (take == in_log) {
-            HIPCHK(ctx, hipMemcpy(out, s.d_ival_log, take * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
             sort_intervals(out, take);
         } else {  // a buffer smaller than the log: the first `cap` of the sorted log
             std::vector<trew_hip_interval> all((size_t) in_log);
-            HIPCHK(ctx, hipMemcpy(all.data(), s.d_ival_log, in_log * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, in_log * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
             sort_intervals(all.data(), in_log);
             memcpy(out, all.data(), take * sizeof(trew_hip_interval));
         }
     }
-    if (ms_kernel) {
-        *ms_kernel = 0.0f;
-        if (s.ival_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_ival[0], s.ev_ival[1]));
-    }
-    return 0;
+    return fetch_end(ctx, st, ms_kernel);
 }
 
 // ---------------------------------------------------------------- telomere variant repeats
 constexpr u64 kVarHistLen = (u64) kAnnotMaxMotifs * 2ull * TREW_VARIANT_BINS;  // values of one histogram of a slot
 
-extern "C" int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
-                                  const trew_hip_motif *motifs, int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with) {
-    const char *e = motifs_error(motifs, n_motifs);
-    if (!e && n_reads && (!words || !offsets || !lengths || !out)) e = "trew_variants_host: null argument";
-    if (e) {
-        g_thread_error = g_init_error = e;
-        return -1;
-    }
-    const size_t hl = (size_t) n_motifs * 2 * TREW_VARIANT_BINS;
-    if (hist) memset(hist, 0, hl * sizeof(uint64_t));
-    if (reads_with) memset(reads_with, 0, hl * sizeof(uint64_t));
-    std::vector<unsigned char> base, state;  // per base: code, or 4 with its nmask bit set; per window: 1 exact, 2 variant
-    std::vector<u32> bin_of;
-    for (u64 r = 0; r < n_reads; r++) {
-        const u32 *w = words + offsets[r];
-        const u32 n = lengths[r];
-        base.resize(n);
-        for (u32 i = 0; i < n; i++) {
-            const u32 j = i >> 5, b = i & 31u;
-            base[i] = ((w[3 * j + 2] >> b) & 1u) ? 4 : (unsigned char) (((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1));
-        }
-        for (int m = 0; m < n_motifs; m++) {
-            const u32 k = (u32) motifs[m].k;
-            u32 res[2][5];
-            for (int s = 0; s < 2; s++) {
-                const u64 t = s ? motif_revcomp(motifs[m].word, (int) k) : motifs[m].word;
-                u32 *o = res[s];
-                o[0] = o[1] = o[2] = o[4] = 0;
-                o[3] = TREW_VARIANT_NONE;
-                if (n < k) continue;
-                const u32 nwin = n - k + 1;
-                state.assign(nwin, 0);
-                bin_of.assign(nwin, 0);
-                for (u32 i = 0; i < nwin; i++) {
-                    u32 mism = 0, jj = 0, cc = 0;
-                    bool valid = true;
-                    for (u32 j = 0; j < k && valid; j++) {
-                        const u32 c = base[i + j];
-                        if (c > 3) valid = false;
-                        else if (c != ((u32) (t >> (2 * (k - 1 - j))) & 3u)) {
-                            mism++;
-                            jj = j;
-                            cc = c;
-                        }
-                    }
-                    if (!valid) continue;
-                    if (mism == 0) state[i] = 1;
-                    if (mism == 1) {
-                        state[i] = 2;
-                        bin_of[i] = s ? 4u * (k - 1u - jj) + (3u - cc) : 4u * jj + cc;
-                    }
-                }
-                u32 bins[TREW_VARIANT_BINS] = {};
-                for (u32 i = 0; i < nwin; i++) {
-                    if (state[i] == 1) o[0]++;
-                    if (state[i] != 2) continue;
-                    const bool anchored = (i >= k && state[i - k] == 1) || ((u64) i + k < nwin && state[i + k] == 1);
-                    if (anchored) {
-                        o[1]++;
-                        bins[bin_of[i]]++;
-                    }
-                }
-                for (u32 b = 0; b < TREW_VARIANT_BINS; b++) {
-                    if (!bins[b]) continue;
-                    o[2]++;
-                    if (bins[b] > o[4]) {  // strictly: the smallest bin keeps a tie
-                        o[4] = bins[b];
-                        o[3] = b;
-                    }
-                    const size_t at = ((size_t) m * 2 + (size_t) s) * TREW_VARIANT_BINS + b;
-                    if (hist) hist[at] += bins[b];
-                    if (reads_with) reads_with[at]++;
-                }
-            }
-            memcpy(&out[r * (u64) n_motifs + (u64) m], res, sizeof(trew_hip_variant));
-        }
-    }
-    return 0;
-}
-
 extern "C" int trew_hip_variants(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
-    if (!ctx || !batch) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
-    HIPCHK(ctx, hipSetDevice(ctx->p.device));
-    Slot &s = ctx->slots[(size_t) slot];
+    Slot *sp = nullptr;
     DevBatch db;
-    if (int rc = stage_batch(ctx, batch, s, &db)) return rc;
-    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
-    for (auto &e : s.ev_var)
-        if (!e) HIPCHK(ctx, hipEventCreate(&e));
-    if (!s.d_var_hist) HIPCHK(ctx, hipMalloc((void **) &s.d_var_hist, 2ull * kVarHistLen * sizeof(unsigned long long)));
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kVariants, no_own_checks, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kVariants];
     const u64 need = db.n_reads * (u64) n_motifs;
-    if (need > s.var_cap) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // nothing may still be writing the old buffer
-        if (s.d_var) HIPCHK(ctx, hipFree(s.d_var));
-        s.d_var = nullptr;
-        s.var_cap = 0;
-        HIPCHK(ctx, hipMalloc((void **) &s.d_var, need * sizeof(trew_hip_variant)));
-        s.var_cap = need;
-    }
-    s.var_valid = true;
-    s.var_timed = false;
-    s.var_n = need;
-    s.var_motifs = n_motifs;
+    if (!st.hist) HIPCHK(ctx, hipMalloc((void **) &st.hist, 2ull * kVarHistLen * sizeof(unsigned long long)));  // a fixed size: never grows
+    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_variant))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    st.n_motifs = n_motifs;
     // both histograms start every call at zero, also a call without reads
-    HIPCHK(ctx, hipMemsetAsync(s.d_var_hist, 0, 2ull * kVarHistLen * sizeof(unsigned long long), s.stream));
+    HIPCHK(ctx, hipMemsetAsync(st.hist, 0, 2ull * kVarHistLen * sizeof(unsigned long long), s.stream));
     if (need == 0) return 0;
-    HIPCHK(ctx, hipEventRecord(s.ev_var[0], s.stream));
-    HIPCHK(ctx, launch_variants(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, s.d_var, s.d_var_hist, s.d_var_hist + kVarHistLen));
-    HIPCHK(ctx, hipEventRecord(s.ev_var[1], s.stream));
-    s.var_timed = true;
-    return 0;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_variants(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, (trew_hip_variant *) st.records.p, st.hist, st.hist + kVarHistLen));
+        return 0;
+    });
 }
 
 extern "C" int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_variant *out, uint64_t cap, uint64_t *n, uint64_t *hist,
                                          uint64_t *reads_with, float *ms_kernel) {
-    if (!ctx) return -1;
-    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    if (cap && !out) return fail(ctx, "trew_hip_variants_results: out must not be null");
-    Slot &s = ctx->slots[(size_t) slot];
-    if (!s.var_valid) return fail(ctx, "no trew_hip_variants on this slot yet");
-    if (int rc = trew_hip_wait(ctx, slot)) return rc;
-    if (n) *n = s.var_n;
-    const u64 take = std::min<u64>(s.var_n, cap);
-    if (out && take) HIPCHK(ctx, hipMemcpy(out, s.d_var, take * sizeof(trew_hip_variant), hipMemcpyDeviceToHost));
-    const size_t hb = (size_t) s.var_motifs * 2 * TREW_VARIANT_BINS * sizeof(uint64_t);
-    if (hist && hb) HIPCHK(ctx, hipMemcpy(hist, s.d_var_hist, hb, hipMemcpyDeviceToHost));
-    if (reads_with && hb) HIPCHK(ctx, hipMemcpy(reads_with, s.d_var_hist + kVarHistLen, hb, hipMemcpyDeviceToHost));
-    if (ms_kernel) {
-        *ms_kernel = 0.0f;
-        if (s.var_timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, s.ev_var[0], s.ev_var[1]));
-    }
-    return 0;
+    // unlike annotate and tracts, which copy nothing when `out` is NULL, a capacity without a buffer is an error here
+    const char *arg_error = cap && !out ? "trew_hip_variants_results: out must not be null" : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kVariants, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kVariants];
+    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_variant), n)) return rc;
+    const size_t hb = (size_t) st.n_motifs * 2 * TREW_VARIANT_BINS * sizeof(uint64_t);
+    if (hist && hb) HIPCHK(ctx, hipMemcpy(hist, st.hist, hb, hipMemcpyDeviceToHost));
+    if (reads_with && hb) HIPCHK(ctx, hipMemcpy(reads_with, st.hist + kVarHistLen, hb, hipMemcpyDeviceToHost));
+    return fetch_end(ctx, st, ms_kernel);
 }
 
 // ---------------------------------------------------------------- host packing

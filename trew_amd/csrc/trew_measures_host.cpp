@@ -1,0 +1,347 @@
+// trew_measures_host.cpp -- the four per-read motif measures on the CPU, base by base from their definitions (see
+// trew_measures_host.hpp).  These are what the kernels are checked against: they are written to be read, not to be fast.
+#include "trew_measures_host.hpp"
+
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace trew {
+
+typedef uint32_t u32;
+typedef uint64_t u64;
+
+u64 motif_revcomp(u64 w, int k) {
+    u64 r = 0;
+    for (int i = 0; i < k; i++) {
+        r = (r << 2) | (3u - (w & 3u));
+        w >>= 2;
+    }
+    return r;
+}
+
+u64 motif_mask(int k) { return k >= 32 ? ~0ull : (1ull << (2 * k)) - 1ull; }
+
+const char *motif_error(const trew_hip_motif &m) {
+    if (m.k < 3 || m.k > 32) return "motif: k must be in [3, 32]";
+    if (m.word & ~motif_mask(m.k)) return "motif: word has bits above 2k";
+    return nullptr;
+}
+
+const char *motifs_error(const trew_hip_motif *motifs, int n_motifs) {
+    if (n_motifs < 1 || n_motifs > TREW_ANNOT_MAX_MOTIFS) return "n_motifs must be in [1, 8]";
+    if (!motifs) return "motifs is NULL";
+    for (int m = 0; m < n_motifs; m++)
+        if (const char *e = motif_error(motifs[m])) return e;
+    return nullptr;
+}
+
+const char *rules_error(const trew_hip_interval_rule *rules, int n_motifs) {
+    if (!rules) return "rules must not be null";
+    for (int m = 0; m < n_motifs; m++)
+        if (rules[m].min_len < 1) return "min_len must be at least 1";
+    return nullptr;
+}
+
+void sort_intervals(trew_hip_interval *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_interval &a, const trew_hip_interval &b) {
+        if (a.read != b.read) return a.read < b.read;
+        if (a.motif != b.motif) return a.motif < b.motif;
+        if (a.strand != b.strand) return a.strand < b.strand;
+        return a.start < b.start;
+    });
+}
+
+std::string motif_parse(const char *text, trew_hip_motif *out) {
+    if (!text || !out) return "trew_motif_parse: null argument";
+    const size_t k = strlen(text);
+    u64 w = 0;
+    for (size_t i = 0; i < k; i++) {
+        u32 c;
+        switch (text[i]) {
+        case 'T': case 't': c = 0; break;
+        case 'G': case 'g': c = 1; break;
+        case 'C': case 'c': c = 2; break;
+        case 'A': case 'a': c = 3; break;
+        default: return std::string("motif '") + text + "': only A, C, G and T are allowed";
+        }
+        if (i < 32) w = (w << 2) | c;
+    }
+    if (k < 3 || k > 32) return std::string("motif '") + text + "': the length must be in [3, 32]";
+    out->k = (int32_t) k;
+    out->reserved = 0;
+    out->word = w;
+    return "";
+}
+
+// base i of a read's packed planes: its code, or 4 with its nmask bit set
+static u32 base_at(const u32 *w, u32 i) {
+    const u32 j = i >> 5, b = i & 31u;
+    if ((w[3 * j + 2] >> b) & 1u) return 4;
+    return ((w[3 * j] >> b) & 1u) | (((w[3 * j + 1] >> b) & 1u) << 1);
+}
+
+// a window matches strand s of a motif when its word is one of the k rotations of the strand's target
+struct Rotations {
+    int k;
+    u64 rot[32];
+    Rotations(const trew_hip_motif &motif, int s) : k(motif.k) {
+        const u64 mask = motif_mask(k);
+        u64 t = s ? motif_revcomp(motif.word, k) : motif.word;
+        for (int i = 0; i < k; i++) {
+            rot[i] = t;
+            t = ((t << 2) | (t >> (2 * (k - 1)))) & mask;
+        }
+    }
+    bool match(u64 word) const {
+        bool hit = false;
+        for (int x = 0; x < k && !hit; x++) hit = word == rot[x];
+        return hit;
+    }
+};
+
+// ---------------------------------------------------------------- per-read annotation against given motifs
+const char *annotate_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
+                          trew_hip_annot *out) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_annotate_host: null argument";
+    std::vector<Rotations> rots;
+    for (int m = 0; m < n_motifs; m++)
+        for (int s = 0; s < 2; s++) rots.emplace_back(motifs[m], s);
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        for (int m = 0; m < n_motifs; m++) {
+            const int k = motifs[m].k;
+            const u64 mask = motif_mask(k);
+            u32 cnt[2] = {0, 0}, best_len[2] = {0, 0}, best_start[2] = {0, 0}, run[2] = {0, 0};
+            u64 word = 0;
+            u32 clean = 0;  // bases since the last one with its nmask bit set
+            for (u32 i = 0; i < n; i++) {
+                const u32 c = base_at(w, i);
+                clean = c > 3 ? 0 : clean + 1;
+                word = ((word << 2) | (c & 3u)) & mask;
+                if (i + 1 < (u32) k) continue;
+                const u32 start = i + 1 - (u32) k;  // the window that ends with base i
+                for (int s = 0; s < 2; s++) {
+                    if (clean >= (u32) k && rots[(size_t) m * 2 + s].match(word)) {
+                        cnt[s]++;
+                        if (++run[s] > best_len[s]) {  // strictly longer: the earliest run wins a tie
+                            best_len[s] = run[s];
+                            best_start[s] = start + 1 - run[s];
+                        }
+                    } else {
+                        run[s] = 0;
+                    }
+                }
+            }
+            trew_hip_annot &o = out[r * (u64) n_motifs + (u64) m];
+            o.windows_fwd = cnt[0];
+            o.windows_rev = cnt[1];
+            o.tract_start_fwd = best_len[0] ? best_start[0] : 0;
+            o.tract_len_fwd = best_len[0] ? best_len[0] + (u32) k - 1 : 0;
+            o.tract_start_rev = best_len[1] ? best_start[1] : 0;
+            o.tract_len_rev = best_len[1] ? best_len[1] + (u32) k - 1 : 0;
+        }
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- per-read error-tolerant terminal tracts
+// cov[p] (p < n) = some matching window of strand s of the motif contains base p: the definition, base by base over the
+// packed planes of one read.  Shared by tracts_host and intervals_host.
+static void host_coverage(const u32 *w, u32 n, const trew_hip_motif &motif, int s, std::vector<unsigned char> &cov) {
+    const int k = motif.k;
+    const u64 mask = motif_mask(k);
+    const Rotations rots(motif, s);
+    cov.assign((size_t) n, 0);
+    u64 word = 0;
+    u32 clean = 0;  // bases since the last one with its nmask bit set
+    for (u32 i = 0; i < n; i++) {
+        const u32 c = base_at(w, i);
+        clean = c > 3 ? 0 : clean + 1;
+        word = ((word << 2) | (c & 3u)) & mask;
+        if (clean < (u32) k) continue;  // also: fewer than k bases so far
+        if (rots.match(word))
+            for (u32 p = i + 1 - (u32) k; p <= i; p++) cov[p] = 1;
+    }
+}
+
+const char *tracts_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
+                        int penalty, trew_hip_tract *out) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_tracts_host: null argument";
+    std::vector<unsigned char> cov;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        for (int m = 0; m < n_motifs; m++) {
+            u32 res[2][5];
+            for (int s = 0; s < 2; s++) {
+                host_coverage(w, n, motifs[m], s, cov);
+                // S(e), e = 0 .. n: the earliest largest value and the latest smallest value; covered counts alongside
+                long long S = 0, hi = 0, lo = 0;
+                u32 e_hi = 0, e_lo = 0, c = 0, c_hi = 0, c_lo = 0;
+                for (u32 p = 0; p < n; p++) {
+                    S += cov[p] ? 1 : -(long long) penalty;
+                    c += cov[p];
+                    if (S > hi) {
+                        hi = S;
+                        e_hi = p + 1;
+                        c_hi = c;
+                    }
+                    if (S <= lo) {
+                        lo = S;
+                        e_lo = p + 1;
+                        c_lo = c;
+                    }
+                }
+                res[s][0] = c;
+                res[s][1] = e_hi;
+                res[s][2] = c_hi;
+                res[s][3] = n - e_lo;
+                res[s][4] = c - c_lo;
+            }
+            trew_hip_tract &o = out[r * (u64) n_motifs + (u64) m];
+            o.covered_fwd = res[0][0];
+            o.head_len_fwd = res[0][1];
+            o.head_cov_fwd = res[0][2];
+            o.tail_len_fwd = res[0][3];
+            o.tail_cov_fwd = res[0][4];
+            o.covered_rev = res[1][0];
+            o.head_len_rev = res[1][1];
+            o.head_cov_rev = res[1][2];
+            o.tail_len_rev = res[1][3];
+            o.tail_cov_rev = res[1][4];
+        }
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- gap-tolerant motif intervals anywhere in a read
+const char *intervals_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs,
+                           const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out, u64 cap, u64 *n, u32 *counts) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (const char *e = rules_error(rules, n_motifs)) return e;
+    if (!n || (cap && !out)) return "trew_intervals_host: null argument";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_intervals_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_intervals_host: more than 2^32 - 1 reads";
+    std::vector<unsigned char> cov;
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 len = lengths[r];
+        for (int m = 0; m < n_motifs; m++) {
+            for (int s = 0; s < 2; s++) {
+                host_coverage(w, len, motifs[m], s, cov);
+                u32 kept = 0;
+                bool open = false;
+                u32 start = 0, last = 0, c = 0;  // of the open interval: first and last covered position, covered bases
+                auto close = [&]() {
+                    if (open && last + 1 - start >= rules[m].min_len) {
+                        if (found < cap) out[found] = trew_hip_interval{(u32) r, (u32) m, (u32) s, start, last + 1, c};
+                        found++;
+                        kept++;
+                    }
+                };
+                for (u32 p = 0; p < len; p++) {
+                    if (!cov[p]) continue;
+                    if (open && p - last - 1 > rules[m].max_gap) {
+                        close();
+                        open = false;
+                    }
+                    if (!open) {
+                        open = true;
+                        start = p;
+                        c = 0;
+                    }
+                    last = p;
+                    c++;
+                }
+                close();
+                if (counts) counts[(r * (u64) n_motifs + (u64) m) * 2ull + (u64) s] = kept;
+            }
+        }
+    }
+    *n = found;
+    sort_intervals(out, std::min<u64>(found, cap));  // already in this order: reads, motifs, strands and positions ascend
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- telomere variant repeats
+const char *variants_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
+                          trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_variants_host: null argument";
+    const size_t hl = (size_t) n_motifs * 2 * TREW_VARIANT_BINS;
+    if (hist) memset(hist, 0, hl * sizeof(uint64_t));
+    if (reads_with) memset(reads_with, 0, hl * sizeof(uint64_t));
+    std::vector<unsigned char> base, state;  // per base: code, or 4 with its nmask bit set; per window: 1 exact, 2 variant
+    std::vector<u32> bin_of;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        base.resize(n);
+        for (u32 i = 0; i < n; i++) base[i] = (unsigned char) base_at(w, i);
+        for (int m = 0; m < n_motifs; m++) {
+            const u32 k = (u32) motifs[m].k;
+            u32 res[2][5];
+            for (int s = 0; s < 2; s++) {
+                const u64 t = s ? motif_revcomp(motifs[m].word, (int) k) : motifs[m].word;
+                u32 *o = res[s];
+                o[0] = o[1] = o[2] = o[4] = 0;
+                o[3] = TREW_VARIANT_NONE;
+                if (n < k) continue;
+                const u32 nwin = n - k + 1;
+                state.assign(nwin, 0);
+                bin_of.assign(nwin, 0);
+                for (u32 i = 0; i < nwin; i++) {
+                    u32 mism = 0, jj = 0, cc = 0;
+                    bool valid = true;
+                    for (u32 j = 0; j < k && valid; j++) {
+                        const u32 c = base[i + j];
+                        if (c > 3) valid = false;
+                        else if (c != ((u32) (t >> (2 * (k - 1 - j))) & 3u)) {
+                            mism++;
+                            jj = j;
+                            cc = c;
+                        }
+                    }
+                    if (!valid) continue;
+                    if (mism == 0) state[i] = 1;
+                    if (mism == 1) {
+                        state[i] = 2;
+                        bin_of[i] = s ? 4u * (k - 1u - jj) + (3u - cc) : 4u * jj + cc;
+                    }
+                }
+                u32 bins[TREW_VARIANT_BINS] = {};
+                for (u32 i = 0; i < nwin; i++) {
+                    if (state[i] == 1) o[0]++;
+                    if (state[i] != 2) continue;
+                    const bool anchored = (i >= k && state[i - k] == 1) || ((u64) i + k < nwin && state[i + k] == 1);
+                    if (anchored) {
+                        o[1]++;
+                        bins[bin_of[i]]++;
+                    }
+                }
+                for (u32 b = 0; b < TREW_VARIANT_BINS; b++) {
+                    if (!bins[b]) continue;
+                    o[2]++;
+                    if (bins[b] > o[4]) {  // strictly: the smallest bin keeps a tie
+                        o[4] = bins[b];
+                        o[3] = b;
+                    }
+                    const size_t at = ((size_t) m * 2 + (size_t) s) * TREW_VARIANT_BINS + b;
+                    if (hist) hist[at] += bins[b];
+                    if (reads_with) reads_with[at]++;
+                }
+            }
+            memcpy(&out[r * (u64) n_motifs + (u64) m], res, sizeof(trew_hip_variant));
+        }
+    }
+    return nullptr;
+}
+
+}  // namespace trew

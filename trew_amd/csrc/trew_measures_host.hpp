@@ -1,0 +1,35 @@
+// trew_measures_host.hpp -- the per-read motif measures computed on the CPU, straight from their definitions
+// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant), and the argument checks the
+// device entry points share with them.  Plain C++17: no HIP, no context.  trew_capi.cpp wraps these into the extern "C"
+// trew_*_host functions and keeps the error strings; tests/harness/measures_host_harness.cpp runs them under sanitizers.
+//
+// Every function that can fail returns nullptr, or the text of the error.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/trew_hip.h"
+
+namespace trew {
+
+uint64_t motif_revcomp(uint64_t w, int k);  // T=0 G=1 C=2 A=3: the complement is 3 - code
+uint64_t motif_mask(int k);
+const char *motif_error(const trew_hip_motif &m);
+const char *motifs_error(const trew_hip_motif *motifs, int n_motifs);
+const char *rules_error(const trew_hip_interval_rule *rules, int n_motifs);
+void sort_intervals(trew_hip_interval *v, uint64_t n);  // by (read, motif, strand, start)
+
+// 'TTAGGG' -> motif; the error text names the motif, so it is built here: "" when the text is a motif
+std::string motif_parse(const char *text, trew_hip_motif *out);
+
+const char *annotate_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                          int n_motifs, trew_hip_annot *out);
+const char *tracts_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                        int n_motifs, int penalty, trew_hip_tract *out);
+const char *intervals_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                           const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+const char *variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                          int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with);
+
+}  // namespace trew
