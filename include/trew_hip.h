@@ -242,8 +242,11 @@ int trew_hip_table_pressure(trew_hip_ctx *ctx, uint64_t *used_slots, uint64_t *t
  * out[5] decide_group(): a 16-lane row gave its segment back to decide() (an N where a class count was needed, a k with
  *        more than 16 runs and no skip slot left, a failed skip check)
  * out[6] reads of the group pass routed and recorded by the wave-per-segment code, out[7] whose k_mer_target was counted by it.
+ * out[8] prefilter, uniform batches of short or paired reads: units of which only one half had to be judged after the fast
+ *        loop (an N in it, or a 4-bucket pass) and was, a lane per half; out[9] units judged whole by the same drain (two or
+ *        more such halves).  Both count items drained, flagged or not.
  * n <= TREW_DEBUG_COUNTERS entries are written. */
-#define TREW_DEBUG_COUNTERS 8
+#define TREW_DEBUG_COUNTERS 10
 int trew_hip_debug_counters(trew_hip_ctx *ctx, uint64_t *out, int n);
 
 /* Diagnostic: the unit indices (reads, or pairs in pair mode) the prefilter of the last submit on `slot` handed to the exact

@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = (
     "trew_hip_intervals", "trew_hip_intervals_results", "trew_intervals_host",
     "trew_hip_variants", "trew_hip_variants_results", "trew_variants_host",
 )
-DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target")
+DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
+                  "half_drain", "unit_drain")
 
 
 class Params(C.Structure):

@@ -1,5 +1,6 @@
 // kernels/prefilter.inc -- part of trew_kernels.hip (included there, inside namespace trew; not a translation unit of its own).
-// filter_kernel<NW>: one lane per read, bit-parallel parity-bucket bound for every (segment, k); general path and uniform-geometry fast path.
+// filter_kernel<NW>: one lane per read, bit-parallel parity-bucket bound for every (segment, k); general path, uniform-geometry fast path
+// and the two drains of what the fast path sets aside (whole units, single halves).
 
 // ------------------------------------------------------------------ prefilter
 
@@ -418,8 +419,8 @@ __device__ __forceinline__ void halves_prefix(const u32 (&lo)[3], const u32 (&hi
 // p = c10 - ithr, q = c01 - ithr, c = c11 - ithr and t = (COUNT - c00) - jthr - 1 come out of the same two subtractions and one
 // three-operand add, and "some bucket reaches ithr" is a sign test: x = p & q & c is negative iff none of the three does, t is
 // negative iff bucket 00 does.  v_max / v_min / v_cmp / v_add3 occupy the SIMD for 4.2 cycles, v_sub / v_bitop3 for 2.3
-// (tools/valu_rate.hip): three max, a min and two compares per k become two v_bitop3 per half, two more to merge the halves'
-// verdicts, and ONE compare.
+// (tools/valu_rate.hip): three max, a min and two compares per k become three v_bitop3 per half -- the third (halves_note) keeps
+// the half's verdict over all k as the sign of an accumulator, so the loop has no compare at all.
 __device__ __forceinline__ u32 bcnt_acc_s(u32 x, int acc) {
     u32 d;
     asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(d) : "v"(x), "s"(acc));
@@ -436,12 +437,8 @@ __device__ __forceinline__ void halves_signs(u32 F1a, u32 F2a, u32 F1b, u32 F2b,
     x = __builtin_amdgcn_bitop3_b32(p, q, c, 0x80);  // p & q & c
     t = a + q + (u32) K;
 }
-// lanes in which some bucket of either half reaches its threshold
-__device__ __forceinline__ u64 halves_verdict(u32 xA, u32 tA, u32 xB, u32 tB) {
-    const u32 y = __builtin_amdgcn_bitop3_b32(xA, xB, tA, 0x40);  // xA & xB & ~tA
-    const u32 z = __builtin_amdgcn_bitop3_b32(y, tB, tB, 0x30);   // y & ~tB
-    return __ballot((int) z >= 0);
-}
+// acc & x & ~t: acc (all ones before the first k) stays negative as long as no bucket of the half has reached its threshold
+__device__ __forceinline__ u32 halves_note(u32 acc, u32 x, u32 t) { return __builtin_amdgcn_bitop3_b32(acc, x, t, 0x40); }
 // {-2 ithr, -ithr, 3 ithr - jthr - 1, ithr} of two consecutive k in one scalar load (the joint rows' table, fill_thresholds)
 struct Thr8 {
     int4 a, b;
@@ -464,11 +461,12 @@ __device__ __forceinline__ int4 load_thr4(const int4 *p) {
 
 __device__ __forceinline__ const int4 *joint_thresholds(const int2 *thr_tab) { return (const int4 *) (thr_tab + kThrRows * kThrRow); }
 
-// Both halves of a read in ONE k loop.  Returns the lanes whose 4-bucket test passes at some k of [klo, khi] in either half.
-// That is all the loop decides: such a read (3 % of them: the telomeric ones and a few near misses) is set aside and judged by
-// the general path with the other set-aside reads, a lane each -- the 8-bucket verdict used to be taken here, by the whole wave
-// for the one lane that needed it (two verdicts per 64 reads: 12 % of the kernel's instructions, plus the third prefix parity
-// of every read).  The loop carries no state but the OR of the verdict masks: no branch on a trigger, no thresholds kept.
+// Both halves of a read in ONE k loop.  passA / passB: this lane's half passes the 4-bucket test at some k of [klo, khi].
+// That is all the loop decides: such a half (3 % of the reads have one: the telomeric ones and a few near misses) is set aside and
+// judged by the drain with the other set-aside halves, a lane each -- the 8-bucket verdict used to be taken here, by the whole
+// wave for the one lane that needed it (two verdicts per 64 reads: 12 % of the kernel's instructions, plus the third prefix
+// parity of every read).  The loop carries no state but one sign accumulator per half: no compare, no branch on a trigger, no
+// thresholds kept.  The verdict of a half is valid whatever the other half holds (an N there spoils only its own).
 // Preconditions (checked by the caller): L <= 95, klo <= 31 and every k of the range has 33..kUniSubsetMax windows, so that
 // only the first 64 windows are ever looked at (uni_windows) and a parity mask is two words.
 // (Tried and dropped, profiles/r03/README.md: carrying the window parities from k to k+1, F_{k+1} = F_k ^ (f >> k), which
@@ -476,30 +474,31 @@ __device__ __forceinline__ const int4 *joint_thresholds(const int2 *thr_tab) { r
 // wm_tab: LDS, wm_tab[i] = all ones >> i (i = 0..31; two words of read-ahead behind them).  The window mask of the second word
 // comes from there as a VECTOR register: a VALU instruction with a scalar source operand occupies the SIMD for 4.1 cycles instead
 // of 2.3 (tools/valu_rate.hip: v_and / v_xor / v_bitop3 with an SGPR source), four of them per k; an LDS load costs no VALU issue.
-__device__ __forceinline__ u64 filter_halves_uni(const HalvesP &A, const HalvesP &Bh, int L, int klo, int khi, const int4 *__restrict__ thr_row,
-                                                 const u32 *wm_tab) {
-    u64 trig = 0;
+__device__ __forceinline__ void filter_halves_uni(const HalvesP &A, const HalvesP &Bh, int L, int klo, int khi, const int4 *__restrict__ thr_row,
+                                                  const u32 *wm_tab, bool &passA, bool &passB) {
+    u32 accA = 0xffffffffu, accB = 0xffffffffu;
     int k = klo;
     const int4 *tp = thr_row + (klo - 1);  // {-2 ithr, -ithr, 3 ithr - jthr - 1, ithr} per k
     // (b) 65 <= COUNT <= kUniSubsetMax: the first 64 windows (thresholds lowered accordingly by fill_thresholds), funnel shifts
     {
         int b = L - 64;
         b = b > khi ? khi : b;
-        auto probe = [&](u32 bs, const int4 t) __attribute__((always_inline)) -> u64 {
+        auto probe = [&](u32 bs, const int4 t) __attribute__((always_inline)) {
             u32 xA, tA, xB, tB;
             halves_signs(A.P1[0] ^ alignbit(A.P1[1], A.P1[0], bs), A.P2[0] ^ alignbit(A.P2[1], A.P2[0], bs), A.P1[1] ^ alignbit(A.P1[2], A.P1[1], bs),
                          A.P2[1] ^ alignbit(A.P2[2], A.P2[1], bs), t.x, t.y, t.z, xA, tA);
             halves_signs(Bh.P1[0] ^ alignbit(Bh.P1[1], Bh.P1[0], bs), Bh.P2[0] ^ alignbit(Bh.P2[1], Bh.P2[0], bs), Bh.P1[1] ^ alignbit(Bh.P1[2], Bh.P1[1], bs),
                          Bh.P2[1] ^ alignbit(Bh.P2[2], Bh.P2[1], bs), t.x, t.y, t.z, xB, tB);
-            return halves_verdict(xA, tA, xB, tB);
+            accA = halves_note(accA, xA, tA);
+            accB = halves_note(accB, xB, tB);
         };
         for (; k + 1 <= b; k += 2, tp += 2) {  // two k per trip, thresholds of both from one scalar load
             const Thr8 t8 = load_thr8(tp);
-            trig |= probe((u32) k, t8.a);
-            trig |= probe((u32) k + 1u, t8.b);
+            probe((u32) k, t8.a);
+            probe((u32) k + 1u, t8.b);
         }
         if (k <= b) {
-            trig |= probe((u32) k, load_thr4(tp));
+            probe((u32) k, load_thr4(tp));
             k++, tp++;
         }
     }
@@ -512,7 +511,7 @@ __device__ __forceinline__ u64 filter_halves_uni(const HalvesP &A, const HalvesP
         typedef const __attribute__((address_space(3))) u32 *lds_u32;
         u32 wa = (u32) (unsigned long long) (lds_u32) wm_tab + 4u * (u32) (63 - (L - k));  // LDS address of this k's mask: COUNT - 32 low bits = all ones >> (64 - COUNT)
         asm volatile("" : "+v"(wa));  // a vector register from here on: advancing it is a v_add of an inline constant
-        auto probe = [&](u32 shk, u32 wmk, const int4 t) __attribute__((always_inline)) -> u64 {
+        auto probe = [&](u32 shk, u32 wmk, const int4 t) __attribute__((always_inline)) {
             const u64 SA1 = QA1 >> shk, SA2 = QA2 >> shk, SB1 = QB1 >> shk, SB2 = QB2 >> shk;
             // (x ^ y) & m in one v_bitop3_b32: the compiler splits it into a xor and an and when left to choose
             const u32 gA1 = xor_and(A.P1[1], (u32) (SA1 >> 32), wmk), gA2 = xor_and(A.P2[1], (u32) (SA2 >> 32), wmk);
@@ -520,22 +519,26 @@ __device__ __forceinline__ u64 filter_halves_uni(const HalvesP &A, const HalvesP
             u32 xA, tA, xB, tB;
             halves_signs(A.P1[0] ^ (u32) SA1, A.P2[0] ^ (u32) SA2, gA1, gA2, t.x, t.y, t.z, xA, tA);
             halves_signs(Bh.P1[0] ^ (u32) SB1, Bh.P2[0] ^ (u32) SB2, gB1, gB2, t.x, t.y, t.z, xB, tB);
-            return halves_verdict(xA, tA, xB, tB);
+            accA = halves_note(accA, xA, tA);
+            accB = halves_note(accB, xB, tB);
         };
         for (; k + 1 <= b; k += 2, sh += 2u, wa += 8u, tp += 2) {
             const Thr8 t8 = load_thr8(tp);
             const u32 wm0 = *(lds_u32) (unsigned long long) wa, wm1 = *(lds_u32) (unsigned long long) (wa + 4u);
-            trig |= probe(sh, wm0, t8.a);
-            trig |= probe(sh + 1u, wm1, t8.b);
+            probe(sh, wm0, t8.a);
+            probe(sh + 1u, wm1, t8.b);
         }
-        if (k <= b) trig |= probe(sh, *(lds_u32) (unsigned long long) wa, load_thr4(tp));
+        if (k <= b) probe(sh, *(lds_u32) (unsigned long long) wa, load_thr4(tp));
     }
-    return trig;
+    passA = (int) accA >= 0;
+    passB = (int) accB >= 0;
 }
 
 // ---- the reads the uniform path set aside, judged in one joint k loop (3-word kernel) ----
 // The fast path sets aside every read with an N in a half (7 % of the synthetic reads) and every read some k of which passes
-// its 4-bucket test (3 %: the telomeric ones and a few near misses).  filter_deferred_uni gives them the verdict the general
+// its 4-bucket test (3 %: the telomeric ones and a few near misses).  Most of them need the drain for ONE half (a single N; a
+// junction read): those go to filter_deferred_half, a lane per half, the rest to filter_deferred_uni, a lane per unit; both run
+// the probes below (drain_probe3 / drain_probe2).  filter_deferred_uni gives a unit the verdict the general
 // path (filter_segment, a call per half) gives when the k loop is the halves' own [kmin, kmax]: a read is flagged exactly when
 // some half has some k whose 8-bucket maximum over the windows without an N reaches ithr(COUNT) -- the general path's first
 // candidate of a segment is always an 8-bucket pass, and m8 <= m4.  Written like the fast loop, with per-lane window masks:
@@ -591,24 +594,68 @@ __device__ __forceinline__ bool drain_pass8(const u32 (&F1)[N], const u32 (&F2)[
     return (int) m8 >= ithr;
 }
 
-// Geometry the drain needs (block-uniform, from the batch's uniform length): the valid segments are exactly the 2 (short) or 4
-// (pair) halves, pairing up as (0, 1) and (2, 3) with the same [kmin, kmax], at most 95 bases and one base apart, k <= length.
+// Geometry the drains need (block-uniform, from the batch's uniform length): the valid segments are exactly the 2 (short) or 4
+// (pair) halves, pairing up as (0, 1) and (2, 3), all with the same [kmin, kmax], at most 95 bases and one base apart, k <= length.
 __device__ __forceinline__ bool drain_uni_applies(const DevParams &P, u32 UL, int gmax_run) {
     const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : (P.mode == TREW_MODE_SHORT ? 2 : 0);
     if (n_halves == 0) return false;
     for (int slot = n_halves; slot < mode_slots(P.mode); slot++)
         if (get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len).valid) return false;
+    const Segment first = get_segment(P.mode, 0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
     for (int p = 0; p < n_halves; p += 2) {
         const Segment a = get_segment(P.mode, p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
         const Segment b = get_segment(P.mode, p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
         const int la = (int) a.len, lb = (int) b.len, lmin = la < lb ? la : lb, lmax = la < lb ? lb : la;
         const int khi = a.kmax < gmax_run ? a.kmax : gmax_run;
         if (!(a.valid && b.valid && a.kmin == b.kmin && a.kmax == b.kmax && lmax <= 95 && lmax - lmin <= 1 && a.kmin >= 1 && khi <= lmin)) return false;
+        if (a.kmin != first.kmin || a.kmax != first.kmax) return false;  // filter_deferred_half: one k loop for halves of either pair
     }
     return true;
 }
 
-// Verdict of one unit (short: a read, pair: two mates) set aside by the uniform path; cnt_thr: LDS, kCntThr entries.
+// One half at one k of the drain: the lanes whose 8-bucket maximum over the windows of V_k reaches ithr(COUNT).  The 8-bucket
+// stage runs only when some lane not in `flag` (the lanes decided already) passes the 4-bucket test.  cnt_thr: LDS, kCntThr entries.
+// k with more than 64 windows in some lane (k <= 31): three words, funnel shifts
+__device__ __forceinline__ u64 drain_probe3(const DrainHalf &h, u32 bs, u64 flag, const int4 *cnt_thr) {
+    const u32 cnt = bcnt_acc(h.V[2], bcnt_acc(h.V[1], __popc(h.V[0])));
+    const int4 th = cnt_thr[cnt];
+    u32 F1[3], F2[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        F1[j] = xor_and(h.P1[j], alignbit(j < 2 ? h.P1[j < 2 ? j + 1 : 0] : 0u, h.P1[j], bs), h.V[j]);
+        F2[j] = xor_and(h.P2[j], alignbit(j < 2 ? h.P2[j < 2 ? j + 1 : 0] : 0u, h.P2[j], bs), h.V[j]);
+    }
+    const u64 p4 = __ballot(drain_signs<3>(F1, F2, th) >= 0);
+    u64 p8 = 0;
+    if (p4 & ~flag) {
+        u32 F3[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) F3[j] = h.P3[j] ^ alignbit(j < 2 ? h.P3[j < 2 ? j + 1 : 0] : 0u, h.P3[j], bs);
+        p8 = __ballot(drain_pass8<3>(F1, F2, F3, h.V, cnt, th.w));
+    }
+    return p8;
+}
+// at most 64 windows: windows 0..63 of P >> k from one 64-bit shift of the container Q = P[s .. s + 64); V = V_k (V[2] is empty)
+__device__ __forceinline__ u64 drain_probe2(const DrainHalf &h, u64 Q1, u64 Q2, u64 V, int s, int k, u64 flag, const int4 *cnt_thr) {
+    const u32 v0 = (u32) V, v1 = (u32) (V >> 32);
+    const u32 cnt = bcnt_acc(v1, __popc(v0));
+    const int4 th = cnt_thr[cnt];
+    const u32 sh = (u32) (k - s);
+    const u64 S1 = Q1 >> sh, S2 = Q2 >> sh;
+    const u32 F1[2] = {xor_and(h.P1[0], (u32) S1, v0), xor_and(h.P1[1], (u32) (S1 >> 32), v1)};
+    const u32 F2[2] = {xor_and(h.P2[0], (u32) S2, v0), xor_and(h.P2[1], (u32) (S2 >> 32), v1)};
+    const u64 p4 = __ballot(drain_signs<2>(F1, F2, th) >= 0);
+    u64 p8 = 0;
+    if (p4 & ~flag) {
+        const u64 S3 = container64(h.P3, s) >> sh;
+        const u32 F3[2] = {h.P3[0] ^ (u32) S3, h.P3[1] ^ (u32) (S3 >> 32)};
+        const u32 Vw[2] = {v0, v1};
+        p8 = __ballot(drain_pass8<2>(F1, F2, F3, Vw, cnt, th.w));
+    }
+    return p8;
+}
+
+// Verdict of one unit (short: a read, pair: two mates) set aside by the uniform path with two or more halves to judge.
 __device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const DevBatch &B, u64 unit, bool active, int gmax_run,
                                                     const int4 *cnt_thr) {
     const u32 UL = B.uniform_length;
@@ -635,64 +682,75 @@ __device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const De
             drain_v_step3(Bh.V);
         }
         int k = klo;
-        // (b) k with more than 64 windows in some half (k <= Lmax - 64 <= 31): three words, funnel shifts
-        {
-            const int b = khi < Lmax - 64 ? khi : Lmax - 64;
-            auto half3 = [&](const DrainHalf &h, u32 bs) __attribute__((always_inline)) -> u64 {
-                const u32 cnt = bcnt_acc(h.V[2], bcnt_acc(h.V[1], __popc(h.V[0])));
-                const int4 th = cnt_thr[cnt];
-                u32 F1[3], F2[3];
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    F1[j] = xor_and(h.P1[j], alignbit(j < 2 ? h.P1[j < 2 ? j + 1 : 0] : 0u, h.P1[j], bs), h.V[j]);
-                    F2[j] = xor_and(h.P2[j], alignbit(j < 2 ? h.P2[j < 2 ? j + 1 : 0] : 0u, h.P2[j], bs), h.V[j]);
-                }
-                const u64 p4 = __ballot(drain_signs<3>(F1, F2, th) >= 0);
-                u64 p8 = 0;
-                if (p4 & ~flag) {
-                    u32 F3[3];
-#pragma unroll
-                    for (int j = 0; j < 3; j++) F3[j] = h.P3[j] ^ alignbit(j < 2 ? h.P3[j < 2 ? j + 1 : 0] : 0u, h.P3[j], bs);
-                    p8 = __ballot(drain_pass8<3>(F1, F2, F3, h.V, cnt, th.w));
-                }
-                return p8;
-            };
-            for (; k <= b && flag != actm; k++) {
-                flag |= half3(A, (u32) k);
-                flag |= half3(Bh, (u32) k);
-                drain_v_step3(A.V);
-                drain_v_step3(Bh.V);
-            }
+        // (b) k with more than 64 windows in some half (k <= Lmax - 64 <= 31)
+        for (const int b = khi < Lmax - 64 ? khi : Lmax - 64; k <= b && flag != actm; k++) {
+            flag |= drain_probe3(A, (u32) k, flag, cnt_thr);
+            flag |= drain_probe3(Bh, (u32) k, flag, cnt_thr);
+            drain_v_step3(A.V);
+            drain_v_step3(Bh.V);
         }
-        // (c) at most 64 windows in either half: windows 0..63 of P >> k from one 64-bit shift of the container Q = P[s .. s + 64)
+        // (c) at most 64 windows in either half
         if (k <= khi && flag != actm) {
             const int oA = LA > 63 ? LA - 63 : 0, oB = LB > 63 ? LB - 63 : 0;  // container offsets
             const u64 QA1 = container64(A.P1, oA), QA2 = container64(A.P2, oA), QB1 = container64(Bh.P1, oB), QB2 = container64(Bh.P2, oB);
             u64 VA = ((u64) A.V[1] << 32) | A.V[0], VB = ((u64) Bh.V[1] << 32) | Bh.V[0];  // V[2] is empty from here on
-            auto half2 = [&](const DrainHalf &h, u64 Q1, u64 Q2, u64 V, int s) __attribute__((always_inline)) -> u64 {
-                const u32 v0 = (u32) V, v1 = (u32) (V >> 32);
-                const u32 cnt = bcnt_acc(v1, __popc(v0));
-                const int4 th = cnt_thr[cnt];
-                const u32 sh = (u32) (k - s);
-                const u64 S1 = Q1 >> sh, S2 = Q2 >> sh;
-                const u32 F1[2] = {xor_and(h.P1[0], (u32) S1, v0), xor_and(h.P1[1], (u32) (S1 >> 32), v1)};
-                const u32 F2[2] = {xor_and(h.P2[0], (u32) S2, v0), xor_and(h.P2[1], (u32) (S2 >> 32), v1)};
-                const u64 p4 = __ballot(drain_signs<2>(F1, F2, th) >= 0);
-                u64 p8 = 0;
-                if (p4 & ~flag) {
-                    const u64 S3 = container64(h.P3, s) >> sh;
-                    const u32 F3[2] = {h.P3[0] ^ (u32) S3, h.P3[1] ^ (u32) (S3 >> 32)};
-                    const u32 Vw[2] = {v0, v1};
-                    p8 = __ballot(drain_pass8<2>(F1, F2, F3, Vw, cnt, th.w));
-                }
-                return p8;
-            };
             for (; k <= khi && flag != actm; k++) {
-                flag |= half2(A, QA1, QA2, VA, oA);
-                flag |= half2(Bh, QB1, QB2, VB, oB);
+                flag |= drain_probe2(A, QA1, QA2, VA, oA, k, flag, cnt_thr);
+                flag |= drain_probe2(Bh, QB1, QB2, VB, oB, k, flag, cnt_thr);
                 VA &= VA >> 1;
                 VB &= VB >> 1;
             }
+        }
+    }
+    return (flag >> lane_id()) & 1ull;
+}
+
+// Verdict of a unit of which only half `half` (its slot: 0..1 short, 0..3 pair) has to be judged, a lane per half: the other
+// halves hold no N and passed no 4-bucket test in the fast loop, and m8 <= m4 over the windows that loop looks at, against the
+// thresholds it uses (fill_thresholds), so they cannot flag the unit.  The k loop is filter_deferred_uni's, once per k instead
+// of twice; every half has the same [kmin, kmax] (drain_uni_applies).  Length, start and container offset are per lane: the
+// halves of an odd-length read differ by one base, and the probes take their window masks from V_k, not from the length.
+__device__ __forceinline__ bool filter_deferred_half(const DevParams &P, const DevBatch &B, u64 unit, u32 half, bool active, int gmax_run,
+                                                     const int4 *cnt_thr) {
+    const u32 UL = B.uniform_length;
+    ReadRef rd[2];
+    unit_reads(P, B, unit, active, rd);
+    Segment sg = get_segment(P.mode, 0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+    int Lmax = (int) sg.len;
+    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : 2;
+    for (int slot = 1; slot < n_halves; slot++) {  // the lane's own half out of the (wave-uniform) geometry of all of them
+        const Segment o = get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        Lmax = (int) o.len > Lmax ? (int) o.len : Lmax;
+        if (half == (u32) slot) {
+            sg.mate = o.mate;
+            sg.start = o.start;
+            sg.len = o.len;
+        }
+    }
+    Lmax = rfl_i(Lmax);
+    const int L = (int) sg.len;
+    const int klo = rfl_i(sg.kmin > P.min_mer ? sg.kmin : P.min_mer), khi = rfl_i(sg.kmax < gmax_run ? sg.kmax : gmax_run);
+    DrainHalf h;
+    {
+        u32 lo[3], hi[3], nm[3];
+        load_planes<3>(sg.mate ? rd[1] : rd[0], sg.start, lo, hi, nm);
+        drain_half_init(lo, hi, nm, L, active, h);
+    }
+    for (int t = 1; t < klo; t++) drain_v_step3(h.V);  // V_klo
+    const u64 actm = __ballot(active);
+    u64 flag = 0;
+    int k = klo;
+    for (const int b = khi < Lmax - 64 ? khi : Lmax - 64; k <= b && flag != actm; k++) {
+        flag |= drain_probe3(h, (u32) k, flag, cnt_thr);
+        drain_v_step3(h.V);
+    }
+    if (k <= khi && flag != actm) {
+        const int o = L > 63 ? L - 63 : 0;
+        const u64 Q1 = container64(h.P1, o), Q2 = container64(h.P2, o);
+        u64 V = ((u64) h.V[1] << 32) | h.V[0];
+        for (; k <= khi && flag != actm; k++) {
+            flag |= drain_probe2(h, Q1, Q2, V, o, k, flag, cnt_thr);
+            V &= V >> 1;
         }
     }
     return (flag >> lane_id()) & 1ull;
@@ -729,8 +787,8 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
 #endif
     __shared__ u32 stage[kStage];
     __shared__ u32 stage_n, flush_base;
-    __shared__ u32 defer_n;  // reads set aside by the fast path (the list itself is declared with the loop below)
-    u32 defer_seen = 0;      // defer_n as of the last append(): block-uniform, see there
+    __shared__ u32 defer_n, half_n;       // units and single halves set aside by the fast path (the lists themselves are declared with the loop below)
+    u32 defer_seen = 0, half_seen = 0;    // defer_n and half_n as of the last append(): block-uniform, see there
     if (threadIdx.x == 0) stage_n = 0;
     __syncthreads();
     auto flush = [&]() __attribute__((always_inline)) {  // block-uniform
@@ -759,7 +817,8 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
         // flushing -- barriers inside flush() then pair up wrongly (seen as a few units twice and a few missing in the worklist,
         // about one pass in five hundred; tools/flag_diff.py).
         const bool full = stage_n > kStage - kFilterThreads;
-        defer_seen = defer_n;  // the same holds for the list of reads set aside: its length is read here, between the barriers
+        defer_seen = defer_n;  // the same holds for the two lists of reads set aside: their lengths are read here, between the barriers
+        if constexpr (NW == 3) half_seen = half_n;
         __syncthreads();
         if (full) flush();
     };
@@ -810,6 +869,9 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
     // a block-full of units is waiting (or the input is exhausted) the general path drains them.
     __shared__ u32 defer[kDefer];
     __shared__ unsigned char defer_kind[kDefer];  // 1: set aside because of an N
+    constexpr u32 kHalfDefer = NW == 3 ? kDefer : 1;  // only the 3-word kernel has the joint loop that fills this list
+    __shared__ u32 hdefer[kHalfDefer];                // units of which one half is set aside (filter_deferred_half), drained like defer[]
+    __shared__ unsigned char hdefer_kind[kHalfDefer];  // bit 0: because of an N; bits 1..2: the half (its slot)
     __shared__ u32 wm_tab[34];  // all ones >> i: the joint loop's window masks (filter_halves_uni)
     if (threadIdx.x < 34) wm_tab[threadIdx.x] = threadIdx.x < 32 ? 0xffffffffu >> threadIdx.x : 0u;
     __shared__ int4 cnt_thr[kCntThr];  // thresholds by window count (filter_deferred_uni)
@@ -821,6 +883,9 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
     // the reads set aside by the uniform path are judged by filter_deferred_uni, or by the general path (any NW, dbg_masks, A/B)
     const bool uni_drain = NW == 3 && uni && !dbg_masks && !(P.flags & TREW_FLAG_DEBUG_NO_UNI_DRAIN) && drain_uni_applies(P, UL, gmax_run);
     if (threadIdx.x == 0) defer_n = 0;
+    if constexpr (NW == 3) {  // the half list is unused, and so not allocated, in the other instantiations
+        if (threadIdx.x == 0) half_n = 0;
+    }
     __syncthreads();
     __shared__ u32 next_chunk[2];  // written by thread 0 in round r (slot r & 1), read by all after that round's barrier
     // Eight counters on separate 128-B lines (a single word serves ~88 atomics a microsecond on MI355X -- 39 k chunks would keep
@@ -842,6 +907,8 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             if (threadIdx.x == 0) nxt = gridDim.x + kChunkShards * atomicAdd(shard_ctr(my_shard), 1u) + my_shard;
             u64 any = 0;
             bool dfr = active, dfr_n = false;  // dfr_n: set aside because of an N
+            bool dfr_half = false;             // set aside for one half only: half `hsel`
+            u32 hsel = 0;
             if constexpr (NW <= 5) {
                 if (uni) {
                     ReadRef rd[2];
@@ -852,6 +919,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                         // halves of equal length whose whole k range has 32..72 windows (150-bp reads at 5..32: 44..71): both
                         // halves of a read in one k loop (filter_halves_uni); anything else takes the per-segment loops below
                         const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : (P.mode == TREW_MODE_SHORT ? 2 : 0);
+                        u32 nneed = 0;  // halves of this unit the drain has to judge
                         for (; slot0 + 1 < n_halves && !dbg_masks && !(P.flags & TREW_FLAG_DEBUG_NO_JOINT); slot0 += 2) {
                             const Segment sA = get_segment(P.mode, slot0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
                             const Segment sB = get_segment(P.mode, slot0 + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
@@ -866,19 +934,24 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                             u32 loA[3], hiA[3], nmA[3], loB[3], hiB[3], nmB[3];
                             load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, loA, hiA, nmA);
                             load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, loB, hiB, nmB);
-                            const u32 anyn = segment_has_n<3>(nmA, L) | segment_has_n<3>(nmB, (int) sB.len);  // an N in the right half's extra base counts
-                            dfr = dfr || (active && anyn != 0);  // a half with an N does not fit the model: the read is set aside
-                            dfr_n = dfr_n || (active && anyn != 0);
+                            const u32 nA = segment_has_n<3>(nmA, L), nB = segment_has_n<3>(nmB, (int) sB.len);  // an N in the right half's extra base counts
+                            dfr_n = dfr_n || (active && (nA | nB) != 0);
                             HalvesP hA, hB;
                             halves_prefix(loA, hiA, L, hA);
                             halves_prefix(loB, hiB, L, hB);
                             // thresholds: halves of the same length share the row of the first; unequal ones have a joint row
-                            const u64 trig = filter_halves_uni(hA, hB, L, klo, khi, joint_thresholds(thr_tab) + (uneq ? 2 + slot0 / 2 : slot0 / 2) * kThrRow, wm_tab);
-                            // a read some k of which passes the 4-bucket test joins the reads set aside: the general path takes its
-                            // 8-bucket verdicts, a lane per read (the verdict of a read never depends on its neighbours, so the
-                            // flagged reads are the same)
-                            dfr = dfr || (active && any == 0 && ((trig >> lane_id()) & 1ull) != 0);
+                            bool passA, passB;
+                            filter_halves_uni(hA, hB, L, klo, khi, joint_thresholds(thr_tab) + (uneq ? 2 + slot0 / 2 : slot0 / 2) * kThrRow, wm_tab, passA, passB);
+                            // A half with an N does not fit the model, and a half some k of which passes the 4-bucket test needs its
+                            // 8-bucket verdicts: the drain takes them, a lane per read or half (the verdict of a read never depends on
+                            // its neighbours, so the flagged reads are the same).  A half that is neither cannot flag the read.
+                            const bool needA = active && (nA != 0 || passA), needB = active && (nB != 0 || passB);
+                            nneed += (u32) needA + (u32) needB;
+                            hsel = needB ? (u32) slot0 + 1u : (needA ? (u32) slot0 : hsel);
+                            dfr = dfr || needA || needB;
                         }
+                        // one half to judge, every half went through the joint loop and the drain knows this geometry: the half list
+                        dfr_half = uni_drain && slot0 == n_halves && nneed == 1u;
                     }
                     for (int slot = slot0; slot < nslots; slot++) {  // wave-uniform geometry: no need to unroll
                         const Segment sg = get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len);
@@ -908,9 +981,13 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                 }
             }
             {
-                wave_append(&defer_n, dfr, [=](u32 at) __attribute__((always_inline)) {  // < kDefer: drained below at one block-full
+                wave_append(&defer_n, dfr && !dfr_half, [=](u32 at) __attribute__((always_inline)) {  // < kDefer: drained below at one block-full
                     defer[at] = (u32) unit;
                     defer_kind[at] = dfr_n ? 1 : 0;
+                });
+                if constexpr (NW == 3) wave_append(&half_n, dfr_half, [=](u32 at) __attribute__((always_inline)) {  // a unit is in one list or the other; < kDefer likewise
+                    hdefer[at] = (u32) unit;
+                    hdefer_kind[at] = (unsigned char) ((hsel << 1) | (dfr_n ? 1u : 0u));
                 });
             }
             if (threadIdx.x == 0) next_chunk[round & 1u] = nxt;
@@ -932,24 +1009,32 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             }
             round++;
         }
-        // block-uniform: the length as every thread read it inside the last append() -- every add of this round happened before
+        // block-uniform: the lengths as every thread read them inside the last append() -- every add of this round happened before
         // that barrier, and no thread can have started the next round's adds.  (Reading defer_n here let a wave that ran a whole
         // round ahead change it under a slower wave's eyes: the block then disagreed about draining, once in ten million rounds,
-        // and a block-full of the list was judged twice while another was lost -- tools/flag_diff.py.)
-        const u32 dn = defer_seen;
-        if (dn >= kFilterThreads || (!more && dn > 0u)) {
-            const u32 take = dn < kFilterThreads ? dn : kFilterThreads;
-            const u32 at = dn - take;
+        // and a block-full of the list was judged twice while another was lost -- tools/flag_diff.py.  half_n is handled the same
+        // way: written by wave_append and, in drain(), by thread 0 behind a barrier; read only into half_seen inside append().)
+        const u32 dn = defer_seen, hn = half_seen;
+        // one block-full (or, at the end of the input, the rest) of a list: whole units, or single halves
+        auto drain = [&](const u32 *list, const unsigned char *kind, u32 *list_n, u32 n, bool halves) __attribute__((always_inline)) {
+            const u32 take = n < kFilterThreads ? n : kFilterThreads;
+            const u32 at = n - take;
             const bool active2 = threadIdx.x < take;
-            const u32 unit2 = active2 ? defer[at + threadIdx.x] : 0u;
-            const bool n2 = active2 && defer_kind[at + threadIdx.x] != 0;
+            const u32 unit2 = active2 ? list[at + threadIdx.x] : 0u;
+            const u32 kind2 = active2 ? kind[at + threadIdx.x] : 0u;
+            const bool n2 = (kind2 & 1u) != 0;
             __syncthreads();
-            if (threadIdx.x == 0) defer_n = at;
+            if (threadIdx.x == 0) {
+                *list_n = at;
+                if (halves || uni_drain) atomicAdd(&g_fallback[halves ? kFallbackHalfDrain : kFallbackUnitDrain], take);
+            }
 #ifndef TREW_AB_SKIP_DRAIN
-            const u64 any2 = uni_drain ? (u64) filter_deferred_uni(P, B, unit2, active2, gmax_run, cnt_thr) : general(unit2, active2);
+            const u64 any2 = halves      ? (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, gmax_run, cnt_thr)
+                             : uni_drain ? (u64) filter_deferred_uni(P, B, unit2, active2, gmax_run, cnt_thr)
+                                         : general(unit2, active2);
 #else  // A/B builds (instruction attribution, profiles/r05): the drain computes nothing; its inputs are kept alive
             u64 any2 = 0;
-            u32 keep = unit2;
+            u32 keep = unit2 + kind2;
             asm volatile("" : "+v"(keep), "+v"(any2));
             (void) keep;
 #endif
@@ -958,6 +1043,13 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             // an N (mixed at random, 12 % of its passes did; exact kernel 0.408 against 0.399 ms with the same reads).
             append(active2 && any2 != 0 && !n2, unit2);
             append(active2 && any2 != 0 && n2, unit2);
+        };
+        const bool drain_units = dn >= kFilterThreads || (!more && dn > 0u), drain_halves = NW == 3 && (hn >= kFilterThreads || (!more && hn > 0u));
+        if (drain_units || drain_halves) {
+            if (drain_units) drain(defer, defer_kind, &defer_n, dn, false);
+            if constexpr (NW == 3) {
+                if (drain_halves) drain(hdefer, hdefer_kind, &half_n, hn, true);
+            }
         } else if (!more) {
             break;
         }

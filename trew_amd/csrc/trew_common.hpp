@@ -71,6 +71,8 @@ enum {
     kFallbackGroupPunt = 3,     // decide_group(): a row gave its segment back (an N, too many heavy k, a failed skip check) and decide() took it
     kFallbackGroupRouted = 4,   // run_short_group(): a read routed and recorded by run_short_routed instead of in row space
     kFallbackGroupTarget = 5,   // run_short_group(): k_mer_target of a read counted by target() (more than 16 runs in the whole read)
+    kFallbackHalfDrain = 6,     // filter_kernel<3>: single halves judged by filter_deferred_half (units of which one half was set aside)
+    kFallbackUnitDrain = 7,     // filter_kernel<3>: whole units judged by filter_deferred_uni
     kFallbackWords = 8
 };
 

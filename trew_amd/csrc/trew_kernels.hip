@@ -29,7 +29,7 @@
 //   helpers.inc        funnel shifts, DPP wave reductions, read descriptors (unit_reads), plane loads, wave_append
 //   bound.inc          the parity-bucket bound's building blocks, shared by the prefilter and the exact kernel: low_mask,
 //                      prefix_parity, segment_setup, segment_has_n, windows_without_n, max_bucket8, class_links
-//   prefilter.inc      filter_kernel<NW> (general path + uniform-geometry fast path + joint halves loop + uniform drain)
+//   prefilter.inc      filter_kernel<NW> (general path + uniform-geometry fast path + joint halves loop + uniform drains of units and of halves)
 //   count_table.inc    table_add / table_add_wide / spill log
 //   exact_core.inc     LDS working set, eval_k / eval_runs (Lemma A), lane_bounds, decide, emit_k, run_short, run_segment
 //   decide_group.inc   decide_group (four segments in lock step, 16 lanes each), run_short_group
