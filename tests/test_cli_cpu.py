@@ -37,6 +37,8 @@ def run(*args):
         (["short", "5", "32", FQ, "--table_log2_slots", "5"], "table_log2_slots must be in range 12 to 30."),
         (["short", "5", "32", FQ, "--batch_mib", "0"], "Usage: short"),
         (["short", "5", "32", FQ, "--devices", "0,x"], "Usage: short"),
+        # (appended, so the ids of the rows above stay what they were)
+        (["long", "5", "32", FQ, "-s", "513"], "SLICE_LENGTH must be at most 512 on the HIP path."),
     ],
 )
 def test_argument_errors(args, msg):
