@@ -30,9 +30,10 @@ extern "C" {
 
 /* Still 4 with the annotation entry points (trew_motif_parse, trew_hip_annotate, trew_hip_annotate_results,
  * trew_annotate_host), the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host), the interval
- * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host) and the variant entry points
- * (trew_hip_variants, trew_hip_variants_results, trew_variants_host): they are purely additive -- no existing structure,
- * enumerator or function changed. */
+ * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host), the variant entry points
+ * (trew_hip_variants, trew_hip_variants_results, trew_variants_host) and the period entry points (trew_hip_periods,
+ * trew_hip_periods_results, trew_periods_host): they are purely additive -- no existing structure, enumerator or function
+ * changed. */
 #define TREW_HIP_ABI_VERSION 4
 
 /* scan modes: which per-read driver of the reference is reproduced */
@@ -412,6 +413,40 @@ int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_variant *out
 /* The same on the host, window by window from the definition, over packed planes; hist / reads_with may be NULL. */
 int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                        int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with);
+
+/* ---- de novo repeat period and unit per read: what repeats in this read, with which unit, and where (no motif given) ----
+ * Integer-exact (tests/period_ref.py is the brute-force form).  Read of n bases, base p valid when its nmask bit
+ * is 0.  Parameters: 1 <= min_period <= max_period <= 32, penalty P in [1, 64], min_score >= 1.
+ * Per period k in [min_period, min(max_period, n - 1)]: eq_k[i] (0 <= i < n - k) = bases i and i + k are both valid and
+ * equal; score(i) = +1 if eq_k[i], else -P; S_k(e) = sum of score(i) over i < e (e in [0, n - k]); score_k = the largest
+ * S_k(e) - min over b <= e of S_k(b), e_k = the smallest e that attains it, b_k = the largest b <= e_k at which S_k is
+ * smallest over [0, e_k]: the best-scoring segment of eq_k, the earliest end on a tie, then the shortest segment.
+ * k* = the smallest k whose score_k is largest.  No k (n <= min_period) or score_k* < min_score: the record is all zero.
+ *   scored_period  k*
+ *   score          score_k*
+ *   start, end     b and e + k* (end exclusive, in bases)
+ *   matches        eq positions in [b, e) = (score + P (e - b)) / (1 + P)
+ *   support        with cnt[j][c] = valid bases p in [start, end) with (p - start) mod k* = j and code c (T 0, G 1, C 2, A 3)
+ *                  and u[j] = the code with the largest count (the smallest code on a tie, 0 without a valid base): the sum
+ *                  of cnt[j][u[j]]
+ *   period         the smallest divisor d of k* with u[j] = u[(j + d) mod k*] for all j (on a noisy tract the multiples of
+ *                  the true period score within a percent of it; the majority unit's primitive root undoes that)
+ *   unit           u[0 .. period - 1] packed like trew_hip_motif.word: first base most significant, no bits above 2 period
+ * Out of scope: more than the one best tract per read (trew_hip_intervals with the unit reports all of them), and periods
+ * above 32 (a 128-bit unit and 256 bins).  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t period, scored_period, score, start, end, matches, support, reserved;
+    uint64_t unit;
+} trew_hip_period;
+/* Like trew_hip_tracts (batch shapes, staging, asynchronous on the slot's stream, a context of any mode, independent of the
+ * scan and of the other four kernels), without motifs; the records are a buffer of its own that the slot's first call
+ * allocates.  One kernel, a wave per read, for every read length. */
+int trew_hip_periods(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score);
+/* Waits for the slot and copies the records of its last trew_hip_periods, one per read; arguments as trew_hip_annotate_results. */
+int trew_hip_periods_results(trew_hip_ctx *ctx, int slot, trew_hip_period *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same on the host, position by position from the definition, over packed planes. */
+int trew_periods_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                      int penalty, uint32_t min_score, trew_hip_period *out);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -27,6 +27,7 @@ from .capi import (  # noqa: F401
     intervals,
     k_mer_check,
     pack_reads,
+    periods,
     tracts,
     variants,
 )

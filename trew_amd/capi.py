@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_tracts", "trew_hip_tracts_results", "trew_tracts_host",
     "trew_hip_intervals", "trew_hip_intervals_results", "trew_intervals_host",
     "trew_hip_variants", "trew_hip_variants_results", "trew_variants_host",
+    "trew_hip_periods", "trew_hip_periods_results", "trew_periods_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -124,6 +125,14 @@ assert VARIANT_DTYPE.itemsize == C.sizeof(Variant) == 40
 VARIANT_BINS = 128
 VARIANT_NONE = 0xFFFFFFFF
 
+
+class Period(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("period", "scored_period", "score", "start", "end", "matches", "support", "reserved")] + [("unit", C.c_uint64)]
+
+
+PERIOD_DTYPE = np.dtype([(name, "<u8" if name == "unit" else "<u4") for name, _ in Period._fields_])
+assert PERIOD_DTYPE.itemsize == C.sizeof(Period) == 40
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -193,6 +202,9 @@ def load():
     lib.trew_hip_variants.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32]
     lib.trew_hip_variants_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), vp, vp, C.POINTER(C.c_float)]
     lib.trew_variants_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, vp, vp, vp]
+    lib.trew_hip_periods.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32]
+    lib.trew_hip_periods_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_float)]
+    lib.trew_periods_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -288,6 +300,18 @@ def tracts_host(reads_or_packed, motifs, penalty=3):
     if lib.trew_tracts_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
         raise TrewHipError("trew_tracts_host failed: %s" % lib.trew_hip_last_error(None).decode())
     return out[:, :nm]
+
+
+def periods_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24):
+    """trew_periods_host: the de novo repeat period and unit of every read computed on the host, position by position from
+    the definition.  reads_or_packed as for annotate_host.  Returns PERIOD_DTYPE records of shape (n_reads,)."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    out = np.zeros(len(offsets), dtype=PERIOD_DTYPE)
+    if lib.trew_periods_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                             int(penalty), int(min_score), out.ctypes.data) != 0:
+        raise TrewHipError("trew_periods_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out
 
 
 def variants_host(reads_or_packed, motifs):
@@ -531,6 +555,17 @@ class TrewHip:
         res = self._fetch_records("tracts", slot, TRACT_DTYPE, want_ms)
         return res if want_ms else res[0]
 
+    def periods(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, slot=0):
+        """Queue the de novo repeat period and unit of every read of `batch` on the slot's stream (no motifs)."""
+        self._queue("periods", slot, batch, None, 1)
+        self._chk(self.lib.trew_hip_periods(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score)),
+                  "trew_hip_periods")
+
+    def periods_results(self, slot=0, want_ms=False):
+        """Records of the slot's last periods: PERIOD_DTYPE array of shape (n_reads,) [, kernel ms]."""
+        res = self._fetch_records("periods", slot, PERIOD_DTYPE, want_ms)
+        return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
+
     def variants(self, batch, motifs, slot=0):
         """Queue the in-phase variant units of every read of `batch` for `motifs` (texts or Motif, at most 8, taken as typed)
         on the slot's stream."""
@@ -759,6 +794,16 @@ def tracts(reads, motifs, penalty=3, device=0):
                  max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
         t.tracts(t.host_batch(words, offsets, lengths), motifs, penalty)
         return t.tracts_results()
+
+
+def periods(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0):
+    """De novo repeat period and unit on the GPU: for every read (bytes / str) the period, the consensus unit and the
+    position of its best-scoring repeat tract, as PERIOD_DTYPE records of shape (n_reads,); no motif is given."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        t.periods(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score)
+        return t.periods_results()
 
 
 def variants(reads, motifs, device=0):

@@ -1,5 +1,6 @@
 // motif_cli.cpp -- what the command lines share: the argument helpers of every subcommand, and the front end of the four
-// per-read motif subcommands `trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ...` (motif_cli_main).  A
+// per-read motif subcommands `trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ...` and of the motif-less
+// `trew periods FASTQ...` (motif_cli_main).  A
 // subcommand's own file (annotate.cpp, ...) holds its usage text, its options and their defaults, its rows and its summary.
 // The conventions are those of `short` and `long`: CSV on stdout, messages on stderr, exit status 1 and an empty stdout on an
 // argument error.
@@ -92,13 +93,13 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
             positional.push_back(a);
         }
     }
-    if (positional.empty()) return bad("MOTIF is required.");
+    if (positional.empty()) return bad(cli.motif_less ? "FASTQ is required." : "MOTIF is required.");
     if (cfg.NUM_THREAD <= 0) return bad("number of threads must be positive.");
     if (const char *e = cli.check()) return bad(e);
 
     // MOTIF[,MOTIF...], printed as given
     std::vector<std::string> names;
-    {
+    if (!cli.motif_less) {
         const std::string &list = positional[0];
         size_t pos = 0;
         while (pos <= list.size()) {
@@ -119,8 +120,9 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
         cli.per_motif(rq, rq.n_motifs, (uint32_t) name.size());
         rq.n_motifs++;
     }
-    if (positional.size() < 2) return bad("FASTQ is required.");
-    std::vector<std::string> files(positional.begin() + 1, positional.end());
+    if (cli.motif_less) cli.fill(rq);
+    if (positional.size() < (cli.motif_less ? 1u : 2u)) return bad("FASTQ is required.");
+    std::vector<std::string> files(positional.begin() + (cli.motif_less ? 0 : 1), positional.end());
     for (const auto &f : files)
         if (!is_regular_file(f)) return bad(f + " : file not found");
     if (cfg.NUM_THREAD - 1 > 16 * (int) cfg.devices.size()) cfg.NUM_THREAD = 16 * (int) cfg.devices.size() + 1;

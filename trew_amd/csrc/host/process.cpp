@@ -1186,11 +1186,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants
-// A per-read motif measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods
+// A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1204,6 +1204,7 @@ struct Annotator {
         std::vector<uint32_t> icounts;
         std::vector<trew_hip_variant> vrecs;  // trew variants
         std::vector<uint64_t> vhist;          // hist, then reads_with, of one batch
+        std::vector<trew_hip_period> precs;   // trew periods
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1399,6 +1400,30 @@ static void fold_variants(const AnnotBatch &x, AnnotFileResult &p) {
         }
 }
 
+uint64_t canonical_unit(uint64_t unit, int k) {
+    return (uint64_t) std::min(get_rot_seq_128(unit, k), get_rot_seq_128(reverse_complement_k(unit, k), k));
+}
+
+// trew periods: one record per read and no motif.  A read with a record (period > 0) is a row; period_units counts the
+// reads and the bases of their tracts per (period, strand-canonical unit).
+static void fold_periods(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    if (trew_hip_periods(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score)) hip_die(x.c, "trew_hip_periods");
+    if (w->precs.size() < x.n) w->precs.resize(x.n);
+    uint64_t got = 0;
+    if (trew_hip_periods_results(x.c, w->slot, w->precs.data(), x.n, &got, nullptr)) hip_die(x.c, "trew_hip_periods_results");
+    for (uint64_t r = 0; r < x.n; r++) {
+        const trew_hip_period &rec = w->precs[r];
+        if (rec.period == 0) continue;
+        auto &u = p.period_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
+        u.first++;
+        u.second += rec.end - rec.start;
+        p.rows.push_back(annot_row(x, r, 0));
+        p.rows.back().p = rec;
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1440,6 +1465,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Tracts: fold_tracts(x, p); break;
             case Measure::Intervals: fold_intervals(x, p); break;
             case Measure::Variants: fold_variants(x, p); break;
+            case Measure::Periods: fold_periods(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1470,9 +1496,14 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         into.var_reads_with[i] += from.var_reads_with[i];
     }
     into.interval_retries += from.interval_retries;
+    for (const auto &kv : from.period_units) {
+        auto &u = into.period_units[kv.first];
+        u.first += kv.second.first;
+        u.second += kv.second.second;
+    }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods"};  // in the order of Measure
 
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
     const auto t0 = std::chrono::steady_clock::now();

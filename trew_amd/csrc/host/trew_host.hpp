@@ -99,17 +99,19 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ...: the per-read motif measures.  One file path for
-// all four (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp, intervals.cpp and
-// variants.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants };
+// ---- trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ... and trew periods FASTQ...: the per-read measures.
+// One file path for all five (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp and periods.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     // a (read, motif) is reported when its longer tract has at least this many bases (variants: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
-    int penalty = 0;                                      // tracts
+    int penalty = 0;                                      // tracts, periods
+    int min_period = 1, max_period = 32;                  // periods (which takes no motifs: n_motifs = 0)
+    uint32_t min_score = 24;                              // periods
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
 };
 struct AnnotRow {
@@ -120,6 +122,7 @@ struct AnnotRow {
         trew_hip_annot a;
         trew_hip_tract t;
         trew_hip_variant v;
+        trew_hip_period p;
     };
 };
 struct IntervalRow {
@@ -139,6 +142,8 @@ struct AnnotFileResult {
     uint64_t interval_retries = 0;  // batches resubmitted because their log overflowed
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     std::vector<uint64_t> var_hist, var_reads_with;  // variants: [motif][strand][bin]; empty for the other kinds
+    // periods: (period, strand-canonical unit) -> {reads, sum of end - start}
+    std::map<std::pair<uint32_t, uint64_t>, std::pair<uint64_t, uint64_t>> period_units;
 };
 void add_totals(AnnotFileResult &into, const AnnotFileResult &from);  // everything but the rows: sums, and the larger of longest*
 struct Annotator;  // device contexts and one slot per worker
@@ -159,12 +164,16 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
+    bool motif_less = false;                      // periods: every positional argument is a file, `names` stays empty
+    std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
 int annotate_main(int argc, char **argv);
 int tracts_main(int argc, char **argv);
 int intervals_main(int argc, char **argv);
 int variants_main(int argc, char **argv);
+int periods_main(int argc, char **argv);
+uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 
 struct RunStats {
     uint64_t reads = 0, bases = 0;

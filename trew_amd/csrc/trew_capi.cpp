@@ -25,9 +25,9 @@ using namespace trew;
 
 namespace {
 
-// The per-read motif measures (trew_hip_annotate, _tracts, _intervals, _variants) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods"};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -40,7 +40,7 @@ struct MeasureState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call
-    u64 n = 0;         // annotate, tracts, variants: its records, n_reads * n_motifs
+    u64 n = 0;         // annotate, tracts, variants: its records, n_reads * n_motifs; periods: n_reads
     u64 max_log = 0;   // intervals: its max_intervals
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2
     int n_motifs = 0;  // variants
@@ -1200,8 +1200,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read motif measures: annotate, tracts, intervals, variants
-// The four measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods
+// The five measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
@@ -1235,6 +1235,11 @@ extern "C" int trew_intervals_host(const uint32_t *words, const uint32_t *offset
 extern "C" int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                                   const trew_hip_motif *motifs, int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with) {
     return host_status(variants_host(words, offsets, lengths, n_reads, motifs, n_motifs, out, hist, reads_with));
+}
+
+extern "C" int trew_periods_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                 int max_period, int penalty, uint32_t min_score, trew_hip_period *out) {
+    return host_status(periods_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out));
 }
 
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
@@ -1275,17 +1280,22 @@ static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs
 
 // What every queue call does before anything of its own: the argument checks in the order callers see them (`own` holds
 // the measure's own checks; it runs behind the motifs' check and in front of the first HIP call), the batch and the motifs onto the slot's stream, and the measure's two events on its first use.
+// The measure without motifs (periods) is known by `which`, not by its arguments: for it there is no motif check and no
+// pattern table, and it passes no motifs.  For the other four, no motifs stays the argument error it always was.
 template <class Own>
 static int measure_begin(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
                          Own own, Slot **slot_out, DevBatch *db) {
     if (!ctx || !batch) return -1;
     if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
+    const bool motif_less = which == kPeriods;
+    if (!motif_less)
+        if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
     if (const char *e = own()) return fail(ctx, e);
     HIPCHK(ctx, hipSetDevice(ctx->p.device));
     Slot &s = ctx->slots[(size_t) slot];
     if (int rc = stage_batch(ctx, batch, s, db)) return rc;  // also: the read index fits a record's u32
-    if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
+    if (!motif_less)
+        if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
     for (auto &e : s.measure[which].ev)
         if (!e) HIPCHK(ctx, hipEventCreate(&e));
     *slot_out = &s;
@@ -1516,6 +1526,34 @@ extern "C" int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_v
     const size_t hb = (size_t) st.n_motifs * 2 * TREW_VARIANT_BINS * sizeof(uint64_t);
     if (hist && hb) HIPCHK(ctx, hipMemcpy(hist, st.hist, hb, hipMemcpyDeviceToHost));
     if (reads_with && hb) HIPCHK(ctx, hipMemcpy(reads_with, st.hist + kVarHistLen, hb, hipMemcpyDeviceToHost));
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- de novo repeat period and unit per read
+extern "C" int trew_hip_periods(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * { return periods_error(min_period, max_period, penalty, min_score); };
+    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kPeriods, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kPeriods];
+    const u64 need = db.n_reads;
+    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_period))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    if (need == 0) return 0;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_periods(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_period *) st.records.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_periods_results(trew_hip_ctx *ctx, int slot, trew_hip_period *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kPeriods, nullptr, &sp)) return rc;
+    const MeasureState &st = sp->measure[kPeriods];
+    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_period), n)) return rc;
     return fetch_end(ctx, st, ms_kernel);
 }
 

@@ -40,6 +40,7 @@
 //   tracts.inc         tracts_wave_kernel (per-read error-tolerant terminal tracts; shares annotate.inc's match word)
 //   intervals.inc      intervals_wave_kernel (gap-tolerant motif intervals anywhere in a read; shares tracts.inc's coverage word)
 //   variants.inc       variants_wave_kernel (in-phase variant units per read and their batch histogram; Hamming distance 1)
+//   periods.inc        periods_wave_kernel (de novo repeat period and consensus unit per read; no motif, the shifted self-comparison)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -74,6 +75,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/tracts.inc"
 #include "kernels/intervals.inc"
 #include "kernels/variants.inc"
+#include "kernels/periods.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -348,6 +350,14 @@ hipError_t launch_variants(hipStream_t st, u32 n_cu, const DevBatch &B, const An
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(variants_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, (u32 *) d_out, d_hist, d_reads_with);
+    return hipGetLastError();
+}
+
+// De novo periods: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_periods(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period *d_out) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(periods_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, (u32 *) d_out);
     return hipGetLastError();
 }
 

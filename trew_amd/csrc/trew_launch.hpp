@@ -40,6 +40,8 @@ hipError_t launch_intervals(hipStream_t st, u32 n_cu, const DevBatch &B, const A
 // when the kernel starts (the caller's memsets on the same stream)
 hipError_t launch_variants(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, trew_hip_variant *d_out,
                            unsigned long long *d_hist, unsigned long long *d_reads_with);
+// trew_hip_periods: the wave-per-read kernel of kernels/periods.inc on the grid of launch_tracts; no motifs
+hipError_t launch_periods(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period *d_out);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);

@@ -1,4 +1,4 @@
-// trew_measures_host.cpp -- the four per-read motif measures on the CPU, base by base from their definitions (see
+// trew_measures_host.cpp -- the per-read measures on the CPU, base by base from their definitions (see
 // trew_measures_host.hpp).  These are what the kernels are checked against: they are written to be read, not to be fast.
 #include "trew_measures_host.hpp"
 
@@ -340,6 +340,82 @@ const char *variants_host(const u32 *words, const u32 *offsets, const u32 *lengt
             }
             memcpy(&out[r * (u64) n_motifs + (u64) m], res, sizeof(trew_hip_variant));
         }
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- de novo repeat period and unit per read
+const char *periods_error(int min_period, int max_period, int penalty, u32 min_score) {
+    if (min_period < 1 || max_period > 32 || min_period > max_period) return "periods: 1 <= min_period <= max_period <= 32 is required";
+    if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
+    if (min_score < 1) return "min_score must be at least 1";
+    return nullptr;
+}
+
+const char *periods_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, trew_hip_period *out) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_periods_host: null argument";
+    std::vector<unsigned char> base;  // per base: code, or 4 with its nmask bit set
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        trew_hip_period &o = out[r];
+        memset(&o, 0, sizeof(o));
+        base.resize(n);
+        for (u32 i = 0; i < n; i++) base[i] = (unsigned char) base_at(w, i);
+        // the best-scoring segment of eq_k for every k; a later k must score strictly more
+        long long best = 0;
+        u32 ks = 0, bs = 0, es = 0;
+        for (u32 k = (u32) min_period; k <= (u32) max_period && k < n; k++) {
+            long long S = 0, lo = 0, score = 0;  // S(e), the smallest S(b) over b <= e, the largest S(e) - lo so far
+            u32 b_lo = 0, b = 0, e = 0;           // the latest b at which S is lo; the segment of `score`
+            for (u32 i = 0; i + k < n; i++) {
+                const bool eq = base[i] < 4 && base[i] == base[i + k];
+                S += eq ? 1 : -(long long) penalty;
+                if (S <= lo) {  // the latest b keeps a tie: the shorter segment
+                    lo = S;
+                    b_lo = i + 1;
+                }
+                if (S - lo > score) {  // strictly: the earliest e keeps a tie
+                    score = S - lo;
+                    e = i + 1;
+                    b = b_lo;
+                }
+            }
+            if (score > best) {
+                best = score;
+                ks = k;
+                bs = b;
+                es = e;
+            }
+        }
+        if (ks == 0 || best < (long long) min_score) continue;
+        o.scored_period = ks;
+        o.score = (u32) best;
+        o.start = bs;
+        o.end = es + ks;
+        o.matches = (u32) (((u64) best + (u64) penalty * (u64) (es - bs)) / (u64) (1 + penalty));
+        u32 cnt[32][4] = {};
+        for (u32 p = o.start; p < o.end; p++)
+            if (base[p] < 4) cnt[(p - o.start) % ks][base[p]]++;
+        u32 u[32];
+        for (u32 j = 0; j < ks; j++) {
+            u[j] = 0;
+            for (u32 c = 1; c < 4; c++)
+                if (cnt[j][c] > cnt[j][u[j]]) u[j] = c;  // strictly: the smallest code keeps a tie
+            o.support += cnt[j][u[j]];
+        }
+        for (u32 d = 1; d <= ks; d++) {
+            if (ks % d) continue;
+            bool periodic = true;
+            for (u32 j = 0; j < ks && periodic; j++) periodic = u[j] == u[(j + d) % ks];
+            if (periodic) {
+                o.period = d;
+                break;
+            }
+        }
+        for (u32 j = 0; j < o.period; j++) o.unit = (o.unit << 2) | u[j];
     }
     return nullptr;
 }

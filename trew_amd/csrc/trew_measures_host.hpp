@@ -1,5 +1,5 @@
-// trew_measures_host.hpp -- the per-read motif measures computed on the CPU, straight from their definitions
-// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant), and the argument checks the
+// trew_measures_host.hpp -- the per-read measures computed on the CPU, straight from their definitions
+// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period), and the argument checks the
 // device entry points share with them.  Plain C++17: no HIP, no context.  trew_capi.cpp wraps these into the extern "C"
 // trew_*_host functions and keeps the error strings; tests/harness/measures_host_harness.cpp runs them under sanitizers.
 //
@@ -31,5 +31,9 @@ const char *intervals_host(const uint32_t *words, const uint32_t *offsets, const
                            const trew_hip_interval_rule *rules, int n_motifs, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts);
 const char *variants_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                           int n_motifs, trew_hip_variant *out, uint64_t *hist, uint64_t *reads_with);
+// de novo repeat period and unit per read: no motifs; periods_error is the argument check the device entry point shares
+const char *periods_error(int min_period, int max_period, int penalty, uint32_t min_score);
+const char *periods_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                         int penalty, uint32_t min_score, trew_hip_period *out);
 
 }  // namespace trew
