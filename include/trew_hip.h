@@ -448,6 +448,48 @@ int trew_hip_periods_results(trew_hip_ctx *ctx, int slot, trew_hip_period *out, 
 int trew_periods_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                       int penalty, uint32_t min_score, trew_hip_period *out);
 
+/* ---- ordered unit chain per read: exact runs and variant units in place (in which order do the units come?) ----
+ * Integer-exact (tests/chain_ref.py is the brute-force form).  Base codes, the typed rotation, T_0 / T_1,
+ * exact_s[i], var_s[i], "anchored" and the bin are those of the variant repeats above, unchanged.  Per (read, motif, strand s)
+ * an ITEM is one of two kinds:
+ *   exact run     a maximal sequence of windows i, i + k, ..., i + (r - 1) k that are all exact_s: it starts at a window i
+ *                 with exact_s[i] and not (i >= k and exact_s[i - k]) and ends at a window e with exact_s[e] and not
+ *                 (e + k <= n - k and exact_s[e + k]).  start = i, count = r >= 1, bin = TREW_VARIANT_NONE
+ *   variant unit  an anchored var_s window i.  start = i, count = 1, bin = the variant's bin (below TREW_VARIANT_BINS)
+ * No two items of a key share a start (a window is exact or variant, never both), so (read, motif, strand, start) is a
+ * total order: the order every interface returns.  Items of different residue classes mod k may overlap (TGT in TGTGT:
+ * windows 0 and 2 are both exact); that is part of the definition.  n < k gives no items.  Every key also has two counts,
+ * {runs, variants}.  Consequences: the counts of a key's runs sum to trew_hip_variant.units_s; its variant items number
+ * variants_s and their bins make the read's histogram; a read that is a primitive M repeated r times has the one forward
+ * item {0, r, NONE}; the rev items of a read are the fwd items of its reverse complement with start -> n - k - start for a
+ * variant and n - k - (start + (count - 1) k) for a run, the bin unchanged; an item does not depend on the rest of the
+ * batch.  Out of scope: units with an inserted or deleted base (they shift the phase).  Also additive:
+ * TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t read, motif, strand, start, count, bin;
+} trew_hip_chain_item;
+/* Like trew_hip_intervals (batch shapes, staging, asynchronous on the slot's stream, a context of any mode, independent of
+ * the scan and of the other five kernels), with buffers of its own that the slot's first call allocates: a log of max_events
+ * entries (>= 1; the log grows when a call asks for more), whose counter is zeroed on the slot's stream in front of every
+ * launch, and the two counts of every key.  The kernel appends EVENTS, not items: a run's start, its end (one event for
+ * both when the run has one unit), a variant unit; an item takes one or two events.  The layout of an event is internal.
+ * A batch holds at most 2^32 - 1 reads.  One kernel, a wave per read, for every read length. */
+int trew_hip_chain(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, uint64_t max_events);
+/* Waits for the slot.  *n_events = the events the kernel found, also when that exceeds max_events; counts (n_reads *
+ * n_motifs * 2 * 2 values, [read][motif][strand]{runs, variants}; may be NULL) is always exact; *n_items = the sum of the
+ * counts, so it is exact even on overflow.  n_items and n_events must not be NULL.  When *n_events <= max_events the host
+ * pairs the events into items and copies min(cap, *n_items) of them sorted by (read, motif, strand, start), so the output
+ * does not depend on device scheduling.  When *n_events > max_events the stored events are an unspecified subset that
+ * cannot be paired: no item is copied, counts, *n_items and *n_events are still exact; repeat trew_hip_chain with
+ * max_events >= *n_events -- one retry always suffices.  That case is no error (the call returns 0), like
+ * trew_hip_intervals_results with too small a log. */
+int trew_hip_chain_results(trew_hip_ctx *ctx, int slot, trew_hip_chain_item *out, uint64_t cap, uint64_t *n_items, uint64_t *n_events,
+                           uint32_t *counts, float *ms_kernel);
+/* The same on the host, window by window from the definition, over packed planes: *n_items = items found, min(cap,
+ * *n_items) items (the first ones of the sorted order), counts as above (may be NULL). */
+int trew_chain_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                    int n_motifs, trew_hip_chain_item *out, uint64_t cap, uint64_t *n_items, uint32_t *counts);
+
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */
 uint64_t trew_pack_words(uint64_t n_bases);

@@ -24,6 +24,7 @@ from .capi import (  # noqa: F401
     TrewHip,
     TrewHipError,
     annotate,
+    chain,
     intervals,
     k_mer_check,
     pack_reads,

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_intervals", "trew_hip_intervals_results", "trew_intervals_host",
     "trew_hip_variants", "trew_hip_variants_results", "trew_variants_host",
     "trew_hip_periods", "trew_hip_periods_results", "trew_periods_host",
+    "trew_hip_chain", "trew_hip_chain_results", "trew_chain_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -133,6 +134,15 @@ class Period(C.Structure):
 PERIOD_DTYPE = np.dtype([(name, "<u8" if name == "unit" else "<u4") for name, _ in Period._fields_])
 assert PERIOD_DTYPE.itemsize == C.sizeof(Period) == 40
 
+
+
+class ChainItem(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("read", "motif", "strand", "start", "count", "bin")]
+
+
+CHAIN_DTYPE = np.dtype([(name, "<u4") for name, _ in ChainItem._fields_])
+assert CHAIN_DTYPE.itemsize == C.sizeof(ChainItem) == 24
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -205,6 +215,9 @@ def load():
     lib.trew_hip_periods.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32]
     lib.trew_hip_periods_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(C.c_float)]
     lib.trew_periods_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp]
+    lib.trew_hip_chain.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, u64]
+    lib.trew_hip_chain_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(C.c_float)]
+    lib.trew_chain_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, vp, u64, C.POINTER(u64), vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -372,6 +385,52 @@ def intervals_host(reads_or_packed, motifs, max_gap=None, min_len=None, cap=None
         out = np.zeros(int(n.value), dtype=INTERVAL_DTYPE)
         call(out)
     return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
+
+
+def chain_host(reads_or_packed, motifs, cap=None):
+    """trew_chain_host: the ordered unit chain computed on the host, window by window from the definition.  reads_or_packed
+    as for annotate_host.  Returns (CHAIN_DTYPE items sorted by (read, motif, strand, start), counts of shape (n_reads,
+    n_motifs, 2, 2) = [read][motif][strand]{runs, variants}, n_items); with `cap` at most that many items."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    arr, nm = _motif_array(motifs)
+    counts = np.zeros((len(offsets), max(nm, 1), 2, 2), dtype=np.uint32)
+    n = C.c_uint64(0)
+
+    def call(out):
+        if lib.trew_chain_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm,
+                               out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
+            raise TrewHipError("trew_chain_host failed: %s" % lib.trew_hip_last_error(None).decode())
+
+    out = np.zeros(0 if cap is None else int(cap), dtype=CHAIN_DTYPE)
+    call(out)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=CHAIN_DTYPE)
+        call(out)
+    return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
+
+
+def chain_unit_text(motif_text, bin_):
+    """A variant's bin as text: the motif as typed (upper case) with base bin // 4 replaced by the bin's base."""
+    t = list((motif_text.decode() if isinstance(motif_text, bytes) else motif_text).upper())
+    if bin_ // 4 < len(t):
+        t[bin_ // 4] = "TGCA"[bin_ & 3]
+    return "".join(t)
+
+
+def chain_signature(items, motif_text):
+    """The signature `trew chain` prints for the items of one (read, motif, strand), given in start order: `=r` for a run of
+    r exact units, a variant unit as its text in motif orientation, and `+d` / `-d` between two consecutive items a and b
+    with d = b.start - (a.start + a.count k) != 0; joined by single spaces."""
+    k = len(motif_text)
+    tokens, at = [], None
+    for it in items:
+        start, count, bin_ = int(it["start"]), int(it["count"]), int(it["bin"])
+        if at is not None and start != at:
+            tokens.append("%+d" % (start - at))
+        tokens.append("=%d" % count if bin_ == VARIANT_NONE else chain_unit_text(motif_text, bin_))
+        at = start + count * k
+    return " ".join(tokens)
 
 
 def synth_short_ascii(seed, first_read, n_reads, read_len):
@@ -608,6 +667,33 @@ class TrewHip:
             self._chk(self.lib.trew_hip_intervals_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_intervals_results")
         return (out, counts, found, ms.value) if want_ms else (out, counts, found)
 
+    def chain(self, batch, motifs, max_events=None, slot=0):
+        """Queue the ordered unit chain of every read of `batch` for `motifs` (texts or Motif, at most 8, taken as typed) on
+        the slot's stream.  max_events: the capacity of the event log for this call (default: four per read, at least 1)."""
+        arr, nm = _motif_array(motifs)
+        if max_events is None:
+            max_events = max(4 * int(batch.n_reads), 1)
+        self._queue("chain", slot, batch, arr, nm, shape=(int(max_events),))
+        self._chk(self.lib.trew_hip_chain(self.ctx, C.byref(batch), slot, arr, nm, int(max_events)), "trew_hip_chain")
+
+    def chain_results(self, slot=0, want_ms=False):
+        """Results of the slot's last chain: (CHAIN_DTYPE items sorted by (read, motif, strand, start), counts of shape
+        (n_reads, n_motifs, 2, 2) = [read][motif][strand]{runs, variants}, n_items, n_events [, kernel ms]).  n_events >
+        max_events: no items (the stored events cannot be paired), counts, n_items and n_events are exact; repeat the call
+        with max_events >= n_events."""
+        n_items, n_events = C.c_uint64(0), C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm, cap = self._queued.get(("chain", slot), (0, 1, 0))
+        counts = np.zeros((n_reads, nm, 2, 2), dtype=np.uint32)
+        self._chk(self.lib.trew_hip_chain_results(self.ctx, slot, None, 0, C.byref(n_items), C.byref(n_events), counts.ctypes.data,
+                                                  C.byref(ms) if want_ms else None), "trew_hip_chain_results")
+        items, events = int(n_items.value), int(n_events.value)
+        out = np.zeros(items if events <= cap else 0, dtype=CHAIN_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_chain_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n_items), C.byref(n_events), None, None),
+                      "trew_hip_chain_results")
+        return (out, counts, items, events, ms.value) if want_ms else (out, counts, items, events)
+
     def submit_reads(self, reads, slot=0):
         b = self.host_batch(*pack_reads(reads))
         self.submit(b, slot)
@@ -833,4 +919,23 @@ def intervals(reads, motifs, max_gap=None, min_len=None, device=0, max_intervals
         if found > cap:
             t.intervals(b, motifs, max_gap, min_len, found)
             out, counts, found = t.intervals_results()
+        return out, counts
+
+
+def chain(reads, motifs, device=0, max_events=None):
+    """Ordered unit chain on the GPU: for every read (bytes / str) and motif (text, taken as typed) the maximal in-phase runs
+    of exact units and every anchored unit with one substituted base, in place, on each strand.  Returns (CHAIN_DTYPE items
+    sorted by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2, 2) = [read][motif][strand]{runs,
+    variants}).  The first call's log holds max_events events (default: four per read); when more are found the call is
+    repeated once with the exact number."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        b = t.host_batch(words, offsets, lengths)
+        cap = max(4 * len(offsets), 1) if max_events is None else int(max_events)
+        t.chain(b, motifs, cap)
+        out, counts, items, events = t.chain_results()
+        if events > cap:
+            t.chain(b, motifs, events)
+            out, counts, items, events = t.chain_results()
         return out, counts

@@ -1,5 +1,5 @@
-// motif_cli.cpp -- what the command lines share: the argument helpers of every subcommand, and the front end of the four
-// per-read motif subcommands `trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ...` and of the motif-less
+// motif_cli.cpp -- what the command lines share: the argument helpers of every subcommand, and the front end of the five
+// per-read motif subcommands `trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ...` and of the motif-less
 // `trew periods FASTQ...` (motif_cli_main).  A
 // subcommand's own file (annotate.cpp, ...) holds its usage text, its options and their defaults, its rows and its summary.
 // The conventions are those of `short` and `long`: CSV on stdout, messages on stderr, exit status 1 and an empty stdout on an
@@ -76,6 +76,9 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
         const MotifOption *own = nullptr;
         for (const auto &o : cli.options)
             if (a == o.name) own = &o;
+        const MotifFlag *flag = nullptr;
+        for (const auto &o : cli.flags)
+            if (a == o.name) flag = &o;
         if (a == "-h" || a == "--help") {
             cli.usage();
             return 0;
@@ -83,6 +86,8 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
             if (!parse_int(need("--thread"), &cfg.NUM_THREAD)) return bad("THREAD must be a number.");
         } else if (own) {
             if (!own->parse(need(own->name))) return bad(own->error);
+        } else if (flag) {
+            flag->set();
         } else if (a == "--stats") {
             cfg.stats = true;
         } else if (a == "--devices") {

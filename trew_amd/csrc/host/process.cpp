@@ -1186,11 +1186,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1205,6 +1205,8 @@ struct Annotator {
         std::vector<trew_hip_variant> vrecs;  // trew variants
         std::vector<uint64_t> vhist;          // hist, then reads_with, of one batch
         std::vector<trew_hip_period> precs;   // trew periods
+        std::vector<trew_hip_chain_item> crecs;  // trew chain
+        std::vector<uint32_t> ccounts;
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1424,6 +1426,54 @@ static void fold_periods(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew chain: a variable number of items.  windows_fwd / windows_rev: the exact units of each strand (the sum of the runs'
+// counts); variants_s: the variant items; runs_s: the runs; longest / longest_tail: the longest run in units of the forward /
+// reverse strand; reported / reported_rev: the (read, motif) whose units + variants on that strand reach MIN_UNITS
+// (AnnotRequest::min_tract) -- only their items become rows.  The log starts at four events per read; a batch whose log
+// overflows is resubmitted once, with the exact number.
+static void fold_chain(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    uint64_t cap = 4 * x.n, items = 0, events = 0;
+    if (w->ccounts.size() < x.n * (size_t) nm * 4) w->ccounts.resize(x.n * (size_t) nm * 4);
+    for (int attempt = 0;; attempt++) {
+        if (trew_hip_chain(x.c, &x.b, w->slot, x.rq->motifs, nm, cap)) hip_die(x.c, "trew_hip_chain");
+        // an item takes at least one event, so a log that fitted holds at most `cap` items
+        if (w->crecs.size() < cap) w->crecs.resize(cap);
+        if (trew_hip_chain_results(x.c, w->slot, w->crecs.data(), cap, &items, &events, w->ccounts.data(), nullptr)) hip_die(x.c, "trew_hip_chain_results");
+        if (events <= cap) break;
+        if (attempt) die("internal error: the chain log overflowed twice");
+        cap = events;  // the exact number: one retry always suffices
+        p.interval_retries++;
+    }
+    // the items are sorted by (read, motif, strand, start): a key's items are consecutive
+    for (uint64_t i = 0; i < items;) {
+        const trew_hip_chain_item &first = w->crecs[i];
+        uint64_t j = i, units = 0, nvar = 0;
+        uint32_t longest = 0;
+        for (; j < items && w->crecs[j].read == first.read && w->crecs[j].motif == first.motif && w->crecs[j].strand == first.strand; j++) {
+            const trew_hip_chain_item &it = w->crecs[j];
+            if (it.bin == TREW_VARIANT_NONE) {
+                units += it.count;
+                longest = std::max(longest, it.count);
+            } else {
+                nvar++;
+            }
+        }
+        const uint32_t m = first.motif;
+        (first.strand ? p.windows_rev : p.windows_fwd)[m] += units;
+        (first.strand ? p.variants_rev : p.variants_fwd)[m] += nvar;
+        (first.strand ? p.runs_rev : p.runs_fwd)[m] += (j - i) - nvar;
+        uint32_t &lg = (first.strand ? p.longest_tail : p.longest)[m];
+        lg = std::max(lg, longest);
+        if (units + nvar >= x.rq->min_tract[m]) {
+            (first.strand ? p.reported_rev : p.reported)[m]++;
+            for (uint64_t q = i; q < j; q++) p.crows.push_back(ChainRow{x.first_read + first.read, x.lengths[first.read], w->crecs[q]});
+        }
+        i = j;
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1466,6 +1516,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Intervals: fold_intervals(x, p); break;
             case Measure::Variants: fold_variants(x, p); break;
             case Measure::Periods: fold_periods(x, p); break;
+            case Measure::Chain: fold_chain(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1486,6 +1537,9 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         into.terminal_rev[m] += from.terminal_rev[m];
         into.variants_fwd[m] += from.variants_fwd[m];
         into.variants_rev[m] += from.variants_rev[m];
+        into.runs_fwd[m] += from.runs_fwd[m];
+        into.runs_rev[m] += from.runs_rev[m];
+        into.reported_rev[m] += from.reported_rev[m];
     }
     if (into.var_hist.size() < from.var_hist.size()) {
         into.var_hist.resize(from.var_hist.size());
@@ -1503,7 +1557,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain"};  // in the order of Measure
 
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1525,12 +1579,19 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         add_totals(out, w.part);
         out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
         out.irows.insert(out.irows.end(), w.part.irows.begin(), w.part.irows.end());
+        out.crows.insert(out.crows.end(), w.part.crows.begin(), w.part.crows.end());
     }
     std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
         if (x.read != y.read) return x.read < y.read;
         if (x.iv.motif != y.iv.motif) return x.iv.motif < y.iv.motif;
         if (x.iv.strand != y.iv.strand) return x.iv.strand < y.iv.strand;
         return x.iv.start < y.iv.start;
+    });
+    std::sort(out.crows.begin(), out.crows.end(), [](const ChainRow &x, const ChainRow &y) {
+        if (x.read != y.read) return x.read < y.read;
+        if (x.it.motif != y.it.motif) return x.it.motif < y.it.motif;
+        if (x.it.strand != y.it.strand) return x.it.strand < y.it.strand;
+        return x.it.start < y.it.start;
     });
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
@@ -1539,6 +1600,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
                 (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, kMeasureNames[(int) rq.kind], (int) a->workers.size());
         if (rq.kind == Measure::Intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.irows.size(), (unsigned long long) out.interval_retries);
+        if (rq.kind == Measure::Chain) fprintf(stderr, "[trew] %s: %llu items, %llu batch(es) resubmitted with a larger log\n", file_name,
+                                  (unsigned long long) out.crows.size(), (unsigned long long) out.interval_retries);
     }
     return out;
 }

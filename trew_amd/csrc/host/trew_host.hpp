@@ -99,14 +99,14 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants MOTIF[,MOTIF...] FASTQ... and trew periods FASTQ...: the per-read measures.
-// One file path for all five (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp and periods.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods };
+// ---- trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ... and trew periods FASTQ...: the per-read measures.
+// One file path for all six (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp and chain.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
-    // a (read, motif) is reported when its longer tract has at least this many bases (variants: MIN_UNITS; intervals: not read)
+    // a (read, motif) is reported when its longer tract has at least this many bases (variants, chain: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
     int penalty = 0;                                      // tracts, periods
@@ -130,16 +130,23 @@ struct IntervalRow {
     uint32_t length;  // bases
     trew_hip_interval iv;  // iv.read is the index inside its batch; iv.motif the index in command-line order
 };
+struct ChainRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_chain_item it;  // it.read is the index inside its batch; it.motif the index in command-line order
+};
 // What one file (or, summed, all files) came to.  What the per-motif counters count depends on the kind: see the function
 // of process.cpp that folds the kind's records into them.
 struct AnnotFileResult {
     std::vector<AnnotRow> rows;      // annotate, tracts, variants: sorted by read, then motif
     std::vector<IntervalRow> irows;  // intervals: sorted by read, motif, strand, start
+    std::vector<ChainRow> crows;     // chain: the items of the reported (read, motif, strand), sorted by read, motif, strand, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
-    uint64_t interval_retries = 0;  // batches resubmitted because their log overflowed
+    uint64_t interval_retries = 0;  // intervals, chain: batches resubmitted because their log overflowed
+    uint64_t runs_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, runs_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported_rev[TREW_ANNOT_MAX_MOTIFS] = {};  // chain
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     std::vector<uint64_t> var_hist, var_reads_with;  // variants: [motif][strand][bin]; empty for the other kinds
     // periods: (period, strand-canonical unit) -> {reads, sum of end - start}
@@ -157,9 +164,14 @@ struct MotifOption {
     std::function<bool(const char *)> parse;   // false: the argument is refused with `error`
     const char *error;
 };
+struct MotifFlag {
+    const char *name;           // "--items"; takes no argument
+    std::function<void()> set;
+};
 struct MotifCli {
     void (*usage)();
     std::vector<MotifOption> options;
+    std::vector<MotifFlag> flags;
     std::function<const char *()> check;  // once all arguments are read: the text of the first complaint about the options, or nullptr
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
@@ -173,6 +185,7 @@ int tracts_main(int argc, char **argv);
 int intervals_main(int argc, char **argv);
 int variants_main(int argc, char **argv);
 int periods_main(int argc, char **argv);
+int chain_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 
 struct RunStats {

@@ -25,25 +25,26 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain"};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
 };
 struct MeasureState {
-    DevBuf records;                         // the records of the last call, grown on demand (intervals: its append log)
-    DevBuf counts;                          // intervals: one u32 per (read, motif, strand), grown on demand
-    unsigned long long *counter = nullptr;  // intervals: the records the kernel found, in the log or not
+    DevBuf records;                         // the records of the last call, grown on demand (intervals, chain: the append log)
+    DevBuf counts;                          // intervals: one u32 per (read, motif, strand), chain: two; grown on demand
+    unsigned long long *counter = nullptr;  // intervals, chain: the records / events the kernel found, in the log or not
     unsigned long long *hist = nullptr;     // variants: the batch histograms hist, then reads_with, kVarHistLen values each
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call
     u64 n = 0;         // annotate, tracts, variants: its records, n_reads * n_motifs; periods: n_reads
-    u64 max_log = 0;   // intervals: its max_intervals
-    u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2
+    u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events
+    u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that
     int n_motifs = 0;  // variants
+    u32 k[kAnnotMaxMotifs] = {};  // chain: the motifs' lengths (pairing a run's events needs start mod k)
 };
 
 struct Slot {
@@ -1200,8 +1201,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods
-// The five measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain
+// The six measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
@@ -1242,6 +1243,11 @@ extern "C" int trew_periods_host(const uint32_t *words, const uint32_t *offsets,
     return host_status(periods_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out));
 }
 
+extern "C" int trew_chain_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                               int n_motifs, trew_hip_chain_item *out, uint64_t cap, uint64_t *n_items, uint32_t *counts) {
+    return host_status(chain_host(words, offsets, lengths, n_reads, motifs, n_motifs, out, cap, n_items, counts));
+}
+
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
 static void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
     memset(d, 0, sizeof(*d));
@@ -1261,7 +1267,7 @@ static void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
         }
 }
 
-// The pattern tables of a slot, shared by the four measures: created by the first call that needs them (each piece on its
+// The pattern tables of a slot, shared by the measures with motifs: created by the first call that needs them (each piece on its
 // own, so that a failed call can simply be repeated); they travel on the slot's stream in front of the kernel, and only when
 // they changed.
 static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs, int n_motifs) {
@@ -1554,6 +1560,89 @@ extern "C" int trew_hip_periods_results(trew_hip_ctx *ctx, int slot, trew_hip_pe
     if (int rc = fetch_begin(ctx, slot, kPeriods, nullptr, &sp)) return rc;
     const MeasureState &st = sp->measure[kPeriods];
     if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_period), n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- ordered unit chain per read
+extern "C" int trew_hip_chain(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, uint64_t max_events) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * { return max_events < 1 ? "max_events must be at least 1" : nullptr; };
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kChain, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kChain];
+    const u64 n_counts = db.n_reads * (u64) n_motifs * 4ull;
+    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
+    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
+    if (int rc = grow(ctx, s, st.records, max_events * sizeof(uint4))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.max_log = max_events;
+    st.n_counts = n_counts;
+    st.n_motifs = n_motifs;
+    for (int m = 0; m < n_motifs; m++) st.k[m] = (u32) motifs[m].k;
+    // the counter starts every call at zero, also a call without reads (its results then report no event)
+    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
+    if (n_counts == 0) return 0;
+    ChainLog lg;
+    lg.counter = st.counter;
+    lg.events = (uint4 *) st.records.p;
+    lg.cap = max_events;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_chain(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, lg, (u32 *) st.counts.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_chain_results(trew_hip_ctx *ctx, int slot, trew_hip_chain_item *out, uint64_t cap, uint64_t *n_items, uint64_t *n_events,
+                                      uint32_t *counts, float *ms_kernel) {
+    const char *arg_error = !n_items || !n_events ? "trew_hip_chain_results: n_items and n_events must not be null"
+                            : cap && !out         ? "trew_hip_chain_results: out must not be null"
+                                                  : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kChain, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kChain];
+    unsigned long long found = 0;
+    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
+    *n_events = found;
+    // the number of items is the sum of the counts, which the kernel stores whether or not the log fitted
+    std::vector<u32> own_counts;
+    if (!counts && st.n_counts) {
+        own_counts.resize((size_t) st.n_counts);
+        counts = own_counts.data();
+    }
+    if (st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
+    u64 items = 0;
+    for (u64 i = 0; i < st.n_counts; i++) items += counts[i];
+    *n_items = items;
+    const u64 take = std::min<u64>(items, cap);
+    if (found <= st.max_log && take) {
+        // Pairing on the host, so the items do not depend on the order in which the waves appended the events: ordered by
+        // (read, motif, strand, start mod k, start), the starts and ends of a residue class alternate.
+        std::vector<uint4> ev((size_t) found);
+        HIPCHK(ctx, hipMemcpy(ev.data(), st.records.p, found * sizeof(uint4), hipMemcpyDeviceToHost));
+        const u32 *kk = st.k;
+        auto motif_of = [](const uint4 &e) { return e.y & 15u; };
+        std::sort(ev.begin(), ev.end(), [&](const uint4 &a, const uint4 &b) {
+            if (a.x != b.x) return a.x < b.x;
+            if ((a.y & 255u) != (b.y & 255u)) return (a.y & 255u) < (b.y & 255u);  // motif, then strand
+            const u32 k = kk[a.y & 15u];
+            if (a.z % k != b.z % k) return a.z % k < b.z % k;
+            return a.z < b.z;
+        });
+        std::vector<trew_hip_chain_item> all;
+        all.reserve((size_t) items);
+        u32 open = 0;  // the start of the residue class's open run
+        for (const uint4 &e : ev) {
+            const u32 kind = e.y >> 8, m = motif_of(e), strand = (e.y >> 4) & 1u;
+            if (kind & kChainVariant) all.push_back(trew_hip_chain_item{e.x, m, strand, e.z, 1, e.w});
+            if (kind & kChainStart) open = e.z;
+            if (kind & kChainEnd) all.push_back(trew_hip_chain_item{e.x, m, strand, open, (e.z - open) / kk[m] + 1u, TREW_VARIANT_NONE});
+        }
+        if (all.size() != items) return fail(ctx, "trew_hip_chain_results: the events do not pair into the counted items");
+        sort_chain_items(all.data(), all.size());
+        memcpy(out, all.data(), take * sizeof(trew_hip_chain_item));
+    }
     return fetch_end(ctx, st, ms_kernel);
 }
 

@@ -152,6 +152,16 @@ struct IntervalLog {
     u64 cap;
 };
 
+// trew_hip_chain's append log (kernels/chain.inc): events, not items -- the host pairs them (trew_capi.cpp).  One event is four
+// u32 {read, meta, start, bin}: meta = motif | strand << 4 | kind << 8, kind a set of the bits below (a one-unit run is one
+// event with both kChainStart and kChainEnd), bin only for a variant.
+constexpr u32 kChainStart = 1u, kChainEnd = 2u, kChainVariant = 4u;
+struct ChainLog {
+    unsigned long long *counter;  // events found; keeps counting past cap
+    uint4 *events;                // cap events
+    u64 cap;
+};
+
 struct Segment {
     u32 mate;   // 0 = first read of the unit, 1 = second (pair mode)
     u32 start;  // first base

@@ -41,6 +41,7 @@
 //   intervals.inc      intervals_wave_kernel (gap-tolerant motif intervals anywhere in a read; shares tracts.inc's coverage word)
 //   variants.inc       variants_wave_kernel (in-phase variant units per read and their batch histogram; Hamming distance 1)
 //   periods.inc        periods_wave_kernel (de novo repeat period and consensus unit per read; no motif, the shifted self-comparison)
+//   chain.inc          chain_wave_kernel (ordered unit chain per read: run and variant events into an append log; shares variants.inc's words)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -76,6 +77,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/intervals.inc"
 #include "kernels/variants.inc"
 #include "kernels/periods.inc"
+#include "kernels/chain.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -358,6 +360,14 @@ hipError_t launch_periods(hipStream_t st, u32 n_cu, const DevBatch &B, int min_p
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(periods_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, (u32 *) d_out);
+    return hipGetLastError();
+}
+
+// Unit chain: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_chain(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const ChainLog &lg, u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(chain_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, lg, d_counts);
     return hipGetLastError();
 }
 

@@ -42,6 +42,9 @@ hipError_t launch_variants(hipStream_t st, u32 n_cu, const DevBatch &B, const An
                            unsigned long long *d_hist, unsigned long long *d_reads_with);
 // trew_hip_periods: the wave-per-read kernel of kernels/periods.inc on the grid of launch_tracts; no motifs
 hipError_t launch_periods(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period *d_out);
+// trew_hip_chain: the wave-per-read kernel of kernels/chain.inc on the grid of launch_tracts; the counter of `lg` is zero when
+// the kernel starts (the caller's memset on the same stream)
+hipError_t launch_chain(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const ChainLog &lg, u32 *d_counts);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);

@@ -344,6 +344,85 @@ const char *variants_host(const u32 *words, const u32 *offsets, const u32 *lengt
     return nullptr;
 }
 
+// ---------------------------------------------------------------- ordered unit chain per read
+void sort_chain_items(trew_hip_chain_item *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_chain_item &a, const trew_hip_chain_item &b) {
+        if (a.read != b.read) return a.read < b.read;
+        if (a.motif != b.motif) return a.motif < b.motif;
+        if (a.strand != b.strand) return a.strand < b.strand;
+        return a.start < b.start;
+    });
+}
+
+const char *chain_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
+                       trew_hip_chain_item *out, u64 cap, u64 *n_items, u32 *counts) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (!n_items || (cap && !out)) return "trew_chain_host: null argument";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_chain_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_chain_host: more than 2^32 - 1 reads";
+    std::vector<unsigned char> base, state;  // per base: code, or 4 with its nmask bit set; per window: 1 exact, 2 variant
+    std::vector<u32> bin_of;
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        const u32 *w = words + offsets[r];
+        const u32 n = lengths[r];
+        base.resize(n);
+        for (u32 i = 0; i < n; i++) base[i] = (unsigned char) base_at(w, i);
+        for (int m = 0; m < n_motifs; m++) {
+            const u32 k = (u32) motifs[m].k;
+            for (int s = 0; s < 2; s++) {
+                u32 runs = 0, nvar = 0;
+                const u32 nwin = n < k ? 0 : n - k + 1;
+                const u64 t = s ? motif_revcomp(motifs[m].word, (int) k) : motifs[m].word;
+                state.assign(nwin, 0);
+                bin_of.assign(nwin, 0);
+                for (u32 i = 0; i < nwin; i++) {
+                    u32 mism = 0, jj = 0, cc = 0;
+                    bool valid = true;
+                    for (u32 j = 0; j < k && valid; j++) {
+                        const u32 c = base[i + j];
+                        if (c > 3) valid = false;
+                        else if (c != ((u32) (t >> (2 * (k - 1 - j))) & 3u)) {
+                            mism++;
+                            jj = j;
+                            cc = c;
+                        }
+                    }
+                    if (!valid) continue;
+                    if (mism == 0) state[i] = 1;
+                    if (mism == 1) {
+                        state[i] = 2;
+                        bin_of[i] = s ? 4u * (k - 1u - jj) + (3u - cc) : 4u * jj + cc;
+                    }
+                }
+                // windows ascend, so the items come out in the order of their starts
+                for (u32 i = 0; i < nwin; i++) {
+                    const bool before = i >= k && state[i - k] == 1, after = (u64) i + k < nwin && state[i + k] == 1;
+                    trew_hip_chain_item it = {(u32) r, (u32) m, (u32) s, i, 1, TREW_VARIANT_NONE};
+                    if (state[i] == 1 && !before) {  // a run starts here: walk its residue class to its end
+                        for (u64 e = (u64) i + k; e < nwin && state[e] == 1; e += k) it.count++;
+                        runs++;
+                    } else if (state[i] == 2 && (before || after)) {
+                        it.bin = bin_of[i];
+                        nvar++;
+                    } else {
+                        continue;
+                    }
+                    if (found < cap) out[found] = it;
+                    found++;
+                }
+                if (counts) {
+                    u32 *c = counts + ((r * (u64) n_motifs + (u64) m) * 2ull + (u64) s) * 2ull;
+                    c[0] = runs;
+                    c[1] = nvar;
+                }
+            }
+        }
+    }
+    *n_items = found;
+    return nullptr;
+}
+
 // ---------------------------------------------------------------- de novo repeat period and unit per read
 const char *periods_error(int min_period, int max_period, int penalty, u32 min_score) {
     if (min_period < 1 || max_period > 32 || min_period > max_period) return "periods: 1 <= min_period <= max_period <= 32 is required";
