@@ -432,8 +432,8 @@ int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uin
  *   period         the smallest divisor d of k* with u[j] = u[(j + d) mod k*] for all j (on a noisy tract the multiples of
  *                  the true period score within a percent of it; the majority unit's primitive root undoes that)
  *   unit           u[0 .. period - 1] packed like trew_hip_motif.word: first base most significant, no bits above 2 period
- * Out of scope: more than the one best tract per read (trew_hip_intervals with the unit reports all of them), and periods
- * above 32 (a 128-bit unit and 256 bins).  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+ * This is the one best tract of a read; trew_hip_repeats below reports every tract.  Out of scope: periods above 32 (a
+ * 128-bit unit and 256 bins).  Also additive: TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
     uint32_t period, scored_period, score, start, end, matches, support, reserved;
     uint64_t unit;
@@ -489,6 +489,43 @@ int trew_hip_chain_results(trew_hip_ctx *ctx, int slot, trew_hip_chain_item *out
  * *n_items) items (the first ones of the sorted order), counts as above (may be NULL). */
 int trew_chain_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                     int n_motifs, trew_hip_chain_item *out, uint64_t cap, uint64_t *n_items, uint32_t *counts);
+
+/* ---- de novo repeats: every tract of a read, not only the best one (no motif given) ----
+ * Integer-exact (tests/repeat_ref.py is the brute-force form).  The parameters are those of trew_hip_periods, with
+ * the same checks.  A PIECE is a half-open base range [lo, hi) of a read.  Its record is the trew_hip_periods record of the
+ * bases lo .. hi - 1 taken as a read of their own -- nothing outside the piece is seen, valid or not -- with start and end
+ * shifted back into read coordinates.
+ *   repeats(piece)  a piece without a record (no admissible k, or score < min_score) yields nothing; otherwise it yields its
+ *                   record R, then repeats([lo, R.start)) and repeats([R.end, hi))
+ * The tracts of a read are repeats([0, n)).  depth is 0 for the read's own record and parent + 1 below it; the other fields
+ * are those of trew_hip_period.  Consequences: the depth-0 record of a read equals its trew_hip_periods record field for
+ * field, and a read without one has no tract; the tracts of a read are disjoint; none scores above the read's depth-0
+ * tract; a read's records do not depend on the rest of the batch; a piece with hi - lo - min_period < min_score cannot
+ * have a record (score_k <= length - k); a read has at most n / (min_score + 1) tracts.  The consensus keeps the fixed phase
+ * of trew_hip_periods: under indels a long tract's unit can come out wrong, here as there.  Out of scope: periods above 32.
+ * Also additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t read, depth, period, scored_period, score, start, end, matches, support, reserved;
+    uint64_t unit;
+} trew_hip_repeat; /* 48 bytes */
+/* Like trew_hip_periods (batch shapes, staging, asynchronous on the slot's stream, a context of any mode, independent of the
+ * scan and of the other six kernels, no motifs), with buffers of its own that the slot's first call allocates: a log of
+ * max_records records (>= 1; the log grows when a call asks for more) to which the kernel appends every tract, and one count
+ * per read; the log's counter and the counts are zeroed on the slot's stream in front of every launch.  A batch holds at most
+ * 2^32 - 1 reads.  One kernel, a wave per read, for every read length; the recursion runs inside the wave. */
+int trew_hip_repeats(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                     uint64_t max_records);
+/* Waits for the slot.  *n = the number of tracts found, also when that exceeds max_records or cap; n must not be NULL.
+ * counts (n_reads values; may be NULL) = the tracts of every read, always exact.  When *n <= max_records, min(cap, *n) records
+ * are copied, sorted by (read, start), so the output does not depend on device scheduling.  When *n > max_records the log
+ * holds an unspecified subset and nothing is copied; counts and *n are still exact: repeat trew_hip_repeats with max_records
+ * >= *n -- one retry always suffices.  That case is no error (the call returns 0), like trew_hip_intervals_results with too
+ * small a log. */
+int trew_hip_repeats_results(trew_hip_ctx *ctx, int slot, trew_hip_repeat *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel);
+/* The same on the host, piece by piece from the definition, over packed planes: *n = tracts found, min(cap, *n) records (the
+ * first ones of the sorted order), counts as above (may be NULL). */
+int trew_repeats_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                      int penalty, uint32_t min_score, trew_hip_repeat *out, uint64_t cap, uint64_t *n, uint32_t *counts);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

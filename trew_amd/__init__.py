@@ -29,6 +29,7 @@ from .capi import (  # noqa: F401
     k_mer_check,
     pack_reads,
     periods,
+    repeats,
     tracts,
     variants,
 )

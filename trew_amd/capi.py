@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_variants", "trew_hip_variants_results", "trew_variants_host",
     "trew_hip_periods", "trew_hip_periods_results", "trew_periods_host",
     "trew_hip_chain", "trew_hip_chain_results", "trew_chain_host",
+    "trew_hip_repeats", "trew_hip_repeats_results", "trew_repeats_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -143,6 +144,15 @@ class ChainItem(C.Structure):
 CHAIN_DTYPE = np.dtype([(name, "<u4") for name, _ in ChainItem._fields_])
 assert CHAIN_DTYPE.itemsize == C.sizeof(ChainItem) == 24
 
+
+class Repeat(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("read", "depth", "period", "scored_period", "score", "start", "end", "matches", "support",
+                                                "reserved")] + [("unit", C.c_uint64)]
+
+
+REPEAT_DTYPE = np.dtype([(name, "<u8" if name == "unit" else "<u4") for name, _ in Repeat._fields_])
+assert REPEAT_DTYPE.itemsize == C.sizeof(Repeat) == 48
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -218,6 +228,9 @@ def load():
     lib.trew_hip_chain.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, u64]
     lib.trew_hip_chain_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(C.c_float)]
     lib.trew_chain_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, vp, u64, C.POINTER(u64), vp]
+    lib.trew_hip_repeats.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64]
+    lib.trew_hip_repeats_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), vp, C.POINTER(C.c_float)]
+    lib.trew_repeats_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp]
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -408,6 +421,28 @@ def chain_host(reads_or_packed, motifs, cap=None):
         out = np.zeros(int(n.value), dtype=CHAIN_DTYPE)
         call(out)
     return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
+
+
+def repeats_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
+    """trew_repeats_host: every de novo repeat tract of every read computed on the host, piece by piece from the definition.
+    reads_or_packed as for annotate_host.  Returns (REPEAT_DTYPE records sorted by (read, start), counts of shape (n_reads,),
+    found); with `cap` at most that many records."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    counts = np.zeros(len(offsets), dtype=np.uint32)
+    n = C.c_uint64(0)
+
+    def call(out):
+        if lib.trew_repeats_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                                 int(penalty), int(min_score), out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
+            raise TrewHipError("trew_repeats_host failed: %s" % lib.trew_hip_last_error(None).decode())
+
+    out = np.zeros(0 if cap is None else int(cap), dtype=REPEAT_DTYPE)
+    call(out)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=REPEAT_DTYPE)
+        call(out)
+    return out[:min(len(out), int(n.value))], counts, int(n.value)
 
 
 def chain_unit_text(motif_text, bin_):
@@ -694,6 +729,31 @@ class TrewHip:
                       "trew_hip_chain_results")
         return (out, counts, items, events, ms.value) if want_ms else (out, counts, items, events)
 
+    def repeats(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
+        """Queue every de novo repeat tract of every read of `batch` on the slot's stream (no motifs).  max_records: the
+        capacity of the log for this call (default: the batch's read count, at least 1)."""
+        if max_records is None:
+            max_records = max(int(batch.n_reads), 1)
+        self._queue("repeats", slot, batch, None, 1, shape=(int(max_records),))
+        self._chk(self.lib.trew_hip_repeats(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
+                                            int(max_records)), "trew_hip_repeats")
+
+    def repeats_results(self, slot=0, want_ms=False):
+        """Results of the slot's last repeats: (REPEAT_DTYPE records sorted by (read, start), counts of shape (n_reads,), found
+        [, kernel ms]).  found > max_records: no records, counts and found are exact; repeat the call with max_records >=
+        found."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, _, cap = self._queued.get(("repeats", slot), (0, 1, 0))
+        counts = np.zeros(n_reads, dtype=np.uint32)
+        self._chk(self.lib.trew_hip_repeats_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
+                  "trew_hip_repeats_results")
+        found = int(n.value)
+        out = np.zeros(found if found <= cap else 0, dtype=REPEAT_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_repeats_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_repeats_results")
+        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+
     def submit_reads(self, reads, slot=0):
         b = self.host_batch(*pack_reads(reads))
         self.submit(b, slot)
@@ -938,4 +998,23 @@ def chain(reads, motifs, device=0, max_events=None):
         if events > cap:
             t.chain(b, motifs, events)
             out, counts, items, events = t.chain_results()
+        return out, counts
+
+
+def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):
+    """Every de novo repeat tract on the GPU: for every read (bytes / str) the period, the consensus unit and the position of
+    its best-scoring tract (depth 0, the record of `periods`) and, in the same way, of what lies in front of it and behind it,
+    until nothing scores min_score.  Returns (REPEAT_DTYPE records sorted by (read, start), counts of shape (n_reads,)).  The
+    first call's log holds max_records records (default: one per read); when more are found the call is repeated once with
+    the exact number."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        b = t.host_batch(words, offsets, lengths)
+        cap = max(len(offsets), 1) if max_records is None else int(max_records)
+        t.repeats(b, min_period, max_period, penalty, min_score, cap)
+        out, counts, found = t.repeats_results()
+        if found > cap:
+            t.repeats(b, min_period, max_period, penalty, min_score, found)
+            out, counts, found = t.repeats_results()
         return out, counts

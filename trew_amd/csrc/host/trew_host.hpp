@@ -99,19 +99,19 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ... and trew periods FASTQ...: the per-read measures.
-// One file path for all six (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp and chain.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain };
+// ---- trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ... and trew periods|repeats FASTQ...: the per-read measures.
+// One file path for all seven (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp and repeats.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     // a (read, motif) is reported when its longer tract has at least this many bases (variants, chain: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
-    int penalty = 0;                                      // tracts, periods
-    int min_period = 1, max_period = 32;                  // periods (which takes no motifs: n_motifs = 0)
-    uint32_t min_score = 24;                              // periods
+    int penalty = 0;                                      // tracts, periods, repeats
+    int min_period = 1, max_period = 32;                  // periods, repeats (which take no motifs: n_motifs = 0)
+    uint32_t min_score = 24;                              // periods, repeats
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
 };
 struct AnnotRow {
@@ -135,22 +135,33 @@ struct ChainRow {
     uint32_t length;  // bases
     trew_hip_chain_item it;  // it.read is the index inside its batch; it.motif the index in command-line order
 };
+struct RepeatRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_repeat rp;  // rp.read is the index inside its batch
+};
+struct RepeatUnit {
+    uint64_t reads = 0, tracts = 0, bases = 0;  // reads with such a tract, the tracts, the sum of their end - start
+};
 // What one file (or, summed, all files) came to.  What the per-motif counters count depends on the kind: see the function
 // of process.cpp that folds the kind's records into them.
 struct AnnotFileResult {
     std::vector<AnnotRow> rows;      // annotate, tracts, variants: sorted by read, then motif
     std::vector<IntervalRow> irows;  // intervals: sorted by read, motif, strand, start
     std::vector<ChainRow> crows;     // chain: the items of the reported (read, motif, strand), sorted by read, motif, strand, start
+    std::vector<RepeatRow> rrows;    // repeats: sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
-    uint64_t interval_retries = 0;  // intervals, chain: batches resubmitted because their log overflowed
+    uint64_t interval_retries = 0;  // intervals, chain, repeats: batches resubmitted because their log overflowed
     uint64_t runs_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, runs_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported_rev[TREW_ANNOT_MAX_MOTIFS] = {};  // chain
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     std::vector<uint64_t> var_hist, var_reads_with;  // variants: [motif][strand][bin]; empty for the other kinds
     // periods: (period, strand-canonical unit) -> {reads, sum of end - start}
     std::map<std::pair<uint32_t, uint64_t>, std::pair<uint64_t, uint64_t>> period_units;
+    // repeats: (period, strand-canonical unit) -> its reads, tracts and bases
+    std::map<std::pair<uint32_t, uint64_t>, RepeatUnit> repeat_units;
 };
 void add_totals(AnnotFileResult &into, const AnnotFileResult &from);  // everything but the rows: sums, and the larger of longest*
 struct Annotator;  // device contexts and one slot per worker
@@ -176,7 +187,7 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
-    bool motif_less = false;                      // periods: every positional argument is a file, `names` stays empty
+    bool motif_less = false;                      // periods, repeats: every positional argument is a file, `names` stays empty
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
@@ -186,6 +197,7 @@ int intervals_main(int argc, char **argv);
 int variants_main(int argc, char **argv);
 int periods_main(int argc, char **argv);
 int chain_main(int argc, char **argv);
+int repeats_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 
 struct RunStats {

@@ -34,13 +34,22 @@
 
 constexpr u32 kPeriodBins = 128;
 
-// eq_k word of 32-base word w: bit i = bases 32 w + i and 32 w + i + k are both valid and equal, and 32 w + i < n - k.
-// nv = the positions of the word below n - k.  Reads word w and word w + 1 where they exist; what a plane holds at and
-// past the end of the read never shows (i + k < n for every bit kept).
-__device__ __forceinline__ u32 period_eq_word(const ReadRef &rd, u32 k, u32 w, u32 &nv) {
-    const long long left = (long long) rd.len - (long long) k - 32ll * (long long) w;  // positions i >= 32 w with i < n - k
-    nv = left >= 32 ? 32u : left > 0 ? (u32) left : 0u;
-    if (nv == 0u) return 0u;  // also: w >= rd.nw
+// A piece [lo, hi) of a read (0 <= lo <= hi <= n) is scored as a read of its own: position p exists only for lo <= p and
+// p + k < hi, and nothing outside the piece is seen.  The whole read is the piece [0, n) (periods_wave_kernel); the children of
+// a tract are pieces (kernels/repeats.inc).  The iteration grid of a piece starts at word lo >> 5.
+struct Piece {
+    u32 lo, hi;
+};
+
+// eq_k word of 32-base word w (w >= lo >> 5): bit i = bases 32 w + i and 32 w + i + k are both valid and equal, and
+// lo <= 32 w + i < hi - k.  vm = the positions of the word that exist.  Reads word w and word w + 1 where they exist; what a
+// plane holds in front of lo or at and past hi never shows (lo <= i and i + k < hi for every bit kept).
+__device__ __forceinline__ u32 period_eq_word(const ReadRef &rd, Piece pc, u32 k, u32 w, u32 &vm) {
+    const long long left = (long long) pc.hi - (long long) k - 32ll * (long long) w;  // positions i >= 32 w with i < hi - k
+    const u32 nv = left >= 32 ? 32u : left > 0 ? (u32) left : 0u;
+    const u32 first = w == (pc.lo >> 5) ? pc.lo & 31u : 0u;  // the bits of the piece's first word in front of lo
+    vm = (nv >= 32u ? 0xffffffffu : (1u << nv) - 1u) & (0xffffffffu << first);
+    if (vm == 0u) return 0u;  // also: w >= rd.nw
     const u32 c0 = rd.w[3ull * w + 0], c1 = rd.w[3ull * w + 1], c2 = rd.w[3ull * w + 2];
     u32 n0 = 0, n1 = 0, n2 = 0xffffffffu;
     if (w + 1u < rd.nw) {
@@ -49,15 +58,13 @@ __device__ __forceinline__ u32 period_eq_word(const ReadRef &rd, u32 k, u32 w, u
         n2 = rd.w[3ull * (w + 1u) + 2];
     }
     const u32 s0 = k >= 32u ? n0 : alignbit(n0, c0, k), s1 = k >= 32u ? n1 : alignbit(n1, c1, k), s2 = k >= 32u ? n2 : alignbit(n2, c2, k);
-    const u32 valid = nv >= 32u ? 0xffffffffu : (1u << nv) - 1u;
-    return ~((c0 ^ s0) | (c1 ^ s1) | c2 | s2) & valid;
+    return ~((c0 ^ s0) | (c1 ^ s1) | c2 | s2) & vm;
 }
 
-// in-word walk over the prefixes e = 1 .. 32 (e = 0: value 0): total, smallest and largest prefix, best segment.  A bit at
-// or past nv scores 0 and changes none of the four.
-__device__ __forceinline__ void period_walk(u32 eq, u32 nv, int P, int &T, int &m, int &M, int &W) {
-    const u32 valid = nv >= 32u ? 0xffffffffu : (1u << nv) - 1u;
-    const u32 ne = valid & ~eq;
+// in-word walk over the prefixes e = 1 .. 32 (e = 0: value 0): total, smallest and largest prefix, best segment.  A position
+// that does not exist (no bit in vm) scores 0 and changes none of the four.
+__device__ __forceinline__ void period_walk(u32 eq, u32 vm, int P, int &T, int &m, int &M, int &W) {
+    const u32 ne = vm & ~eq;
     int s = 0, mn = 0, mx = 0, bw = 0;
 #pragma unroll
     for (int i = 0; i < 32; i++) {
@@ -92,14 +99,15 @@ __device__ __forceinline__ PeriodPlace period_place(int T, int m) {
     return p;
 }
 
-// score_k of one read: the largest V_k(e)
-__device__ __forceinline__ u32 period_score(const ReadRef &rd, u32 k, int P) {
+// score_k of one piece: the largest V_k(e)
+__device__ __forceinline__ u32 period_score(const ReadRef &rd, Piece pc, u32 k, int P) {
     long long run = 0, gmin = 0, best = 0;  // S at the start of the iteration; the smallest S so far; the largest V so far
-    for (u32 t0 = 0; t0 < rd.nw; t0 += 64u) {
-        u32 nv;
-        const u32 eq = period_eq_word(rd, k, t0 + lane_id(), nv);
+    const u32 wend = (u32) (((u64) pc.hi + 31ull) >> 5);  // one past the piece's last word
+    for (u32 t0 = pc.lo >> 5; t0 < wend; t0 += 64u) {
+        u32 vm;
+        const u32 eq = period_eq_word(rd, pc, k, t0 + lane_id(), vm);
         int T, m, M, W;
-        period_walk(eq, nv, P, T, m, M, W);
+        period_walk(eq, vm, P, T, m, M, W);
         const PeriodPlace pl = period_place(T, m);
         const int hi = pl.off + M;
         const u32 v_in = wave_max_u32((u32) max(W, hi - pl.pmin));         // against the words of this iteration; W >= 0
@@ -111,16 +119,18 @@ __device__ __forceinline__ u32 period_score(const ReadRef &rd, u32 k, int P) {
     return (u32) best;
 }
 
-// the segment of score_k: e = the smallest e with V_k(e) = score, b = the largest b <= e with S_k(b) smallest over [0, e]
-__device__ __forceinline__ void period_locate(const ReadRef &rd, u32 k, int P, u32 score, u32 &b_out, u32 &e_out) {
+// the segment of score_k (score > 0): e = the smallest e with V_k(e) = score, b = the largest b in [lo, e] with S_k(b)
+// smallest over [lo, e]; both in read coordinates
+__device__ __forceinline__ void period_locate(const ReadRef &rd, Piece pc, u32 k, int P, u32 score, u32 &b_out, u32 &e_out) {
     const u32 lane = lane_id();
     long long run = 0, gmin = 0, s_end = 0;
     u32 e_star = 0;
-    for (u32 t0 = 0; t0 < rd.nw; t0 += 64u) {
-        u32 nv;
-        const u32 eq = period_eq_word(rd, k, t0 + lane, nv);
+    const u32 wlo = pc.lo >> 5, wend = (u32) (((u64) pc.hi + 31ull) >> 5);
+    for (u32 t0 = wlo; t0 < wend; t0 += 64u) {
+        u32 vm;
+        const u32 eq = period_eq_word(rd, pc, k, t0 + lane, vm);
         int T, m, M, W;
-        period_walk(eq, nv, P, T, m, M, W);
+        period_walk(eq, vm, P, T, m, M, W);
         const PeriodPlace pl = period_place(T, m);
         // second walk, relative to the word's start: mn = the smallest S in front (the start itself included, so <= 0)
         long long s = 0, mn = min(gmin - run, (long long) pl.pmin) - (long long) pl.off;
@@ -128,7 +138,7 @@ __device__ __forceinline__ void period_locate(const ReadRef &rd, u32 k, int P, u
         long long s_loc = 0;
 #pragma unroll
         for (u32 i = 0; i < 32u; i++) {
-            if (i < nv) {
+            if ((vm >> i) & 1u) {
                 s += ((eq >> i) & 1u) ? 1ll : -(long long) P;
                 mn = min(mn, s);
                 if (e_loc == 0u && s - mn == (long long) score) {
@@ -148,31 +158,30 @@ __device__ __forceinline__ void period_locate(const ReadRef &rd, u32 k, int P, u
         gmin = min(gmin, run + (long long) pl.itmin);
         run += (long long) pl.total;
     }
-    const long long lowest = s_end - (long long) score;  // min over b <= e* of S(b)
+    const long long lowest = s_end - (long long) score;  // min over lo <= b <= e* of S(b)
     u32 b1 = 0;                                          // b + 1 of the latest prefix found at that value
     run = 0;
-    for (u32 t0 = 0; t0 <= (e_star >> 5) && t0 < rd.nw; t0 += 64u) {
+    for (u32 t0 = wlo; t0 <= (e_star >> 5) && t0 < wend; t0 += 64u) {
         const u32 w = t0 + lane;
-        u32 nv;
-        const u32 eq = period_eq_word(rd, k, w, nv);
+        u32 vm;
+        const u32 eq = period_eq_word(rd, pc, k, w, vm);
         int T, m, M, W;
-        period_walk(eq, nv, P, T, m, M, W);
+        period_walk(eq, vm, P, T, m, M, W);
         const u32 incl = wave_scan_u32((u32) T);
         long long s = run + (long long) (int) (incl - (u32) T);
         u32 mine = 0;
         const u64 b0 = (u64) w << 5;
-        if (b0 <= (u64) e_star && s == lowest) mine = (u32) b0 + 1u;  // the word's start: the end of the word in front, or b = 0
+        // b exists for lo <= b <= e*; S does not move in front of lo, so b = lo is found with the value 0 wherever lo lies in its word
+        if (b0 >= (u64) pc.lo && b0 <= (u64) e_star && s == lowest) mine = (u32) b0 + 1u;  // the word's start: the end of the word in front, or b = lo
 #pragma unroll
         for (u32 i = 0; i < 32u; i++) {
-            if (i < nv) {
-                s += ((eq >> i) & 1u) ? 1ll : -(long long) P;
-                if (b0 + i + 1u <= (u64) e_star && s == lowest) mine = (u32) b0 + i + 2u;
-            }
+            if ((vm >> i) & 1u) s += ((eq >> i) & 1u) ? 1ll : -(long long) P;
+            if (b0 + i + 1u >= (u64) pc.lo && b0 + i + 1u <= (u64) e_star && s == lowest) mine = (u32) b0 + i + 2u;
         }
         b1 = max(b1, wave_max_u32(mine));
         run += (long long) __builtin_amdgcn_readlane((int) incl, 63);
     }
-    b_out = b1 - 1u;  // b1 >= 1: the minimum over [0, e*] is attained
+    b_out = b1 - 1u;  // b1 >= 1: the minimum over [lo, e*] is attained
     e_out = e_star;
 }
 
@@ -212,6 +221,53 @@ __device__ __forceinline__ void period_consensus(const ReadRef &rd, u32 k, u32 s
     if (lane >= k) u = cnt_u = 0;
 }
 
+// The record of one piece: rec[0 .. 9] = the ten words of trew_hip_period (period, scored_period, score, start, end, matches,
+// support, reserved, unit), start and end in read coordinates; all zero and false without a record (no admissible k, or
+// score < min_score).  Wave-uniform.  h: the wave's bins.
+__device__ __forceinline__ bool period_record(const ReadRef &rd, Piece pc, u32 kmin, u32 kmax, int P, u32 min_score, u32 *h, u32 (&rec)[10]) {
+    const u32 lane = lane_id();
+    const u32 len = pc.hi - pc.lo;
+    u32 best = 0, ks = 0;
+    for (u32 k = kmin; k <= kmax && k < len; k++) {
+        const u32 sc = period_score(rd, pc, k, P);
+        if (sc > best) {  // strictly: the smallest k keeps a tie
+            best = sc;
+            ks = k;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) rec[i] = 0;
+    if (ks == 0u || best < min_score) return false;  // wave-uniform
+    u32 b, e;
+    period_locate(rd, pc, ks, P, best, b, e);
+    const u32 start = b, end = e + ks;
+    u32 u, cnt_u;
+    period_consensus(rd, ks, start, end, h, u, cnt_u);
+    u32 d = ks;
+    for (u32 c = 1; c < ks; c++) {
+        if (ks % c) continue;
+        const u32 src = lane + c >= ks ? lane + c - ks : lane + c;  // (j + c) mod k* for the lanes j < k*
+        const u32 other = (u32) __builtin_amdgcn_ds_bpermute((int) ((src & 63u) << 2), (int) u);
+        if (__ballot(lane < ks && other != u) == 0ull) {
+            d = c;
+            break;
+        }
+    }
+    // unit: u[0 .. d - 1], first base most significant; the lanes' terms have no bit in common, so their sum is their OR
+    const u32 sh = lane < d ? 2u * (d - 1u - lane) : 0u;
+    const u64 term = lane < d ? (u64) u << sh : 0ull;
+    rec[0] = d;
+    rec[1] = ks;
+    rec[2] = best;
+    rec[3] = start;
+    rec[4] = end;
+    rec[5] = tract_div((u64) best + (u64) (u32) P * (u64) (e - b), (u32) P + 1u);
+    rec[6] = wave_sum_u32(cnt_u);
+    rec[8] = wave_sum_u32((u32) term);
+    rec[9] = wave_sum_u32((u32) (term >> 32));
+    return true;
+}
+
 __global__ void __launch_bounds__(256) periods_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, u32 *__restrict__ out) {
     __shared__ u32 bins[4][kPeriodBins];
     const u32 lane = lane_id();
@@ -226,45 +282,8 @@ __global__ void __launch_bounds__(256) periods_wave_kernel(DevBatch B, int min_p
     const u32 kmin = (u32) rfl_i(min_period), kmax = (u32) rfl_i(max_period);
     for (u64 r = wave; r < B.n_reads; r += n_waves) {
         const ReadRef rd = uni(get_read(B, r));
-        u32 best = 0, ks = 0;
-        for (u32 k = kmin; k <= kmax && k < rd.len; k++) {
-            const u32 sc = period_score(rd, k, P);
-            if (sc > best) {  // strictly: the smallest k keeps a tie
-                best = sc;
-                ks = k;
-            }
-        }
-        // the record's ten words (trew_hip_period): period, scored_period, score, start, end, matches, support, reserved, unit
-        u32 rec[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (ks != 0u && best >= min_score) {  // wave-uniform
-            u32 b, e;
-            period_locate(rd, ks, P, best, b, e);
-            const u32 start = b, end = e + ks;
-            u32 u, cnt_u;
-            period_consensus(rd, ks, start, end, h, u, cnt_u);
-            u32 d = ks;
-            for (u32 c = 1; c < ks; c++) {
-                if (ks % c) continue;
-                const u32 src = lane + c >= ks ? lane + c - ks : lane + c;  // (j + c) mod k* for the lanes j < k*
-                const u32 other = (u32) __builtin_amdgcn_ds_bpermute((int) ((src & 63u) << 2), (int) u);
-                if (__ballot(lane < ks && other != u) == 0ull) {
-                    d = c;
-                    break;
-                }
-            }
-            // unit: u[0 .. d - 1], first base most significant; the lanes' terms have no bit in common, so their sum is their OR
-            const u32 sh = lane < d ? 2u * (d - 1u - lane) : 0u;
-            const u64 term = lane < d ? (u64) u << sh : 0ull;
-            rec[0] = d;
-            rec[1] = ks;
-            rec[2] = best;
-            rec[3] = start;
-            rec[4] = end;
-            rec[5] = tract_div((u64) best + (u64) (u32) P * (u64) (e - b), (u32) P + 1u);
-            rec[6] = wave_sum_u32(cnt_u);
-            rec[8] = wave_sum_u32((u32) term);
-            rec[9] = wave_sum_u32((u32) (term >> 32));
-        }
+        u32 rec[10];
+        period_record(rd, Piece{0u, rd.len}, kmin, kmax, P, min_score, h, rec);  // the whole read
         u32 x = rec[9];
 #pragma unroll
         for (int i = 8; i >= 0; i--) x = lane == (u32) i ? rec[i] : x;

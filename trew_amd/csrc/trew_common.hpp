@@ -162,6 +162,13 @@ struct ChainLog {
     u64 cap;
 };
 
+// trew_hip_repeats' append log (kernels/repeats.inc): records of twelve u32 (trew_hip_repeat)
+struct RepeatLog {
+    unsigned long long *counter;  // tracts found; keeps counting past cap
+    u32 *recs;                    // cap records
+    u64 cap;
+};
+
 struct Segment {
     u32 mate;   // 0 = first read of the unit, 1 = second (pair mode)
     u32 start;  // first base

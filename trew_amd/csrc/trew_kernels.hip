@@ -42,6 +42,7 @@
 //   variants.inc       variants_wave_kernel (in-phase variant units per read and their batch histogram; Hamming distance 1)
 //   periods.inc        periods_wave_kernel (de novo repeat period and consensus unit per read; no motif, the shifted self-comparison)
 //   chain.inc          chain_wave_kernel (ordered unit chain per read: run and variant events into an append log; shares variants.inc's words)
+//   repeats.inc        repeats_wave_kernel (de novo repeats: every tract of a read, the recursion over pieces inside the wave; shares periods.inc's functions)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -78,6 +79,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/variants.inc"
 #include "kernels/periods.inc"
 #include "kernels/chain.inc"
+#include "kernels/repeats.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -368,6 +370,15 @@ hipError_t launch_chain(hipStream_t st, u32 n_cu, const DevBatch &B, const Annot
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(chain_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, lg, d_counts);
+    return hipGetLastError();
+}
+
+// De novo repeats, every tract: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_repeats(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &lg,
+                          u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(repeats_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
     return hipGetLastError();
 }
 

@@ -431,71 +431,125 @@ const char *periods_error(int min_period, int max_period, int penalty, u32 min_s
     return nullptr;
 }
 
+// The record of the piece [lo, hi) of a read, its bases taken as a read of their own: nothing outside the piece is seen, start
+// and end are in read coordinates.  base: per base of the read its code, or 4 with its nmask bit set.  All zero without a record.
+static void period_piece(const unsigned char *base, u32 lo, u32 hi, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period &o) {
+    memset(&o, 0, sizeof(o));
+    const u32 n = hi - lo;
+    base += lo;
+    // the best-scoring segment of eq_k for every k; a later k must score strictly more
+    long long best = 0;
+    u32 ks = 0, bs = 0, es = 0;
+    for (u32 k = (u32) min_period; k <= (u32) max_period && k < n; k++) {
+        long long S = 0, low = 0, score = 0;  // S(e), the smallest S(b) over b <= e, the largest S(e) - low so far
+        u32 b_lo = 0, b = 0, e = 0;           // the latest b at which S is low; the segment of `score`
+        for (u32 i = 0; i + k < n; i++) {
+            const bool eq = base[i] < 4 && base[i] == base[i + k];
+            S += eq ? 1 : -(long long) penalty;
+            if (S <= low) {  // the latest b keeps a tie: the shorter segment
+                low = S;
+                b_lo = i + 1;
+            }
+            if (S - low > score) {  // strictly: the earliest e keeps a tie
+                score = S - low;
+                e = i + 1;
+                b = b_lo;
+            }
+        }
+        if (score > best) {
+            best = score;
+            ks = k;
+            bs = b;
+            es = e;
+        }
+    }
+    if (ks == 0 || best < (long long) min_score) return;
+    o.scored_period = ks;
+    o.score = (u32) best;
+    o.matches = (u32) (((u64) best + (u64) penalty * (u64) (es - bs)) / (u64) (1 + penalty));
+    const u32 start = bs, end = es + ks;  // in the piece
+    u32 cnt[32][4] = {};
+    for (u32 p = start; p < end; p++)
+        if (base[p] < 4) cnt[(p - start) % ks][base[p]]++;
+    u32 u[32];
+    for (u32 j = 0; j < ks; j++) {
+        u[j] = 0;
+        for (u32 c = 1; c < 4; c++)
+            if (cnt[j][c] > cnt[j][u[j]]) u[j] = c;  // strictly: the smallest code keeps a tie
+        o.support += cnt[j][u[j]];
+    }
+    for (u32 d = 1; d <= ks; d++) {
+        if (ks % d) continue;
+        bool periodic = true;
+        for (u32 j = 0; j < ks && periodic; j++) periodic = u[j] == u[(j + d) % ks];
+        if (periodic) {
+            o.period = d;
+            break;
+        }
+    }
+    for (u32 j = 0; j < o.period; j++) o.unit = (o.unit << 2) | u[j];
+    o.start = lo + start;
+    o.end = lo + end;
+}
+
+static void unpack_bases(const u32 *w, u32 n, std::vector<unsigned char> &base) {
+    base.resize(n);
+    for (u32 i = 0; i < n; i++) base[i] = (unsigned char) base_at(w, i);
+}
+
 const char *periods_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
                          u32 min_score, trew_hip_period *out) {
     if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
     if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_periods_host: null argument";
     std::vector<unsigned char> base;  // per base: code, or 4 with its nmask bit set
     for (u64 r = 0; r < n_reads; r++) {
-        const u32 *w = words + offsets[r];
-        const u32 n = lengths[r];
-        trew_hip_period &o = out[r];
-        memset(&o, 0, sizeof(o));
-        base.resize(n);
-        for (u32 i = 0; i < n; i++) base[i] = (unsigned char) base_at(w, i);
-        // the best-scoring segment of eq_k for every k; a later k must score strictly more
-        long long best = 0;
-        u32 ks = 0, bs = 0, es = 0;
-        for (u32 k = (u32) min_period; k <= (u32) max_period && k < n; k++) {
-            long long S = 0, lo = 0, score = 0;  // S(e), the smallest S(b) over b <= e, the largest S(e) - lo so far
-            u32 b_lo = 0, b = 0, e = 0;           // the latest b at which S is lo; the segment of `score`
-            for (u32 i = 0; i + k < n; i++) {
-                const bool eq = base[i] < 4 && base[i] == base[i + k];
-                S += eq ? 1 : -(long long) penalty;
-                if (S <= lo) {  // the latest b keeps a tie: the shorter segment
-                    lo = S;
-                    b_lo = i + 1;
-                }
-                if (S - lo > score) {  // strictly: the earliest e keeps a tie
-                    score = S - lo;
-                    e = i + 1;
-                    b = b_lo;
-                }
-            }
-            if (score > best) {
-                best = score;
-                ks = k;
-                bs = b;
-                es = e;
-            }
-        }
-        if (ks == 0 || best < (long long) min_score) continue;
-        o.scored_period = ks;
-        o.score = (u32) best;
-        o.start = bs;
-        o.end = es + ks;
-        o.matches = (u32) (((u64) best + (u64) penalty * (u64) (es - bs)) / (u64) (1 + penalty));
-        u32 cnt[32][4] = {};
-        for (u32 p = o.start; p < o.end; p++)
-            if (base[p] < 4) cnt[(p - o.start) % ks][base[p]]++;
-        u32 u[32];
-        for (u32 j = 0; j < ks; j++) {
-            u[j] = 0;
-            for (u32 c = 1; c < 4; c++)
-                if (cnt[j][c] > cnt[j][u[j]]) u[j] = c;  // strictly: the smallest code keeps a tie
-            o.support += cnt[j][u[j]];
-        }
-        for (u32 d = 1; d <= ks; d++) {
-            if (ks % d) continue;
-            bool periodic = true;
-            for (u32 j = 0; j < ks && periodic; j++) periodic = u[j] == u[(j + d) % ks];
-            if (periodic) {
-                o.period = d;
-                break;
-            }
-        }
-        for (u32 j = 0; j < o.period; j++) o.unit = (o.unit << 2) | u[j];
+        unpack_bases(words + offsets[r], lengths[r], base);
+        period_piece(base.data(), 0, lengths[r], min_period, max_period, penalty, min_score, out[r]);  // the whole read
     }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- de novo repeats: every tract of a read
+void sort_repeats(trew_hip_repeat *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_repeat &a, const trew_hip_repeat &b) { return a.read != b.read ? a.read < b.read : a.start < b.start; });
+}
+
+const char *repeats_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, trew_hip_repeat *out, u64 cap, u64 *n, u32 *counts) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    if (!n) return "trew_repeats_host: n must not be null";
+    if (cap && !out) return "trew_repeats_host: out must not be null";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_repeats_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_repeats_host: a batch holds at most 2^32 - 1 reads";
+    struct Todo {
+        u32 lo, hi, depth;
+    };
+    std::vector<unsigned char> base;
+    std::vector<Todo> todo;
+    std::vector<trew_hip_repeat> mine;  // the tracts of one read
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        mine.clear();
+        todo.assign(1, Todo{0, lengths[r], 0});
+        while (!todo.empty()) {  // the definition piece by piece; no piece is pruned, a piece without a record ends its branch
+            const Todo t = todo.back();
+            todo.pop_back();
+            trew_hip_period p;
+            period_piece(base.data(), t.lo, t.hi, min_period, max_period, penalty, min_score, p);
+            if (p.scored_period == 0) continue;
+            mine.push_back(trew_hip_repeat{(u32) r, t.depth, p.period, p.scored_period, p.score, p.start, p.end, p.matches, p.support, 0, p.unit});
+            todo.push_back(Todo{p.end, t.hi, t.depth + 1});
+            todo.push_back(Todo{t.lo, p.start, t.depth + 1});
+        }
+        sort_repeats(mine.data(), mine.size());  // disjoint, so by start
+        for (const trew_hip_repeat &x : mine) {
+            if (found < cap) out[found] = x;
+            found++;
+        }
+        if (counts) counts[r] = (u32) mine.size();
+    }
+    *n = found;
     return nullptr;
 }
 
