@@ -31,8 +31,9 @@ extern "C" {
 /* Still 4 with the annotation entry points (trew_motif_parse, trew_hip_annotate, trew_hip_annotate_results,
  * trew_annotate_host), the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host), the interval
  * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host), the variant entry points
- * (trew_hip_variants, trew_hip_variants_results, trew_variants_host) and the period entry points (trew_hip_periods,
- * trew_hip_periods_results, trew_periods_host): they are purely additive -- no existing structure, enumerator or function
+ * (trew_hip_variants, trew_hip_variants_results, trew_variants_host), the period entry points (trew_hip_periods,
+ * trew_hip_periods_results, trew_periods_host) and the satellite entry points (trew_hip_satellites,
+ * trew_hip_satellites_results, trew_satellites_host): they are purely additive -- no existing structure, enumerator or function
  * changed. */
 #define TREW_HIP_ABI_VERSION 4
 
@@ -432,8 +433,8 @@ int trew_variants_host(const uint32_t *words, const uint32_t *offsets, const uin
  *   period         the smallest divisor d of k* with u[j] = u[(j + d) mod k*] for all j (on a noisy tract the multiples of
  *                  the true period score within a percent of it; the majority unit's primitive root undoes that)
  *   unit           u[0 .. period - 1] packed like trew_hip_motif.word: first base most significant, no bits above 2 period
- * This is the one best tract of a read; trew_hip_repeats below reports every tract.  Out of scope: periods above 32 (a
- * 128-bit unit and 256 bins).  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+ * This is the one best tract of a read; trew_hip_repeats below reports every tract.  Periods above 32 are the business of
+ * trew_hip_satellites (further below), not of this record.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
     uint32_t period, scored_period, score, start, end, matches, support, reserved;
     uint64_t unit;
@@ -502,8 +503,8 @@ int trew_chain_host(const uint32_t *words, const uint32_t *offsets, const uint32
  * field, and a read without one has no tract; the tracts of a read are disjoint; none scores above the read's depth-0
  * tract; a read's records do not depend on the rest of the batch; a piece with hi - lo - min_period < min_score cannot
  * have a record (score_k <= length - k); a read has at most n / (min_score + 1) tracts.  The consensus keeps the fixed phase
- * of trew_hip_periods: under indels a long tract's unit can come out wrong, here as there.  Out of scope: periods above 32.
- * Also additive: TREW_HIP_ABI_VERSION stays 4. */
+ * of trew_hip_periods: under indels a long tract's unit can come out wrong, here as there.  Periods above 32:
+ * trew_hip_satellites below.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
     uint32_t read, depth, period, scored_period, score, start, end, matches, support, reserved;
     uint64_t unit;
@@ -526,6 +527,44 @@ int trew_hip_repeats_results(trew_hip_ctx *ctx, int slot, trew_hip_repeat *out, 
  * first ones of the sorted order), counts as above (may be NULL). */
 int trew_repeats_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                       int penalty, uint32_t min_score, trew_hip_repeat *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+
+/* ---- de novo repeats with periods up to 256: minisatellites and satellite monomers (no motif given) ----
+ * Integer-exact (tests/satellite_ref.py is the brute-force form).  trew_hip_repeats with
+ * 1 <= min_period <= max_period <= TREW_SATELLITE_MAX_PERIOD and a unit wide enough for the result; penalty and min_score as
+ * there.  The definition is unchanged: the record of a piece is that of trew_hip_periods with k over
+ * [min_period, min(max_period, length - 1)] (tie rules, matches, support, the majority with the smallest code on a tie, code
+ * 0 for a phase without a valid base, the primitive root), the recursion over pieces, depth, counts, the order (read, start)
+ * and the overflow protocol are those of trew_hip_repeats.
+ *   unit   base j of the unit (j < period) lies in bits [2 (j & 15), 2 (j & 15) + 2) of unit[j >> 4]; codes T 0, G 1, C 2,
+ *          A 3; every bit at or above base `period` is zero
+ * Consequences: with max_period <= 32 the records equal those of trew_hip_repeats on the same input record for record and
+ * field for field, the two units decoding to the same string, and so do counts and *n; the depth-0 record then equals the
+ * trew_hip_periods record.  Over the whole range, as for trew_hip_repeats: the tracts of a read are disjoint; none scores
+ * above the read's depth-0 tract; a read's records do not depend on the rest of the batch; pruning the pieces with
+ * hi - lo - min_period < min_score changes nothing; score and scored_period are invariant under reverse complement; period
+ * divides scored_period.
+ * Limits: periods are at most 256.  eq_k compares NEIGHBOURING copies, so an array whose monomers have diverged (human alpha
+ * satellite monomers differ from each other by a fifth or more) does not score at the default penalty; higher-order repeat
+ * units of kilobases are out of reach; the consensus keeps the fixed phase of trew_hip_periods, so under indels a long
+ * tract's unit can come out wrong.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+#define TREW_SATELLITE_MAX_PERIOD 256
+typedef struct {
+    uint32_t read, depth, period, scored_period, score, start, end, matches, support, reserved;
+    uint32_t unit[16];
+} trew_hip_satellite; /* 104 bytes */
+/* Like trew_hip_repeats in every respect (batch shapes, staging, the log of max_records records >= 1 with its counter, one
+ * count per read, at most 2^32 - 1 reads a batch), with buffers of its own and independent of the scan and of the other seven
+ * kernels.  Argument error: "1 <= min_period <= max_period <= 256".  One kernel, a wave per read, for every read length. */
+int trew_hip_satellites(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                        uint64_t max_records);
+/* The contract of trew_hip_repeats_results: *n is exact also beyond max_records or cap (n must not be NULL), counts (n_reads
+ * values; may be NULL) is always exact, min(cap, *n) records sorted by (read, start) when *n <= max_records, nothing copied
+ * otherwise and no error: repeat trew_hip_satellites with max_records >= *n -- one retry always suffices. */
+int trew_hip_satellites_results(trew_hip_ctx *ctx, int slot, trew_hip_satellite *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel);
+/* The same on the host, piece by piece from the definition, over packed planes: *n = tracts found, min(cap, *n) records (the
+ * first ones of the sorted order), counts as above (may be NULL). */
+int trew_satellites_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                         int penalty, uint32_t min_score, trew_hip_satellite *out, uint64_t cap, uint64_t *n, uint32_t *counts);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -30,6 +30,7 @@ from .capi import (  # noqa: F401
     pack_reads,
     periods,
     repeats,
+    satellites,
     tracts,
     variants,
 )

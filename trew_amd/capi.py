@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_periods", "trew_hip_periods_results", "trew_periods_host",
     "trew_hip_chain", "trew_hip_chain_results", "trew_chain_host",
     "trew_hip_repeats", "trew_hip_repeats_results", "trew_repeats_host",
+    "trew_hip_satellites", "trew_hip_satellites_results", "trew_satellites_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -153,6 +154,17 @@ class Repeat(C.Structure):
 REPEAT_DTYPE = np.dtype([(name, "<u8" if name == "unit" else "<u4") for name, _ in Repeat._fields_])
 assert REPEAT_DTYPE.itemsize == C.sizeof(Repeat) == 48
 
+SATELLITE_MAX_PERIOD = 256  # TREW_SATELLITE_MAX_PERIOD
+
+
+class Satellite(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("read", "depth", "period", "scored_period", "score", "start", "end", "matches", "support",
+                                                "reserved")] + [("unit", C.c_uint32 * 16)]
+
+
+SATELLITE_DTYPE = np.dtype([(name, "<u4", (16,)) if name == "unit" else (name, "<u4") for name, _ in Satellite._fields_])
+assert SATELLITE_DTYPE.itemsize == C.sizeof(Satellite) == 104
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -231,6 +243,9 @@ def load():
     lib.trew_hip_repeats.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64]
     lib.trew_hip_repeats_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), vp, C.POINTER(C.c_float)]
     lib.trew_repeats_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp]
+    lib.trew_hip_satellites.argtypes = lib.trew_hip_repeats.argtypes
+    lib.trew_hip_satellites_results.argtypes = lib.trew_hip_repeats_results.argtypes
+    lib.trew_satellites_host.argtypes = lib.trew_repeats_host.argtypes
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -443,6 +458,35 @@ def repeats_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sc
         out = np.zeros(int(n.value), dtype=REPEAT_DTYPE)
         call(out)
     return out[:min(len(out), int(n.value))], counts, int(n.value)
+
+
+def satellites_host(reads_or_packed, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, cap=None):
+    """trew_satellites_host: repeats_host with periods up to 256 and SATELLITE_DTYPE records (unit: sixteen words, see
+    satellite_unit_text).  Returns (records sorted by (read, start), counts of shape (n_reads,), found); with `cap` at most that
+    many records."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    counts = np.zeros(len(offsets), dtype=np.uint32)
+    n = C.c_uint64(0)
+
+    def call(out):
+        if lib.trew_satellites_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                                    int(penalty), int(min_score), out.ctypes.data if len(out) else None, len(out), C.byref(n),
+                                    counts.ctypes.data) != 0:
+            raise TrewHipError("trew_satellites_host failed: %s" % lib.trew_hip_last_error(None).decode())
+
+    out = np.zeros(0 if cap is None else int(cap), dtype=SATELLITE_DTYPE)
+    call(out)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=SATELLITE_DTYPE)
+        call(out)
+    return out[:min(len(out), int(n.value))], counts, int(n.value)
+
+
+def satellite_unit_text(unit, period):
+    """The unit of a SATELLITE_DTYPE record as text: base j (j < period) lies in bits [2 (j & 15), 2 (j & 15) + 2) of
+    unit[j >> 4], codes T 0, G 1, C 2, A 3."""
+    return "".join("TGCA"[(int(unit[j >> 4]) >> (2 * (j & 15))) & 3] for j in range(int(period)))
 
 
 def chain_unit_text(motif_text, bin_):
@@ -754,6 +798,32 @@ class TrewHip:
             self._chk(self.lib.trew_hip_repeats_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_repeats_results")
         return (out, counts, found, ms.value) if want_ms else (out, counts, found)
 
+    def satellites(self, batch, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, max_records=None, slot=0):
+        """Queue every de novo repeat tract with a period of up to 256 of every read of `batch` on the slot's stream (no
+        motifs).  max_records: the capacity of the log for this call (default: the batch's read count, at least 1)."""
+        if max_records is None:
+            max_records = max(int(batch.n_reads), 1)
+        self._queue("satellites", slot, batch, None, 1, shape=(int(max_records),))
+        self._chk(self.lib.trew_hip_satellites(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
+                                               int(max_records)), "trew_hip_satellites")
+
+    def satellites_results(self, slot=0, want_ms=False):
+        """Results of the slot's last satellites: (SATELLITE_DTYPE records sorted by (read, start), counts of shape (n_reads,),
+        found [, kernel ms]).  found > max_records: no records, counts and found are exact; repeat the call with max_records
+        >= found."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, _, cap = self._queued.get(("satellites", slot), (0, 1, 0))
+        counts = np.zeros(n_reads, dtype=np.uint32)
+        self._chk(self.lib.trew_hip_satellites_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
+                  "trew_hip_satellites_results")
+        found = int(n.value)
+        out = np.zeros(found if found <= cap else 0, dtype=SATELLITE_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_satellites_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None),
+                      "trew_hip_satellites_results")
+        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+
     def submit_reads(self, reads, slot=0):
         b = self.host_batch(*pack_reads(reads))
         self.submit(b, slot)
@@ -1017,4 +1087,22 @@ def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=
         if found > cap:
             t.repeats(b, min_period, max_period, penalty, min_score, found)
             out, counts, found = t.repeats_results()
+        return out, counts
+
+
+def satellites(reads, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, device=0, max_records=None):
+    """`repeats` with periods up to 256 on the GPU: minisatellites and satellite monomers.  Returns (SATELLITE_DTYPE records
+    sorted by (read, start), counts of shape (n_reads,)); satellite_unit_text turns a record's unit into text.  The first
+    call's log holds max_records records (default: one per read); when more are found the call is repeated once with the
+    exact number."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        b = t.host_batch(words, offsets, lengths)
+        cap = max(len(offsets), 1) if max_records is None else int(max_records)
+        t.satellites(b, min_period, max_period, penalty, min_score, cap)
+        out, counts, found = t.satellites_results()
+        if found > cap:
+            t.satellites(b, min_period, max_period, penalty, min_score, found)
+            out, counts, found = t.satellites_results()
         return out, counts

@@ -1186,11 +1186,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1208,6 +1208,7 @@ struct Annotator {
         std::vector<trew_hip_chain_item> crecs;  // trew chain
         std::vector<uint32_t> ccounts;
         std::vector<trew_hip_repeat> rrecs;  // trew repeats
+        std::vector<trew_hip_satellite> srecs;  // trew satellites
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1508,6 +1509,37 @@ static void fold_repeats(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew satellites: fold_repeats with the wide record; the key's unit is a string of codes.
+static void fold_satellites(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    uint64_t cap = x.n, found = 0;
+    for (int attempt = 0;; attempt++) {
+        if (trew_hip_satellites(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, cap)) hip_die(x.c, "trew_hip_satellites");
+        if (w->srecs.size() < cap) w->srecs.resize(cap);
+        if (trew_hip_satellites_results(x.c, w->slot, w->srecs.data(), cap, &found, nullptr, nullptr)) hip_die(x.c, "trew_hip_satellites_results");
+        if (found <= cap) break;
+        if (attempt) die("internal error: the satellite log overflowed twice");
+        cap = found;  // the exact number: one retry always suffices
+        p.interval_retries++;
+    }
+    // the records are sorted by (read, start): a read's tracts are consecutive
+    std::vector<std::pair<uint32_t, std::string>> seen;  // the keys of the read at hand
+    for (uint64_t i = 0; i < found; i++) {
+        const trew_hip_satellite &rec = w->srecs[i];
+        if (i == 0 || w->srecs[i - 1].read != rec.read) seen.clear();
+        const std::pair<uint32_t, std::string> key{rec.period, satellite_canonical(satellite_codes(rec))};
+        RepeatUnit &u = p.satellite_units[key];
+        if (std::find(seen.begin(), seen.end(), key) == seen.end()) {
+            seen.push_back(key);
+            u.reads++;
+        }
+        u.tracts++;
+        u.bases += rec.end - rec.start;
+        p.srows.push_back(SatelliteRow{x.first_read + rec.read, x.lengths[rec.read], rec});
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1552,6 +1584,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Periods: fold_periods(x, p); break;
             case Measure::Chain: fold_chain(x, p); break;
             case Measure::Repeats: fold_repeats(x, p); break;
+            case Measure::Satellites: fold_satellites(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1596,9 +1629,15 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         u.tracts += kv.second.tracts;
         u.bases += kv.second.bases;
     }
+    for (const auto &kv : from.satellite_units) {
+        RepeatUnit &u = into.satellite_units[kv.first];
+        u.reads += kv.second.reads;
+        u.tracts += kv.second.tracts;
+        u.bases += kv.second.bases;
+    }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites"};  // in the order of Measure
 
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1622,6 +1661,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         out.irows.insert(out.irows.end(), w.part.irows.begin(), w.part.irows.end());
         out.crows.insert(out.crows.end(), w.part.crows.begin(), w.part.crows.end());
         out.rrows.insert(out.rrows.end(), w.part.rrows.begin(), w.part.rrows.end());
+        out.srows.insert(out.srows.end(), w.part.srows.begin(), w.part.srows.end());
     }
     std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
         if (x.read != y.read) return x.read < y.read;
@@ -1637,6 +1677,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     });
     std::sort(out.rrows.begin(), out.rrows.end(),
               [](const RepeatRow &x, const RepeatRow &y) { return x.read != y.read ? x.read < y.read : x.rp.start < y.rp.start; });
+    std::sort(out.srows.begin(), out.srows.end(),
+              [](const SatelliteRow &x, const SatelliteRow &y) { return x.read != y.read ? x.read < y.read : x.st.start < y.st.start; });
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1648,6 +1690,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
                                   (unsigned long long) out.crows.size(), (unsigned long long) out.interval_retries);
         if (rq.kind == Measure::Repeats) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.rrows.size(), (unsigned long long) out.interval_retries);
+        if (rq.kind == Measure::Satellites) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
+                                  (unsigned long long) out.srows.size(), (unsigned long long) out.interval_retries);
     }
     return out;
 }

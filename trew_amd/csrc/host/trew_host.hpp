@@ -99,19 +99,19 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ... and trew periods|repeats FASTQ...: the per-read measures.
-// One file path for all seven (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp and repeats.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats };
+// ---- trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites FASTQ...: the per-read measures.
+// One file path for all eight (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp and satellites.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     // a (read, motif) is reported when its longer tract has at least this many bases (variants, chain: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
-    int penalty = 0;                                      // tracts, periods, repeats
-    int min_period = 1, max_period = 32;                  // periods, repeats (which take no motifs: n_motifs = 0)
-    uint32_t min_score = 24;                              // periods, repeats
+    int penalty = 0;                                      // tracts, periods, repeats, satellites
+    int min_period = 1, max_period = 32;                  // periods, repeats, satellites (which take no motifs: n_motifs = 0)
+    uint32_t min_score = 24;                              // periods, repeats, satellites
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
 };
 struct AnnotRow {
@@ -140,6 +140,11 @@ struct RepeatRow {
     uint32_t length;  // bases
     trew_hip_repeat rp;  // rp.read is the index inside its batch
 };
+struct SatelliteRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_satellite st;  // st.read is the index inside its batch
+};
 struct RepeatUnit {
     uint64_t reads = 0, tracts = 0, bases = 0;  // reads with such a tract, the tracts, the sum of their end - start
 };
@@ -150,11 +155,12 @@ struct AnnotFileResult {
     std::vector<IntervalRow> irows;  // intervals: sorted by read, motif, strand, start
     std::vector<ChainRow> crows;     // chain: the items of the reported (read, motif, strand), sorted by read, motif, strand, start
     std::vector<RepeatRow> rrows;    // repeats: sorted by read, start
+    std::vector<SatelliteRow> srows; // satellites: sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
-    uint64_t interval_retries = 0;  // intervals, chain, repeats: batches resubmitted because their log overflowed
+    uint64_t interval_retries = 0;  // intervals, chain, repeats, satellites: batches resubmitted because their log overflowed
     uint64_t runs_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, runs_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported_rev[TREW_ANNOT_MAX_MOTIFS] = {};  // chain
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     std::vector<uint64_t> var_hist, var_reads_with;  // variants: [motif][strand][bin]; empty for the other kinds
@@ -162,6 +168,8 @@ struct AnnotFileResult {
     std::map<std::pair<uint32_t, uint64_t>, std::pair<uint64_t, uint64_t>> period_units;
     // repeats: (period, strand-canonical unit) -> its reads, tracts and bases
     std::map<std::pair<uint32_t, uint64_t>, RepeatUnit> repeat_units;
+    // satellites: the same, the canonical unit as its codes (one char a base, T 0, G 1, C 2, A 3; see satellite_canonical)
+    std::map<std::pair<uint32_t, std::string>, RepeatUnit> satellite_units;
 };
 void add_totals(AnnotFileResult &into, const AnnotFileResult &from);  // everything but the rows: sums, and the larger of longest*
 struct Annotator;  // device contexts and one slot per worker
@@ -187,7 +195,7 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
-    bool motif_less = false;                      // periods, repeats: every positional argument is a file, `names` stays empty
+    bool motif_less = false;                      // periods, repeats, satellites: every positional argument is a file, `names` stays empty
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
@@ -198,7 +206,12 @@ int variants_main(int argc, char **argv);
 int periods_main(int argc, char **argv);
 int chain_main(int argc, char **argv);
 int repeats_main(int argc, char **argv);
+int satellites_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
+// the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
+// base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement
+std::string satellite_codes(const trew_hip_satellite &rec);
+std::string satellite_canonical(const std::string &codes);
 
 struct RunStats {
     uint64_t reads = 0, bases = 0;

@@ -31,6 +31,9 @@
 // and adds one to bin 4 phase + code with an LDS atomic (4 k* <= 128 bins per wave, the mechanism of kernels/variants.inc).
 // Lane j < k* then reads its phase's four bins and takes the majority; the bins are cleared for the wave's next user.  The
 // primitive root compares u with itself rotated by every divisor d of k* (one ds_bpermute a divisor).
+//
+// period_eq_word, period_score and period_locate take a template parameter kWide for kernels/satellites.inc (k up to 256); the
+// kernels of this file and of repeats.inc use the instantiation without it, which is the code as it was.
 
 constexpr u32 kPeriodBins = 128;
 
@@ -44,6 +47,12 @@ struct Piece {
 // eq_k word of 32-base word w (w >= lo >> 5): bit i = bases 32 w + i and 32 w + i + k are both valid and equal, and
 // lo <= 32 w + i < hi - k.  vm = the positions of the word that exist.  Reads word w and word w + 1 where they exist; what a
 // plane holds in front of lo or at and past hi never shows (lo <= i and i + k < hi for every bit kept).
+//
+// kWide (kernels/satellites.inc): k may exceed 32.  For k = 32 q + r the partner of word w is word w + q and word w + q + 1,
+// aligned by r (for r = 0 word w + q itself: v_alignbit by 0 returns its low operand); a partner word at or past rd.nw reads
+// as all N.  Every lane loads its own partners, so an iteration seam still carries only sums.  The instantiation without
+// kWide is the code as it was for k <= 32: q = 0, and k = 32 takes the next word.
+template <bool kWide = false>
 __device__ __forceinline__ u32 period_eq_word(const ReadRef &rd, Piece pc, u32 k, u32 w, u32 &vm) {
     const long long left = (long long) pc.hi - (long long) k - 32ll * (long long) w;  // positions i >= 32 w with i < hi - k
     const u32 nv = left >= 32 ? 32u : left > 0 ? (u32) left : 0u;
@@ -51,6 +60,26 @@ __device__ __forceinline__ u32 period_eq_word(const ReadRef &rd, Piece pc, u32 k
     vm = (nv >= 32u ? 0xffffffffu : (1u << nv) - 1u) & (0xffffffffu << first);
     if (vm == 0u) return 0u;  // also: w >= rd.nw
     const u32 c0 = rd.w[3ull * w + 0], c1 = rd.w[3ull * w + 1], c2 = rd.w[3ull * w + 2];
+    if constexpr (kWide) {
+        const u32 q = k >> 5, wa = w + q, wb = wa + 1u;  // w < rd.nw <= 2^27 and q <= 8: no wrap
+        u32 a0 = c0, a1 = c1, a2 = c2, b0 = 0, b1 = 0, b2 = 0xffffffffu;
+        if (q != 0u) {
+            a0 = a1 = 0;
+            a2 = 0xffffffffu;
+            if (wa < rd.nw) {
+                a0 = rd.w[3ull * wa + 0];
+                a1 = rd.w[3ull * wa + 1];
+                a2 = rd.w[3ull * wa + 2];
+            }
+        }
+        if (wb < rd.nw) {
+            b0 = rd.w[3ull * wb + 0];
+            b1 = rd.w[3ull * wb + 1];
+            b2 = rd.w[3ull * wb + 2];
+        }
+        const u32 t0 = alignbit(b0, a0, k), t1 = alignbit(b1, a1, k), t2 = alignbit(b2, a2, k);
+        return ~((c0 ^ t0) | (c1 ^ t1) | c2 | t2) & vm;
+    }
     u32 n0 = 0, n1 = 0, n2 = 0xffffffffu;
     if (w + 1u < rd.nw) {
         n0 = rd.w[3ull * (w + 1u) + 0];
@@ -100,12 +129,13 @@ __device__ __forceinline__ PeriodPlace period_place(int T, int m) {
 }
 
 // score_k of one piece: the largest V_k(e)
+template <bool kWide = false>
 __device__ __forceinline__ u32 period_score(const ReadRef &rd, Piece pc, u32 k, int P) {
     long long run = 0, gmin = 0, best = 0;  // S at the start of the iteration; the smallest S so far; the largest V so far
     const u32 wend = (u32) (((u64) pc.hi + 31ull) >> 5);  // one past the piece's last word
     for (u32 t0 = pc.lo >> 5; t0 < wend; t0 += 64u) {
         u32 vm;
-        const u32 eq = period_eq_word(rd, pc, k, t0 + lane_id(), vm);
+        const u32 eq = period_eq_word<kWide>(rd, pc, k, t0 + lane_id(), vm);
         int T, m, M, W;
         period_walk(eq, vm, P, T, m, M, W);
         const PeriodPlace pl = period_place(T, m);
@@ -121,6 +151,7 @@ __device__ __forceinline__ u32 period_score(const ReadRef &rd, Piece pc, u32 k, 
 
 // the segment of score_k (score > 0): e = the smallest e with V_k(e) = score, b = the largest b in [lo, e] with S_k(b)
 // smallest over [lo, e]; both in read coordinates
+template <bool kWide = false>
 __device__ __forceinline__ void period_locate(const ReadRef &rd, Piece pc, u32 k, int P, u32 score, u32 &b_out, u32 &e_out) {
     const u32 lane = lane_id();
     long long run = 0, gmin = 0, s_end = 0;
@@ -128,7 +159,7 @@ __device__ __forceinline__ void period_locate(const ReadRef &rd, Piece pc, u32 k
     const u32 wlo = pc.lo >> 5, wend = (u32) (((u64) pc.hi + 31ull) >> 5);
     for (u32 t0 = wlo; t0 < wend; t0 += 64u) {
         u32 vm;
-        const u32 eq = period_eq_word(rd, pc, k, t0 + lane, vm);
+        const u32 eq = period_eq_word<kWide>(rd, pc, k, t0 + lane, vm);
         int T, m, M, W;
         period_walk(eq, vm, P, T, m, M, W);
         const PeriodPlace pl = period_place(T, m);
@@ -164,7 +195,7 @@ __device__ __forceinline__ void period_locate(const ReadRef &rd, Piece pc, u32 k
     for (u32 t0 = wlo; t0 <= (e_star >> 5) && t0 < wend; t0 += 64u) {
         const u32 w = t0 + lane;
         u32 vm;
-        const u32 eq = period_eq_word(rd, pc, k, w, vm);
+        const u32 eq = period_eq_word<kWide>(rd, pc, k, w, vm);
         int T, m, M, W;
         period_walk(eq, vm, P, T, m, M, W);
         const u32 incl = wave_scan_u32((u32) T);

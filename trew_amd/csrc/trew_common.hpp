@@ -162,7 +162,8 @@ struct ChainLog {
     u64 cap;
 };
 
-// trew_hip_repeats' append log (kernels/repeats.inc): records of twelve u32 (trew_hip_repeat)
+// trew_hip_repeats' append log (kernels/repeats.inc): records of twelve u32 (trew_hip_repeat); trew_hip_satellites' as well
+// (kernels/satellites.inc): records of 26 u32 (trew_hip_satellite)
 struct RepeatLog {
     unsigned long long *counter;  // tracts found; keeps counting past cap
     u32 *recs;                    // cap records

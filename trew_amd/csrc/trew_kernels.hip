@@ -43,6 +43,7 @@
 //   periods.inc        periods_wave_kernel (de novo repeat period and consensus unit per read; no motif, the shifted self-comparison)
 //   chain.inc          chain_wave_kernel (ordered unit chain per read: run and variant events into an append log; shares variants.inc's words)
 //   repeats.inc        repeats_wave_kernel (de novo repeats: every tract of a read, the recursion over pieces inside the wave; shares periods.inc's functions)
+//   satellites.inc     satellites_wave_kernel (de novo repeats with periods up to 256: the wide eq word, 1024 consensus bins and a 16-word unit; shares periods.inc's and repeats.inc's functions)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/periods.inc"
 #include "kernels/chain.inc"
 #include "kernels/repeats.inc"
+#include "kernels/satellites.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -379,6 +381,15 @@ hipError_t launch_repeats(hipStream_t st, u32 n_cu, const DevBatch &B, int min_p
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(repeats_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
+    return hipGetLastError();
+}
+
+// De novo repeats with periods up to 256: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_satellites(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score,
+                             const RepeatLog &lg, u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(satellites_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
     return hipGetLastError();
 }
 

@@ -424,17 +424,30 @@ const char *chain_host(const u32 *words, const u32 *offsets, const u32 *lengths,
 }
 
 // ---------------------------------------------------------------- de novo repeat period and unit per read
-const char *periods_error(int min_period, int max_period, int penalty, u32 min_score) {
-    if (min_period < 1 || max_period > 32 || min_period > max_period) return "periods: 1 <= min_period <= max_period <= 32 is required";
+static const char *penalty_score_error(int penalty, u32 min_score) {
     if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
     if (min_score < 1) return "min_score must be at least 1";
     return nullptr;
 }
 
+const char *periods_error(int min_period, int max_period, int penalty, u32 min_score) {
+    if (min_period < 1 || max_period > 32 || min_period > max_period) return "periods: 1 <= min_period <= max_period <= 32 is required";
+    return penalty_score_error(penalty, min_score);
+}
+
+static_assert(TREW_SATELLITE_MAX_PERIOD == 256, "the text below");
+const char *satellites_error(int min_period, int max_period, int penalty, u32 min_score) {
+    if (min_period < 1 || max_period > TREW_SATELLITE_MAX_PERIOD || min_period > max_period)
+        return "satellites: 1 <= min_period <= max_period <= 256 is required";
+    return penalty_score_error(penalty, min_score);
+}
+
 // The record of the piece [lo, hi) of a read, its bases taken as a read of their own: nothing outside the piece is seen, start
 // and end are in read coordinates.  base: per base of the read its code, or 4 with its nmask bit set.  All zero without a record.
-static void period_piece(const unsigned char *base, u32 lo, u32 hi, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period &o) {
-    memset(&o, 0, sizeof(o));
+// What period_piece and satellite_piece share: everything but the packing of the unit.  u: the codes of the primitive unit,
+// u[0 .. period - 1] (kMaxK entries, kMaxK >= max_period).  False without a record; o's fields but `unit` are set otherwise.
+template <u32 kMaxK, class Rec>
+static bool piece_record(const unsigned char *base, u32 lo, u32 hi, int min_period, int max_period, int penalty, u32 min_score, Rec &o, u32 *u) {
     const u32 n = hi - lo;
     base += lo;
     // the best-scoring segment of eq_k for every k; a later k must score strictly more
@@ -463,15 +476,14 @@ static void period_piece(const unsigned char *base, u32 lo, u32 hi, int min_peri
             es = e;
         }
     }
-    if (ks == 0 || best < (long long) min_score) return;
+    if (ks == 0 || best < (long long) min_score) return false;
     o.scored_period = ks;
     o.score = (u32) best;
     o.matches = (u32) (((u64) best + (u64) penalty * (u64) (es - bs)) / (u64) (1 + penalty));
     const u32 start = bs, end = es + ks;  // in the piece
-    u32 cnt[32][4] = {};
+    u32 cnt[kMaxK][4] = {};
     for (u32 p = start; p < end; p++)
         if (base[p] < 4) cnt[(p - start) % ks][base[p]]++;
-    u32 u[32];
     for (u32 j = 0; j < ks; j++) {
         u[j] = 0;
         for (u32 c = 1; c < 4; c++)
@@ -487,9 +499,24 @@ static void period_piece(const unsigned char *base, u32 lo, u32 hi, int min_peri
             break;
         }
     }
-    for (u32 j = 0; j < o.period; j++) o.unit = (o.unit << 2) | u[j];
     o.start = lo + start;
     o.end = lo + end;
+    return true;
+}
+
+static void period_piece(const unsigned char *base, u32 lo, u32 hi, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period &o) {
+    memset(&o, 0, sizeof(o));
+    u32 u[32];
+    if (!piece_record<32>(base, lo, hi, min_period, max_period, penalty, min_score, o, u)) return;
+    for (u32 j = 0; j < o.period; j++) o.unit = (o.unit << 2) | u[j];
+}
+
+// the same with periods up to 256 and the unit of trew_hip_satellite; read and depth are the caller's
+static void satellite_piece(const unsigned char *base, u32 lo, u32 hi, int min_period, int max_period, int penalty, u32 min_score, trew_hip_satellite &o) {
+    memset(&o, 0, sizeof(o));
+    u32 u[TREW_SATELLITE_MAX_PERIOD];
+    if (!piece_record<TREW_SATELLITE_MAX_PERIOD>(base, lo, hi, min_period, max_period, penalty, min_score, o, u)) return;
+    for (u32 j = 0; j < o.period; j++) o.unit[j >> 4] |= u[j] << (2 * (j & 15u));
 }
 
 static void unpack_bases(const u32 *w, u32 n, std::vector<unsigned char> &base) {
@@ -544,6 +571,52 @@ const char *repeats_host(const u32 *words, const u32 *offsets, const u32 *length
         }
         sort_repeats(mine.data(), mine.size());  // disjoint, so by start
         for (const trew_hip_repeat &x : mine) {
+            if (found < cap) out[found] = x;
+            found++;
+        }
+        if (counts) counts[r] = (u32) mine.size();
+    }
+    *n = found;
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- de novo repeats with periods up to 256
+void sort_satellites(trew_hip_satellite *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_satellite &a, const trew_hip_satellite &b) { return a.read != b.read ? a.read < b.read : a.start < b.start; });
+}
+
+const char *satellites_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                            u32 min_score, trew_hip_satellite *out, u64 cap, u64 *n, u32 *counts) {
+    if (const char *e = satellites_error(min_period, max_period, penalty, min_score)) return e;
+    if (!n) return "trew_satellites_host: n must not be null";
+    if (cap && !out) return "trew_satellites_host: out must not be null";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_satellites_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_satellites_host: a batch holds at most 2^32 - 1 reads";
+    struct Todo {
+        u32 lo, hi, depth;
+    };
+    std::vector<unsigned char> base;
+    std::vector<Todo> todo;
+    std::vector<trew_hip_satellite> mine;  // the tracts of one read
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        mine.clear();
+        todo.assign(1, Todo{0, lengths[r], 0});
+        while (!todo.empty()) {  // the definition piece by piece, as in repeats_host: no piece is pruned
+            const Todo t = todo.back();
+            todo.pop_back();
+            trew_hip_satellite p;
+            satellite_piece(base.data(), t.lo, t.hi, min_period, max_period, penalty, min_score, p);
+            if (p.scored_period == 0) continue;
+            p.read = (u32) r;
+            p.depth = t.depth;
+            mine.push_back(p);
+            todo.push_back(Todo{p.end, t.hi, t.depth + 1});
+            todo.push_back(Todo{t.lo, p.start, t.depth + 1});
+        }
+        sort_satellites(mine.data(), mine.size());  // disjoint, so by start
+        for (const trew_hip_satellite &x : mine) {
             if (found < cap) out[found] = x;
             found++;
         }

@@ -1,5 +1,5 @@
 // trew_measures_host.hpp -- the per-read measures computed on the CPU, straight from their definitions
-// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat), and the argument checks the
+// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite), and the argument checks the
 // device entry points share with them.  Plain C++17: no HIP, no context.  trew_capi.cpp wraps these into the extern "C"
 // trew_*_host functions and keeps the error strings; tests/harness/measures_host_harness.cpp runs them under sanitizers.
 //
@@ -39,6 +39,11 @@ const char *periods_host(const uint32_t *words, const uint32_t *offsets, const u
 const char *repeats_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                          int penalty, uint32_t min_score, trew_hip_repeat *out, uint64_t cap, uint64_t *n, uint32_t *counts);
 void sort_repeats(trew_hip_repeat *v, uint64_t n);  // by (read, start)
+// de novo repeats with periods up to 256: repeats_host with the wider range, check and record
+const char *satellites_error(int min_period, int max_period, int penalty, uint32_t min_score);
+const char *satellites_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                            int penalty, uint32_t min_score, trew_hip_satellite *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+void sort_satellites(trew_hip_satellite *v, uint64_t n);  // by (read, start)
 // ordered unit chain per read: items sorted by (read, motif, strand, start), counts [read][motif][strand]{runs, variants}
 void sort_chain_items(trew_hip_chain_item *v, uint64_t n);  // by (read, motif, strand, start)
 const char *chain_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
