@@ -32,8 +32,9 @@ extern "C" {
  * trew_annotate_host), the tract entry points (trew_hip_tracts, trew_hip_tracts_results, trew_tracts_host), the interval
  * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host), the variant entry points
  * (trew_hip_variants, trew_hip_variants_results, trew_variants_host), the period entry points (trew_hip_periods,
- * trew_hip_periods_results, trew_periods_host) and the satellite entry points (trew_hip_satellites,
- * trew_hip_satellites_results, trew_satellites_host): they are purely additive -- no existing structure, enumerator or function
+ * trew_hip_periods_results, trew_periods_host), the satellite entry points (trew_hip_satellites,
+ * trew_hip_satellites_results, trew_satellites_host) and the alignment entry points (trew_hip_align, trew_hip_align_results,
+ * trew_align_host): they are purely additive -- no existing structure, enumerator or function
  * changed. */
 #define TREW_HIP_ABI_VERSION 4
 
@@ -565,6 +566,42 @@ int trew_hip_satellites_results(trew_hip_ctx *ctx, int slot, trew_hip_satellite 
  * first ones of the sorted order), counts as above (may be NULL). */
 int trew_satellites_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                          int penalty, uint32_t min_score, trew_hip_satellite *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+
+/* ---- indel-aware motif tract per read: a local alignment of the read against the motif repeated without end ----
+ * (how many copies of the unit does this read hold, where do they begin and end when bases are missing or extra, and how
+ * many of the errors are substitutions, insertions and deletions?)  Wraparound dynamic programming.  For strand s (fwd: the
+ * motif M, rev: its reverse complement) the text is T[j] = M_s[j mod k]; an N in the read matches nothing; 1 <= penalty <= 64.
+ * A cell holds a tuple (score, start, consumed, matches); tuples compare lexicographically, score as a signed integer, and
+ * the larger tuple wins.  H[0][j] = (0, 0, 0, 0) for 0 <= j < k; for i = 1 .. n, V[i][j] is the largest of
+ *   the fresh start             (0, i, 0, 0)
+ *   the diagonal                with (s, b, C, m) = H[i-1][(j-1) mod k]: (s + 1, b, C + 1, m + 1) when x[i-1] = M_s[j],
+ *                               else (s - penalty, b, C + 1, m)
+ *   the inserted read base      with (s, b, C, m) = H[i-1][j]: (s - penalty, b, C, m)
+ * and H[i][j] is the largest, over d = 0 .. k-1 deleted motif bases, of (s - penalty d, b, C + d, m) with
+ * (s, b, C, m) = V[i][(j-d) mod k].  The record of a strand is the cell with the largest (score, -i, start, consumed,
+ * matches): on a tie in score the earliest end wins, then the later start -- the shorter tract at both ends, as for
+ * trew_hip_tract.  A largest score of 0 gives zeros.
+ *   score_s     matches - penalty * (mismatches + insertions + deletions)
+ *   start_s, end_s   the tract is the bases [start, end) of the read
+ *   consumed_s  motif bases the alignment went through (matches + mismatches + deletions); copies = consumed / k
+ *   matches_s   matching bases
+ * Exact consequences, with L = end - start and E = (matches - score) / penalty: deletions = E - (L - matches), insertions =
+ * E - (consumed - matches), mismatches = L - matches - insertions.  Every rotation of a motif gives the same record.  One
+ * tract per strand, the best one; linear gap cost.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t score_fwd, start_fwd, end_fwd, consumed_fwd, matches_fwd;
+    uint32_t score_rev, start_rev, end_rev, consumed_rev, matches_rev;
+} trew_hip_alignment;
+/* Like trew_hip_tracts in every respect (batch shapes, staging, asynchronous on the slot's stream, a context of any mode, the
+ * motif and penalty checks and their error texts), with a result buffer of its own that the slot's first call allocates and
+ * independent of the scan and of the other eight kernels.  Records are laid out out[r * n_motifs + m].  One kernel, a wave
+ * per read, for every read length. */
+int trew_hip_align(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty);
+/* Waits for the slot and copies the records of its last trew_hip_align; arguments as trew_hip_annotate_results. */
+int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same records on the host, base by base from the definition, over packed planes. */
+int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                    const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_alignment *out);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -23,6 +23,7 @@ from .capi import (  # noqa: F401
     TABLE_NAMES,
     TrewHip,
     TrewHipError,
+    align,
     annotate,
     chain,
     intervals,

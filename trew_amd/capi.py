@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_chain", "trew_hip_chain_results", "trew_chain_host",
     "trew_hip_repeats", "trew_hip_repeats_results", "trew_repeats_host",
     "trew_hip_satellites", "trew_hip_satellites_results", "trew_satellites_host",
+    "trew_hip_align", "trew_hip_align_results", "trew_align_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -165,6 +166,14 @@ class Satellite(C.Structure):
 SATELLITE_DTYPE = np.dtype([(name, "<u4", (16,)) if name == "unit" else (name, "<u4") for name, _ in Satellite._fields_])
 assert SATELLITE_DTYPE.itemsize == C.sizeof(Satellite) == 104
 
+
+class Alignment(C.Structure):
+    _fields_ = [(name + sfx, C.c_uint32) for sfx in ("_fwd", "_rev") for name in ("score", "start", "end", "consumed", "matches")]
+
+
+ALIGN_DTYPE = np.dtype([(name, "<u4") for name, _ in Alignment._fields_])
+assert ALIGN_DTYPE.itemsize == C.sizeof(Alignment) == 40
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -246,6 +255,9 @@ def load():
     lib.trew_hip_satellites.argtypes = lib.trew_hip_repeats.argtypes
     lib.trew_hip_satellites_results.argtypes = lib.trew_hip_repeats_results.argtypes
     lib.trew_satellites_host.argtypes = lib.trew_repeats_host.argtypes
+    lib.trew_hip_align.argtypes = lib.trew_hip_tracts.argtypes
+    lib.trew_hip_align_results.argtypes = lib.trew_hip_tracts_results.argtypes
+    lib.trew_align_host.argtypes = lib.trew_tracts_host.argtypes
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -341,6 +353,32 @@ def tracts_host(reads_or_packed, motifs, penalty=3):
     if lib.trew_tracts_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
         raise TrewHipError("trew_tracts_host failed: %s" % lib.trew_hip_last_error(None).decode())
     return out[:, :nm]
+
+
+def align_host(reads_or_packed, motifs, penalty=3):
+    """trew_align_host: the indel-aware motif tract of every read (wraparound alignment) computed on the host, cell by cell
+    from the definition.  reads_or_packed as for annotate_host.  Returns ALIGN_DTYPE records of shape (n_reads, n_motifs)."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    arr, nm = _motif_array(motifs)
+    out = np.zeros((len(offsets), max(nm, 1)), dtype=ALIGN_DTYPE)
+    if lib.trew_align_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
+        raise TrewHipError("trew_align_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out[:, :nm]
+
+
+def align_columns(record, k, penalty):
+    """What follows exactly from an ALIGN_DTYPE record (or an array of them), the motif's length k and the penalty: a dict of
+    copies, mismatches, insertions and deletions with the keys name_fwd and name_rev."""
+    out = {}
+    for sfx in ("_fwd", "_rev"):
+        score, start, end, consumed, matches = (np.asarray(record[f + sfx]).astype(np.int64) for f in ("score", "start", "end", "consumed", "matches"))
+        errors = (matches - score) // int(penalty)
+        out["copies" + sfx] = consumed // int(k)
+        out["insertions" + sfx] = errors - (consumed - matches)
+        out["deletions" + sfx] = errors - (end - start - matches)
+        out["mismatches" + sfx] = end - start - matches - out["insertions" + sfx]
+    return out
 
 
 def periods_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24):
@@ -693,6 +731,18 @@ class TrewHip:
         res = self._fetch_records("tracts", slot, TRACT_DTYPE, want_ms)
         return res if want_ms else res[0]
 
+    def align(self, batch, motifs, penalty=3, slot=0):
+        """Queue the indel-aware motif tract (wraparound alignment) of every read of `batch` for `motifs` (texts or Motif, at
+        most 8) on the slot's stream."""
+        arr, nm = _motif_array(motifs)
+        self._queue("align", slot, batch, arr, nm)
+        self._chk(self.lib.trew_hip_align(self.ctx, C.byref(batch), slot, arr, nm, int(penalty)), "trew_hip_align")
+
+    def align_results(self, slot=0, want_ms=False):
+        """Records of the slot's last align: ALIGN_DTYPE array of shape (n_reads, n_motifs) [, kernel ms]."""
+        res = self._fetch_records("align", slot, ALIGN_DTYPE, want_ms)
+        return res if want_ms else res[0]
+
     def periods(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, slot=0):
         """Queue the de novo repeat period and unit of every read of `batch` on the slot's stream (no motifs)."""
         self._queue("periods", slot, batch, None, 1)
@@ -1010,6 +1060,17 @@ def tracts(reads, motifs, penalty=3, device=0):
                  max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
         t.tracts(t.host_batch(words, offsets, lengths), motifs, penalty)
         return t.tracts_results()
+
+
+def align(reads, motifs, penalty=3, device=0):
+    """Indel-aware motif tracts on the GPU: for every read (bytes / str) and motif (text) the best local alignment against the
+    motif repeated without end on each strand -- score, start, end, motif bases consumed and matches -- as ALIGN_DTYPE records
+    of shape (n_reads, n_motifs); align_columns gives the copies, mismatches, insertions and deletions."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        t.align(t.host_batch(words, offsets, lengths), motifs, penalty)
+        return t.align_results()
 
 
 def periods(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0):

@@ -1186,11 +1186,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1209,6 +1209,7 @@ struct Annotator {
         std::vector<uint32_t> ccounts;
         std::vector<trew_hip_repeat> rrecs;  // trew repeats
         std::vector<trew_hip_satellite> srecs;  // trew satellites
+        std::vector<trew_hip_alignment> arecs;  // trew align
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1540,6 +1541,34 @@ static void fold_satellites(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew align: a row per (read, motif, strand) whose score reaches MIN_SCORE; align_sums: the sums over those rows.
+static void fold_align(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    if (trew_hip_align(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty)) hip_die(x.c, "trew_hip_align");
+    if (w->arecs.size() < x.n * (size_t) nm) w->arecs.resize(x.n * (size_t) nm);
+    uint64_t got = 0;
+    if (trew_hip_align_results(x.c, w->slot, w->arecs.data(), x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_align_results");
+    for (uint64_t r = 0; r < x.n; r++)
+        for (int m = 0; m < nm; m++) {
+            const trew_hip_alignment &rec = w->arecs[r * (size_t) nm + (size_t) m];
+            for (int s = 0; s < 2; s++) {
+                const uint32_t *f = s ? &rec.score_rev : &rec.score_fwd;  // five consecutive u32
+                if (f[0] < x.rq->min_score) continue;
+                AlignRow row;
+                row.read = x.first_read + r;
+                row.length = x.lengths[r];
+                row.motif = m;
+                row.strand = s;
+                for (int i = 0; i < 5; i++) row.rec[i] = f[i];
+                p.arows.push_back(row);
+                const AlignColumns c = align_columns(row.rec, (uint32_t) x.rq->motifs[m].k, x.rq->penalty);
+                const uint64_t add[kAlignSums] = {1, (uint64_t) f[2] - f[1], f[0], c.copies, f[3], f[4], c.mismatches, c.insertions, c.deletions};
+                for (int i = 0; i < kAlignSums; i++) p.align_sums[m][s][i] += add[i];
+            }
+        }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1585,6 +1614,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Chain: fold_chain(x, p); break;
             case Measure::Repeats: fold_repeats(x, p); break;
             case Measure::Satellites: fold_satellites(x, p); break;
+            case Measure::Align: fold_align(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1608,6 +1638,8 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         into.runs_fwd[m] += from.runs_fwd[m];
         into.runs_rev[m] += from.runs_rev[m];
         into.reported_rev[m] += from.reported_rev[m];
+        for (int s = 0; s < 2; s++)
+            for (int i = 0; i < kAlignSums; i++) into.align_sums[m][s][i] += from.align_sums[m][s][i];
     }
     if (into.var_hist.size() < from.var_hist.size()) {
         into.var_hist.resize(from.var_hist.size());
@@ -1637,7 +1669,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"};  // in the order of Measure
 
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1662,6 +1694,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         out.crows.insert(out.crows.end(), w.part.crows.begin(), w.part.crows.end());
         out.rrows.insert(out.rrows.end(), w.part.rrows.begin(), w.part.rrows.end());
         out.srows.insert(out.srows.end(), w.part.srows.begin(), w.part.srows.end());
+        out.arows.insert(out.arows.end(), w.part.arows.begin(), w.part.arows.end());
     }
     std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
         if (x.read != y.read) return x.read < y.read;
@@ -1679,6 +1712,10 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
               [](const RepeatRow &x, const RepeatRow &y) { return x.read != y.read ? x.read < y.read : x.rp.start < y.rp.start; });
     std::sort(out.srows.begin(), out.srows.end(),
               [](const SatelliteRow &x, const SatelliteRow &y) { return x.read != y.read ? x.read < y.read : x.st.start < y.st.start; });
+    std::sort(out.arows.begin(), out.arows.end(), [](const AlignRow &x, const AlignRow &y) {
+        if (x.read != y.read) return x.read < y.read;
+        return x.motif != y.motif ? x.motif < y.motif : x.strand < y.strand;
+    });
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

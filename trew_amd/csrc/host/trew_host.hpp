@@ -99,19 +99,19 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites FASTQ...: the per-read measures.
-// One file path for all eight (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp and satellites.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites };
+// ---- trew annotate|tracts|intervals|variants|chain|align MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites FASTQ...: the per-read measures.
+// One file path for all nine (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp and align.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     // a (read, motif) is reported when its longer tract has at least this many bases (variants, chain: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
-    int penalty = 0;                                      // tracts, periods, repeats, satellites
+    int penalty = 0;                                      // tracts, periods, repeats, satellites, align
     int min_period = 1, max_period = 32;                  // periods, repeats, satellites (which take no motifs: n_motifs = 0)
-    uint32_t min_score = 24;                              // periods, repeats, satellites
+    uint32_t min_score = 24;                              // periods, repeats, satellites, align
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
 };
 struct AnnotRow {
@@ -145,6 +145,20 @@ struct SatelliteRow {
     uint32_t length;  // bases
     trew_hip_satellite st;  // st.read is the index inside its batch
 };
+struct AlignRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    int motif;        // index in command-line order
+    int strand;       // 0 = the motif, 1 = its reverse complement
+    uint32_t rec[5];  // score, start, end, consumed, matches: one strand's half of a trew_hip_alignment
+};
+struct AlignColumns {
+    uint32_t copies, mismatches, insertions, deletions;
+};
+// what follows exactly from one strand's five fields, the motif's length and the penalty (include/trew_hip.h)
+AlignColumns align_columns(const uint32_t rec[5], uint32_t k, int penalty);
+// the sums of `trew align`'s summary: rows, end - start, score, copies, consumed, matches, mismatches, insertions, deletions
+constexpr int kAlignSums = 9;
 struct RepeatUnit {
     uint64_t reads = 0, tracts = 0, bases = 0;  // reads with such a tract, the tracts, the sum of their end - start
 };
@@ -156,6 +170,8 @@ struct AnnotFileResult {
     std::vector<ChainRow> crows;     // chain: the items of the reported (read, motif, strand), sorted by read, motif, strand, start
     std::vector<RepeatRow> rrows;    // repeats: sorted by read, start
     std::vector<SatelliteRow> srows; // satellites: sorted by read, start
+    std::vector<AlignRow> arows;     // align: sorted by read, motif, strand
+    uint64_t align_sums[TREW_ANNOT_MAX_MOTIFS][2][kAlignSums] = {};  // align: [motif][strand], over the rows
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
@@ -207,6 +223,7 @@ int periods_main(int argc, char **argv);
 int chain_main(int argc, char **argv);
 int repeats_main(int argc, char **argv);
 int satellites_main(int argc, char **argv);
+int align_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement

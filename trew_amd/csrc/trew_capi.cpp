@@ -25,9 +25,9 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -40,7 +40,7 @@ struct MeasureState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call
-    u64 n = 0;         // annotate, tracts, variants: its records, n_reads * n_motifs; periods: n_reads
+    u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods: n_reads
     u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites: their max_records
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites: n_reads
     int n_motifs = 0;  // variants
@@ -1201,8 +1201,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites
-// The eight measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align
+// The nine measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
@@ -1257,6 +1257,11 @@ extern "C" int trew_satellites_host(const uint32_t *words, const uint32_t *offse
                                     int max_period, int penalty, uint32_t min_score, trew_hip_satellite *out, uint64_t cap, uint64_t *n,
                                     uint32_t *counts) {
     return host_status(satellites_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out, cap, n, counts));
+}
+
+extern "C" int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                               const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_alignment *out) {
+    return host_status(align_host(words, offsets, lengths, n_reads, motifs, n_motifs, penalty, out));
 }
 
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
@@ -1436,6 +1441,34 @@ extern "C" int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tra
     if (int rc = fetch_begin(ctx, slot, kTracts, nullptr, &sp)) return rc;
     const MeasureState &st = sp->measure[kTracts];
     if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_tract), n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- indel-aware motif tract per read (wraparound alignment)
+extern "C" int trew_hip_align(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * { return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr; };
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kAlign, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kAlign];
+    const u64 need = db.n_reads * (u64) n_motifs;
+    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_alignment))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    if (need == 0) return 0;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_align(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_alignment *) st.records.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kAlign, nullptr, &sp)) return rc;
+    const MeasureState &st = sp->measure[kAlign];
+    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_alignment), n)) return rc;
     return fetch_end(ctx, st, ms_kernel);
 }
 

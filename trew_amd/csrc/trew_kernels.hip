@@ -44,6 +44,7 @@
 //   chain.inc          chain_wave_kernel (ordered unit chain per read: run and variant events into an append log; shares variants.inc's words)
 //   repeats.inc        repeats_wave_kernel (de novo repeats: every tract of a read, the recursion over pieces inside the wave; shares periods.inc's functions)
 //   satellites.inc     satellites_wave_kernel (de novo repeats with periods up to 256: the wide eq word, 1024 consensus bins and a 16-word unit; shares periods.inc's and repeats.inc's functions)
+//   align.inc          align_wave_kernel (indel-aware motif tract per read: wraparound alignment, the row of the table in registers, a phase per lane)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -82,6 +83,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/chain.inc"
 #include "kernels/repeats.inc"
 #include "kernels/satellites.inc"
+#include "kernels/align.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -390,6 +392,14 @@ hipError_t launch_satellites(hipStream_t st, u32 n_cu, const DevBatch &B, int mi
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(satellites_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
+    return hipGetLastError();
+}
+
+// Indel-aware motif tract: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_alignment *d_out) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(align_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, (u32 *) d_out);
     return hipGetLastError();
 }
 

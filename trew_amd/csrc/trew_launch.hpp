@@ -53,6 +53,8 @@ hipError_t launch_repeats(hipStream_t st, u32 n_cu, const DevBatch &B, int min_p
 // records of 26 u32, its counter is zero when the kernel starts (the caller's memset on the same stream)
 hipError_t launch_satellites(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score,
                              const RepeatLog &lg, u32 *d_counts);
+// trew_hip_align: the wave-per-read kernel of kernels/align.inc on the grid of launch_tracts
+hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_alignment *d_out);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);

@@ -626,4 +626,78 @@ const char *satellites_host(const u32 *words, const u32 *offsets, const u32 *len
     return nullptr;
 }
 
+// ---------------------------------------------------------------- indel-aware motif tract per read (wraparound alignment)
+// A cell of the alignment (trew_hip_alignment, include/trew_hip.h): compared field by field in this order, the larger wins.
+struct AlignCell {
+    long long score;
+    u32 start, consumed, matches;
+    bool operator<(const AlignCell &o) const {
+        if (score != o.score) return score < o.score;
+        if (start != o.start) return start < o.start;
+        if (consumed != o.consumed) return consumed < o.consumed;
+        return matches < o.matches;
+    }
+};
+
+// one strand of one motif over one read: o = {score, start, end, consumed, matches}
+static void align_strand_host(const u32 *w, u32 n, const trew_hip_motif &motif, int s, int penalty, u32 (&o)[5]) {
+    const int k = motif.k;
+    const u64 target = s ? motif_revcomp(motif.word, k) : motif.word;
+    u32 t[32];
+    for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;  // first base most significant
+    AlignCell H[32], V[32];
+    for (int j = 0; j < k; j++) H[j] = AlignCell{0, 0, 0, 0};
+    AlignCell best{0, 0, 0, 0};
+    u32 best_end = 0;
+    for (u32 i = 1; i <= n; i++) {
+        const u32 c = base_at(w, i - 1);  // 4: an N, which matches nothing
+        for (int j = 0; j < k; j++) {
+            const AlignCell &d = H[(j + k - 1) % k];
+            const AlignCell diag = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
+                                             : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
+            const AlignCell ins{H[j].score - penalty, H[j].start, H[j].consumed, H[j].matches};
+            V[j] = std::max(AlignCell{0, i, 0, 0}, std::max(diag, ins));
+        }
+        for (int j = 0; j < k; j++) {
+            H[j] = V[j];
+            for (int d = 1; d < k; d++) {
+                const AlignCell &v = V[(j + k - d) % k];
+                H[j] = std::max(H[j], AlignCell{v.score - (long long) penalty * d, v.start, v.consumed + (u32) d, v.matches});
+            }
+        }
+        // the largest (score, -end, start, consumed, matches): rows come in the order of their end
+        for (int j = 0; j < k; j++)
+            if (H[j].score > best.score || (H[j].score == best.score && best_end == i && best < H[j])) {
+                best = H[j];
+                best_end = i;
+            }
+    }
+    if (best.score <= 0) {
+        for (u32 &x : o) x = 0;
+        return;
+    }
+    o[0] = (u32) best.score;
+    o[1] = best.start;
+    o[2] = best_end;
+    o[3] = best.consumed;
+    o[4] = best.matches;
+}
+
+const char *align_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
+                       int penalty, trew_hip_alignment *out) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_align_host: null argument";
+    for (u64 r = 0; r < n_reads; r++)
+        for (int m = 0; m < n_motifs; m++) {
+            u32 f[5], v[5];
+            align_strand_host(words + offsets[r], lengths[r], motifs[m], 0, penalty, f);
+            align_strand_host(words + offsets[r], lengths[r], motifs[m], 1, penalty, v);
+            trew_hip_alignment &o = out[r * (u64) n_motifs + (u64) m];
+            o.score_fwd = f[0], o.start_fwd = f[1], o.end_fwd = f[2], o.consumed_fwd = f[3], o.matches_fwd = f[4];
+            o.score_rev = v[0], o.start_rev = v[1], o.end_rev = v[2], o.consumed_rev = v[3], o.matches_rev = v[4];
+        }
+    return nullptr;
+}
+
 }  // namespace trew

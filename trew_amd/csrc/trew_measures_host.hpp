@@ -1,5 +1,5 @@
 // trew_measures_host.hpp -- the per-read measures computed on the CPU, straight from their definitions
-// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite), and the argument checks the
+// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite, trew_hip_alignment), and the argument checks the
 // device entry points share with them.  Plain C++17: no HIP, no context.  trew_capi.cpp wraps these into the extern "C"
 // trew_*_host functions and keeps the error strings; tests/harness/measures_host_harness.cpp runs them under sanitizers.
 //
@@ -48,5 +48,8 @@ void sort_satellites(trew_hip_satellite *v, uint64_t n);  // by (read, start)
 void sort_chain_items(trew_hip_chain_item *v, uint64_t n);  // by (read, motif, strand, start)
 const char *chain_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                        int n_motifs, trew_hip_chain_item *out, uint64_t cap, uint64_t *n_items, uint32_t *counts);
+// indel-aware motif tract per read: the wraparound alignment of include/trew_hip.h, cell by cell; the checks of tracts_host
+const char *align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                       int n_motifs, int penalty, trew_hip_alignment *out);
 
 }  // namespace trew
