@@ -14,6 +14,8 @@ matches), all zero when the largest score is 0.
 
 Two forms that must agree: align_read (the definition above in plain Python tuples, O(n k^2)) and align (the max over d
 replaced by the five doubling steps 1, 2, 4, 8, 16 on the cyclic order, vectorised over j and over many reads with numpy)."""
+import os
+
 import numpy as np
 
 FIELDS = tuple(name + sfx for sfx in ("_fwd", "_rev") for name in ("score", "start", "end", "consumed", "matches"))
@@ -143,3 +145,25 @@ def columns(score, start, end, consumed, matches, k, penalty):
     deletions = E - (L - matches)
     insertions = E - (consumed - matches)
     return dict(copies=consumed // k, mismatches=L - matches - insertions, insertions=insertions, deletions=deletions)
+
+
+def cli_lines(path, reads, motifs, a, penalty, min_score=24):
+    """stdout of `trew align`, formatted from the records a"""
+    lines = [">" + os.path.realpath(path), "read,length,motif,strand,start,end,score,copies,consumed,matches,mismatches,insertions,deletions"]
+    sums = {(m, s): [0] * 9 for m in range(len(motifs)) for s in range(2)}
+    for r, read in enumerate(reads):
+        for m, motif in enumerate(motifs):
+            for s, sfx in enumerate(("_fwd", "_rev")):
+                score, start, end, consumed, matches = (int(a[f + sfx][r, m]) for f in ("score", "start", "end", "consumed", "matches"))
+                if score < min_score:
+                    continue
+                c = columns(score, start, end, consumed, matches, len(motif), penalty)
+                row = (start, end, score, c["copies"], consumed, matches, c["mismatches"], c["insertions"], c["deletions"])
+                lines.append("%d,%d,%s,%s,%s" % (r, len(read), motif, "+-"[s], ",".join(str(x) for x in row)))
+                add = (1, end - start) + row[2:]
+                sums[(m, s)] = [x + y for x, y in zip(sums[(m, s)], add)]
+    lines += [">Summary", "motif,strand,reads,reads_reported,bases,score,copies,consumed,matches,mismatches,insertions,deletions"]
+    for m, motif in enumerate(motifs):
+        for s in range(2):
+            lines.append("%s,%s,%d,%s" % (motif, "+-"[s], len(reads), ",".join(str(x) for x in sums[(m, s)])))
+    return lines

@@ -9,6 +9,8 @@ matching windows (the earliest on a tie) gives tract_start_s = its first window 
 Independent of the library and of oracle/: plain Python for single reads (annotate_read), numpy over all windows of many
 reads at once (annotate) -- every window still gets its validity, its smallest rotation and one comparison.
 """
+import os
+
 import numpy as np
 
 CODE = {"T": 0, "G": 1, "C": 2, "A": 3, "t": 0, "g": 1, "c": 2, "a": 3}
@@ -132,3 +134,23 @@ def annotate(reads, motifs):
             out["tract_start_" + sfx][rread[pick], mi] = rs[pick] - starts[rread[pick]]
             out["tract_len_" + sfx][rread[pick], mi] = rlen[pick] + k - 1
     return out
+
+
+def cli_lines(path, reads, motifs, a, min_tract=None):
+    """stdout of `trew annotate` for one file, formatted from the records a of shape (reads, motifs)"""
+    lines = [">" + os.path.realpath(path),
+             "read,length,motif,windows_fwd,windows_rev,tract_start_fwd,tract_len_fwd,tract_start_rev,tract_len_rev"]
+    reported = [0] * len(motifs)
+    for r, read in enumerate(reads):
+        for m, motif in enumerate(motifs):
+            x = a[r, m]
+            if max(int(x["tract_len_fwd"]), int(x["tract_len_rev"])) >= (min_tract if min_tract is not None else 4 * len(motif)):
+                reported[m] += 1
+                lines.append("%d,%d,%s,%s" % (r, len(read), motif, ",".join(str(int(x[f])) for f in FIELDS)))
+    lines += [">Summary", "motif,reads,reads_reported,bases,windows_fwd,windows_rev,longest_tract"]
+    bases = sum(len(r) for r in reads)
+    for m, motif in enumerate(motifs):
+        longest = max([0] + [max(int(x["tract_len_fwd"]), int(x["tract_len_rev"])) for x in a[:, m]])
+        lines.append("%s,%d,%d,%d,%d,%d,%d" % (motif, len(reads), reported[m], bases, int(a["windows_fwd"][:, m].astype(np.uint64).sum()),
+                                                int(a["windows_rev"][:, m].astype(np.uint64).sum()), longest))
+    return lines

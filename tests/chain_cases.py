@@ -1,7 +1,10 @@
 """Inputs and comparisons shared by test_chain_cpu.py and test_gpu_chain.py."""
+import os
+
 import numpy as np
 
 import chain_ref as R
+from trew_amd import capi
 from variant_cases import MOTIFS, noisy_reads, rc_read  # noqa: F401
 
 TEL, RTEL = "TTAGGG", "CCCTAA"
@@ -98,3 +101,37 @@ def mirrored(items, counts, lengths, ks):
     out["start"] = (n - k - (items["start"].astype(np.int64) + (items["count"].astype(np.int64) - 1) * k)).astype(np.uint32)
     order = np.lexsort((out["start"], out["strand"], out["motif"], out["read"]))
     return out[order], counts[:, :, ::-1, :]
+
+
+def cli_lines(files, motifs, min_units=4, per_item=False, results=None):
+    """stdout of `trew chain`; files = [(path, reads)], formatted from results = [(items, counts, n_items)], one per file (default:
+    trew_chain_host's)"""
+    lines = []
+    nm = len(motifs)
+    tot = np.zeros((nm, 2, 5), dtype=np.int64)  # reads, units, variants, runs, longest run
+    for i, (path, reads) in enumerate(files):
+        items, counts, _ = results[i] if results is not None else capi.chain_host(reads, motifs)
+        lines += [">" + os.path.realpath(path), "read,length,motif,strand,start,count,unit" if per_item else "read,length,motif,strand,start,end,units,variants,runs,signature"]
+        keys = np.stack([items["read"], items["motif"], items["strand"]], axis=1)
+        cuts = np.flatnonzero(np.any(np.diff(keys, axis=0) != 0, axis=1)) + 1 if len(items) else np.zeros(0, dtype=np.int64)
+        for grp in (np.split(items, cuts) if len(items) else []):
+            r, m, s = int(grp["read"][0]), int(grp["motif"][0]), int(grp["strand"][0])
+            k = len(motifs[m])
+            is_run = grp["bin"] == NONE
+            units, nvar, runs = int(grp["count"][is_run].sum()), int((~is_run).sum()), int(is_run.sum())
+            tot[m, s, 1:4] += (units, nvar, runs)
+            tot[m, s, 4] = max(tot[m, s, 4], int(grp["count"][is_run].max()) if runs else 0)
+            if units + nvar < min_units:
+                continue
+            tot[m, s, 0] += 1
+            head = "%d,%d,%s,%s" % (r, len(reads[r]), motifs[m], "-" if s else "+")
+            if per_item:
+                lines += ["%s,%d,%d,%s" % (head, x["start"], x["count"], "=" if x["bin"] == NONE else capi.chain_unit_text(motifs[m], int(x["bin"]))) for x in grp]
+            else:
+                end = int((grp["start"].astype(np.int64) + grp["count"].astype(np.int64) * k).max())
+                lines.append("%s,%d,%d,%d,%d,%d,%s" % (head, grp["start"][0], end, units, nvar, runs, capi.chain_signature(grp, motifs[m])))
+    lines += [">Summary", "motif,strand,reads,units,variants,runs,longest_run"]
+    for m, motif in enumerate(motifs):
+        for s in (0, 1):
+            lines.append("%s,%s,%d,%d,%d,%d,%d" % ((motif, "-" if s else "+") + tuple(tot[m, s].tolist())))
+    return lines

@@ -10,6 +10,8 @@ Independent of the library and of oracle/: plain Python for single reads (interv
 numpy for many reads at once (intervals: every window canonicalised, coverage as a difference array, the groups from the
 differences of the covered positions).  Records are (read, motif, strand, start, end, covered), sorted in that order.
 """
+import os
+
 import numpy as np
 
 import annot_ref as A
@@ -121,3 +123,22 @@ def intervals(reads, motifs, max_gap, min_len):
                 recs.append(g)
     out = np.concatenate(recs) if recs else np.zeros(0, dtype=INTERVAL_DTYPE)
     return out[np.lexsort((out["start"], out["strand"], out["motif"], out["read"]))], counts
+
+
+def cli_lines(path, reads, motifs, want):
+    """stdout of `trew intervals`, rendered from the reference (records, counts)"""
+    recs, counts = want
+    lines = [">" + os.path.realpath(path), "read,length,motif,strand,start,end,covered"]
+    for x in recs:
+        lines.append("%d,%d,%s,%s,%d,%d,%d" % (x["read"], len(reads[x["read"]]), motifs[x["motif"]], "+-"[x["strand"]], x["start"], x["end"], x["covered"]))
+    lines += [">Summary", "motif,reads,reads_with_interval,bases,intervals_fwd,intervals_rev,longest_fwd,longest_rev,terminal_fwd,terminal_rev"]
+    bases = sum(len(r) for r in reads)
+    lens = np.array([len(r) for r in reads], dtype=np.int64)
+    for m, motif in enumerate(motifs):
+        row = [motif, len(reads), int((counts[:, m].sum(axis=1) > 0).sum()), bases]
+        per = [recs[(recs["motif"] == m) & (recs["strand"] == s)] for s in (0, 1)]
+        row += [len(p) for p in per]
+        row += [int((p["end"].astype(np.int64) - p["start"]).max()) if len(p) else 0 for p in per]
+        row += [int(((p["start"] == 0) | (p["end"] == lens[p["read"]])).sum()) for p in per]
+        lines.append(",".join(str(v) for v in row))
+    return lines

@@ -328,23 +328,7 @@ def write_fastq(path, reads):
 
 def expected_cli(path, reads, motifs, min_tract=None):
     """stdout of `trew annotate`, formatted from the reference"""
-    a = R.annotate(reads, motifs)
-    lines = [">" + os.path.realpath(path),
-             "read,length,motif,windows_fwd,windows_rev,tract_start_fwd,tract_len_fwd,tract_start_rev,tract_len_rev"]
-    reported = [0] * len(motifs)
-    for r, read in enumerate(reads):
-        for m, motif in enumerate(motifs):
-            x = a[r, m]
-            if max(int(x["tract_len_fwd"]), int(x["tract_len_rev"])) >= (min_tract if min_tract is not None else 4 * len(motif)):
-                reported[m] += 1
-                lines.append("%d,%d,%s,%s" % (r, len(read), motif, ",".join(str(int(x[f])) for f in R.FIELDS)))
-    lines += [">Summary", "motif,reads,reads_reported,bases,windows_fwd,windows_rev,longest_tract"]
-    bases = sum(len(r) for r in reads)
-    for m, motif in enumerate(motifs):
-        longest = max([0] + [max(int(x["tract_len_fwd"]), int(x["tract_len_rev"])) for x in a[:, m]])
-        lines.append("%s,%d,%d,%d,%d,%d,%d" % (motif, len(reads), reported[m], bases, int(a["windows_fwd"][:, m].astype(np.uint64).sum()),
-                                                int(a["windows_rev"][:, m].astype(np.uint64).sum()), longest))
-    return lines
+    return R.cli_lines(path, reads, motifs, R.annotate(reads, motifs), min_tract)
 
 
 def run_cli(*args):

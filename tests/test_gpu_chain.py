@@ -16,7 +16,7 @@ import interval_ref as I
 import oracle as O
 import tract_ref as T
 import variant_ref as V
-from chain_cases import (EDGE_BITS, EDGE_MOTIFS, EDGE_WORDS, K32, MOTIFS, NONE, TEL, dirty_planes, filler, key_items, noisy_reads, run_end_read,
+from chain_cases import (EDGE_BITS, EDGE_MOTIFS, EDGE_WORDS, K32, MOTIFS, NONE, TEL, cli_lines, dirty_planes, filler, key_items, noisy_reads, run_end_read,
                          run_start_read, same, subst, variant_back_anchor_read, variant_fwd_anchor_read)
 from trew_amd import capi
 
@@ -429,37 +429,7 @@ def write_fastq(path, reads):
         f.write(data)
 
 
-def expected_cli(files, motifs, min_units=4, per_item=False):
-    """stdout of `trew chain`, formatted in Python from trew_chain_host; files = [(path, reads)]"""
-    lines = []
-    nm = len(motifs)
-    tot = np.zeros((nm, 2, 5), dtype=np.int64)  # reads, units, variants, runs, longest run
-    for path, reads in files:
-        items, counts, _ = capi.chain_host(reads, motifs)
-        lines += [">" + os.path.realpath(path), "read,length,motif,strand,start,count,unit" if per_item else "read,length,motif,strand,start,end,units,variants,runs,signature"]
-        keys = np.stack([items["read"], items["motif"], items["strand"]], axis=1)
-        cuts = np.flatnonzero(np.any(np.diff(keys, axis=0) != 0, axis=1)) + 1 if len(items) else np.zeros(0, dtype=np.int64)
-        for grp in (np.split(items, cuts) if len(items) else []):
-            r, m, s = int(grp["read"][0]), int(grp["motif"][0]), int(grp["strand"][0])
-            k = len(motifs[m])
-            is_run = grp["bin"] == NONE
-            units, nvar, runs = int(grp["count"][is_run].sum()), int((~is_run).sum()), int(is_run.sum())
-            tot[m, s, 1:4] += (units, nvar, runs)
-            tot[m, s, 4] = max(tot[m, s, 4], int(grp["count"][is_run].max()) if runs else 0)
-            if units + nvar < min_units:
-                continue
-            tot[m, s, 0] += 1
-            head = "%d,%d,%s,%s" % (r, len(reads[r]), motifs[m], "-" if s else "+")
-            if per_item:
-                lines += ["%s,%d,%d,%s" % (head, x["start"], x["count"], "=" if x["bin"] == NONE else capi.chain_unit_text(motifs[m], int(x["bin"]))) for x in grp]
-            else:
-                end = int((grp["start"].astype(np.int64) + grp["count"].astype(np.int64) * k).max())
-                lines.append("%s,%d,%d,%d,%d,%d,%s" % (head, grp["start"][0], end, units, nvar, runs, capi.chain_signature(grp, motifs[m])))
-    lines += [">Summary", "motif,strand,reads,units,variants,runs,longest_run"]
-    for m, motif in enumerate(motifs):
-        for s in (0, 1):
-            lines.append("%s,%s,%d,%d,%d,%d,%d" % ((motif, "-" if s else "+") + tuple(tot[m, s].tolist())))
-    return lines
+expected_cli = cli_lines
 
 
 def run_cli(*args):

@@ -385,23 +385,7 @@ def write_fastq(path, reads):
         f.write(data)
 
 
-def expected_cli(path, reads, motifs, want):
-    """stdout of `trew intervals`, rendered from the reference (records, counts)"""
-    recs, counts = want
-    lines = [">" + os.path.realpath(path), "read,length,motif,strand,start,end,covered"]
-    for x in recs:
-        lines.append("%d,%d,%s,%s,%d,%d,%d" % (x["read"], len(reads[x["read"]]), motifs[x["motif"]], "+-"[x["strand"]], x["start"], x["end"], x["covered"]))
-    lines += [">Summary", "motif,reads,reads_with_interval,bases,intervals_fwd,intervals_rev,longest_fwd,longest_rev,terminal_fwd,terminal_rev"]
-    bases = sum(len(r) for r in reads)
-    lens = np.array([len(r) for r in reads], dtype=np.int64)
-    for m, motif in enumerate(motifs):
-        row = [motif, len(reads), int((counts[:, m].sum(axis=1) > 0).sum()), bases]
-        per = [recs[(recs["motif"] == m) & (recs["strand"] == s)] for s in (0, 1)]
-        row += [len(p) for p in per]
-        row += [int((p["end"].astype(np.int64) - p["start"]).max()) if len(p) else 0 for p in per]
-        row += [int(((p["start"] == 0) | (p["end"] == lens[p["read"]])).sum()) for p in per]
-        lines.append(",".join(str(v) for v in row))
-    return lines
+expected_cli = R.cli_lines
 
 
 def run_cli(*args):

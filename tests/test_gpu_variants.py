@@ -433,39 +433,7 @@ def read_fastq(path):
         return f.read().split(b"\n")[1::4]
 
 
-def expected_cli(files, motifs, min_units=4):
-    """stdout of `trew variants`, formatted from the reference; files = [(path, reads)]"""
-    lines = []
-    nm = len(motifs)
-    tot = dict(reads=0, bases=0, rep=[0] * nm, uf=[0] * nm, ur=[0] * nm, vf=[0] * nm, vr=[0] * nm)
-    hist = np.zeros((nm, 2, R.BINS), dtype=np.uint64)
-    rw = np.zeros_like(hist)
-    for path, reads in files:
-        rec, h, w, _ = R.variants(reads, motifs)
-        hist += h
-        rw += w
-        lines += [">" + os.path.realpath(path), "read,length,motif," + ",".join(R.FIELDS)]
-        for r, read in enumerate(reads):
-            for m, motif in enumerate(motifs):
-                x = {f: int(rec[f][r, m]) for f in R.FIELDS}
-                if max(x["units_fwd"] + x["variants_fwd"], x["units_rev"] + x["variants_rev"]) >= min_units:
-                    tot["rep"][m] += 1
-                    x["top_fwd"], x["top_rev"] = R.bin_text(motif, x["top_fwd"]), R.bin_text(motif, x["top_rev"])
-                    lines.append("%d,%d,%s,%s" % (r, len(read), motif, ",".join(str(x[f]) for f in R.FIELDS)))
-        tot["reads"] += len(reads)
-        tot["bases"] += sum(len(r) for r in reads)
-        for m in range(nm):
-            for key, f in (("uf", "units_fwd"), ("ur", "units_rev"), ("vf", "variants_fwd"), ("vr", "variants_rev")):
-                tot[key][m] += int(rec[f][:, m].astype(np.uint64).sum())
-    lines += [">Summary", "motif,reads,reads_reported,bases,units_fwd,units_rev,variants_fwd,variants_rev"]
-    for m, motif in enumerate(motifs):
-        lines.append("%s,%d,%d,%d,%d,%d,%d,%d" % (motif, tot["reads"], tot["rep"][m], tot["bases"], tot["uf"][m], tot["ur"][m], tot["vf"][m], tot["vr"][m]))
-    lines += [">Variants", "motif,variant,pos,base,count_fwd,reads_fwd,count_rev,reads_rev"]
-    for m, motif in enumerate(motifs):
-        both = hist[m, 0] + hist[m, 1]
-        for b in sorted(np.flatnonzero(both).tolist(), key=lambda b: (-int(both[b]), b)):
-            lines.append("%s,%s,%d,%s,%d,%d,%d,%d" % (motif, R.bin_text(motif, b), b // 4, R.BASES[b & 3], hist[m, 0, b], rw[m, 0, b], hist[m, 1, b], rw[m, 1, b]))
-    return lines
+expected_cli = R.cli_lines
 
 
 def run_cli(*args):

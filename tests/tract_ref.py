@@ -10,6 +10,8 @@ them.  On ties the shorter tract wins at both ends; n < k gives zeros.
 Independent of the library and of oracle/: plain Python for single reads (tracts_read: window by window, base by base),
 numpy for many reads at once (tracts: every window canonicalised, coverage as a difference array, S as a cumulative sum).
 """
+import os
+
 import numpy as np
 
 import annot_ref as A
@@ -104,3 +106,25 @@ def tracts(reads, motifs, penalty):
                 out["tail_len" + sfx][r, mi] = n - b
                 out["tail_cov" + sfx][r, mi] = c[n] - c[b]
     return out
+
+
+def cli_lines(path, reads, motifs, t, min_tract=None):
+    """stdout of `trew tracts`, formatted from the reference records t"""
+    lines = [">" + os.path.realpath(path), "read,length,motif," + ",".join(FIELDS)]
+    reported = [0] * len(motifs)
+    lens = ("head_len_fwd", "head_len_rev", "tail_len_fwd", "tail_len_rev")
+    for r, read in enumerate(reads):
+        for m, motif in enumerate(motifs):
+            x = t[r, m]
+            if max(int(x[f]) for f in lens) >= (min_tract if min_tract is not None else 4 * len(motif)):
+                reported[m] += 1
+                lines.append("%d,%d,%s,%s" % (r, len(read), motif, ",".join(str(int(x[f])) for f in FIELDS)))
+    lines += [">Summary", "motif,reads,reads_reported,bases,covered_fwd,covered_rev,longest_head,longest_tail"]
+    bases = sum(len(r) for r in reads)
+    for m, motif in enumerate(motifs):
+        lines.append("%s,%d,%d,%d,%d,%d,%d,%d" % (
+            motif, len(reads), reported[m], bases, int(t["covered_fwd"][:, m].astype(np.uint64).sum()),
+            int(t["covered_rev"][:, m].astype(np.uint64).sum()),
+            max(int(t["head_len_fwd"][:, m].max()), int(t["head_len_rev"][:, m].max())),
+            max(int(t["tail_len_fwd"][:, m].max()), int(t["tail_len_rev"][:, m].max()))))
+    return lines

@@ -12,6 +12,8 @@ the reads' bin counts, reads_with[m][s][bin] = reads whose bin count is non-zero
 Independent of the library and of oracle/: plain Python for single reads (variants_read: window by window, base by base),
 numpy for many reads at once (variants: one mismatch matrix of windows x k per read and strand).
 """
+import os
+
 import numpy as np
 
 CODE = {"T": 0, "G": 1, "C": 2, "A": 3, "t": 0, "g": 1, "c": 2, "a": 3}
@@ -131,3 +133,39 @@ def variants(reads, motifs):
                     out["top" + sfx][r, m] = bins.argmax()  # the first, i.e. smallest, bin with the largest count
                     out["top_count" + sfx][r, m] = bins.max()
     return out, per_read.sum(axis=0), (per_read != 0).sum(axis=0).astype(np.uint64), per_read
+
+
+def cli_lines(files, motifs, min_units=4, results=None):
+    """stdout of `trew variants`; files = [(path, reads)], formatted from results = [(records, hist, reads_with)], one per file
+    (default: the reference's)"""
+    lines = []
+    nm = len(motifs)
+    tot = dict(reads=0, bases=0, rep=[0] * nm, uf=[0] * nm, ur=[0] * nm, vf=[0] * nm, vr=[0] * nm)
+    hist = np.zeros((nm, 2, BINS), dtype=np.uint64)
+    rw = np.zeros_like(hist)
+    for i, (path, reads) in enumerate(files):
+        rec, h, w = results[i] if results is not None else variants(reads, motifs)[:3]
+        hist += h
+        rw += w
+        lines += [">" + os.path.realpath(path), "read,length,motif," + ",".join(FIELDS)]
+        for r, read in enumerate(reads):
+            for m, motif in enumerate(motifs):
+                x = {f: int(rec[f][r, m]) for f in FIELDS}
+                if max(x["units_fwd"] + x["variants_fwd"], x["units_rev"] + x["variants_rev"]) >= min_units:
+                    tot["rep"][m] += 1
+                    x["top_fwd"], x["top_rev"] = bin_text(motif, x["top_fwd"]), bin_text(motif, x["top_rev"])
+                    lines.append("%d,%d,%s,%s" % (r, len(read), motif, ",".join(str(x[f]) for f in FIELDS)))
+        tot["reads"] += len(reads)
+        tot["bases"] += sum(len(r) for r in reads)
+        for m in range(nm):
+            for key, f in (("uf", "units_fwd"), ("ur", "units_rev"), ("vf", "variants_fwd"), ("vr", "variants_rev")):
+                tot[key][m] += int(rec[f][:, m].astype(np.uint64).sum())
+    lines += [">Summary", "motif,reads,reads_reported,bases,units_fwd,units_rev,variants_fwd,variants_rev"]
+    for m, motif in enumerate(motifs):
+        lines.append("%s,%d,%d,%d,%d,%d,%d,%d" % (motif, tot["reads"], tot["rep"][m], tot["bases"], tot["uf"][m], tot["ur"][m], tot["vf"][m], tot["vr"][m]))
+    lines += [">Variants", "motif,variant,pos,base,count_fwd,reads_fwd,count_rev,reads_rev"]
+    for m, motif in enumerate(motifs):
+        both = hist[m, 0] + hist[m, 1]
+        for b in sorted(np.flatnonzero(both).tolist(), key=lambda b: (-int(both[b]), b)):
+            lines.append("%s,%s,%d,%s,%d,%d,%d,%d" % (motif, bin_text(motif, b), b // 4, BASES[b & 3], hist[m, 0, b], rw[m, 0, b], hist[m, 1, b], rw[m, 1, b]))
+    return lines

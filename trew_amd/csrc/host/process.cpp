@@ -37,6 +37,7 @@
 
 #include "bgzf_reader.hpp"
 #include "fastq_blocks.hpp"
+#include "fastq_chunks.hpp"
 #include "trew_host.hpp"
 
 namespace trew_host {
@@ -428,40 +429,29 @@ static char *alloc_buffer() {
 // read_fastq_thread (kmer.cpp:987-1038) and read_fastq_long_thread (1166-1213): 4 MiB chunks, sequence lines by counting
 // newlines, a sequence line split across two chunks carried over.  This thread is the serial part of a compressed run, so it
 // only COUNTS the newlines of a chunk (AVX2) and leaves finding the lines to the consumer (Chunk::located).
-static void read_fastq_thread(FileReader &fr, ChunkQueue *q) {
-    int64_t num = 0;
-    int shift = 0;
-    char *buffer = alloc_buffer();
-    for (;;) {
-        Chunk *ch = new Chunk();
-        const int bytes_read = fr.read(buffer + shift, LENGTH - 1 - shift);
-        const int total = (bytes_read > 0 ? bytes_read : 0) + shift;
-        buffer[total] = '\0';
-        ch->buffer1 = buffer;
-        ch->located = false;
-        ch->total = total;
-        ch->num_before = num;
-        num += (int64_t) count_newlines(buffer, (size_t) total);
-        if (bytes_read <= 0) {
-            q->push(ch);
-            if (fr.eof()) break;
-            fprintf(stderr, "File-IO Error: %s.\n", fr.error());  // kmer.cpp:1021-1022
-            fflush(stdout);
-            fflush(stderr);
-            _exit(EXIT_FAILURE);
-        }
-        char *buffer_new = alloc_buffer();
-        shift = 0;
-        if ((num & 3) == 1) {  // inside a sequence line: carry it over (kmer.cpp:1026-1029)
-            const char *last = (const char *) memrchr(buffer, '\n', (size_t) total);
-            const int idx = last ? (int) (last - buffer) : -1;
-            const int rest = total - idx - 1;
-            memcpy(buffer_new, buffer + idx + 1, (size_t) rest);
-            shift = rest;
-            if (shift >= LENGTH - 2) die("a read does not fit one 4 MiB chunk");
-        }
-        q->push(ch);
-        buffer = buffer_new;
+static void read_fastq_thread(FileReader &fr, ChunkQueue *q, int chunk = LENGTH) {
+    const ChunkEnd end = read_fastq_chunks([&](char *p, int n) { return fr.read(p, n); }, [&] { return fr.eof(); }, chunk,
+                                           [&](char *buffer, int total, int64_t num_before) {
+                                               Chunk *ch = new Chunk();
+                                               ch->buffer1 = buffer;
+                                               ch->located = false;
+                                               ch->total = total;
+                                               ch->num_before = num_before;
+                                               q->push(ch);
+                                           });
+    if (end == ChunkEnd::NoMemory) die("memory allocation failure");
+    if (end == ChunkEnd::TooLong) {
+        if (chunk == LENGTH) die("a read does not fit one 4 MiB chunk");
+        fprintf(stderr, "a read does not fit one %d-byte chunk\n", chunk);
+        fflush(stdout);
+        fflush(stderr);
+        _exit(EXIT_FAILURE);
+    }
+    if (end == ChunkEnd::IoError) {
+        fprintf(stderr, "File-IO Error: %s.\n", fr.error());  // kmer.cpp:1021-1022
+        fflush(stdout);
+        fflush(stderr);
+        _exit(EXIT_FAILURE);
     }
 }
 
@@ -1577,18 +1567,9 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             delete ch;
             break;
         }
-        // the newline that makes num & 3 == 2 closes a sequence line (see worker_loop); no length limit here
+        // the newline that makes num & 3 == 2 closes a sequence line (locate_chunk_lines); no length limit here
         if (w->nl.size() < (size_t) LENGTH + 2) w->nl.resize((size_t) LENGTH + 2);
-        const size_t cnt = scan_newlines(ch->buffer1, (size_t) ch->total, w->nl.data());
-        const size_t j0 = (size_t) ((1 - ch->num_before) & 3);
-        const uint64_t first_read = (uint64_t) (ch->num_before + (int64_t) j0) >> 2;
-        w->st.clear();
-        w->nd.clear();
-        for (size_t j = j0; j < cnt; j += 4) {
-            const int64_t start = j > 0 ? (int64_t) w->nl[j - 1] + 1 : 0, len = (int64_t) w->nl[j] - start;
-            w->st.push_back(start);
-            w->nd.push_back(start + len - 1);
-        }
+        const uint64_t first_read = locate_chunk_lines(ch->buffer1, (size_t) ch->total, ch->num_before, w->nl, w->st, w->nd);
         const uint64_t n = w->st.size();
         if (n > a->reads_cap) die("internal error: a chunk holds more reads than the slot");
         if (n) {
@@ -1603,6 +1584,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             x.b.lengths = lengths;
             x.b.n_reads = n;
             AnnotFileResult &p = w->part;
+            p.batches++;
             p.reads += n;
             for (uint64_t r = 0; r < n; r++) p.bases += lengths[r];
             switch (rq->kind) {
@@ -1650,6 +1632,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         into.var_reads_with[i] += from.var_reads_with[i];
     }
     into.interval_retries += from.interval_retries;
+    into.batches += from.batches;
     for (const auto &kv : from.period_units) {
         auto &u = into.period_units[kv.first];
         u.first += kv.second.first;
@@ -1671,6 +1654,17 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
 
 static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"};  // in the order of Measure
 
+// The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
+// experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
+// slots stay sized for LENGTH).  Anything else is ignored.
+static int measure_chunk_bytes() {
+    if (const char *e = getenv("TREW_MEASURE_CHUNK_BYTES")) {
+        int v;
+        if (parse_int(e, &v) && v >= 64 && v <= LENGTH) return v;
+    }
+    return LENGTH;
+}
+
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
     const auto t0 = std::chrono::steady_clock::now();
     for (auto &w : a->workers) w.part = AnnotFileResult();
@@ -1678,7 +1672,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     std::vector<std::thread> th;
     for (auto &w : a->workers) th.emplace_back(annotate_worker_loop, a, &w, &q, &rq);
     FileReader f = open_reader(file_name, is_gz, cfg.NUM_THREAD);
-    read_fastq_thread(f, &q);
+    const int chunk = measure_chunk_bytes();
+    read_fastq_thread(f, &q, chunk);
     f.close();
     for (size_t i = 0; i < a->workers.size(); i++) {
         Chunk *c = new Chunk();
@@ -1721,6 +1716,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + %s; serial reader, %d worker(s))\n", file_name,
                 (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, kMeasureNames[(int) rq.kind], (int) a->workers.size());
+        fprintf(stderr, "[trew] %s: %llu batch(es) submitted, chunk length %d bytes\n", file_name, (unsigned long long) out.batches, chunk);
         if (rq.kind == Measure::Intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.irows.size(), (unsigned long long) out.interval_retries);
         if (rq.kind == Measure::Chain) fprintf(stderr, "[trew] %s: %llu items, %llu batch(es) resubmitted with a larger log\n", file_name,

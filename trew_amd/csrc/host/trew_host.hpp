@@ -177,6 +177,7 @@ struct AnnotFileResult {
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t interval_retries = 0;  // intervals, chain, repeats, satellites: batches resubmitted because their log overflowed
+    uint64_t batches = 0;           // the non-empty chunks, each of which is one batch
     uint64_t runs_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, runs_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported_rev[TREW_ANNOT_MAX_MOTIFS] = {};  // chain
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
     std::vector<uint64_t> var_hist, var_reads_with;  // variants: [motif][strand][bin]; empty for the other kinds
