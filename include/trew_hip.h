@@ -33,8 +33,8 @@ extern "C" {
  * entry points (trew_hip_intervals, trew_hip_intervals_results, trew_intervals_host), the variant entry points
  * (trew_hip_variants, trew_hip_variants_results, trew_variants_host), the period entry points (trew_hip_periods,
  * trew_hip_periods_results, trew_periods_host), the satellite entry points (trew_hip_satellites,
- * trew_hip_satellites_results, trew_satellites_host) and the alignment entry points (trew_hip_align, trew_hip_align_results,
- * trew_align_host): they are purely additive -- no existing structure, enumerator or function
+ * trew_hip_satellites_results, trew_satellites_host), the alignment entry points (trew_hip_align, trew_hip_align_results,
+ * trew_align_host) and the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host): they are purely additive -- no existing structure, enumerator or function
  * changed. */
 #define TREW_HIP_ABI_VERSION 4
 
@@ -602,6 +602,55 @@ int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out,
 /* The same records on the host, base by base from the definition, over packed planes. */
 int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                     const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_alignment *out);
+
+/* ---- de novo repeats under indels: seed a unit, align against it with wraparound, re-vote the unit from the alignment ----
+ * (what repeats in this noisy long read, with which unit, from where to where, and how many copies?)  Integer-exact.  The
+ * read x has n bases, with the codes and the N handling of trew_hip_periods; min_period, max_period (<= 32), penalty P and
+ * min_score are those of trew_hip_periods, with the same checks and error texts.
+ * 1. Periods.  R is the trew_hip_period record of the read.  If R is zero, the record is zero.  Otherwise k = scored_period,
+ *    b = start, e = end - k.
+ * 2. Seed.  Among i in [b, e) take the longest run of consecutive positions with eq_k[i] true (bases i and i + k both valid
+ *    and equal), the first of the longest; rs is its start, or b without one.  S0[j] = x[rs + j] for j < k, an invalid base
+ *    replaced by the base of phase (rs + j - start) mod k of the unreduced consensus of trew_hip_periods.  S is S0 reduced to
+ *    its primitive root, of length seed_period.  A run of k or more positions is two identical copies: S0 is a literal unit
+ *    of the read, not an average over slipped phases.
+ * 3. Align.  A1 is the forward-strand record of the wraparound recurrence of trew_hip_alignment, above, of x against S:
+ *    the same tuples, tie rules and record, here for every unit length 1 .. 32.
+ * 4. Vote.  The same recurrence again over x[A1.start, A1.end) only: H = (0, 0, 0, 0) in every phase at A1.start, positions
+ *    count from A1.start.  At each row i, j* is the phase with the largest V[i][j] tuple, the smallest j on a tie (V, not H:
+ *    the V cell is where the base was consumed, before any deleted motif bases).  If x[i-1] is valid and the diagonal
+ *    candidate of (i, j*) equals V[i][j*], then cnt[j*][x[i-1]] += 1.  A forward decode: no traceback.
+ * 5. Re-vote.  U0[j] = S[j] if cnt[j][S[j]] is the largest count of phase j, otherwise the smallest code among the largest
+ *    (a phase without votes keeps the seed).  U is U0 reduced to its primitive root.  support = the sum of cnt[j][U0[j]];
+ *    changed = the number of phases with U0[j] != S[j].
+ * 6. Final.  If U = S, A2 = A1.  Otherwise A2 is the forward record of x against U, and if A2.score < A1.score the seed is
+ *    kept: U := S, A2 := A1, changed := 0.  One round only.
+ *   period, unit            the length of U and U, packed as trew_hip_period's unit
+ *   seed_period, seed_unit  the same of S
+ *   scored_period           k of step 1
+ *   changed, support        of step 5 (changed: 0 when the seed is kept)
+ *   score, start, end, consumed, matches   A2, as in trew_hip_alignment; seed_score = A1.score
+ * Consequences: score >= seed_score; unit is primitive; copies = consumed / period and the mismatches, insertions and
+ * deletions follow as for trew_hip_alignment with k = period.  Limits: one tract per read, the best one; periods <= 32; linear
+ * gap cost; a wrong scored_period (a multiple or a neighbour of the true period) is not repaired; the vote is a forward
+ * decode, not a traceback (an indel misplaces the few bases until the penalised path overtakes); one refinement round.
+ * Also additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t period, seed_period, scored_period, changed;
+    uint32_t score, start, end, consumed, matches;
+    uint32_t seed_score, support, reserved;
+    uint64_t unit, seed_unit;
+} trew_hip_refined;
+/* Like trew_hip_periods in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, the checks and their error texts), with a result buffer of its own that the slot's
+ * first call allocates and independent of the scan and of the other nine kernels.  One record per read.  One kernel, a wave
+ * per read, for every read length. */
+int trew_hip_refine(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score);
+/* Waits for the slot and copies the records of its last trew_hip_refine; arguments as trew_hip_periods_results. */
+int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_refined *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same records on the host, step by step from the definition, over packed planes. */
+int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                     int penalty, uint32_t min_score, trew_hip_refined *out);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

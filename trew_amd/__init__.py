@@ -30,6 +30,7 @@ from .capi import (  # noqa: F401
     k_mer_check,
     pack_reads,
     periods,
+    refine,
     repeats,
     satellites,
     tracts,

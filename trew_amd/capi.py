@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_repeats", "trew_hip_repeats_results", "trew_repeats_host",
     "trew_hip_satellites", "trew_hip_satellites_results", "trew_satellites_host",
     "trew_hip_align", "trew_hip_align_results", "trew_align_host",
+    "trew_hip_refine", "trew_hip_refine_results", "trew_refine_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -174,6 +175,15 @@ class Alignment(C.Structure):
 ALIGN_DTYPE = np.dtype([(name, "<u4") for name, _ in Alignment._fields_])
 assert ALIGN_DTYPE.itemsize == C.sizeof(Alignment) == 40
 
+
+class Refined(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("period", "seed_period", "scored_period", "changed", "score", "start", "end", "consumed", "matches",
+                                                "seed_score", "support", "reserved")] + [("unit", C.c_uint64), ("seed_unit", C.c_uint64)]
+
+
+REFINE_DTYPE = np.dtype([(name, "<u8" if name in ("unit", "seed_unit") else "<u4") for name, _ in Refined._fields_])
+assert REFINE_DTYPE.itemsize == C.sizeof(Refined) == 64
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -258,6 +268,9 @@ def load():
     lib.trew_hip_align.argtypes = lib.trew_hip_tracts.argtypes
     lib.trew_hip_align_results.argtypes = lib.trew_hip_tracts_results.argtypes
     lib.trew_align_host.argtypes = lib.trew_tracts_host.argtypes
+    lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
+    lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
+    lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -496,6 +509,30 @@ def repeats_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sc
         out = np.zeros(int(n.value), dtype=REPEAT_DTYPE)
         call(out)
     return out[:min(len(out), int(n.value))], counts, int(n.value)
+
+
+def refine_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24):
+    """trew_refine_host: the refined de novo repeat of every read (the period and tract of `periods`, a seed unit from the
+    longest run, wraparound alignment, re-voted unit) computed on the host, step by step from the definition.
+    reads_or_packed as for annotate_host.  Returns REFINE_DTYPE records of shape (n_reads,)."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    out = np.zeros(len(offsets), dtype=REFINE_DTYPE)
+    if lib.trew_refine_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                            int(penalty), int(min_score), out.ctypes.data) != 0:
+        raise TrewHipError("trew_refine_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out
+
+
+def refine_columns(record, penalty):
+    """What follows exactly from a REFINE_DTYPE record (or an array of them) and the penalty: a dict of copies, mismatches,
+    insertions and deletions, as align_columns with k = period (all zero for a zero record)."""
+    period, score, start, end, consumed, matches = (np.asarray(record[f]).astype(np.int64)
+                                                    for f in ("period", "score", "start", "end", "consumed", "matches"))
+    errors = (matches - score) // int(penalty)
+    insertions = errors - (consumed - matches)
+    return {"copies": consumed // np.maximum(period, 1), "mismatches": end - start - matches - insertions, "insertions": insertions,
+            "deletions": errors - (end - start - matches)}
 
 
 def satellites_host(reads_or_packed, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, cap=None):
@@ -752,6 +789,17 @@ class TrewHip:
     def periods_results(self, slot=0, want_ms=False):
         """Records of the slot's last periods: PERIOD_DTYPE array of shape (n_reads,) [, kernel ms]."""
         res = self._fetch_records("periods", slot, PERIOD_DTYPE, want_ms)
+        return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
+
+    def refine(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, slot=0):
+        """Queue the refined de novo repeat of every read of `batch` on the slot's stream (no motifs)."""
+        self._queue("refine", slot, batch, None, 1)
+        self._chk(self.lib.trew_hip_refine(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score)),
+                  "trew_hip_refine")
+
+    def refine_results(self, slot=0, want_ms=False):
+        """Records of the slot's last refine: REFINE_DTYPE array of shape (n_reads,) [, kernel ms]."""
+        res = self._fetch_records("refine", slot, REFINE_DTYPE, want_ms)
         return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
 
     def variants(self, batch, motifs, slot=0):
@@ -1081,6 +1129,18 @@ def periods(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=
                  max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
         t.periods(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score)
         return t.periods_results()
+
+
+def refine(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0):
+    """De novo repeats under indels on the GPU: for every read (bytes / str) the period and tract of `periods`, a seed unit
+    taken from the read, the wraparound alignment against it and the unit re-voted from that alignment -- unit, tract, motif
+    bases consumed and matches -- as REFINE_DTYPE records of shape (n_reads,); refine_columns gives the copies, mismatches,
+    insertions and deletions.  No motif is given."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        t.refine(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score)
+        return t.refine_results()
 
 
 def variants(reads, motifs, device=0):

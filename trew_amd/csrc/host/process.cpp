@@ -1176,11 +1176,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1200,6 +1200,7 @@ struct Annotator {
         std::vector<trew_hip_repeat> rrecs;  // trew repeats
         std::vector<trew_hip_satellite> srecs;  // trew satellites
         std::vector<trew_hip_alignment> arecs;  // trew align
+        std::vector<trew_hip_refined> frecs;    // trew refine
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1559,6 +1560,26 @@ static void fold_align(const AnnotBatch &x, AnnotFileResult &p) {
         }
 }
 
+// trew refine: one record per read and no motif.  A read whose final score reaches MIN_SCORE is a row; refine_units counts
+// the rows, the bases of their tracts and their copies per (period, strand-canonical unit).
+static void fold_refine(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    if (trew_hip_refine(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score)) hip_die(x.c, "trew_hip_refine");
+    if (w->frecs.size() < x.n) w->frecs.resize(x.n);
+    uint64_t got = 0;
+    if (trew_hip_refine_results(x.c, w->slot, w->frecs.data(), x.n, &got, nullptr)) hip_die(x.c, "trew_hip_refine_results");
+    for (uint64_t r = 0; r < x.n; r++) {
+        const trew_hip_refined &rec = w->frecs[r];
+        if (rec.period == 0 || rec.score < rq.min_score) continue;
+        RefineUnit &u = p.refine_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
+        u.reads++;
+        u.bases += rec.end - rec.start;
+        u.copies += rec.consumed / rec.period;
+        p.frows.push_back(RefineRow{x.first_read + r, x.lengths[r], rec});
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1597,6 +1618,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Repeats: fold_repeats(x, p); break;
             case Measure::Satellites: fold_satellites(x, p); break;
             case Measure::Align: fold_align(x, p); break;
+            case Measure::Refine: fold_refine(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1633,6 +1655,12 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
     into.interval_retries += from.interval_retries;
     into.batches += from.batches;
+    for (const auto &kv : from.refine_units) {
+        RefineUnit &u = into.refine_units[kv.first];
+        u.reads += kv.second.reads;
+        u.bases += kv.second.bases;
+        u.copies += kv.second.copies;
+    }
     for (const auto &kv : from.period_units) {
         auto &u = into.period_units[kv.first];
         u.first += kv.second.first;
@@ -1652,7 +1680,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -1690,6 +1718,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         out.rrows.insert(out.rrows.end(), w.part.rrows.begin(), w.part.rrows.end());
         out.srows.insert(out.srows.end(), w.part.srows.begin(), w.part.srows.end());
         out.arows.insert(out.arows.end(), w.part.arows.begin(), w.part.arows.end());
+        out.frows.insert(out.frows.end(), w.part.frows.begin(), w.part.frows.end());
     }
     std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
         if (x.read != y.read) return x.read < y.read;
@@ -1711,6 +1740,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         if (x.read != y.read) return x.read < y.read;
         return x.motif != y.motif ? x.motif < y.motif : x.strand < y.strand;
     });
+    std::sort(out.frows.begin(), out.frows.end(), [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

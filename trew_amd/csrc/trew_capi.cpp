@@ -25,9 +25,9 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine"};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -40,7 +40,7 @@ struct MeasureState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call
-    u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods: n_reads
+    u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods, refine: n_reads
     u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites: their max_records
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites: n_reads
     int n_motifs = 0;  // variants
@@ -1201,8 +1201,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align
-// The nine measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine
+// The ten measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
@@ -1264,6 +1264,11 @@ extern "C" int trew_align_host(const uint32_t *words, const uint32_t *offsets, c
     return host_status(align_host(words, offsets, lengths, n_reads, motifs, n_motifs, penalty, out));
 }
 
+extern "C" int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                int max_period, int penalty, uint32_t min_score, trew_hip_refined *out) {
+    return host_status(refine_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out));
+}
+
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
 static void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
     memset(d, 0, sizeof(*d));
@@ -1302,14 +1307,14 @@ static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs
 
 // What every queue call does before anything of its own: the argument checks in the order callers see them (`own` holds
 // the measure's own checks; it runs behind the motifs' check and in front of the first HIP call), the batch and the motifs onto the slot's stream, and the measure's two events on its first use.
-// The measures without motifs (periods, repeats, satellites) are known by `which`, not by their arguments: for them there is no motif check
+// The measures without motifs (periods, repeats, satellites, refine) are known by `which`, not by their arguments: for them there is no motif check
 // and no pattern table, and they pass no motifs.  For the others, no motifs stays the argument error it always was.
 template <class Own>
 static int measure_begin(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
                          Own own, Slot **slot_out, DevBatch *db) {
     if (!ctx || !batch) return -1;
     if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    const bool motif_less = which == kPeriods || which == kRepeats || which == kSatellites;
+    const bool motif_less = which == kPeriods || which == kRepeats || which == kSatellites || which == kRefine;
     if (!motif_less)
         if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
     if (const char *e = own()) return fail(ctx, e);
@@ -1604,6 +1609,34 @@ extern "C" int trew_hip_periods_results(trew_hip_ctx *ctx, int slot, trew_hip_pe
     if (int rc = fetch_begin(ctx, slot, kPeriods, nullptr, &sp)) return rc;
     const MeasureState &st = sp->measure[kPeriods];
     if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_period), n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- de novo repeats under indels: seed, align, re-vote
+extern "C" int trew_hip_refine(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * { return periods_error(min_period, max_period, penalty, min_score); };
+    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kRefine, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kRefine];
+    const u64 need = db.n_reads;
+    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_refined))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    if (need == 0) return 0;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_refine(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_refined *) st.records.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_refined *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kRefine, nullptr, &sp)) return rc;
+    const MeasureState &st = sp->measure[kRefine];
+    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_refined), n)) return rc;
     return fetch_end(ctx, st, ms_kernel);
 }
 

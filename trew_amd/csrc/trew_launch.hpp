@@ -55,6 +55,8 @@ hipError_t launch_satellites(hipStream_t st, u32 n_cu, const DevBatch &B, int mi
                              const RepeatLog &lg, u32 *d_counts);
 // trew_hip_align: the wave-per-read kernel of kernels/align.inc on the grid of launch_tracts
 hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_alignment *d_out);
+// trew_hip_refine: the wave-per-read kernel of kernels/refine.inc on the grid of launch_tracts; no motifs
+hipError_t launch_refine(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined *d_out);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);

@@ -639,24 +639,29 @@ struct AlignCell {
     }
 };
 
-// one strand of one motif over one read: o = {score, start, end, consumed, matches}
-static void align_strand_host(const u32 *w, u32 n, const trew_hip_motif &motif, int s, int penalty, u32 (&o)[5]) {
-    const int k = motif.k;
-    const u64 target = s ? motif_revcomp(motif.word, k) : motif.word;
-    u32 t[32];
-    for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;  // first base most significant
-    AlignCell H[32], V[32];
+// the alignment of a read against the unit t[0 .. k - 1] repeated without end (1 <= k <= 32): o = {score, start, end,
+// consumed, matches}.  base[i]: the read's codes, 4: an N, which matches nothing.  With cnt (trew_hip_refined's vote) also the
+// forward decode: at every row the phase j* with the largest V, the smallest on a tie, and cnt[j*][base] += 1 when the base is
+// valid and the diagonal is that cell.
+static void align_codes_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5], u32 (*cnt)[4] = nullptr) {
+    AlignCell H[32], V[32], D[32];
     for (int j = 0; j < k; j++) H[j] = AlignCell{0, 0, 0, 0};
     AlignCell best{0, 0, 0, 0};
     u32 best_end = 0;
     for (u32 i = 1; i <= n; i++) {
-        const u32 c = base_at(w, i - 1);  // 4: an N, which matches nothing
+        const u32 c = base[i - 1];
         for (int j = 0; j < k; j++) {
             const AlignCell &d = H[(j + k - 1) % k];
-            const AlignCell diag = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
-                                             : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
+            D[j] = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
+                             : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
             const AlignCell ins{H[j].score - penalty, H[j].start, H[j].consumed, H[j].matches};
-            V[j] = std::max(AlignCell{0, i, 0, 0}, std::max(diag, ins));
+            V[j] = std::max(AlignCell{0, i, 0, 0}, std::max(D[j], ins));
+        }
+        if (cnt) {
+            int js = 0;
+            for (int j = 1; j < k; j++)
+                if (V[js] < V[j]) js = j;  // strictly: the smallest j keeps a tie
+            if (c < 4 && !(D[js] < V[js])) cnt[js][c]++;  // V >= D always: equal
         }
         for (int j = 0; j < k; j++) {
             H[j] = V[j];
@@ -683,20 +688,122 @@ static void align_strand_host(const u32 *w, u32 n, const trew_hip_motif &motif, 
     o[4] = best.matches;
 }
 
+// one strand of one motif over one read: o = {score, start, end, consumed, matches}
+static void align_strand_host(const unsigned char *base, u32 n, const trew_hip_motif &motif, int s, int penalty, u32 (&o)[5]) {
+    const int k = motif.k;
+    const u64 target = s ? motif_revcomp(motif.word, k) : motif.word;
+    u32 t[32];
+    for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;  // first base most significant
+    align_codes_host(base, n, t, k, penalty, o);
+}
+
 const char *align_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
                        int penalty, trew_hip_alignment *out) {
     if (const char *e = motifs_error(motifs, n_motifs)) return e;
     if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
     if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_align_host: null argument";
-    for (u64 r = 0; r < n_reads; r++)
+    std::vector<unsigned char> base;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
         for (int m = 0; m < n_motifs; m++) {
             u32 f[5], v[5];
-            align_strand_host(words + offsets[r], lengths[r], motifs[m], 0, penalty, f);
-            align_strand_host(words + offsets[r], lengths[r], motifs[m], 1, penalty, v);
+            align_strand_host(base.data(), lengths[r], motifs[m], 0, penalty, f);
+            align_strand_host(base.data(), lengths[r], motifs[m], 1, penalty, v);
             trew_hip_alignment &o = out[r * (u64) n_motifs + (u64) m];
             o.score_fwd = f[0], o.start_fwd = f[1], o.end_fwd = f[2], o.consumed_fwd = f[3], o.matches_fwd = f[4];
             o.score_rev = v[0], o.start_rev = v[1], o.end_rev = v[2], o.consumed_rev = v[3], o.matches_rev = v[4];
         }
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- de novo repeats under indels: seed, align, re-vote
+// the length of the primitive root of u[0 .. k - 1]
+static u32 primitive_root(const u32 *u, u32 k) {
+    for (u32 d = 1; d < k; d++) {
+        if (k % d) continue;
+        bool periodic = true;
+        for (u32 j = 0; j < k && periodic; j++) periodic = u[j] == u[(j + d) % k];
+        if (periodic) return d;
+    }
+    return k;
+}
+
+static u64 pack_unit(const u32 *u, u32 k) {
+    u64 w = 0;
+    for (u32 j = 0; j < k; j++) w = (w << 2) | u[j];
+    return w;
+}
+
+// the record of one read, step by step from the definition (trew_hip_refined, include/trew_hip.h)
+static void refine_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined &o) {
+    memset(&o, 0, sizeof(o));
+    // 1. periods: the record and the unreduced consensus
+    trew_hip_period R;
+    memset(&R, 0, sizeof(R));
+    u32 cons[32];
+    if (!piece_record<32>(base, 0, n, min_period, max_period, penalty, min_score, R, cons)) return;
+    const u32 k = R.scored_period, b = R.start, e = R.end - k;
+    // 2. seed: the longest run of eq_k in [b, e), the first of the longest
+    u32 rs = b, longest = 0, run = 0;
+    for (u32 i = b; i < e; i++) {
+        run = base[i] < 4 && base[i] == base[i + k] ? run + 1 : 0;
+        if (run > longest) {
+            longest = run;
+            rs = i + 1 - run;
+        }
+    }
+    u32 S[32], U[32];
+    for (u32 j = 0; j < k; j++) S[j] = base[rs + j] < 4 ? base[rs + j] : cons[(rs + j - R.start) % k];
+    const u32 ks = primitive_root(S, k);
+    // 3. align against the seed
+    u32 a1[5], a2[5];
+    align_codes_host(base, n, S, (int) ks, penalty, a1);
+    // 4. vote over the tract alone
+    u32 cnt[32][4] = {};
+    align_codes_host(base + a1[1], a1[2] - a1[1], S, (int) ks, penalty, a2, cnt);
+    // 5. re-vote
+    u32 changed = 0, support = 0;
+    for (u32 j = 0; j < ks; j++) {
+        u32 top = 0;
+        for (u32 c = 1; c < 4; c++)
+            if (cnt[j][c] > cnt[j][top]) top = c;  // strictly: the smallest code among the largest
+        U[j] = cnt[j][S[j]] == cnt[j][top] ? S[j] : top;
+        support += cnt[j][U[j]];
+        changed += U[j] != S[j];
+    }
+    u32 ku = primitive_root(U, ks);
+    // 6. final
+    for (int i = 0; i < 5; i++) a2[i] = a1[i];
+    if (changed) {
+        align_codes_host(base, n, U, (int) ku, penalty, a2);
+        if (a2[0] < a1[0]) {  // the seed is kept
+            for (int i = 0; i < 5; i++) a2[i] = a1[i];
+            for (u32 j = 0; j < ks; j++) U[j] = S[j];
+            ku = ks;
+            changed = 0;
+        }
+    }
+    o.period = ku;
+    o.seed_period = ks;
+    o.scored_period = k;
+    o.changed = changed;
+    o.score = a2[0], o.start = a2[1], o.end = a2[2], o.consumed = a2[3], o.matches = a2[4];
+    o.seed_score = a1[0];
+    o.support = support;
+    o.unit = pack_unit(U, ku);
+    o.seed_unit = pack_unit(S, ks);
+}
+
+const char *refine_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                        u32 min_score, trew_hip_refined *out) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_refine_host: null argument";
+    std::vector<unsigned char> base;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, out[r]);
+    }
     return nullptr;
 }
 

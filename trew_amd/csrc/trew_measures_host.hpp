@@ -1,5 +1,5 @@
 // trew_measures_host.hpp -- the per-read measures computed on the CPU, straight from their definitions
-// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite, trew_hip_alignment), and the argument checks the
+// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite, trew_hip_alignment, trew_hip_refined), and the argument checks the
 // device entry points share with them.  Plain C++17: no HIP, no context.  trew_capi.cpp wraps these into the extern "C"
 // trew_*_host functions and keeps the error strings; tests/harness/measures_host_harness.cpp runs them under sanitizers.
 //
@@ -51,5 +51,8 @@ const char *chain_host(const uint32_t *words, const uint32_t *offsets, const uin
 // indel-aware motif tract per read: the wraparound alignment of include/trew_hip.h, cell by cell; the checks of tracts_host
 const char *align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                        int n_motifs, int penalty, trew_hip_alignment *out);
+// de novo repeats under indels: seed, wraparound alignment, re-vote (include/trew_hip.h); the checks of periods_host
+const char *refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                        int penalty, uint32_t min_score, trew_hip_refined *out);
 
 }  // namespace trew
