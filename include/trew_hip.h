@@ -34,8 +34,9 @@ extern "C" {
  * (trew_hip_variants, trew_hip_variants_results, trew_variants_host), the period entry points (trew_hip_periods,
  * trew_hip_periods_results, trew_periods_host), the satellite entry points (trew_hip_satellites,
  * trew_hip_satellites_results, trew_satellites_host), the alignment entry points (trew_hip_align, trew_hip_align_results,
- * trew_align_host) and the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host): they are purely additive -- no existing structure, enumerator or function
- * changed. */
+ * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host) and the tandem
+ * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host): they are purely additive -- no existing
+ * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
 /* scan modes: which per-read driver of the reference is reproduced */
@@ -651,6 +652,54 @@ int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_refined *out, 
 /* The same records on the host, step by step from the definition, over packed planes. */
 int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                      int penalty, uint32_t min_score, trew_hip_refined *out);
+
+/* ---- de novo repeats under indels, every tract of a read: trew_hip_repeats' recursion with trew_hip_refine per piece ----
+ * (a noisy long read with 900 bases of (AATGG)n beside 600 bases of (TTAGGG)n: both tracts whole, each with its unit)
+ * Integer-exact (tests/tandem_ref.py is the reference).  The parameters, checks and error texts are those of
+ * trew_hip_refine.  A PIECE is a half-open base range [lo, hi) of a read.  Its REFINED RECORD is the trew_hip_refined record
+ * (all six steps) of the bases lo .. hi - 1 taken as a read of their own -- nothing outside the piece is seen, valid or not --
+ * with start and end shifted back into read coordinates.  Its PERIODS TRACT is [R.start, R.end) of step 1 of that same
+ * computation, shifted likewise.
+ *   tandems(piece)  1. if step 1 gives no periods record, the piece yields nothing;
+ *                   2. if the refined record X has score >= min_score, the piece yields X, then tandems([lo, X.start)) and
+ *                      tandems([X.end, hi));
+ *                   3. otherwise (a WEAK piece) it yields no record, then tandems([lo, R.start)) and tandems([R.end, hi)):
+ *                      step 1 promised a repeat that no single unit aligns to with min_score (a drifting unit:
+ *                      "AAAC" x 5 + "AAAG" x 5 + "AACG" x 5 has a periods score of 48 and a refined score of 23 at the
+ *                      defaults); it is used up, and the recursion shrinks.
+ * The tracts of a read are tandems([0, n)).  depth is 0 for the read's own piece and parent + 1 below it; a weak piece has a
+ * depth but no record.  The other fields are those of trew_hip_refined.  Consequences: the depth-0 record of a read equals its
+ * trew_hip_refine record field for field whenever that record's score reaches min_score; a read without a periods record has
+ * no tract; the tracts of a read are disjoint and every one scores >= min_score; a read's records do not depend on the rest of
+ * the batch; a piece with hi - lo - min_period < min_score cannot have a periods record and need not be walked; on perfect
+ * repeats with flanks the (period, unit) pairs are those of trew_hip_repeats, and start, end and score those of
+ * trew_hip_align against that unit.  NOT a consequence, unlike trew_hip_repeats: "none scores above the first" -- alignment
+ * scores are not ordered by the periods score that picks the tract first.
+ * Limits: periods <= 32; linear gap cost; a wrong scored_period is not repaired; a weak piece is dropped, with whatever
+ * shorter tract a unit of its own would have aligned to inside it; the cost is that of trew_hip_refine per piece.  Also
+ * additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t read, depth;
+    uint32_t period, seed_period, scored_period, changed;
+    uint32_t score, start, end, consumed, matches;
+    uint32_t seed_score, support, reserved;
+    uint64_t unit, seed_unit;
+} trew_hip_tandem; /* 72 bytes: read, depth, the sixteen words of trew_hip_refined */
+/* Like trew_hip_repeats in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, no motifs, the log of max_records records >= 1 with its counter, one count per read, at
+ * most 2^32 - 1 reads a batch), with buffers of its own and independent of the scan and of the other ten kernels.  One kernel,
+ * a wave per read, for every read length; the recursion runs inside the wave. */
+int trew_hip_tandems(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                     uint64_t max_records);
+/* The contract of trew_hip_repeats_results: *n is exact also beyond max_records or cap (n must not be NULL), counts (n_reads
+ * values; may be NULL) is always exact, min(cap, *n) records sorted by (read, start) when *n <= max_records; when *n >
+ * max_records the log holds an unspecified subset, nothing is copied and the call returns 0: repeat trew_hip_tandems with
+ * max_records >= *n -- one retry always suffices. */
+int trew_hip_tandems_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel);
+/* The same on the host, piece by piece from the definition, over packed planes: *n = tracts found, min(cap, *n) records (the
+ * first ones of the sorted order), counts as above (may be NULL). */
+int trew_tandems_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                      int penalty, uint32_t min_score, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -33,6 +33,7 @@ from .capi import (  # noqa: F401
     refine,
     repeats,
     satellites,
+    tandems,
     tracts,
     variants,
 )

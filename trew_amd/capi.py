@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_satellites", "trew_hip_satellites_results", "trew_satellites_host",
     "trew_hip_align", "trew_hip_align_results", "trew_align_host",
     "trew_hip_refine", "trew_hip_refine_results", "trew_refine_host",
+    "trew_hip_tandems", "trew_hip_tandems_results", "trew_tandems_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -184,6 +185,14 @@ class Refined(C.Structure):
 REFINE_DTYPE = np.dtype([(name, "<u8" if name in ("unit", "seed_unit") else "<u4") for name, _ in Refined._fields_])
 assert REFINE_DTYPE.itemsize == C.sizeof(Refined) == 64
 
+
+class Tandem(C.Structure):
+    _fields_ = [("read", C.c_uint32), ("depth", C.c_uint32)] + list(Refined._fields_)
+
+
+TANDEM_DTYPE = np.dtype([(name, "<u8" if name in ("unit", "seed_unit") else "<u4") for name, _ in Tandem._fields_])
+assert TANDEM_DTYPE.itemsize == C.sizeof(Tandem) == 72
+
 ROW_DTYPE = np.dtype([("k", "<i4"), ("table", "<i4"), ("word_lo", "<u8"), ("word_hi", "<u8"), ("count", "<u8")])
 assert ROW_DTYPE.itemsize == C.sizeof(Row)
 
@@ -271,6 +280,9 @@ def load():
     lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
     lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
+    lib.trew_hip_tandems.argtypes = lib.trew_hip_repeats.argtypes
+    lib.trew_hip_tandems_results.argtypes = lib.trew_hip_repeats_results.argtypes
+    lib.trew_tandems_host.argtypes = lib.trew_repeats_host.argtypes
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -524,6 +536,29 @@ def refine_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sco
     return out
 
 
+def tandems_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
+    """trew_tandems_host: every de novo repeat tract of every read under indels computed on the host, piece by piece from the
+    definition (the refined record of a piece, then what lies in front of its tract and behind it).  reads_or_packed as for
+    annotate_host.  Returns (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,), found); with `cap` at most
+    that many records."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    counts = np.zeros(len(offsets), dtype=np.uint32)
+    n = C.c_uint64(0)
+
+    def call(out):
+        if lib.trew_tandems_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                                 int(penalty), int(min_score), out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
+            raise TrewHipError("trew_tandems_host failed: %s" % lib.trew_hip_last_error(None).decode())
+
+    out = np.zeros(0 if cap is None else int(cap), dtype=TANDEM_DTYPE)
+    call(out)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=TANDEM_DTYPE)
+        call(out)
+    return out[:min(len(out), int(n.value))], counts, int(n.value)
+
+
 def refine_columns(record, penalty):
     """What follows exactly from a REFINE_DTYPE record (or an array of them) and the penalty: a dict of copies, mismatches,
     insertions and deletions, as align_columns with k = period (all zero for a zero record)."""
@@ -533,6 +568,11 @@ def refine_columns(record, penalty):
     insertions = errors - (consumed - matches)
     return {"copies": consumed // np.maximum(period, 1), "mismatches": end - start - matches - insertions, "insertions": insertions,
             "deletions": errors - (end - start - matches)}
+
+
+def tandem_columns(record, penalty):
+    """refine_columns for a TANDEM_DTYPE record (or an array of them): copies, mismatches, insertions and deletions."""
+    return refine_columns(record, penalty)
 
 
 def satellites_host(reads_or_packed, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, cap=None):
@@ -896,6 +936,31 @@ class TrewHip:
             self._chk(self.lib.trew_hip_repeats_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_repeats_results")
         return (out, counts, found, ms.value) if want_ms else (out, counts, found)
 
+    def tandems(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
+        """Queue every de novo repeat tract under indels of every read of `batch` on the slot's stream (no motifs).
+        max_records: the capacity of the log for this call (default: the batch's read count, at least 1)."""
+        if max_records is None:
+            max_records = max(int(batch.n_reads), 1)
+        self._queue("tandems", slot, batch, None, 1, shape=(int(max_records),))
+        self._chk(self.lib.trew_hip_tandems(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
+                                            int(max_records)), "trew_hip_tandems")
+
+    def tandems_results(self, slot=0, want_ms=False):
+        """Results of the slot's last tandems: (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,), found
+        [, kernel ms]).  found > max_records: no records, counts and found are exact; repeat the call with max_records >=
+        found."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, _, cap = self._queued.get(("tandems", slot), (0, 1, 0))
+        counts = np.zeros(n_reads, dtype=np.uint32)
+        self._chk(self.lib.trew_hip_tandems_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
+                  "trew_hip_tandems_results")
+        found = int(n.value)
+        out = np.zeros(found if found <= cap else 0, dtype=TANDEM_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_tandems_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_tandems_results")
+        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+
     def satellites(self, batch, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract with a period of up to 256 of every read of `batch` on the slot's stream (no
         motifs).  max_records: the capacity of the log for this call (default: the batch's read count, at least 1)."""
@@ -1208,6 +1273,26 @@ def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=
         if found > cap:
             t.repeats(b, min_period, max_period, penalty, min_score, found)
             out, counts, found = t.repeats_results()
+        return out, counts
+
+
+def tandems(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):
+    """Every de novo repeat tract under indels on the GPU: for every read (bytes / str) what `refine` gives it (depth 0) and, in
+    the same way, what it gives the bases in front of that tract and behind it, each piece a read of its own, until nothing
+    repeats; a piece whose refined score stays below min_score gives no record and is searched around its `periods` tract.
+    Returns (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,)); tandem_columns gives the copies,
+    mismatches, insertions and deletions.  The first call's log holds max_records records (default: one per read); when more
+    are found the call is repeated once with the exact number."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        b = t.host_batch(words, offsets, lengths)
+        cap = max(len(offsets), 1) if max_records is None else int(max_records)
+        t.tandems(b, min_period, max_period, penalty, min_score, cap)
+        out, counts, found = t.tandems_results()
+        if found > cap:
+            t.tandems(b, min_period, max_period, penalty, min_score, found)
+            out, counts, found = t.tandems_results()
         return out, counts
 
 

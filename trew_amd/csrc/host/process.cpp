@@ -1176,11 +1176,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1201,6 +1201,7 @@ struct Annotator {
         std::vector<trew_hip_satellite> srecs;  // trew satellites
         std::vector<trew_hip_alignment> arecs;  // trew align
         std::vector<trew_hip_refined> frecs;    // trew refine
+        std::vector<trew_hip_tandem> tdrecs;    // trew tandems
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1580,6 +1581,39 @@ static void fold_refine(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew tandems: fold_repeats with the refined record; every record is a row (the kernel stores only those that reach MIN_SCORE).
+// tandem_units counts per (period, strand-canonical unit) the reads that have such a tract, the tracts, their bases and copies.
+static void fold_tandems(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    uint64_t cap = x.n, found = 0;
+    for (int attempt = 0;; attempt++) {
+        if (trew_hip_tandems(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, cap)) hip_die(x.c, "trew_hip_tandems");
+        if (w->tdrecs.size() < cap) w->tdrecs.resize(cap);
+        if (trew_hip_tandems_results(x.c, w->slot, w->tdrecs.data(), cap, &found, nullptr, nullptr)) hip_die(x.c, "trew_hip_tandems_results");
+        if (found <= cap) break;
+        if (attempt) die("internal error: the tandem log overflowed twice");
+        cap = found;  // the exact number: one retry always suffices
+        p.interval_retries++;
+    }
+    // the records are sorted by (read, start): a read's tracts are consecutive
+    std::vector<std::pair<uint32_t, uint64_t>> seen;  // the keys of the read at hand
+    for (uint64_t i = 0; i < found; i++) {
+        const trew_hip_tandem &rec = w->tdrecs[i];
+        if (i == 0 || w->tdrecs[i - 1].read != rec.read) seen.clear();
+        const std::pair<uint32_t, uint64_t> key{rec.period, canonical_unit(rec.unit, (int) rec.period)};
+        TandemUnit &u = p.tandem_units[key];
+        if (std::find(seen.begin(), seen.end(), key) == seen.end()) {
+            seen.push_back(key);
+            u.reads++;
+        }
+        u.tracts++;
+        u.bases += rec.end - rec.start;
+        u.copies += rec.consumed / rec.period;
+        p.trows.push_back(TandemRow{x.first_read + rec.read, x.lengths[rec.read], rec});
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1619,6 +1653,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Satellites: fold_satellites(x, p); break;
             case Measure::Align: fold_align(x, p); break;
             case Measure::Refine: fold_refine(x, p); break;
+            case Measure::Tandems: fold_tandems(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1661,6 +1696,13 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         u.bases += kv.second.bases;
         u.copies += kv.second.copies;
     }
+    for (const auto &kv : from.tandem_units) {
+        TandemUnit &u = into.tandem_units[kv.first];
+        u.reads += kv.second.reads;
+        u.tracts += kv.second.tracts;
+        u.bases += kv.second.bases;
+        u.copies += kv.second.copies;
+    }
     for (const auto &kv : from.period_units) {
         auto &u = into.period_units[kv.first];
         u.first += kv.second.first;
@@ -1680,7 +1722,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -1719,6 +1761,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         out.srows.insert(out.srows.end(), w.part.srows.begin(), w.part.srows.end());
         out.arows.insert(out.arows.end(), w.part.arows.begin(), w.part.arows.end());
         out.frows.insert(out.frows.end(), w.part.frows.begin(), w.part.frows.end());
+        out.trows.insert(out.trows.end(), w.part.trows.begin(), w.part.trows.end());
     }
     std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
         if (x.read != y.read) return x.read < y.read;
@@ -1741,6 +1784,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         return x.motif != y.motif ? x.motif < y.motif : x.strand < y.strand;
     });
     std::sort(out.frows.begin(), out.frows.end(), [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
+    std::sort(out.trows.begin(), out.trows.end(),
+              [](const TandemRow &x, const TandemRow &y) { return x.read != y.read ? x.read < y.read : x.td.start < y.td.start; });
     std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1753,6 +1798,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
                                   (unsigned long long) out.crows.size(), (unsigned long long) out.interval_retries);
         if (rq.kind == Measure::Repeats) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.rrows.size(), (unsigned long long) out.interval_retries);
+        if (rq.kind == Measure::Tandems) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
+                                  (unsigned long long) out.trows.size(), (unsigned long long) out.interval_retries);
         if (rq.kind == Measure::Satellites) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.srows.size(), (unsigned long long) out.interval_retries);
     }

@@ -45,15 +45,15 @@ __device__ __forceinline__ void refine_pack(u32 u, u32 d, u32 &lo, u32 &hi) {
     hi = wave_sum_u32((u32) (term >> 32));
 }
 
-// the start of the longest run of set bits of eq_k among the positions [b, e), the first of the longest; b without one
-__device__ __forceinline__ u32 refine_longest_run(const ReadRef &rd, u32 k, u32 b, u32 e) {
+// the start of the longest run of set bits of the piece's eq_k among the positions [b, e), the first of the longest; b without one
+__device__ __forceinline__ u32 refine_longest_run(const ReadRef &rd, Piece pc, u32 k, u32 b, u32 e) {
     const u32 lane = lane_id();
     u32 best_len = 0, best_start = b, carry = 0;  // carry: the run that ends at the end of the iteration in front
     for (u32 t0 = b >> 5; ((u64) t0 << 5) < (u64) e; t0 += 64u) {
         const u32 w = t0 + lane;
         const u64 p0 = (u64) w << 5;
         u32 vm;
-        u32 eq = period_eq_word(rd, Piece{0u, rd.len}, k, w, vm);
+        u32 eq = period_eq_word(rd, pc, k, w, vm);
         const u32 first = p0 >= (u64) b ? 0u : (u64) b - p0 >= 32u ? 32u : b - (u32) p0;   // bits in front of b
         const u32 last = p0 >= (u64) e ? 0u : (u64) e - p0 >= 32u ? 32u : e - (u32) p0;    // one past the last bit in front of e
         eq &= (last >= 32u ? 0xffffffffu : (1u << last) - 1u) & (first >= 32u ? 0u : 0xffffffffu << first);
@@ -160,10 +160,111 @@ __device__ __forceinline__ void refine_pass(const ReadRef &rd, u32 lo_pos, u32 h
     }
 }
 
+// The refined record of one piece (DESIGN 4.7f, all six steps, over the bases [pc.lo, pc.hi) taken as a read of their own; nothing
+// outside the piece is seen): rec[0 .. 15] = the sixteen words of trew_hip_refined, start and end in read coordinates.  False
+// without a periods record (step 1), rec all zero; otherwise r_start and r_end hold the periods tract of step 1, in read
+// coordinates as well (kernels/tandems.inc splits a weak piece there).  Wave-uniform.  h: the wave's bins.
+__device__ __forceinline__ bool refine_piece(const ReadRef &rd, Piece pc, u32 kmin, u32 kmax, int P, u32 min_score, u32 *h, u32 (&rec)[16], u32 &r_start,
+                                             u32 &r_end) {
+    const u32 lane = lane_id();
+    const u32 j = lane & 31u;
+    // 1. periods: the scored k and its segment
+    u32 score = 0, k = 0;
+    for (u32 kk = kmin; kk <= kmax && kk < pc.hi - pc.lo; kk++) {
+        const u32 sc = period_score(rd, pc, kk, P);
+        if (sc > score) {  // strictly: the smallest k keeps a tie
+            score = sc;
+            k = kk;
+        }
+    }
+    if (k == 0u || score < min_score) {  // wave-uniform: a zero record
+#pragma unroll
+        for (int i = 0; i < 16; i++) rec[i] = 0;
+        return false;
+    }
+    u32 b, e;
+    period_locate(rd, pc, k, P, score, b, e);
+    const u32 start = b, end = e + k;
+    r_start = start;
+    r_end = end;
+    u32 cons, cons_cnt;
+    period_consensus(rd, k, start, end, h, cons, cons_cnt);
+    // 2. seed: the k bases at the longest run, an N replaced by its phase of the consensus
+    const u32 rs = refine_longest_run(rd, pc, k, b, e);
+    u32 s0 = 8;
+    {
+        const u32 pos = rs + j;  // < end for j < k
+        const u32 ph = (pos - start) % k;
+        const u32 cu = lane_read(cons, ph << 2);
+        if (j < k && pos < pc.hi) {
+            const u32 w = pos >> 5, bit = pos & 31u;
+            const u32 c0 = rd.w[3ull * w + 0], c1 = rd.w[3ull * w + 1], c2 = rd.w[3ull * w + 2];
+            s0 = (c2 >> bit) & 1u ? cu : ((c0 >> bit) & 1u) | (((c1 >> bit) & 1u) << 1);
+        }
+    }
+    const u32 ks = refine_root(s0, k);
+    const u32 S = j < ks ? lane_read(s0, j << 2) : 8u;  // both halves alike
+    u32 cnt[4] = {0, 0, 0, 0};
+    // 3. align against the seed
+    AlignCell a1;
+    u32 a1_end;
+    refine_pass<false>(rd, pc.lo, pc.hi, S, ks, P, a1, a1_end, cnt);
+    const u32 a1_start = rfl(a1.start);  // the best cell is in every lane; 0 and 0 without one
+    a1_end = rfl(a1_end);
+    // 4. vote over the tract alone
+    {
+        AlignCell av;
+        u32 av_end;
+        refine_pass<true>(rd, pc.lo + a1_start, pc.lo + a1_end, S, ks, P, av, av_end, cnt);
+    }
+    // 5. re-vote: the seed's base where its count is the largest, else the smallest code among the largest
+    u32 top = 0;
+#pragma unroll
+    for (u32 x = 1; x < 4u; x++) top = cnt[x] > cnt[top] ? x : top;  // strictly
+    u32 cs = 0;
+#pragma unroll
+    for (u32 x = 0; x < 4u; x++) cs = (S & 3u) == x ? cnt[x] : cs;
+    const bool lane_k = lane < ks;  // one half counts
+    const u32 U0 = j < ks ? (cs == cnt[top] ? S : top) : 8u;
+    u32 changed = (u32) __popcll(__ballot(lane_k && U0 != S));
+    const u32 support = wave_sum_u32(lane_k ? (U0 == S ? cs : cnt[top]) : 0u);
+    u32 ku = ks;
+    u32 U = S;
+    AlignCell a2 = a1;
+    u32 a2_end = a1_end;
+    // 6. final: align against the re-voted unit; a lower score keeps the seed
+    if (changed) {  // wave-uniform
+        ku = refine_root(U0, ks);
+        U = j < ku ? U0 : 8u;
+        refine_pass<false>(rd, pc.lo, pc.hi, U, ku, P, a2, a2_end, cnt);
+        if (rfl(a2.score) < rfl(a1.score)) {
+            a2 = a1;
+            a2_end = a1_end;
+            U = S;
+            ku = ks;
+            changed = 0;
+        }
+    }
+    rec[0] = ku;
+    rec[1] = ks;
+    rec[2] = k;
+    rec[3] = changed;
+    rec[4] = a2.score;
+    rec[5] = pc.lo + a2.start;  // refine_pass counts from the piece's first base
+    rec[6] = pc.lo + a2_end;
+    rec[7] = a2.consumed;
+    rec[8] = a2.matches;
+    rec[9] = a1.score;
+    rec[10] = support;
+    rec[11] = 0;
+    refine_pack(U, ku, rec[12], rec[13]);
+    refine_pack(S, ks, rec[14], rec[15]);
+    return true;
+}
+
 __global__ void __launch_bounds__(256) refine_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, u32 *__restrict__ out) {
     __shared__ u32 bins[4][kPeriodBins];
     const u32 lane = lane_id();
-    const u32 j = lane & 31u;
     u32 *h = bins[threadIdx.x >> 6];
     h[lane] = 0;
     h[lane + 64u] = 0;
@@ -175,96 +276,8 @@ __global__ void __launch_bounds__(256) refine_wave_kernel(DevBatch B, int min_pe
     const u32 kmin = (u32) rfl_i(min_period), kmax = (u32) rfl_i(max_period);
     for (u64 r = wave; r < B.n_reads; r += n_waves) {
         const ReadRef rd = uni(get_read(B, r));
-        const Piece pc{0u, rd.len};
-        // 1. periods: the scored k and its segment
-        u32 score = 0, k = 0;
-        for (u32 kk = kmin; kk <= kmax && kk < rd.len; kk++) {
-            const u32 sc = period_score(rd, pc, kk, P);
-            if (sc > score) {  // strictly: the smallest k keeps a tie
-                score = sc;
-                k = kk;
-            }
-        }
-        if (k == 0u || score < min_score) {  // wave-uniform: a zero record
-            if (lane < 16) out[r * 16ull + lane] = 0;
-            continue;
-        }
-        u32 b, e;
-        period_locate(rd, pc, k, P, score, b, e);
-        const u32 start = b, end = e + k;
-        u32 cons, cons_cnt;
-        period_consensus(rd, k, start, end, h, cons, cons_cnt);
-        // 2. seed: the k bases at the longest run, an N replaced by its phase of the consensus
-        const u32 rs = refine_longest_run(rd, k, b, e);
-        u32 s0 = 8;
-        {
-            const u32 pos = rs + j;  // < end for j < k
-            const u32 ph = (pos - start) % k;
-            const u32 cu = lane_read(cons, ph << 2);
-            if (j < k && pos < rd.len) {
-                const u32 w = pos >> 5, bit = pos & 31u;
-                const u32 c0 = rd.w[3ull * w + 0], c1 = rd.w[3ull * w + 1], c2 = rd.w[3ull * w + 2];
-                s0 = (c2 >> bit) & 1u ? cu : ((c0 >> bit) & 1u) | (((c1 >> bit) & 1u) << 1);
-            }
-        }
-        const u32 ks = refine_root(s0, k);
-        const u32 S = j < ks ? lane_read(s0, j << 2) : 8u;  // both halves alike
-        u32 cnt[4] = {0, 0, 0, 0};
-        // 3. align against the seed
-        AlignCell a1;
-        u32 a1_end;
-        refine_pass<false>(rd, 0u, rd.len, S, ks, P, a1, a1_end, cnt);
-        const u32 a1_start = rfl(a1.start);  // the best cell is in every lane; 0 and 0 without one
-        a1_end = rfl(a1_end);
-        // 4. vote over the tract alone
-        {
-            AlignCell av;
-            u32 av_end;
-            refine_pass<true>(rd, a1_start, a1_end, S, ks, P, av, av_end, cnt);
-        }
-        // 5. re-vote: the seed's base where its count is the largest, else the smallest code among the largest
-        u32 top = 0;
-#pragma unroll
-        for (u32 x = 1; x < 4u; x++) top = cnt[x] > cnt[top] ? x : top;  // strictly
-        u32 cs = 0;
-#pragma unroll
-        for (u32 x = 0; x < 4u; x++) cs = (S & 3u) == x ? cnt[x] : cs;
-        const bool lane_k = lane < ks;  // one half counts
-        const u32 U0 = j < ks ? (cs == cnt[top] ? S : top) : 8u;
-        u32 changed = (u32) __popcll(__ballot(lane_k && U0 != S));
-        const u32 support = wave_sum_u32(lane_k ? (U0 == S ? cs : cnt[top]) : 0u);
-        u32 ku = ks;
-        u32 U = S;
-        AlignCell a2 = a1;
-        u32 a2_end = a1_end;
-        // 6. final: align against the re-voted unit; a lower score keeps the seed
-        if (changed) {  // wave-uniform
-            ku = refine_root(U0, ks);
-            U = j < ku ? U0 : 8u;
-            refine_pass<false>(rd, 0u, rd.len, U, ku, P, a2, a2_end, cnt);
-            if (rfl(a2.score) < rfl(a1.score)) {
-                a2 = a1;
-                a2_end = a1_end;
-                U = S;
-                ku = ks;
-                changed = 0;
-            }
-        }
-        u32 rec[16];
-        rec[0] = ku;
-        rec[1] = ks;
-        rec[2] = k;
-        rec[3] = changed;
-        rec[4] = a2.score;
-        rec[5] = a2.start;  // a largest score of 0 left zeros, as in trew_hip_alignment
-        rec[6] = a2_end;
-        rec[7] = a2.consumed;
-        rec[8] = a2.matches;
-        rec[9] = a1.score;
-        rec[10] = support;
-        rec[11] = 0;
-        refine_pack(U, ku, rec[12], rec[13]);
-        refine_pack(S, ks, rec[14], rec[15]);
+        u32 rec[16], r_start, r_end;  // the periods tract and the returned flag are for kernels/tandems.inc: not used here
+        refine_piece(rd, Piece{0u, rd.len}, kmin, kmax, P, min_score, h, rec, r_start, r_end);  // the whole read; all zero without a record
         // sixteen lanes write the record's sixteen words (trew_hip_refined): one vector store
         u32 x = rec[15];
 #pragma unroll

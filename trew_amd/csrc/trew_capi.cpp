@@ -25,24 +25,24 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems"};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
 };
 struct MeasureState {
-    DevBuf records;                         // the records of the last call, grown on demand (intervals, chain, repeats, satellites: the append log)
-    DevBuf counts;                          // intervals: one u32 per (read, motif, strand), chain: two; repeats, satellites: one per read; grown on demand
-    unsigned long long *counter = nullptr;  // intervals, chain, repeats, satellites: the records / events the kernel found, in the log or not
+    DevBuf records;                         // the records of the last call, grown on demand (intervals, chain, repeats, satellites, tandems: the append log)
+    DevBuf counts;                          // intervals: one u32 per (read, motif, strand), chain: two; repeats, satellites, tandems: one per read; grown on demand
+    unsigned long long *counter = nullptr;  // intervals, chain, repeats, satellites, tandems: the records / events the kernel found, in the log or not
     unsigned long long *hist = nullptr;     // variants: the batch histograms hist, then reads_with, kVarHistLen values each
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call
     u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods, refine: n_reads
-    u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites: their max_records
-    u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites: n_reads
+    u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites, tandems: their max_records
+    u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites, tandems: n_reads
     int n_motifs = 0;  // variants
     u32 k[kAnnotMaxMotifs] = {};  // chain: the motifs' lengths (pairing a run's events needs start mod k)
 };
@@ -1201,8 +1201,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine
-// The ten measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems
+// The eleven measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
@@ -1269,6 +1269,11 @@ extern "C" int trew_refine_host(const uint32_t *words, const uint32_t *offsets, 
     return host_status(refine_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out));
 }
 
+extern "C" int trew_tandems_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                 int max_period, int penalty, uint32_t min_score, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts) {
+    return host_status(tandems_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out, cap, n, counts));
+}
+
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
 static void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
     memset(d, 0, sizeof(*d));
@@ -1307,14 +1312,14 @@ static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs
 
 // What every queue call does before anything of its own: the argument checks in the order callers see them (`own` holds
 // the measure's own checks; it runs behind the motifs' check and in front of the first HIP call), the batch and the motifs onto the slot's stream, and the measure's two events on its first use.
-// The measures without motifs (periods, repeats, satellites, refine) are known by `which`, not by their arguments: for them there is no motif check
+// The measures without motifs (periods, repeats, satellites, refine, tandems) are known by `which`, not by their arguments: for them there is no motif check
 // and no pattern table, and they pass no motifs.  For the others, no motifs stays the argument error it always was.
 template <class Own>
 static int measure_begin(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
                          Own own, Slot **slot_out, DevBatch *db) {
     if (!ctx || !batch) return -1;
     if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    const bool motif_less = which == kPeriods || which == kRepeats || which == kSatellites || which == kRefine;
+    const bool motif_less = which == kPeriods || which == kRepeats || which == kSatellites || which == kRefine || which == kTandems;
     if (!motif_less)
         if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
     if (const char *e = own()) return fail(ctx, e);
@@ -1840,6 +1845,67 @@ extern "C" int trew_hip_satellites_results(trew_hip_ctx *ctx, int slot, trew_hip
             HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found * sizeof(trew_hip_satellite), hipMemcpyDeviceToHost));
             sort_satellites(all.data(), found);
             memcpy(out, all.data(), take * sizeof(trew_hip_satellite));
+        }
+    }
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- de novo repeats under indels: every tract of a read
+// trew_hip_repeats with the record and the kernel of its own; a MeasureState of its own.
+static_assert(sizeof(trew_hip_tandem) == 72, "18 words: what tandems_wave_kernel stores");
+extern "C" int trew_hip_tandems(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                                uint64_t max_records) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * {
+        if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+        return max_records < 1 ? "max_records must be at least 1" : nullptr;
+    };
+    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kTandems, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kTandems];
+    const u64 n_counts = db.n_reads;
+    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
+    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
+    if (int rc = grow(ctx, s, st.records, max_records * sizeof(trew_hip_tandem))) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.max_log = max_records;
+    st.n_counts = n_counts;
+    // the counter and the counts start every call at zero, also a call without reads (its results then report no tract)
+    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
+    if (n_counts == 0) return 0;
+    HIPCHK(ctx, hipMemsetAsync(st.counts.p, 0, n_counts * sizeof(u32), s.stream));
+    RepeatLog lg;
+    lg.counter = st.counter;
+    lg.recs = (u32 *) st.records.p;
+    lg.cap = max_records;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_tandems(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, (u32 *) st.counts.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_tandems_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel) {
+    const char *arg_error = !n ? "trew_hip_tandems_results: n must not be null" : cap && !out ? "trew_hip_tandems_results: out must not be null" : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kTandems, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kTandems];
+    unsigned long long found = 0;
+    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
+    *n = found;
+    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
+    const u64 take = std::min<u64>(found, cap);
+    if (found <= st.max_log && take) {  // an overflowed log holds an unspecified subset: nothing is copied
+        // sorted on the host, so the records do not depend on the order in which the waves appended them
+        if (take == found) {
+            HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(trew_hip_tandem), hipMemcpyDeviceToHost));
+            sort_tandems(out, take);
+        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
+            std::vector<trew_hip_tandem> all((size_t) found);
+            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found * sizeof(trew_hip_tandem), hipMemcpyDeviceToHost));
+            sort_tandems(all.data(), found);
+            memcpy(out, all.data(), take * sizeof(trew_hip_tandem));
         }
     }
     return fetch_end(ctx, st, ms_kernel);

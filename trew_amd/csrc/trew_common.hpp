@@ -163,7 +163,8 @@ struct ChainLog {
 };
 
 // trew_hip_repeats' append log (kernels/repeats.inc): records of twelve u32 (trew_hip_repeat); trew_hip_satellites' as well
-// (kernels/satellites.inc): records of 26 u32 (trew_hip_satellite)
+// (kernels/satellites.inc): records of 26 u32 (trew_hip_satellite); trew_hip_tandems' too (kernels/tandems.inc): records of 18
+// u32 (trew_hip_tandem)
 struct RepeatLog {
     unsigned long long *counter;  // tracts found; keeps counting past cap
     u32 *recs;                    // cap records

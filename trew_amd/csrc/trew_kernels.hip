@@ -46,6 +46,7 @@
 //   satellites.inc     satellites_wave_kernel (de novo repeats with periods up to 256: the wide eq word, 1024 consensus bins and a 16-word unit; shares periods.inc's and repeats.inc's functions)
 //   align.inc          align_wave_kernel (indel-aware motif tract per read: wraparound alignment, the row of the table in registers, a phase per lane)
 //   refine.inc         refine_wave_kernel (de novo repeats under indels: periods.inc's period and tract, a seed unit from the longest run of eq_k, align.inc's row step for the alignment, the vote and the re-voted unit)
+//   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: repeats.inc's recursion over pieces with refine.inc's refine_piece per piece)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -86,6 +87,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/satellites.inc"
 #include "kernels/align.inc"
 #include "kernels/refine.inc"
+#include "kernels/tandems.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -410,6 +412,15 @@ hipError_t launch_refine(hipStream_t st, u32 n_cu, const DevBatch &B, int min_pe
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(refine_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, (u32 *) d_out);
+    return hipGetLastError();
+}
+
+// De novo repeats under indels, every tract: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &lg,
+                          u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(tandems_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
     return hipGetLastError();
 }
 

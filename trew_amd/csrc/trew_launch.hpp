@@ -57,6 +57,10 @@ hipError_t launch_satellites(hipStream_t st, u32 n_cu, const DevBatch &B, int mi
 hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_alignment *d_out);
 // trew_hip_refine: the wave-per-read kernel of kernels/refine.inc on the grid of launch_tracts; no motifs
 hipError_t launch_refine(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined *d_out);
+// trew_hip_tandems: the wave-per-read kernel of kernels/tandems.inc on the grid of launch_tracts; no motifs; `lg` holds records
+// of 18 u32, its counter is zero when the kernel starts (the caller's memset on the same stream)
+hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &lg,
+                          u32 *d_counts);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);

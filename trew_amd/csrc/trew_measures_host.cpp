@@ -735,11 +735,12 @@ static u64 pack_unit(const u32 *u, u32 k) {
     return w;
 }
 
-// the record of one read, step by step from the definition (trew_hip_refined, include/trew_hip.h)
-static void refine_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined &o) {
+// the record of one read, step by step from the definition (trew_hip_refined, include/trew_hip.h); R: the periods record of step 1
+// (scored_period 0 without one), for trew_hip_tandems' weak pieces
+static void refine_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined &o,
+                             trew_hip_period &R) {
     memset(&o, 0, sizeof(o));
     // 1. periods: the record and the unreduced consensus
-    trew_hip_period R;
     memset(&R, 0, sizeof(R));
     u32 cons[32];
     if (!piece_record<32>(base, 0, n, min_period, max_period, penalty, min_score, R, cons)) return;
@@ -802,8 +803,59 @@ const char *refine_host(const u32 *words, const u32 *offsets, const u32 *lengths
     std::vector<unsigned char> base;
     for (u64 r = 0; r < n_reads; r++) {
         unpack_bases(words + offsets[r], lengths[r], base);
-        refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, out[r]);
+        trew_hip_period R;
+        refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, out[r], R);
     }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- de novo repeats under indels: every tract of a read
+void sort_tandems(trew_hip_tandem *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_tandem &a, const trew_hip_tandem &b) { return a.read != b.read ? a.read < b.read : a.start < b.start; });
+}
+
+const char *tandems_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, trew_hip_tandem *out, u64 cap, u64 *n, u32 *counts) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    if (!n) return "trew_tandems_host: n must not be null";
+    if (cap && !out) return "trew_tandems_host: out must not be null";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_tandems_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_tandems_host: a batch holds at most 2^32 - 1 reads";
+    struct Todo {
+        u32 lo, hi, depth;
+    };
+    std::vector<unsigned char> base;
+    std::vector<Todo> todo;
+    std::vector<trew_hip_tandem> mine;  // the tracts of one read
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        mine.clear();
+        todo.assign(1, Todo{0, lengths[r], 0});
+        while (!todo.empty()) {  // the definition piece by piece, as in repeats_host: no piece is pruned
+            const Todo t = todo.back();
+            todo.pop_back();
+            trew_hip_refined x;
+            trew_hip_period R;
+            refine_read_host(base.data() + t.lo, t.hi - t.lo, min_period, max_period, penalty, min_score, x, R);  // the piece as a read of its own
+            if (R.scored_period == 0) continue;
+            u32 start = t.lo + R.start, end = t.lo + R.end;  // a weak piece: around the periods tract
+            if (x.score >= min_score) {
+                start = t.lo + x.start, end = t.lo + x.end;
+                mine.push_back(trew_hip_tandem{(u32) r, t.depth, x.period, x.seed_period, x.scored_period, x.changed, x.score, start, end, x.consumed,
+                                               x.matches, x.seed_score, x.support, 0, x.unit, x.seed_unit});
+            }
+            todo.push_back(Todo{end, t.hi, t.depth + 1});
+            todo.push_back(Todo{t.lo, start, t.depth + 1});
+        }
+        sort_tandems(mine.data(), mine.size());  // disjoint, so by start
+        for (const trew_hip_tandem &x : mine) {
+            if (found < cap) out[found] = x;
+            found++;
+        }
+        if (counts) counts[r] = (u32) mine.size();
+    }
+    *n = found;
     return nullptr;
 }
 
