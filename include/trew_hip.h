@@ -84,6 +84,9 @@ enum {
                                 of deciding four segments in lock step, 16 lanes each (decide_group); results are identical */
     TREW_FLAG_DEBUG_ANNOT_GENERAL = 8192, /* tests: trew_hip_annotate gives every batch a wave per read, also where its reads are
                                 short enough for the lane-per-read kernel; results are identical */
+    TREW_FLAG_DEBUG_SMALL_BOUNDS = 16384, /* tests: the buffer in which the bounds pass hands the packed bounds of the flagged short reads
+                                to the exact kernel holds 64 worklist entries instead of a share of max_batch_reads, so that a small
+                                batch has reads on either side of it (stored bounds / bounds in row layout); results are identical */
     TREW_FLAG_TRACK_PRESSURE = 256 /* every batch ends with a copy of the table's fill counters into pinned host memory, and
                                 trew_hip_table_pressure answers from those copies (and from what collect / add_rows /
                                 reset read since) instead of asking the device: for hosts that ask before every batch.
@@ -273,7 +276,8 @@ int trew_hip_filter_masks(trew_hip_ctx *ctx, const trew_hip_batch *batch, uint64
 
 /* Mean kernel timings of the submits on `slot` since the previous call (HIP events on the
  * slot's own stream, at most the last 128 submits), milliseconds; n_flagged (optional) = reads
- * the prefilter passed to the exact kernel in the last submit. */
+ * the prefilter passed to the exact kernel in the last submit.  ms_exact covers everything queued
+ * behind the prefilter: the bounds pass over the worklist, where a batch takes one, and the exact kernel. */
 int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filter, float *ms_exact, uint64_t *n_flagged);
 
 /* ---- per-read annotation against given motifs (no counterpart in the reference, which only sums over reads) ----

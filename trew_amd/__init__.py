@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     FLAG_DEBUG_NO_GROUP,
     FLAG_DEBUG_NO_JOINT,
     FLAG_DEBUG_NO_UNI_DRAIN,
+    FLAG_DEBUG_SMALL_BOUNDS,
     FLAG_DEBUG_WIDE_NO_WAIT,
     MODE_LONG,
     MODE_PAIR,

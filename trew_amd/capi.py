@@ -24,6 +24,7 @@ FLAG_DEBUG_NO_JOINT = 2048  # tests: the prefilter's uniform path without the jo
 FLAG_DEBUG_NO_UNI_DRAIN = 4096  # tests / A-B: the prefilter's set-aside reads judged by the general path (not filter_deferred_uni)
 FLAG_DEBUG_NO_GROUP = 1024  # tests / A-B: every segment decided by a wave of its own (no decide_group)
 FLAG_DEBUG_ANNOT_GENERAL = 8192  # tests: annotate gives every batch a wave per read (the lane-per-read kernel is never picked)
+FLAG_DEBUG_SMALL_BOUNDS = 16384  # tests: the bounds pass hands over 64 worklist entries only (stored bounds and row bounds in one small batch)
 FLAG_DEBUG_WIDE_NO_WAIT = 128  # tests: the wide table never waits for a slot's ready bit (forces its time-out path)
 TABLE_NAMES = ("forward_high", "forward_low", "backward_high", "backward_low", "both_high", "both_low")
 

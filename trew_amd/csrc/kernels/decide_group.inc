@@ -592,12 +592,57 @@ __device__ __forceinline__ WT strand_flip(WT w, int k) {
 // more than 16 runs -- goes through decide_halves / run_short_routed / target as before.
 // rdA / rdB: reads whose triples are staged in LDS, both with valid halves (n >= 4 MIN_MER); haveB = false: rdA alone (rows 2
 // and 3 idle).  Only instantiated where the k range fits 32 indices.
-template <int NW, typename WT>
-__device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, const ReadRef rdA, const ReadRef rdB, bool haveB) {
+// SB: the worklist positions of the two reads, by which the packed bounds the bounds pass (bounds_pass.inc) left for them are
+// found -- StoredBounds (positions at or beyond the buffer's capacity have none), or NoStoredBounds in the instantiations that
+// never have any.  Where both reads have stored bounds, lane (row g, j) loads word j and word 16 + j of its half and the row needs
+// no parities; otherwise the rows bound their k themselves (row_prepare, bound_at_k).
+constexpr u32 kBoundWords = 32;                   // packed words per half, index k - MIN_MER: every k of a run the group pass takes
+constexpr u32 kBoundItemWords = 2 * kBoundWords;  // per worklist entry: left half, right half
+struct NoStoredBounds {
+    static constexpr bool kAny = false;
+};
+struct StoredBounds {
+    static constexpr bool kAny = true;
+    u32 posA, posB;  // worklist positions of rdA and rdB (wave-uniform)
+};
+// The argument list of exact_kernel as the kernarg ABI lays it out (natural alignment, in order).  The kernel hands a pointer into
+// the segment down as its table descriptor (TableRef), and run_short_group reads the last two arguments from it where it wants
+// them: scalar loads, cached, instead of SGPRs held across every pass (see fetch_words in exact_kernel.inc).
+struct ExactKernArgs {
+    DevParams P;
+    DevBatch B;
+    DevTableG1 TG;
+    const u32 *wl;
+    u32 *wl_count, *wl_count_next;
+    u32 wl_cap;
+    SegResults R;
+    u32 cap, rawwords;
+    const u32 *bnd;  // the packed bounds of the first bnd_cap worklist entries (bounds_pass.inc), bnd_cap = 0: none
+    u32 bnd_cap;
+};
+template <int NW, typename WT, typename SB>
+__device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, const ReadRef rdA, const ReadRef rdB, bool haveB, const SB sb) {
     const u32 lane = lane_id();
 #if defined(TREW_AB_SKIP) && TREW_AB_SKIP >= 5  // A/B builds (instruction attribution, profiles/r04): 5 = chunk fetch only
     return;
 #endif
+    // the stored bounds start travelling before the bases are staged: they are wanted behind that
+    u32 st0 = 0, st1 = 0;
+    bool stored = false;
+    if constexpr (SB::kAny) {
+        typedef const __attribute__((address_space(4))) u64 *c64;
+        typedef const __attribute__((address_space(4))) u32 *c32;
+        const u64 ka = (u64) __builtin_amdgcn_kernarg_segment_ptr();
+        const u32 bcap = *(c32) (ka + offsetof(ExactKernArgs, bnd_cap));
+        const u32 posA = rfl(sb.posA), posB = rfl(sb.posB);  // (wave-uniform, see rfl_i)
+        stored = posA < bcap && posB < bcap;  // both reads of the pass have stored bounds
+        if (stored && (lane < 32u || haveB)) {
+            const u32 *const base = (const u32 *) *(c64) (ka + offsetof(ExactKernArgs, bnd));
+            const u32 *src = base + ((u64) (lane < 32u ? posA : posB) * 2u + ((lane >> 4) & 1u)) * kBoundWords + (lane & 15u);
+            st0 = src[0];
+            st1 = src[16];
+        }
+    }
     TREW_MARK(stage);
     PH_T0(t_stage);
     stage_two(sm, rdA, rdB, haveB);
@@ -617,17 +662,35 @@ __device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, co
     const bool rowvalid = sg.valid && (!second || haveB);
     TREW_MARK(bounds);
     PH_T0(t_bounds);
-    lds_sync();
-    row_prepare<NW>(sm, rd, sg, rowvalid);
-    lds_sync();
     RowSeg<NW> rs;
-    row_load<NW>(sm, (int) sg.len, rs);
-    u32 bnd0;
-    if (P.min_mer + 15 < 32)  // wave-uniform
-        bnd0 = rowvalid ? bound_at_k<NW, true>(rs, (int) sg.len, P.min_mer + (int) j, P.max_mer, P) : 0u;
-    else
-        bnd0 = rowvalid ? bound_at_k<NW, false>(rs, (int) sg.len, P.min_mer + (int) j, P.max_mer, P) : 0u;
-    const u32 bnd1 = rowvalid ? bound_at_k<NW>(rs, (int) sg.len, P.min_mer + 16 + (int) j, P.max_mer, P) : 0u;
+    u32 bnd0, bnd1;
+    if (stored) {  // wave-uniform
+        // what decide_group reads of the segment besides its bounds: the planes, the valid bases (eval_row, segments with an N) and has_n
+        u32 nm[NW];
+        ReadRef r = rd;
+        if (!rowvalid) r.nw = 0;
+        load_planes_lds<NW>(r, sg.start, rs.lo, rs.hi, nm);
+        u32 anyn = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            rs.v1[w] = ~nm[w] & low_mask((int) sg.len - 32 * w);
+            rs.P1[w] = rs.P2[w] = rs.P3[w] = 0;
+            anyn |= ~rs.v1[w] & low_mask((int) sg.len - 32 * w);
+        }
+        rs.has_n = anyn != 0u ? 1u : 0u;
+        bnd0 = rowvalid ? st0 : 0u;
+        bnd1 = rowvalid ? st1 : 0u;
+    } else {
+        lds_sync();
+        row_prepare<NW>(sm, rd, sg, rowvalid);
+        lds_sync();
+        row_load<NW>(sm, (int) sg.len, rs);
+        if (P.min_mer + 15 < 32)  // wave-uniform
+            bnd0 = rowvalid ? bound_at_k<NW, true>(rs, (int) sg.len, P.min_mer + (int) j, P.max_mer, P) : 0u;
+        else
+            bnd0 = rowvalid ? bound_at_k<NW, false>(rs, (int) sg.len, P.min_mer + (int) j, P.max_mer, P) : 0u;
+        bnd1 = rowvalid ? bound_at_k<NW>(rs, (int) sg.len, P.min_mer + 16 + (int) j, P.max_mer, P) : 0u;
+    }
 #if defined(TREW_AB_SKIP) && TREW_AB_SKIP >= 3  // 3 = + bounds (kept alive: results nobody reads are not computed)
     asm volatile("" ::"v"(bnd0), "v"(bnd1));
     return;

@@ -21,17 +21,16 @@ constexpr int exact_waves(bool narrow) {
 }
 template <int NW, int MODE, typename WT>
 __global__ __launch_bounds__(64, (exact_waves<NW, MODE>(sizeof(WT) == 8))) void exact_kernel(DevParams P, DevBatch B, DevTableG1 TG, const u32 *wl,
-                                                   u32 *wl_count, u32 *wl_count_next, u32 wl_cap, SegResults R, u32 cap, u32 rawwords) {
+                                                   u32 *wl_count, u32 *wl_count_next, u32 wl_cap, SegResults R, u32 cap, u32 rawwords,
+                                                   const u32 *bnd, u32 bnd_cap) {
+    // bnd / bnd_cap: the packed bounds the bounds pass left for the first bnd_cap worklist entries (kernels/bounds_pass.inc; 0: none --
+    // only the short-read kernel on 3-word masks is ever given any)
     // The table descriptor is a by-value kernel argument that the kernel never touches as such: it hands a POINTER to it --
     // into the kernarg segment of this very dispatch -- down to the functions that add rows (TableRef, exact_core.inc), which
     // read its fields with scalar loads when they need them.  (A device-resident copy of the descriptor, written once at
     // init, was the first form of this: the kernarg segment is the one piece of memory whose visibility to a dispatch the
     // launch itself guarantees, whatever other contexts left in the caches at the address of a freed and re-used copy.)
-    struct KernArgs {  // the argument list up to the descriptor, as the kernarg ABI lays it out (natural alignment, in order)
-        DevParams P;
-        DevBatch B;
-        DevTableG1 TG;
-    };
+    typedef ExactKernArgs KernArgs;  // the argument list as the kernarg ABI lays it out (decide_group.inc)
     // the kernarg ABI lays arguments out in order at their natural alignment: all three are 8-byte aligned structs of 8-byte
     // multiples, so TG sits right behind P and B.  A change of either struct that breaks this fails here, not at run time.
     static_assert(alignof(DevParams) == 8 && alignof(DevBatch) == 8 && alignof(DevTableG1) == 8, "kernarg layout: 8-byte aligned argument structs");
@@ -223,6 +222,7 @@ __global__ __launch_bounds__(64, (exact_waves<NW, MODE>(sizeof(WT) == 8))) void 
             held.w = nullptr;
             held.len = held.nw = 0;
             bool have_held = false;
+            u32 held_pos = 0;  // its worklist position (run_short_group: the stored bounds of an item are found by it)
             for (u32 t = 0; t <= nit; t++) {  // not unrolled: one copy of each driver; trip nit flushes a read left waiting
                 if (t == hook && nxt_nit) {  // P1: the entries are there; the next chunk's words start travelling, and the head after it
                     PH_T0(t_p1);
@@ -262,13 +262,26 @@ __global__ __launch_bounds__(64, (exact_waves<NW, MODE>(sizeof(WT) == 8))) void 
                     }
                 }
                 if constexpr (kGroup) {
+                    const u32 pos = (u32) cur + t;  // (worklist positions fit 32 bits: n <= wl_cap)
                     if (ok && !have_held) {
                         held = rd;
+                        held_pos = pos;
                         have_held = true;
                     } else if (have_held) {
                         ReadRef second = held;  // (by value: a reference to one of two structs would put both in scratch memory)
                         if (ok) second = rd;
-                        run_short_group<NW, WT>(sm, P, T, held, second, ok);
+                        if constexpr (NW == 3) {
+                            StoredBounds sb;
+                            sb.posA = held_pos;
+                            sb.posB = ok ? pos : held_pos;
+                            // (the triples of a read follow from its length: held.nw is not kept across the trips, held_pos takes its register)
+                            ReadRef first = held;
+                            first.nw = (first.len + 31u) >> 5;
+                            second.nw = (second.len + 31u) >> 5;
+                            run_short_group<NW, WT>(sm, P, T, first, second, ok, sb);
+                        } else {
+                            run_short_group<NW, WT>(sm, P, T, held, second, ok, NoStoredBounds());
+                        }
                         have_held = false;
                     }
                 }

@@ -54,6 +54,10 @@ struct Slot {
     unsigned char *d_ascii = nullptr;  // text batches: [word_offsets][byte_offsets][lengths][bases], max_batch_ascii_bytes + slack
     u32 *d_wl = nullptr;
     u32 *d_wl_count = nullptr;
+    // the hand-over of the bounds pass (kernels/bounds_pass.inc): the packed bounds of the first bnd_cap worklist entries of the
+    // slot's batch, written between its prefilter and its exact kernel (nullptr / 0: a context whose batches never take that pass)
+    u32 *d_bnd = nullptr;
+    u32 bnd_cap = 0;
     int2 *d_thr = nullptr;   // pass thresholds of the prefilter's uniform-geometry path (kThrRows * kThrRow)
     int2 *h_thr = nullptr;   // pinned staging of the same
     hipEvent_t ev_tail = nullptr, ev_copied = nullptr;  // order the context's copy stream behind / in front of this slot's stream (BatchCopy)
@@ -339,6 +343,15 @@ extern "C" int trew_hip_init(const trew_hip_params *params, trew_hip_ctx **out) 
         s.h_seen = (u32 *) ((char *) s.h_thr + kThrTableBytes);
         memset(s.h_seen, 0, kDiagWords * 4);
         if ((e = hipMalloc((void **) &s.d_wl, p.max_batch_reads * sizeof(u32))) != hipSuccess) return bail("hipMalloc(worklist)", e);
+        if (bounds_pass_applies(ctx->dp, 1)) {  // (by mode, k range and flags; the batch's geometry decides again at every submit)
+            // 256 bytes an entry: not for every read of a batch.  1 to 2 % of WGS-like reads are flagged; a thirty-second of the
+            // batch (but room for 64 k entries, a small batch in full) leaves a margin, and entries beyond it are bounded by the
+            // exact kernel's rows as before; never more than 4 M entries (1 GiB).  TREW_FLAG_DEBUG_SMALL_BOUNDS: 64 entries, so that a
+            // small batch takes both paths.
+            const u64 share = std::min<u64>(std::max<u64>(p.max_batch_reads / 32, std::min<u64>(p.max_batch_reads, 1ull << 16)), 1ull << 22);
+            s.bnd_cap = (p.flags & TREW_FLAG_DEBUG_SMALL_BOUNDS) ? 64u : (u32) share;
+            if ((e = hipMalloc((void **) &s.d_bnd, (size_t) s.bnd_cap * bounds_entry_bytes())) != hipSuccess) return bail("hipMalloc(bounds)", e);
+        }
         if ((e = hipMalloc((void **) &s.d_wl_count, 2 * kWlCountBytes)) != hipSuccess) return bail("hipMalloc(wl_count)", e);
         if ((e = hipMemsetAsync(s.d_wl_count, 0, 2 * kWlCountBytes, ctx->fill_stream)) != hipSuccess) return bail("hipMemsetAsync", e);
         if (p.mode == TREW_MODE_SEGMENT) {
@@ -373,6 +386,7 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         if (s.d_thr) (void) hipFree(s.d_thr);
         if (s.h_thr) (void) hipHostFree(s.h_thr);
         if (s.d_wl) (void) hipFree(s.d_wl);
+        if (s.d_bnd) (void) hipFree(s.d_bnd);
         if (s.d_wl_count) (void) hipFree(s.d_wl_count);
         if (s.res.k_high) (void) hipFree(s.res.k_high);
         if (s.res.k_low) (void) hipFree(s.res.k_low);
@@ -659,7 +673,11 @@ static int launch_batch(trew_hip_ctx *ctx, Slot &s, const DevBatch &db, u32 max_
         share = hipStreamQuery(ctx->slots[(size_t) prev].stream) == hipErrorNotReady;
         (void) hipGetLastError();
     }
-    SUBMIT_CHK(launch_exact(s.stream, (u32) ctx->n_cu, db.n_units, ctx->dp, db, ctx->table_g1, s.d_wl, wl_count, wl_count_next, wl_cap, s.res, cap, rawwords, max_seg, share));
+    // the bounds pass, on the slot's stream between the two kernels (exact_ms of last_timing includes it); no stream of its own
+    const bool with_bounds = s.d_bnd != nullptr && bounds_pass_applies(ctx->dp, max_seg);
+    if (with_bounds) SUBMIT_CHK(launch_bounds(s.stream, (u32) ctx->n_cu, db.n_units, ctx->dp, db, s.d_wl, wl_count, wl_cap, s.d_bnd, s.bnd_cap));
+    SUBMIT_CHK(launch_exact(s.stream, (u32) ctx->n_cu, db.n_units, ctx->dp, db, ctx->table_g1, s.d_wl, wl_count, wl_count_next, wl_cap, s.res, cap, rawwords, max_seg, share,
+                            with_bounds ? s.d_bnd : nullptr, s.bnd_cap));
     if (timed) SUBMIT_CHK(hipEventRecord(ev[2], s.stream));
     if (compat_g1) {  // the stale rows of this batch's pairs (and of the previous batch's tail) are added again, in file order
         SUBMIT_CHK(launch_g1_apply(s.stream, ctx->table, ctx->g1, db, ctx->dp.min_mer, ctx->g1_carry[ctx->g1_batches & 1], ctx->g1_carry[(ctx->g1_batches + 1) & 1],

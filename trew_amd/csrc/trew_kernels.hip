@@ -33,6 +33,7 @@
 //   count_table.inc    table_add / table_add_wide / spill log
 //   exact_core.inc     LDS working set, eval_k / eval_runs (Lemma A), lane_bounds, decide, emit_k, run_short, run_segment
 //   decide_group.inc   decide_group (four segments in lock step, 16 lanes each), run_short_group
+//   bounds_pass.inc    bounds_kernel<3> (the packed bounds of the flagged short reads, a lane per half; run_short_group reads them back)
 //   driver_long.inc    run_long        driver_pair.inc   run_pair
 //   exact_kernel.inc   exact_kernel<NW, MODE, WT>
 //   table_kernels.inc  add-rows / compaction kernels      synth_kernels.inc  workload generators
@@ -71,6 +72,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/count_table.inc"
 #include "kernels/exact_core.inc"
 #include "kernels/decide_group.inc"
+#include "kernels/bounds_pass.inc"
 #include "kernels/driver_long.inc"
 #include "kernels/driver_pair.inc"
 #include "kernels/exact_kernel.inc"
@@ -206,9 +208,30 @@ hipError_t launch_g1_apply(hipStream_t st, const DevTable &T, const DevG1 &G, co
     return hipGetLastError();
 }
 
+// The batches whose exact kernel reads stored bounds (run_short_group): short reads on 64-bit words in the 3-word instantiation
+// with a k range the group pass takes.  launch_batch asks before it queues the bounds pass.
+bool bounds_pass_applies(const DevParams &P, u32 max_seg_len) {
+    return P.mode == TREW_MODE_SHORT && P.max_mer <= 32 && !(P.flags & TREW_FLAG_NO_FILTER) && pick_nw(max_seg_len) == 3 &&
+           P.max_mer - P.min_mer < (int) kBoundWords && !(P.flags & TREW_FLAG_DEBUG_NO_GROUP);
+}
+size_t bounds_entry_bytes() { return kBoundItemWords * sizeof(u32); }
+
+// The bounds pass over the worklist of one batch, between its prefilter and its exact kernel: bnd gets kBoundItemWords words for
+// each of the first bnd_cap worklist entries.  A fixed grid: the worklist's length is on the device only.
+hipError_t launch_bounds(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const u32 *wl, const u32 *wl_count,
+                         u32 wl_cap, u32 *bnd, u32 bnd_cap) {
+    if (n_units == 0 || bnd_cap == 0) return hipSuccess;
+    // a lane per half, a wave per block; sixteen waves a CU hold every wave the kernel's 8.4 KB of LDS lets a CU keep, and a small
+    // batch starts no more waves than its reads could fill
+    const u64 most = (std::min<u64>(n_units, bnd_cap) * 2 + 63) / 64;
+    const u32 grid = (u32) std::min<u64>((u64) n_cu * 16ull, most);
+    hipLaunchKernelGGL(bounds_kernel<3>, dim3(grid), dim3(64), 0, st, P, B, wl, wl_count, wl_cap, bnd, bnd_cap);
+    return hipGetLastError();
+}
+
 hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const DevTableG1 &T,
                         const u32 *wl, u32 *wl_count, u32 *wl_count_next, u32 wl_cap, const SegResults &R, u32 cap, u32 rawwords,
-                        u32 max_seg_len, bool share) {
+                        u32 max_seg_len, bool share, const u32 *bnd, u32 bnd_cap) {
     // lane_bounds needs every staged segment (< cap) to fit its NW words
     const bool wide = P.max_mer > 32;  // 128-bit words, k_mer_check_128 (kmer.cpp:100, 180)
     const u32 lds = exact_lds_bytes(cap, rawwords, wide ? 16u : 8u);
@@ -220,8 +243,9 @@ hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &
     // 0: no lane bounds -- NO_FILTER, and segments above 319 bases (pick_nw's 32, which the switches below map to 0)
     const int nw = (P.flags & TREW_FLAG_NO_FILTER) ? 0 : pick_nw(bound_len);
     // one block = one wave; fill the chip exactly once (persistent, self-scheduling waves)
-    typedef void (*kern_t)(DevParams, DevBatch, DevTableG1, const u32 *, u32 *, u32 *, u32, SegResults, u32, u32);
+    typedef void (*kern_t)(DevParams, DevBatch, DevTableG1, const u32 *, u32 *, u32 *, u32, SegResults, u32, u32, const u32 *, u32);
     kern_t fn = nullptr;
+    if (!bounds_pass_applies(P, max_seg_len)) bnd = nullptr;  // no other instantiation reads stored bounds
 #define TREW_PICK_MODE(NWV, WTV)                                                      \
     switch (P.mode) {                                                                 \
     case TREW_MODE_SHORT: fn = exact_kernel<NWV, TREW_MODE_SHORT, WTV>; break;        \
@@ -274,7 +298,7 @@ hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &
     // prefilter) one wave per 16 units, so that a launch does not start thousands of waves that find the queue empty.
     const u64 full = (u64) n_cu * (u64) per_cu;
     const u32 grid = (u32) std::min<u64>(full, std::max<u64>(n_units / 16, 64));
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, st, P, B, T, wl, wl_count, wl_count_next, wl_cap, R, cap, rawwords);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, st, P, B, T, wl, wl_count, wl_count_next, wl_cap, R, cap, rawwords, bnd, bnd ? bnd_cap : 0u);
     return hipGetLastError();
 }
 
