@@ -34,8 +34,9 @@ extern "C" {
  * (trew_hip_variants, trew_hip_variants_results, trew_variants_host), the period entry points (trew_hip_periods,
  * trew_hip_periods_results, trew_periods_host), the satellite entry points (trew_hip_satellites,
  * trew_hip_satellites_results, trew_satellites_host), the alignment entry points (trew_hip_align, trew_hip_align_results,
- * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host) and the tandem
- * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host): they are purely additive -- no existing
+ * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host), the tandem
+ * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host) and the traceback entry points (trew_hip_trace,
+ * trew_hip_trace_results, trew_trace_host): they are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
@@ -399,7 +400,7 @@ int trew_intervals_host(const uint32_t *words, const uint32_t *offsets, const ui
  * Consequences: the bins of a read's histogram sum to variants_s; units_s <= trew_hip_annot.windows_s; a read that is an exact
  * periodic repeat of M has variants = 0; the rev record of a read equals the fwd record of its reverse complement and vice
  * versa, the histograms likewise; for a self-reverse-complementary motif strand rev is strand fwd under (j, c) ->
- * (k-1-j, 3-c).  Only substitutions are variants: a unit with an inserted or deleted base is out of scope (it shifts the
+ * (k-1-j, 3-c).  Only substitutions are variants: a unit with an inserted or deleted base is trew_hip_trace_item's, below, not this measure's (it shifts the
  * phase and is seen by no window).  Also additive: TREW_HIP_ABI_VERSION stays 4. */
 #define TREW_VARIANT_BINS 128
 #define TREW_VARIANT_NONE 0xffffffffu
@@ -470,7 +471,7 @@ int trew_periods_host(const uint32_t *words, const uint32_t *offsets, const uint
  * variants_s and their bins make the read's histogram; a read that is a primitive M repeated r times has the one forward
  * item {0, r, NONE}; the rev items of a read are the fwd items of its reverse complement with start -> n - k - start for a
  * variant and n - k - (start + (count - 1) k) for a run, the bin unchanged; an item does not depend on the rest of the
- * batch.  Out of scope: units with an inserted or deleted base (they shift the phase).  Also additive:
+ * batch.  Units with an inserted or deleted base (they shift the phase) are left to trew_hip_trace, below.  Also additive:
  * TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
     uint32_t read, motif, strand, start, count, bin;
@@ -704,6 +705,60 @@ int trew_hip_tandems_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *out, 
  * first ones of the sorted order), counts as above (may be NULL). */
 int trew_tandems_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                       int penalty, uint32_t min_score, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+
+/* ---- units in place under indels: the traceback of trew_hip_alignment's wraparound alignment, cut into copies of the motif ----
+ * (what is this telomere made of, and in which order, when bases are missing or extra?  trew_hip_chain for reads with indels;
+ * its columns also say where the mismatches, insertions and deletions of trew_hip_alignment lie.)  Integer-exact.  Everything
+ * is trew_hip_alignment's, unchanged: the codes, M_s, the penalty P, the tuples (score, start, consumed, matches), V, H and the
+ * record of a strand.  Three tie rules are added, because equal tuples can come from different cells:
+ *   1. V[i][j]: among candidates with equal tuples the fresh start comes first, then the diagonal, then the inserted read
+ *      base; op in {F, D, I} names the winner.
+ *   2. H[i][j]: d is the smallest d < k that attains the largest tuple.
+ *   3. The end cell is the cell (end, j*) of the record; on equal (score, -i, start, consumed, matches) the smallest j wins.
+ * The traceback starts at the end cell.  At H[i][j] it emits d columns `del`, for the motif phases j, j - 1, ..., j - d + 1,
+ * sets j <- (j - d) mod k and looks at op of V[i][j]: F ends the walk (here i = start); D emits `eq` or `sub`, according to
+ * whether x[i-1] = M_s[j], for (read base i - 1, phase j) and goes to H[i-1][(j-1) mod k]; I emits `ins` (read base i - 1, no
+ * phase) and goes to H[i-1][j].  Reversed, the columns are the alignment in read order.  A segment begins at the first column
+ * and in front of every column whose phase is 0; an `ins` column has no phase and stays in the running segment.  A segment is
+ * one item:
+ *   start       its first read base
+ *   bases       its read bases
+ *   phase       the phase of its first phased column
+ *   consumed    its phased columns
+ *   mismatches, insertions, deletions   as counted in its columns
+ *   count       1
+ * A segment is a complete exact copy when phase = 0, consumed = k and it has no error; consecutive complete exact copies merge
+ * into one item with count = r, bases = consumed = r k and the first copy's start.  A key (read, motif, strand) has items if
+ * and only if its alignment score is >= min_score (>= 1).  Consequences: the items of a key tile [start, end) of its record
+ * without a gap; their consumed, mismatches, insertions and deletions sum to the record's; every item has bases >= 1; only the
+ * first item can have phase != 0.  Limits, as for trew_hip_alignment: one tract per key, linear gaps, k <= 32.  Also
+ * additive: TREW_HIP_ABI_VERSION stays 4. */
+typedef struct {
+    uint32_t read, motif, strand, start, bases, count, phase, consumed, mismatches, insertions, deletions, reserved; /* reserved = 0 */
+} trew_hip_trace_item; /* 48 bytes */
+/* Like trew_hip_align in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, the motif and penalty checks and their error texts), with buffers of its own and
+ * independent of the scan and of the other eleven kernels.  Further argument errors: "min_score must be at least 1",
+ * "max_items must be at least 1", "max_rows must be at least 1".  The kernel appends items to a log of max_items items and
+ * keeps the directions of the traced tracts in a workspace of max_rows rows of 64 bytes; both grow only.  How many rows a
+ * (read, motif) claims is internal: at most the read's length, none when neither strand reaches min_score.  At most 2^32 - 1
+ * reads a batch.  One kernel, a wave per read, for every read length. */
+int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty,
+                   uint32_t min_score, uint64_t max_items, uint64_t max_rows);
+/* Waits for the slot.  *n_items and *n_rows (neither may be NULL) are the items found and the rows claimed, exact also beyond
+ * max_items, max_rows or cap; counts (n_reads * n_motifs * 2 values at [read][motif][strand]; may be NULL) the items of every
+ * key, always exact; records (n_reads * n_motifs; may be NULL) the trew_hip_alignment of every (read, motif), equal to
+ * trew_hip_align's.  min(cap, *n_items) items sorted by (read, motif, strand, start) go to `items` when *n_items <= max_items
+ * and *n_rows <= max_rows; otherwise nothing is copied into `items` and the call returns 0: repeat trew_hip_trace with both at
+ * least what was reported -- one retry always suffices.  (A tract whose rows did not fit is still traced, by recomputing its
+ * rows block after block, which costs time quadratic in its length: size max_rows so that this stays the exception.) */
+int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                           uint32_t *counts, trew_hip_alignment *records, float *ms_kernel);
+/* The definition on the host with the full table, over packed planes: *n_items = items found, min(cap, *n_items) items (the
+ * first ones of the sorted order), counts and records as above (each may be NULL). */
+int trew_trace_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                    int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
+                    trew_hip_alignment *records);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

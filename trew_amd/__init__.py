@@ -35,6 +35,7 @@ from .capi import (  # noqa: F401
     repeats,
     satellites,
     tandems,
+    trace,
     tracts,
     variants,
 )

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_align", "trew_hip_align_results", "trew_align_host",
     "trew_hip_refine", "trew_hip_refine_results", "trew_refine_host",
     "trew_hip_tandems", "trew_hip_tandems_results", "trew_tandems_host",
+    "trew_hip_trace", "trew_hip_trace_results", "trew_trace_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -178,6 +179,15 @@ ALIGN_DTYPE = np.dtype([(name, "<u4") for name, _ in Alignment._fields_])
 assert ALIGN_DTYPE.itemsize == C.sizeof(Alignment) == 40
 
 
+class TraceItem(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("read", "motif", "strand", "start", "bases", "count", "phase", "consumed", "mismatches",
+                                                "insertions", "deletions", "reserved")]
+
+
+TRACE_DTYPE = np.dtype([(name, "<u4") for name, _ in TraceItem._fields_])
+assert TRACE_DTYPE.itemsize == C.sizeof(TraceItem) == 48
+
+
 class Refined(C.Structure):
     _fields_ = [(name, C.c_uint32) for name in ("period", "seed_period", "scored_period", "changed", "score", "start", "end", "consumed", "matches",
                                                 "seed_score", "support", "reserved")] + [("unit", C.c_uint64), ("seed_unit", C.c_uint64)]
@@ -278,6 +288,9 @@ def load():
     lib.trew_hip_align.argtypes = lib.trew_hip_tracts.argtypes
     lib.trew_hip_align_results.argtypes = lib.trew_hip_tracts_results.argtypes
     lib.trew_align_host.argtypes = lib.trew_tracts_host.argtypes
+    lib.trew_hip_trace.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, i32, C.c_uint32, u64, u64]
+    lib.trew_hip_trace_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(C.c_float)]
+    lib.trew_trace_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
     lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
     lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
@@ -500,6 +513,59 @@ def chain_host(reads_or_packed, motifs, cap=None):
         out = np.zeros(int(n.value), dtype=CHAIN_DTYPE)
         call(out)
     return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
+
+
+def trace_host(reads_or_packed, motifs, penalty=3, min_score=24, cap=None):
+    """trew_trace_host: the traceback of the wraparound alignment, cut into copies of the motif, computed on the host with the
+    full table.  reads_or_packed as for annotate_host.  Returns (TRACE_DTYPE items sorted by (read, motif, strand, start),
+    counts of shape (n_reads, n_motifs, 2), ALIGN_DTYPE records of shape (n_reads, n_motifs), n_items); with `cap` at most
+    that many items."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    arr, nm = _motif_array(motifs)
+    counts = np.zeros((len(offsets), max(nm, 1), 2), dtype=np.uint32)
+    records = np.zeros((len(offsets), max(nm, 1)), dtype=ALIGN_DTYPE)
+    n = C.c_uint64(0)
+
+    def call(out):
+        if lib.trew_trace_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), int(min_score),
+                               out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data, records.ctypes.data) != 0:
+            raise TrewHipError("trew_trace_host failed: %s" % lib.trew_hip_last_error(None).decode())
+
+    out = np.zeros(0 if cap is None else int(cap), dtype=TRACE_DTYPE)
+    call(out)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=TRACE_DTYPE)
+        call(out)
+    return out[:min(len(out), int(n.value))], counts[:, :nm], records[:, :nm], int(n.value)
+
+
+_TRACE_COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+
+def trace_signature(items, read, k):
+    """(units, edited, signature) as `trew trace` prints them for the TRACE_DTYPE items of one (read, motif, strand), given in
+    start order, `read` the read's text and k the motif's length: `=r` for a run of r complete exact copies, a complete copy with
+    errors as its read bases in upper case, an end piece (consumed < k) as its read bases in lower case; on strand rev the bases
+    of an item are reverse-complemented (motif orientation).  units: the copies of the items with consumed = k count; edited:
+    the items with an error."""
+    if isinstance(read, (bytes, bytearray)):
+        read = read.decode("latin-1")
+    units = edited = 0
+    tokens = []
+    for it in items:
+        count, consumed = int(it["count"]), int(it["consumed"])
+        errors = int(it["mismatches"]) + int(it["insertions"]) + int(it["deletions"])
+        units += count if consumed == k * count else 0
+        edited += errors > 0
+        if consumed == k * count and int(it["phase"]) == 0 and not errors:
+            tokens.append("=%d" % count)
+            continue
+        text = read[int(it["start"]):int(it["start"]) + int(it["bases"])].upper()
+        if int(it["strand"]):
+            text = "".join(_TRACE_COMP.get(c, "N") for c in reversed(text))
+        tokens.append(text if consumed == k else text.lower())
+    return units, edited, " ".join(tokens)
 
 
 def repeats_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
@@ -912,6 +978,46 @@ class TrewHip:
                       "trew_hip_chain_results")
         return (out, counts, items, events, ms.value) if want_ms else (out, counts, items, events)
 
+    def trace(self, batch, motifs, penalty=3, min_score=24, max_items=None, max_rows=None, slot=0):
+        """Queue the traceback of the wraparound alignment of every read of `batch` for `motifs` (texts or Motif, at most 8) on
+        the slot's stream.  max_items: the capacity of the item log for this call (default: four per read and motif, at least
+        1); max_rows: the rows of the direction workspace, 64 bytes each.  A row per base and motif always suffices and
+        is the default where the lengths are known on the host (256 per read and motif for ragged device-resident batches); a
+        tract whose rows do not fit costs time quadratic in its length."""
+        arr, nm = _motif_array(motifs)
+        if max_items is None:
+            max_items = max(4 * int(batch.n_reads) * nm, 1)
+        if max_rows is None:
+            n = int(batch.n_reads)
+            if not batch.lengths:  # uniform reads
+                bases = n * int(batch.uniform_length)
+            elif not batch.on_device:
+                bases = int(np.ctypeslib.as_array(C.cast(batch.lengths, C.POINTER(C.c_uint32)), shape=(n,)).sum(dtype=np.uint64)) if n else 0
+            else:
+                bases = 256 * n  # lengths in device memory: a guess, the results say when it was too small
+            max_rows = max(bases * nm, 1)
+        self._queue("trace", slot, batch, arr, nm, shape=(int(max_items), int(max_rows)))
+        self._chk(self.lib.trew_hip_trace(self.ctx, C.byref(batch), slot, arr, nm, int(penalty), int(min_score), int(max_items), int(max_rows)),
+                  "trew_hip_trace")
+
+    def trace_results(self, slot=0, want_ms=False):
+        """Results of the slot's last trace: (TRACE_DTYPE items sorted by (read, motif, strand, start), counts of shape (n_reads,
+        n_motifs, 2), ALIGN_DTYPE records of shape (n_reads, n_motifs), n_items, n_rows [, kernel ms]).  n_items > max_items or
+        n_rows > max_rows: no items, everything else is exact; repeat the call with both at least what was reported."""
+        n_items, n_rows = C.c_uint64(0), C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm, max_items, max_rows = self._queued.get(("trace", slot), (0, 1, 0, 0))
+        counts = np.zeros((n_reads, nm, 2), dtype=np.uint32)
+        records = np.zeros((n_reads, nm), dtype=ALIGN_DTYPE)
+        self._chk(self.lib.trew_hip_trace_results(self.ctx, slot, None, 0, C.byref(n_items), C.byref(n_rows), counts.ctypes.data, records.ctypes.data,
+                                                  C.byref(ms) if want_ms else None), "trew_hip_trace_results")
+        items, rows = int(n_items.value), int(n_rows.value)
+        out = np.zeros(items if items <= max_items and rows <= max_rows else 0, dtype=TRACE_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_trace_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n_items), C.byref(n_rows), None, None, None),
+                      "trew_hip_trace_results")
+        return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
+
     def repeats(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract of every read of `batch` on the slot's stream (no motifs).  max_records: the
         capacity of the log for this call (default: the batch's read count, at least 1)."""
@@ -1256,6 +1362,27 @@ def chain(reads, motifs, device=0, max_events=None):
             t.chain(b, motifs, events)
             out, counts, items, events = t.chain_results()
         return out, counts
+
+
+def trace(reads, motifs, penalty=3, min_score=24, device=0, max_items=None, max_rows=None):
+    """Units in place under indels on the GPU: for every read (bytes / str) and motif (text) the traceback of `align`'s
+    wraparound alignment on each strand whose score reaches min_score, cut into copies of the motif -- runs of complete exact
+    copies, copies with their substitutions, insertions and deletions, and the end pieces, in place.  Returns (TRACE_DTYPE items
+    sorted by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2), ALIGN_DTYPE records of shape (n_reads,
+    n_motifs)); trace_signature turns a key's items into text.  The first call's log and workspace hold max_items items
+    and max_rows rows (defaults: TrewHip.trace's; its max_rows, a row per base and motif, always suffices); when more are found
+    the call is repeated once with the exact numbers."""
+    words, offsets, lengths = pack_reads(reads)
+    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
+        b = t.host_batch(words, offsets, lengths)
+        t.trace(b, motifs, penalty, min_score, max_items, max_rows)
+        out, counts, records, items, rows = t.trace_results()
+        cap_items, cap_rows = t._queued[("trace", 0)][2:]
+        if items > cap_items or rows > cap_rows:
+            t.trace(b, motifs, penalty, min_score, max(items, cap_items), max(rows, cap_rows))
+            out, counts, records, items, rows = t.trace_results()
+        return out, counts, records
 
 
 def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):

@@ -1176,11 +1176,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1202,6 +1202,7 @@ struct Annotator {
         std::vector<trew_hip_alignment> arecs;  // trew align
         std::vector<trew_hip_refined> frecs;    // trew refine
         std::vector<trew_hip_tandem> tdrecs;    // trew tandems
+        std::vector<trew_hip_trace_item> xrecs; // trew trace
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1264,6 +1265,7 @@ struct AnnotBatch {
     trew_hip_batch b;
     const uint32_t *lengths;
     uint64_t n, first_read;  // reads of the chunk, ordinal of the first
+    const char *text;        // the chunk: read r is text[w->st[r] .. w->nd[r]]
 };
 
 static AnnotRow annot_row(const AnnotBatch &x, uint64_t r, int m) {
@@ -1614,6 +1616,60 @@ static void fold_tandems(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew trace: fold_align's rows and sums from the records that come with the items, and the items of those keys with the read
+// bases of every item that is no run (the signature prints them).  trace_sums: units (the copies of the items with consumed =
+// k count), edited (the items with an error), items.  The workspace holds a row for every base and motif, which no batch
+// exceeds; the log starts at sixteen items per read and motif, and a batch whose log overflows is resubmitted once, with the
+// exact numbers.
+static void fold_trace(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    uint64_t bases = 0;
+    for (uint64_t r = 0; r < x.n; r++) bases += x.lengths[r];
+    uint64_t cap = 16 * x.n * (uint64_t) nm + 1024, rows_cap = std::max<uint64_t>(bases * (uint64_t) nm, 1), items = 0, rows = 0;
+    if (w->arecs.size() < x.n * (size_t) nm) w->arecs.resize(x.n * (size_t) nm);
+    for (int attempt = 0;; attempt++) {
+        if (trew_hip_trace(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty, x.rq->min_score, cap, rows_cap)) hip_die(x.c, "trew_hip_trace");
+        if (w->xrecs.size() < cap) w->xrecs.resize(cap);
+        if (trew_hip_trace_results(x.c, w->slot, w->xrecs.data(), cap, &items, &rows, nullptr, w->arecs.data(), nullptr)) hip_die(x.c, "trew_hip_trace_results");
+        if (items <= cap && rows <= rows_cap) break;
+        if (attempt) die("internal error: the trace log overflowed twice");
+        cap = std::max(cap, items);  // the exact numbers: one retry always suffices
+        rows_cap = std::max(rows_cap, rows);
+        p.interval_retries++;
+    }
+    for (uint64_t r = 0; r < x.n; r++)
+        for (int m = 0; m < nm; m++) {
+            const trew_hip_alignment &rec = w->arecs[r * (size_t) nm + (size_t) m];
+            for (int s = 0; s < 2; s++) {
+                const uint32_t *f = s ? &rec.score_rev : &rec.score_fwd;  // five consecutive u32
+                if (f[0] < x.rq->min_score) continue;
+                AlignRow row;
+                row.read = x.first_read + r;
+                row.length = x.lengths[r];
+                row.motif = m;
+                row.strand = s;
+                for (int i = 0; i < 5; i++) row.rec[i] = f[i];
+                p.arows.push_back(row);
+                const AlignColumns c = align_columns(row.rec, (uint32_t) x.rq->motifs[m].k, x.rq->penalty);
+                const uint64_t add[kAlignSums] = {1, (uint64_t) f[2] - f[1], f[0], c.copies, f[3], f[4], c.mismatches, c.insertions, c.deletions};
+                for (int i = 0; i < kAlignSums; i++) p.align_sums[m][s][i] += add[i];
+            }
+        }
+    for (uint64_t i = 0; i < items; i++) {
+        const trew_hip_trace_item &it = w->xrecs[i];
+        const uint32_t k = (uint32_t) x.rq->motifs[it.motif].k;
+        const bool errors = it.mismatches || it.insertions || it.deletions;
+        uint64_t *sums = p.trace_sums[it.motif][it.strand];
+        if (it.consumed == k * it.count) sums[0] += it.count;
+        sums[1] += errors;
+        sums[2]++;
+        const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
+        p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
+                                   run ? std::string() : std::string(x.text + w->st[it.read] + it.start, (size_t) it.bases)});
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1631,7 +1687,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             uint32_t *offsets = w->h_buf, *lengths = w->h_buf + n, *words = w->h_buf + 2 * n;
             const uint64_t nw = trew_pack_reads(ch->buffer1, w->st.data(), w->nd.data(), n, words, a->words_cap, offsets, lengths);
             if (nw == (uint64_t) -1) die("internal error: packed chunk exceeds the slot buffer");
-            AnnotBatch x{c, w, rq, trew_hip_batch(), lengths, n, first_read};
+            AnnotBatch x{c, w, rq, trew_hip_batch(), lengths, n, first_read, ch->buffer1};
             memset(&x.b, 0, sizeof(x.b));
             x.b.words = words;
             x.b.n_words = nw;
@@ -1654,6 +1710,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Align: fold_align(x, p); break;
             case Measure::Refine: fold_refine(x, p); break;
             case Measure::Tandems: fold_tandems(x, p); break;
+            case Measure::Trace: fold_trace(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1679,6 +1736,8 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         into.reported_rev[m] += from.reported_rev[m];
         for (int s = 0; s < 2; s++)
             for (int i = 0; i < kAlignSums; i++) into.align_sums[m][s][i] += from.align_sums[m][s][i];
+        for (int s = 0; s < 2; s++)
+            for (int i = 0; i < kTraceSums; i++) into.trace_sums[m][s][i] += from.trace_sums[m][s][i];
     }
     if (into.var_hist.size() < from.var_hist.size()) {
         into.var_hist.resize(from.var_hist.size());
@@ -1722,7 +1781,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -1762,6 +1821,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         out.arows.insert(out.arows.end(), w.part.arows.begin(), w.part.arows.end());
         out.frows.insert(out.frows.end(), w.part.frows.begin(), w.part.frows.end());
         out.trows.insert(out.trows.end(), w.part.trows.begin(), w.part.trows.end());
+        out.xrows.insert(out.xrows.end(), w.part.xrows.begin(), w.part.xrows.end());
     }
     std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
         if (x.read != y.read) return x.read < y.read;
@@ -1783,6 +1843,12 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         if (x.read != y.read) return x.read < y.read;
         return x.motif != y.motif ? x.motif < y.motif : x.strand < y.strand;
     });
+    std::sort(out.xrows.begin(), out.xrows.end(), [](const TraceRow &x, const TraceRow &y) {
+        if (x.read != y.read) return x.read < y.read;
+        if (x.it.motif != y.it.motif) return x.it.motif < y.it.motif;
+        if (x.it.strand != y.it.strand) return x.it.strand < y.it.strand;
+        return x.it.start < y.it.start;
+    });
     std::sort(out.frows.begin(), out.frows.end(), [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
     std::sort(out.trows.begin(), out.trows.end(),
               [](const TandemRow &x, const TandemRow &y) { return x.read != y.read ? x.read < y.read : x.td.start < y.td.start; });
@@ -1800,6 +1866,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
                                   (unsigned long long) out.rrows.size(), (unsigned long long) out.interval_retries);
         if (rq.kind == Measure::Tandems) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.trows.size(), (unsigned long long) out.interval_retries);
+        if (rq.kind == Measure::Trace) fprintf(stderr, "[trew] %s: %llu items, %llu batch(es) resubmitted with a larger log\n", file_name,
+                                  (unsigned long long) out.xrows.size(), (unsigned long long) out.interval_retries);
         if (rq.kind == Measure::Satellites) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
                                   (unsigned long long) out.srows.size(), (unsigned long long) out.interval_retries);
     }

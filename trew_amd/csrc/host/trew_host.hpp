@@ -99,19 +99,19 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain|align MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems FASTQ...: the per-read measures.
-// One file path for all eleven (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp and tandems.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems };
+// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems FASTQ...: the per-read measures.
+// One file path for all twelve (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp and trace.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     // a (read, motif) is reported when its longer tract has at least this many bases (variants, chain: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
     int n_motifs = 0;
-    int penalty = 0;                                      // tracts, periods, repeats, satellites, align, refine, tandems
+    int penalty = 0;                                      // tracts, periods, repeats, satellites, align, refine, tandems, trace
     int min_period = 1, max_period = 32;                  // periods, repeats, satellites, refine, tandems (which take no motifs: n_motifs = 0)
-    uint32_t min_score = 24;                              // periods, repeats, satellites, align, refine, tandems
+    uint32_t min_score = 24;                              // periods, repeats, satellites, align, refine, tandems, trace
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
 };
 struct AnnotRow {
@@ -159,6 +159,14 @@ struct AlignColumns {
 AlignColumns align_columns(const uint32_t rec[5], uint32_t k, int penalty);
 // the sums of `trew align`'s summary: rows, end - start, score, copies, consumed, matches, mismatches, insertions, deletions
 constexpr int kAlignSums = 9;
+struct TraceRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_trace_item it;  // it.read is the index inside its batch; it.motif the index in command-line order
+    std::string text;        // the item's read bases as the file has them; empty for a run of complete exact copies
+};
+// the further sums of `trew trace`'s summary, behind align's: units, edited, items
+constexpr int kTraceSums = 3;
 struct RefineRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
     uint32_t length;  // bases
@@ -188,13 +196,15 @@ struct AnnotFileResult {
     std::vector<SatelliteRow> srows; // satellites: sorted by read, start
     std::vector<AlignRow> arows;     // align: sorted by read, motif, strand
     uint64_t align_sums[TREW_ANNOT_MAX_MOTIFS][2][kAlignSums] = {};  // align: [motif][strand], over the rows
+    std::vector<TraceRow> xrows;     // trace: the items of its arows' keys, sorted by read, motif, strand, start
+    uint64_t trace_sums[TREW_ANNOT_MAX_MOTIFS][2][kTraceSums] = {};  // trace: [motif][strand], over the rows
     std::vector<RefineRow> frows;    // refine: sorted by read
     std::vector<TandemRow> trows;    // tandems: sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
     uint64_t terminal_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, terminal_rev[TREW_ANNOT_MAX_MOTIFS] = {};
-    uint64_t interval_retries = 0;  // intervals, chain, repeats, satellites, tandems: batches resubmitted because their log overflowed
+    uint64_t interval_retries = 0;  // intervals, chain, repeats, satellites, tandems, trace: batches resubmitted because their log overflowed
     uint64_t batches = 0;           // the non-empty chunks, each of which is one batch
     uint64_t runs_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, runs_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported_rev[TREW_ANNOT_MAX_MOTIFS] = {};  // chain
     uint64_t variants_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, variants_rev[TREW_ANNOT_MAX_MOTIFS] = {};
@@ -249,6 +259,7 @@ int satellites_main(int argc, char **argv);
 int align_main(int argc, char **argv);
 int refine_main(int argc, char **argv);
 int tandems_main(int argc, char **argv);
+int trace_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement

@@ -25,9 +25,9 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -45,6 +45,10 @@ struct MeasureState {
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites, tandems: n_reads
     int n_motifs = 0;  // variants
     u32 k[kAnnotMaxMotifs] = {};  // chain: the motifs' lengths (pairing a run's events needs start mod k)
+    // trace: `records` is its item log, `counter` two values (items, rows), `counts` one u32 per (read, motif, strand); beside them
+    DevBuf rows;       // the direction workspace, 64 bytes a row, grown on demand
+    DevBuf aligned;    // the trew_hip_alignment of every (read, motif)
+    u64 max_rows = 0;  // the max_rows of the last call (max_log: its max_items; n: its alignment records)
 };
 
 struct Slot {
@@ -400,7 +404,7 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         if (s.d_motifs) (void) hipFree(s.d_motifs);
         if (s.h_motifs) (void) hipHostFree(s.h_motifs);
         for (auto &st : s.measure) {
-            for (void *p : {st.records.p, st.counts.p, (void *) st.counter, (void *) st.hist})
+            for (void *p : {st.records.p, st.counts.p, st.rows.p, st.aligned.p, (void *) st.counter, (void *) st.hist})
                 if (p) (void) hipFree(p);
             for (auto e : st.ev)
                 if (e) (void) hipEventDestroy(e);
@@ -1219,8 +1223,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems
-// The eleven measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace
+// The twelve measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
@@ -1290,6 +1294,12 @@ extern "C" int trew_refine_host(const uint32_t *words, const uint32_t *offsets, 
 extern "C" int trew_tandems_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
                                  int max_period, int penalty, uint32_t min_score, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts) {
     return host_status(tandems_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out, cap, n, counts));
+}
+
+extern "C" int trew_trace_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
+                               int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items,
+                               uint32_t *counts, trew_hip_alignment *records) {
+    return host_status(trace_host(words, offsets, lengths, n_reads, motifs, n_motifs, penalty, min_score, items, cap, n_items, counts, records));
 }
 
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
@@ -1497,6 +1507,81 @@ extern "C" int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alig
     if (int rc = fetch_begin(ctx, slot, kAlign, nullptr, &sp)) return rc;
     const MeasureState &st = sp->measure[kAlign];
     if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_alignment), n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- units in place under indels: the traceback of the alignment
+static_assert(sizeof(trew_hip_trace_item) == 48, "twelve words: what trace_wave_kernel stores");
+extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty,
+                              uint32_t min_score, uint64_t max_items, uint64_t max_rows) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    auto own = [&]() -> const char * {
+        return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]"
+               : min_score < 1             ? "min_score must be at least 1"
+               : max_items < 1             ? "max_items must be at least 1"
+               : max_rows < 1              ? "max_rows must be at least 1"
+                                           : nullptr;
+    };
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kTrace, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[kTrace];
+    const u64 need = db.n_reads * (u64) n_motifs;
+    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, 2 * sizeof(unsigned long long)));  // a fixed size: never grows
+    if (int rc = grow(ctx, s, st.aligned, need * sizeof(trew_hip_alignment))) return rc;
+    if (int rc = grow(ctx, s, st.counts, need * 2ull * sizeof(u32))) return rc;
+    if (int rc = grow(ctx, s, st.records, max_items * sizeof(trew_hip_trace_item))) return rc;
+    if (int rc = grow(ctx, s, st.rows, max_rows * 64ull)) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    st.n_counts = need * 2ull;
+    st.max_log = max_items;
+    st.max_rows = max_rows;
+    // both counters start every call at zero, also a call without reads (its results then report no item and no row)
+    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, 2 * sizeof(unsigned long long), s.stream));
+    if (need == 0) return 0;
+    TraceLog lg;
+    lg.counter = st.counter;
+    lg.recs = (u32 *) st.records.p;
+    lg.cap = max_items;  // this call's capacities, not the (possibly larger) buffers': the overflow contract is per call
+    lg.row_counter = st.counter + 1;
+    lg.rows = (unsigned char *) st.rows.p;
+    lg.max_rows = max_rows;
+    return timed_launch(ctx, s, st, [&]() -> int {
+        HIPCHK(ctx, launch_trace(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
+                                 (u32 *) st.counts.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                                      uint32_t *counts, trew_hip_alignment *records, float *ms_kernel) {
+    const char *arg_error = !n_items || !n_rows ? "trew_hip_trace_results: n_items and n_rows must not be null"
+                            : cap && !items     ? "trew_hip_trace_results: items must not be null"
+                                                : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kTrace, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kTrace];
+    unsigned long long found[2] = {0, 0};
+    HIPCHK(ctx, hipMemcpy(found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
+    *n_items = found[0];
+    *n_rows = found[1];
+    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
+    if (records && st.n) HIPCHK(ctx, hipMemcpy(records, st.aligned.p, st.n * sizeof(trew_hip_alignment), hipMemcpyDeviceToHost));
+    const u64 take = std::min<u64>(found[0], cap);
+    if (found[0] <= st.max_log && found[1] <= st.max_rows && take) {  // an overflowed log holds an unspecified subset: nothing is copied
+        // sorted on the host, so the items do not depend on the order in which the waves appended them
+        if (take == found[0]) {
+            HIPCHK(ctx, hipMemcpy(items, st.records.p, take * sizeof(trew_hip_trace_item), hipMemcpyDeviceToHost));
+            sort_trace_items(items, take);
+        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
+            std::vector<trew_hip_trace_item> all((size_t) found[0]);
+            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found[0] * sizeof(trew_hip_trace_item), hipMemcpyDeviceToHost));
+            sort_trace_items(all.data(), found[0]);
+            memcpy(items, all.data(), take * sizeof(trew_hip_trace_item));
+        }
+    }
     return fetch_end(ctx, st, ms_kernel);
 }
 

@@ -171,6 +171,17 @@ struct RepeatLog {
     u64 cap;
 };
 
+// trew_hip_trace's item log and direction workspace (kernels/trace.inc): items of twelve u32 (trew_hip_trace_item), rows of 64
+// bytes (a direction byte a lane)
+struct TraceLog {
+    unsigned long long *counter;      // items found; keeps counting past cap
+    u32 *recs;                        // cap items
+    u64 cap;
+    unsigned long long *row_counter;  // rows claimed; keeps counting past max_rows
+    unsigned char *rows;              // max_rows rows
+    u64 max_rows;
+};
+
 struct Segment {
     u32 mate;   // 0 = first read of the unit, 1 = second (pair mode)
     u32 start;  // first base

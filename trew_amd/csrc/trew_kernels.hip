@@ -48,6 +48,7 @@
 //   align.inc          align_wave_kernel (indel-aware motif tract per read: wraparound alignment, the row of the table in registers, a phase per lane)
 //   refine.inc         refine_wave_kernel (de novo repeats under indels: periods.inc's period and tract, a seed unit from the longest run of eq_k, align.inc's row step for the alignment, the vote and the re-voted unit)
 //   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: repeats.inc's recursion over pieces with refine.inc's refine_piece per piece)
+//   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -90,6 +91,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/align.inc"
 #include "kernels/refine.inc"
 #include "kernels/tandems.inc"
+#include "kernels/trace.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -445,6 +447,15 @@ hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_p
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(tandems_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
+    return hipGetLastError();
+}
+
+// Units in place under indels: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, u32 min_score,
+                        const TraceLog &lg, trew_hip_alignment *d_out, u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(trace_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, min_score, lg, (u32 *) d_out, d_counts);
     return hipGetLastError();
 }
 

@@ -859,4 +859,153 @@ const char *tandems_host(const u32 *words, const u32 *offsets, const u32 *length
     return nullptr;
 }
 
+// ---------------------------------------------------------------- units in place under indels: the traceback of the alignment
+void sort_trace_items(trew_hip_trace_item *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_trace_item &a, const trew_hip_trace_item &b) {
+        if (a.read != b.read) return a.read < b.read;
+        if (a.motif != b.motif) return a.motif < b.motif;
+        if (a.strand != b.strand) return a.strand < b.strand;
+        return a.start < b.start;
+    });
+}
+
+// One strand of one motif over one read (trew_hip_trace_item, include/trew_hip.h): the full table with a direction byte a cell
+// (op of V in bits 0 .. 1: 0 fresh, 1 diagonal, 2 inserted read base; d of H above them), o = the record as in
+// align_codes_host, and the walk from the end cell when the score reaches min_score.  The walk meets the columns last to
+// first, so a segment closes at its first column, an item is known when its segment closes, and a run of complete exact
+// copies when a segment that is none closes behind it; the items are appended to `items` last to first.
+static void trace_codes_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 min_score, u32 (&o)[5],
+                             std::vector<unsigned char> &dirs, trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &items) {
+    AlignCell H[32], V[32];
+    for (int j = 0; j < k; j++) H[j] = AlignCell{0, 0, 0, 0};
+    dirs.assign(((size_t) n + 1) * (size_t) k, 0);
+    AlignCell best{0, 0, 0, 0};
+    u32 best_end = 0;
+    int best_j = 0;
+    for (u32 i = 1; i <= n; i++) {
+        const u32 c = base[i - 1];
+        unsigned char *row = dirs.data() + (size_t) i * (size_t) k;
+        for (int j = 0; j < k; j++) {
+            const AlignCell &d = H[(j + k - 1) % k];
+            const AlignCell diag = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
+                                             : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
+            const AlignCell ins{H[j].score - penalty, H[j].start, H[j].consumed, H[j].matches};
+            V[j] = AlignCell{0, i, 0, 0};  // rule 1: the fresh start, then the diagonal, then the inserted read base
+            if (V[j] < diag) V[j] = diag, row[j] = 1;
+            if (V[j] < ins) V[j] = ins, row[j] = 2;
+        }
+        for (int j = 0; j < k; j++) {
+            H[j] = V[j];
+            for (int d = 1; d < k; d++) {  // rule 2: the smallest d
+                const AlignCell &v = V[(j + k - d) % k];
+                const AlignCell cand{v.score - (long long) penalty * d, v.start, v.consumed + (u32) d, v.matches};
+                if (H[j] < cand) H[j] = cand, row[j] = (unsigned char) ((row[j] & 3) | (d << 2));
+            }
+        }
+        for (int j = 0; j < k; j++)  // rule 3: the smallest j
+            if (H[j].score > best.score || (H[j].score == best.score && best_end == i && best < H[j])) {
+                best = H[j];
+                best_end = i;
+                best_j = j;
+            }
+    }
+    if (best.score <= 0) {
+        for (u32 &x : o) x = 0;
+        return;
+    }
+    o[0] = (u32) best.score;
+    o[1] = best.start;
+    o[2] = best_end;
+    o[3] = best.consumed;
+    o[4] = best.matches;
+    if (o[0] < min_score) return;
+    u32 i = best_end, seg_end = best_end, consumed = 0, sub = 0, ins = 0, del = 0, phase = 0, cols = 0, run = 0, run_start = 0;
+    int j = best_j;
+    auto flush_run = [&]() {
+        if (!run) return;
+        trew_hip_trace_item it = proto;
+        it.start = run_start, it.bases = it.consumed = run * (u32) k, it.count = run;
+        items.push_back(it);
+        run = 0;
+    };
+    auto close = [&]() {  // the running segment begins at read base i
+        if (phase == 0 && consumed == (u32) k && !sub && !ins && !del) {
+            run++;
+            run_start = i;
+        } else {
+            flush_run();
+            trew_hip_trace_item it = proto;
+            it.start = i, it.bases = seg_end - i, it.count = 1, it.phase = phase, it.consumed = consumed;
+            it.mismatches = sub, it.insertions = ins, it.deletions = del;
+            items.push_back(it);
+        }
+        seg_end = i;
+        consumed = sub = ins = del = phase = cols = 0;
+    };
+    for (;;) {
+        const u32 d = dirs[(size_t) i * (size_t) k + (size_t) j] >> 2;
+        for (u32 q = 0; q < d; q++) {
+            phase = (u32) j;
+            consumed++, del++, cols++;
+            if (j == 0) close();
+            j = j ? j - 1 : k - 1;
+        }
+        const u32 op = dirs[(size_t) i * (size_t) k + (size_t) j] & 3u;
+        if (op == 0) break;
+        i--;
+        cols++;
+        if (op == 1) {
+            phase = (u32) j;
+            consumed++;
+            sub += base[i] != t[j];
+            if (j == 0) close();
+            j = j ? j - 1 : k - 1;
+        } else {
+            ins++;
+        }
+    }
+    if (cols) close();
+    flush_run();
+}
+
+const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
+                       int penalty, u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_alignment *records) {
+    if (const char *e = motifs_error(motifs, n_motifs)) return e;
+    if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
+    if (min_score < 1) return "min_score must be at least 1";
+    if (!n_items || (cap && !items)) return "trew_trace_host: null argument";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_trace_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_trace_host: more than 2^32 - 1 reads";
+    std::vector<unsigned char> base, dirs;
+    std::vector<trew_hip_trace_item> mine;
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        for (int m = 0; m < n_motifs; m++) {
+            const int k = motifs[m].k;
+            u32 rec[2][5];
+            for (int s = 0; s < 2; s++) {
+                const u64 target = s ? motif_revcomp(motifs[m].word, k) : motifs[m].word;
+                u32 t[32];
+                for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;  // first base most significant
+                mine.clear();
+                trace_codes_host(base.data(), lengths[r], t, k, penalty, min_score, rec[s], dirs,
+                                 trew_hip_trace_item{(u32) r, (u32) m, (u32) s, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mine);
+                for (size_t q = mine.size(); q-- > 0;) {  // last to first: ascending starts
+                    if (found < cap) items[found] = mine[q];
+                    found++;
+                }
+                if (counts) counts[(r * (u64) n_motifs + (u64) m) * 2ull + (u64) s] = (u32) mine.size();
+            }
+            if (records) {
+                trew_hip_alignment &o = records[r * (u64) n_motifs + (u64) m];
+                o.score_fwd = rec[0][0], o.start_fwd = rec[0][1], o.end_fwd = rec[0][2], o.consumed_fwd = rec[0][3], o.matches_fwd = rec[0][4];
+                o.score_rev = rec[1][0], o.start_rev = rec[1][1], o.end_rev = rec[1][2], o.consumed_rev = rec[1][3], o.matches_rev = rec[1][4];
+            }
+        }
+    }
+    *n_items = found;
+    return nullptr;
+}
+
 }  // namespace trew
