@@ -1,5 +1,5 @@
 """The file of tests/test_gpu_measure_cli.py -- one generated FASTQ of a few hundred KB that is cut into many chunks by a small
-TREW_MEASURE_CHUNK_BYTES -- and what the nine measure commands must print for it, formatted from the CPU definitions
+TREW_MEASURE_CHUNK_BYTES -- and what the twelve measure commands must print for it, formatted from the CPU definitions
 (capi.*_host) over the whole file, with file-wide ordinals, by the formatters of the measures' own tests."""
 import os
 import random
@@ -10,8 +10,11 @@ import align_ref
 import annot_ref
 import interval_ref
 import period_ref
+import refine_ref
 import repeat_ref
 import satellite_ref
+import tandem_ref
+import trace_ref
 import tract_ref
 import variant_ref
 from chain_cases import cli_lines as chain_cli_lines
@@ -23,15 +26,17 @@ SEED = 20260117
 CHUNK = 4096
 MOTIFS = ["TTAGGG", "AATGG"]
 SAT_MAX_PERIOD = 180  # keeps satellites_host short; the planted 171-mer is within it
-COMMANDS = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"]
-LOGGED = ["intervals", "chain", "repeats", "satellites"]  # the four with an append log that can overflow
+COMMANDS = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"]
+LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace"]  # the six with an append log that can overflow
 _RC = str.maketrans("ACGTacgt", "TGCAtgca")
 
 
 def command_line(name, paths):
     """arguments of `trew` for one command at its defaults"""
-    if name in ("periods", "repeats"):
+    if name in ("periods", "repeats", "refine", "tandems"):
         return [name, *paths]
+    if name == "trace":  # a row per item: the log's records themselves, in place
+        return [name, "--items", ",".join(MOTIFS), *paths]
     if name == "satellites":
         return [name, "--max_period", str(SAT_MAX_PERIOD), *paths]
     return [name, ",".join(MOTIFS), *paths]
@@ -154,7 +159,7 @@ def reads_of(data):
 
 
 def host_results(reads):
-    """the CPU definitions of the nine commands over the whole file, at the commands' defaults"""
+    """the CPU definitions of the twelve commands over the whole file, at the commands' defaults"""
     p = capi.pack_reads(reads)
     return {
         "annotate": capi.annotate_host(p, MOTIFS),
@@ -166,6 +171,9 @@ def host_results(reads):
         "repeats": capi.repeats_host(p),
         "satellites": capi.satellites_host(p, max_period=SAT_MAX_PERIOD),
         "align": capi.align_host(p, MOTIFS, 3),
+        "refine": capi.refine_host(p),
+        "tandems": capi.tandems_host(p),
+        "trace": capi.trace_host(p, MOTIFS, 3, 24),
     }
 
 
@@ -192,6 +200,12 @@ def _one_file(name, path, reads, res):
         return repeat_ref.cli_lines(real, reads, res[0])
     elif name == "satellites":
         return satellite_ref.cli_lines(real, reads, res[0])
+    elif name == "refine":
+        return refine_ref.cli_lines(path, reads, res, 3)
+    elif name == "tandems":
+        return tandem_ref.cli_lines(path, reads, res[0], 3)
+    elif name == "trace":
+        lines = trace_ref.cli_lines(path, reads, MOTIFS, res, 3, per_item=True)
     at = lines.index(">Summary")
     return lines[:at], lines[at:]
 
@@ -208,8 +222,10 @@ def expected(name, paths, reads, res):
         return sections[0][0] + sections[0][1]
     assert len(paths) == 2
     n = len(reads)
-    if name in ("annotate", "tracts", "align", "periods"):
+    if name in ("annotate", "tracts", "align", "periods", "refine"):
         both = np.concatenate([res, res])
+    elif name == "trace":
+        both = (_shifted(res[0], n), np.concatenate([res[1], res[1]]), np.concatenate([res[2], res[2]]))
     elif name == "intervals":
         both = (_shifted(res[0], n), np.concatenate([res[1], res[1]]))
     else:
@@ -224,8 +240,9 @@ def reported_reads(name, lines):
 
 
 def summary_keys(name, lines):
-    """(period, canonical) -> ordinals of the reads with such a row, from the rows of periods, repeats or satellites"""
-    col = 2 if name == "periods" else 3
+    """(period, canonical) -> ordinals of the reads with such a row, from the rows of periods, refine, repeats, satellites or
+    tandems"""
+    col = 2 if name in ("periods", "refine") else 3
     out = {}
     for ln in lines[2:lines.index(">Summary")]:
         f = ln.split(",")

@@ -1,4 +1,4 @@
-"""The file path all nine per-read measures share (host/process.cpp: process_annotate, the serial chunk reader, the
+"""The file path all twelve per-read measures share (host/process.cpp: process_annotate, the serial chunk reader, the
 workers' folds, add_totals and the sorts at the end) with many chunks a file: one generated FASTQ of a few hundred KB, cut
 by TREW_MEASURE_CHUNK_BYTES into about a hundred (4096) or a few hundred (1777) batches that one, three or sixteen workers
 share, must give byte for byte what the CPU definitions (capi.*_host) give over the whole file -- plain, gzip, BGZF, given
@@ -52,11 +52,14 @@ def run_cli(args, chunk=None, ok=True):
 
 def overflowing_chunks(f, name):
     """how many chunks hold more records of a logged measure than the first log of their batch takes (one record per read;
-    chain: four events per read, and an item takes at least one event -- so for chain a lower bound)"""
+    chain: four events per read, and an item takes at least one event -- so for chain a lower bound; trace: sixteen items per
+    read and motif and 1024 more, which no chunk of this file fills -- its workspace, a row per base and motif, none can)"""
     recs = f.host[name][0]
     per_read = [0] * len(f.reads)
     for r in recs["read"]:
         per_read[int(r)] += 1
+    if name == "trace":
+        return sum(1 for c in f.chunk_reads if sum(per_read[i] for i in c) > 16 * len(c) * len(M.MOTIFS) + 1024)
     room = 4 if name == "chain" else 1
     return sum(1 for c in f.chunk_reads if sum(per_read[i] for i in c) > room * len(c))
 
@@ -83,21 +86,22 @@ def test_the_file_and_its_borders_are_not_vacuous(the_file):
         assert 2 * sum(1 for c in f.chunk_reads if reported & set(c)) >= len(f.spans), name
         carried = sum(1 for (_, carried, _, _), c in zip(f.spans, f.chunk_reads) if carried > 0 and c and c[0] in reported)
         assert carried >= 10, name
+    assert overflowing_chunks(f, "trace") == 0 and len(f.host["trace"][0]) > 16 * len(f.reads)
     for name in M.LOGGED:
-        assert 0 < overflowing_chunks(f, name) and sum(1 for c in f.chunk_reads if c and not any(int(r) in set(c) for r in f.host[name][0]["read"])) > 0, name
+        assert (0 < overflowing_chunks(f, name) or name == "trace") and sum(1 for c in f.chunk_reads if c and not any(int(r) in set(c) for r in f.host[name][0]["read"])) > 0, name
         if name != "chain":
             assert overflowing_chunks(f, name) < batches
-    for name in ("periods", "repeats", "satellites"):
+    for name in ("periods", "repeats", "satellites", "refine", "tandems"):
         chunk_of = {i: n for n, c in enumerate(f.chunk_reads) for i in c}
         keys = M.summary_keys(name, f.want[name])
         assert len(f.want[name]) - f.want[name].index(">Summary") - 2 == len(keys) >= 3
         assert sum(1 for who in keys.values() if len({chunk_of[i] for i in who}) >= 2) >= 3, name
     assert any(k[0] == "171" for k in M.summary_keys("satellites", f.want["satellites"]))
     # rows of both motifs and both strands, so that no sort key of the merged rows is idle
-    for name in ("annotate", "tracts", "intervals", "variants", "chain", "align"):
+    for name in ("annotate", "tracts", "intervals", "variants", "chain", "align", "trace"):
         rows = f.want[name][2:f.want[name].index(">Summary")]
         assert all(sum(1 for ln in rows if "," + m + "," in ln) >= 20 for m in M.MOTIFS), name
-    for name in ("intervals", "chain", "align"):
+    for name in ("intervals", "chain", "align", "trace"):
         rows = f.want[name][2:f.want[name].index(">Summary")]
         assert all(sum(1 for ln in rows if "," + s + "," in ln) >= 20 for s in "+-"), name
 
@@ -115,7 +119,7 @@ def test_many_chunks_one_to_sixteen_workers(the_file, name, chunk):
             assert "%d batch(es) submitted, chunk length %d bytes" % (batches, chunk or 1 << 22) in r.stderr
             if name in M.LOGGED and chunk == M.CHUNK:
                 resubmitted = int(re.search(r"(\d+) batch\(es\) resubmitted with a larger log", r.stderr).group(1))
-                assert 0 < resubmitted < batches, (name, resubmitted, batches)
+                assert 0 < resubmitted < batches or name == "trace", (name, resubmitted, batches)
                 if name != "chain":
                     assert resubmitted == overflowing_chunks(f, name)
                 else:

@@ -1,4 +1,4 @@
-"""The per-measure state of a slot (trew_capi.cpp: MeasureState, stage_motifs, grow, the log counters): the nine per-read
+"""The per-measure state of a slot (trew_capi.cpp: MeasureState, stage_motifs, grow, the log counters): the twelve per-read
 measures queued back to back on one slot, each with a motif list (or none) and a batch of its own, keep their results apart;
 the pattern tables are restaged exactly when they have to be; every buffer grows when a larger batch comes and carries nothing
 over to the next call; a log that overflowed leaves nothing behind for the next call; a results call without its queue call
@@ -12,7 +12,7 @@ from trew_amd import capi
 pytestmark = pytest.mark.gpu
 
 # lists of 1, 2, 8 and 3 motifs with k = 3, 6 and 32 among them.  stage_motifs skips a list that is a prefix of what the slot
-# holds, so no list here is a prefix of the one queued in front of it (annotate follows align in the rounds of the grow
+# holds, so no list here is a prefix of the one queued in front of it (annotate follows trace in the rounds of the grow
 # test): every call restages, variants with fewer motifs than are staged.  test_pattern_tables_are_restaged_when_they_must_be
 # takes the other path on purpose
 MOTIFS = {
@@ -22,6 +22,7 @@ MOTIFS = {
     "variants": [K32, "TTG", "TTAGGG"],
     "chain": ["TTAGGG", "TTG"],
     "align": [K32],
+    "trace": ["TTG", "TTAGGG"],
 }
 # the lists of the second sequence: other lengths, other motifs, k = 3 and k = 32 again
 MOTIFS_B = {
@@ -31,11 +32,13 @@ MOTIFS_B = {
     "variants": ["TTAGGG", "TCAGGG", "TTG", K32, "GGGTTA"],
     "chain": [K32],
     "align": ["TTG", "TTAGGG", "TTAGG", "AATGG"],
+    "trace": ["TTAGGG", K32],
 }
-ORDER = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align"]  # of the queue calls in sequence_a
+ORDER = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"]  # of the queue calls in sequence_a
 WITH_MOTIFS = [name for name in ORDER if name in MOTIFS]
-LOGGED = ["intervals", "chain", "repeats", "satellites"]  # the measures with an append log and a counter
+LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace"]  # the measures with an append log and a counter
 ROOMY = 1 << 16  # a log no batch of this file fills
+ROOMY_ROWS = 1 << 18  # a trace workspace (64 bytes a row) no batch of this file fills
 READS = make_reads()
 SMALL = [READS[i] for i in (23, 29, 17, 11)]  # 65, 2017, 33 and 6 bases
 
@@ -56,10 +59,23 @@ class Expected:
         motifs = MOTIFS.get(name) if motifs is None else motifs
         key = (name, tuple(motifs or ()))
         if key not in self._host:
-            extra = {"tracts": (3,), "align": (3,)}.get(name, ())
+            extra = {"tracts": (3,), "align": (3,), "trace": (3, 24)}.get(name, ())
             f = getattr(capi, name + "_host")
             self._host[key] = f(self.packed, *(() if motifs is None else (motifs,)), *extra)
         return self._host[key]
+
+    def found(self, name, motifs=None):
+        """the records (chain, trace: items) of a logged measure, as its host definition counts them"""
+        return self.host(name, motifs)[3 if name == "trace" else 2]
+
+    def trace_rows(self, motifs=None):
+        """the workspace rows trace claims: for every (read, motif) with a strand whose score reaches min_score, the bases
+        from the first start to the last end of those strands"""
+        a = self.host("trace", motifs)[2].astype([(f, "<i8") for f in capi.ALIGN_DTYPE.names])
+        fwd, rev = a["score_fwd"] >= 24, a["score_rev"] >= 24
+        lo = np.minimum(np.where(fwd, a["start_fwd"], 1 << 40), np.where(rev, a["start_rev"], 1 << 40))
+        hi = np.maximum(np.where(fwd, a["end_fwd"], 0), np.where(rev, a["end_rev"], 0))
+        return int((hi - lo)[fwd | rev].sum())
 
 
 @pytest.fixture(scope="module")
@@ -78,18 +94,21 @@ def same(got, want, what):
     assert got.tobytes() == want.tobytes(), "%s differs at %s" % (what, np.argwhere(got != want)[:1].tolist())
 
 
-def queue(t, name, e, motifs=None, cap=ROOMY, slot=0):
-    """one queue call of measure `name` for the batch of `e`; cap: the log of the four logged measures"""
+def queue(t, name, e, motifs=None, cap=ROOMY, slot=0, rows=ROOMY_ROWS):
+    """one queue call of measure `name` for the batch of `e`; cap: the log of the six logged measures; rows: the workspace
+    of trace"""
     b = t.host_batch(*e.packed)
     motifs = MOTIFS.get(name) if motifs is None else motifs
     if name == "intervals":
         t.intervals(b, motifs, max_intervals=cap, slot=slot)
     elif name == "chain":
         t.chain(b, motifs, max_events=cap, slot=slot)
-    elif name in ("repeats", "satellites"):
+    elif name in ("repeats", "satellites", "tandems"):
         getattr(t, name)(b, max_records=cap, slot=slot)
-    elif name == "periods":
-        t.periods(b, slot=slot)
+    elif name in ("periods", "refine"):
+        getattr(t, name)(b, slot=slot)
+    elif name == "trace":
+        t.trace(b, motifs, 3, 24, max_items=cap, max_rows=rows, slot=slot)
     elif name in ("tracts", "align"):
         getattr(t, name)(b, motifs, 3, slot=slot)
     else:
@@ -98,20 +117,24 @@ def queue(t, name, e, motifs=None, cap=ROOMY, slot=0):
 
 def fetch(t, name, e, motifs=None, slot=0, overflowed=False):
     """the results call of `name`, compared with the host definition of the batch of `e`.  overflowed: the log was too small --
-    the counts and the numbers found are exact all the same; intervals keeps as many records as the log held, the other three
-    none"""
+    the counts and the numbers found are exact all the same; intervals keeps as many records as the log held, the other five
+    none (trace: its log or its workspace was too small; its alignment records and its rows are exact as well)"""
     want = e.host(name, motifs)
     what = "%s (slot %d)" % (name, slot)
     got = getattr(t, name + "_results")(slot=slot)
-    if name in ("annotate", "tracts", "align", "periods"):
+    if name in ("annotate", "tracts", "align", "periods", "refine"):
         same(got, want, what)
     elif name == "variants":
         for g, w, part in zip(got, want, ("records", "hist", "reads_with")):
             same(g, w, what + " " + part)
     else:
-        recs, counts, found = got[:3]
-        assert found == want[2], what
+        recs, counts = got[:2]
+        found = got[3 if name == "trace" else 2]
+        assert found == e.found(name, motifs), what
         same(counts, want[1], what + " counts")
+        if name == "trace":
+            same(got[2], want[2], what + " alignment records")
+            assert got[4] == e.trace_rows(motifs), what
         if name == "chain":
             assert got[3] >= found, what  # an item takes at least one event
         if not overflowed:
@@ -124,7 +147,7 @@ def fetch(t, name, e, motifs=None, slot=0, overflowed=False):
 
 
 def sequence_a(t, e):
-    """the nine measures queued back to back on slot 0, fetched in reverse order; returns the variants histograms"""
+    """the twelve measures queued back to back on slot 0, fetched in reverse order; returns the variants histograms"""
     found = e.intervals[2]
     for name in ORDER:
         queue(t, name, e, cap=max(found, 1) if name == "intervals" else ROOMY)
@@ -146,7 +169,7 @@ def test_results_call_without_its_queue_call_fails():
     """first in the file: needs a context of its own on which nothing was queued"""
     with capi.TrewHip(mode=capi.MODE_SHORT, n_slots=1, max_batch_words=1 << 12, max_batch_reads=16, table_log2_slots=12) as fresh:
         fetch = {name: getattr(fresh, name + "_results") for name in ORDER}
-        assert len(fetch) == 9
+        assert len(fetch) == 12
         for name, f in fetch.items():
             with pytest.raises(capi.TrewHipError, match="no trew_hip_%s on this slot yet" % name):
                 f()
@@ -160,18 +183,22 @@ def test_results_call_without_its_queue_call_fails():
 def test_the_expected_results_are_not_trivial(expected):
     e = expected["full"]
     assert len(READS) == 40 and e.intervals[2] > len(READS)
-    for i, name in enumerate(WITH_MOTIFS):  # no list is a prefix of the one staged in front of it, round after round
-        assert MOTIFS[WITH_MOTIFS[i - 1]][:len(MOTIFS[name])] != MOTIFS[name], name
+    assert WITH_MOTIFS[-1] == "trace" and set(MOTIFS) == set(MOTIFS_B) == set(WITH_MOTIFS)
+    for lists in (MOTIFS, MOTIFS_B):
+        for i, name in enumerate(WITH_MOTIFS):  # no list is a prefix of the one staged in front of it, round after round
+            assert lists[WITH_MOTIFS[i - 1]][:len(lists[name])] != lists[name], name
     assert e.annotate["windows_fwd"].sum() > 1000 and e.annotate["windows_rev"].sum() > 1000
     assert all((e.tracts["head_len_fwd"][:, m] > 0).any() for m in range(2))
     assert all(e.variants[1][m].sum() > 0 for m in range(3))
     assert all((e.intervals[1][:, m] > 0).any() for m in range(4))
-    # the five newer measures: records on both batches, and more than the one record (chain: event) of the overflow test's log
+    # the eight newer measures: records on both batches, and more than the one record (chain: event) of the overflow test's log
     for key in ("small", "full"):
         x = expected[key]
-        assert (x.host("periods")["period"] > 0).sum() >= 2
+        assert (x.host("periods")["period"] > 0).sum() >= 2 and (x.host("refine")["period"] > 0).sum() >= 2
         for name in LOGGED:
-            assert 2 * x.n // 5 < x.host(name)[2] < ROOMY // 8, (key, name)
+            assert 2 * x.n // 5 < x.found(name) < ROOMY // 8, (key, name)
+        assert x.found("tandems") > 1 and x.found("trace") > 1
+        assert 1 < x.trace_rows() and max(x.trace_rows(), x.trace_rows(MOTIFS_B["trace"])) < ROOMY_ROWS // 2
         assert all((x.host("chain")[1][:, m] > 0).any() for m in range(2))
     assert (e.host("align")["score_fwd"] > 24).any() and (e.host("align")["score_rev"] > 24).any()
     assert len({r["period"] for r in e.host("satellites")[0]}) >= 3 and len({r["period"] for r in e.host("repeats")[0]}) >= 3
@@ -181,13 +208,13 @@ def test_the_expected_results_are_not_trivial(expected):
 
 
 def test_four_measures_back_to_back_on_one_slot(t, expected):
-    """(all nine since the five newer ones came; the name is the one the test has always had)"""
+    """(all twelve since the eight newer ones came; the name is the one the test has always had)"""
     sequence_a(t, expected["full"])
 
 
 def test_alternating_batches_and_other_motif_lists(t, expected):
     """consecutive calls use different batches (the small and the full one in turn) and the lists of MOTIFS_B; nothing is
-    fetched until all nine are queued, then in the order of the queue calls"""
+    fetched until all twelve are queued, then in the order of the queue calls"""
     batch = {name: expected["small" if i % 2 == 0 else "full"] for i, name in enumerate(ORDER)}
     for name in ORDER:
         queue(t, name, batch[name], MOTIFS_B.get(name))
@@ -238,13 +265,29 @@ def test_a_log_that_overflowed_leaves_nothing_behind(t, expected, name):
         queue(t, name, e, cap=1)
         fetch(t, name, e, overflowed=True)
         queue(t, other, e)
-        queue(t, name, e, cap=e.host(name)[2] if name != "chain" else ROOMY)
+        queue(t, name, e, cap=e.found(name) if name != "chain" else ROOMY)
         fetch(t, name, e)
         fetch(t, other, e)
     # queued back to back without a fetch in between: the second call's counter starts at zero
     queue(t, name, expected["full"], cap=1)
     queue(t, name, expected["small"])
     fetch(t, name, expected["small"])
+
+
+def test_a_trace_workspace_that_overflowed_leaves_nothing_behind(t, expected):
+    """the overflow test once more for trace's second counter: a log with room and a workspace of one row, another measure's
+    call, then room for both -- exactly the rows the first call reported"""
+    for key in ("full", "small", "full"):
+        e = expected[key]
+        queue(t, "trace", e, rows=1)
+        fetch(t, "trace", e, overflowed=True)
+        queue(t, "align", e)
+        queue(t, "trace", e, cap=e.found("trace"), rows=e.trace_rows())
+        fetch(t, "trace", e)
+        fetch(t, "align", e)
+    queue(t, "trace", expected["full"], rows=1)
+    queue(t, "trace", expected["small"])
+    fetch(t, "trace", expected["small"])
 
 
 def test_buffers_grow_and_nothing_accumulates(expected):
@@ -258,7 +301,7 @@ def test_buffers_grow_and_nothing_accumulates(expected):
 
 
 def test_two_slots_interleaved(expected):
-    """the nine measures on slots 0 and 1, interleaved call by call with different batches and motif lists; slot 1 is fetched
+    """the twelve measures on slots 0 and 1, interleaved call by call with different batches and motif lists; slot 1 is fetched
     first, in reverse order"""
     with capi.TrewHip(mode=capi.MODE_SHORT, n_slots=2, max_batch_words=1 << 14, max_batch_reads=64, table_log2_slots=12) as ctx:
         for name in ORDER:

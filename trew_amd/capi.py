@@ -468,6 +468,23 @@ def _rule_array(arr, nm, max_gap, min_len):
     return rules
 
 
+def _sized_call(call, dtype, cap):
+    """The log of a host definition: call(ptr, room, n) fills the buffer at `ptr` (None: no buffer) with up to `room` records and
+    sets n (a c_uint64) to the number found.  With `cap` one call into a `dtype` buffer of that size; without, a first call that
+    only counts and a second one into a buffer of exactly that size.  Returns (the records in the buffer, found)."""
+    n = C.c_uint64(0)
+    out = np.zeros(0 if cap is None else int(cap), dtype=dtype)
+    call(out.ctypes.data if len(out) else None, len(out), n)
+    if cap is None and n.value:
+        out = np.zeros(int(n.value), dtype=dtype)
+        call(out.ctypes.data, len(out), n)
+    return out[:min(len(out), int(n.value))], int(n.value)
+
+
+def _host_fail(what):
+    raise TrewHipError("%s failed: %s" % (what, load().trew_hip_last_error(None).decode()))
+
+
 def intervals_host(reads_or_packed, motifs, max_gap=None, min_len=None, cap=None):
     """trew_intervals_host: the gap-tolerant motif intervals computed on the host, base by base from the definition.
     reads_or_packed as for annotate_host; max_gap / min_len as for TrewHip.intervals.  Returns (INTERVAL_DTYPE records sorted
@@ -477,19 +494,14 @@ def intervals_host(reads_or_packed, motifs, max_gap=None, min_len=None, cap=None
     arr, nm = _motif_array(motifs)
     rules = _rule_array(arr, min(max(nm, 0), MAX_MOTIFS), max_gap, min_len)
     counts = np.zeros((len(offsets), max(nm, 1), 2), dtype=np.uint32)
-    n = C.c_uint64(0)
 
-    def call(out):
+    def call(ptr, room, n):
         if lib.trew_intervals_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, rules, nm,
-                                   out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
-            raise TrewHipError("trew_intervals_host failed: %s" % lib.trew_hip_last_error(None).decode())
+                                   ptr, room, C.byref(n), counts.ctypes.data) != 0:
+            _host_fail("trew_intervals_host")
 
-    out = np.zeros(0 if cap is None else int(cap), dtype=INTERVAL_DTYPE)
-    call(out)
-    if cap is None and n.value:
-        out = np.zeros(int(n.value), dtype=INTERVAL_DTYPE)
-        call(out)
-    return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
+    out, found = _sized_call(call, INTERVAL_DTYPE, cap)
+    return out, counts[:, :nm], found
 
 
 def chain_host(reads_or_packed, motifs, cap=None):
@@ -500,19 +512,14 @@ def chain_host(reads_or_packed, motifs, cap=None):
     words, offsets, lengths = _packed(reads_or_packed)
     arr, nm = _motif_array(motifs)
     counts = np.zeros((len(offsets), max(nm, 1), 2, 2), dtype=np.uint32)
-    n = C.c_uint64(0)
 
-    def call(out):
+    def call(ptr, room, n):
         if lib.trew_chain_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm,
-                               out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
-            raise TrewHipError("trew_chain_host failed: %s" % lib.trew_hip_last_error(None).decode())
+                               ptr, room, C.byref(n), counts.ctypes.data) != 0:
+            _host_fail("trew_chain_host")
 
-    out = np.zeros(0 if cap is None else int(cap), dtype=CHAIN_DTYPE)
-    call(out)
-    if cap is None and n.value:
-        out = np.zeros(int(n.value), dtype=CHAIN_DTYPE)
-        call(out)
-    return out[:min(len(out), int(n.value))], counts[:, :nm], int(n.value)
+    out, found = _sized_call(call, CHAIN_DTYPE, cap)
+    return out, counts[:, :nm], found
 
 
 def trace_host(reads_or_packed, motifs, penalty=3, min_score=24, cap=None):
@@ -525,19 +532,15 @@ def trace_host(reads_or_packed, motifs, penalty=3, min_score=24, cap=None):
     arr, nm = _motif_array(motifs)
     counts = np.zeros((len(offsets), max(nm, 1), 2), dtype=np.uint32)
     records = np.zeros((len(offsets), max(nm, 1)), dtype=ALIGN_DTYPE)
-    n = C.c_uint64(0)
 
-    def call(out):
+    def call(ptr, room, n):
         if lib.trew_trace_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), int(min_score),
-                               out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data, records.ctypes.data) != 0:
-            raise TrewHipError("trew_trace_host failed: %s" % lib.trew_hip_last_error(None).decode())
+                               ptr, room, C.byref(n), counts.ctypes.data,
+                               records.ctypes.data) != 0:
+            _host_fail("trew_trace_host")
 
-    out = np.zeros(0 if cap is None else int(cap), dtype=TRACE_DTYPE)
-    call(out)
-    if cap is None and n.value:
-        out = np.zeros(int(n.value), dtype=TRACE_DTYPE)
-        call(out)
-    return out[:min(len(out), int(n.value))], counts[:, :nm], records[:, :nm], int(n.value)
+    out, found = _sized_call(call, TRACE_DTYPE, cap)
+    return out, counts[:, :nm], records[:, :nm], found
 
 
 _TRACE_COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
@@ -568,26 +571,26 @@ def trace_signature(items, read, k):
     return units, edited, " ".join(tokens)
 
 
+def _tracts_host(name, dtype, reads_or_packed, min_period, max_period, penalty, min_score, cap):
+    """trew_repeats_host, trew_satellites_host and trew_tandems_host, which differ in the record only"""
+    f = getattr(load(), name)
+    words, offsets, lengths = _packed(reads_or_packed)
+    counts = np.zeros(len(offsets), dtype=np.uint32)
+
+    def call(ptr, room, n):
+        if f(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period), int(penalty), int(min_score),
+             ptr, room, C.byref(n), counts.ctypes.data) != 0:
+            _host_fail(name)
+
+    out, found = _sized_call(call, dtype, cap)
+    return out, counts, found
+
+
 def repeats_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
     """trew_repeats_host: every de novo repeat tract of every read computed on the host, piece by piece from the definition.
     reads_or_packed as for annotate_host.  Returns (REPEAT_DTYPE records sorted by (read, start), counts of shape (n_reads,),
     found); with `cap` at most that many records."""
-    lib = load()
-    words, offsets, lengths = _packed(reads_or_packed)
-    counts = np.zeros(len(offsets), dtype=np.uint32)
-    n = C.c_uint64(0)
-
-    def call(out):
-        if lib.trew_repeats_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
-                                 int(penalty), int(min_score), out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
-            raise TrewHipError("trew_repeats_host failed: %s" % lib.trew_hip_last_error(None).decode())
-
-    out = np.zeros(0 if cap is None else int(cap), dtype=REPEAT_DTYPE)
-    call(out)
-    if cap is None and n.value:
-        out = np.zeros(int(n.value), dtype=REPEAT_DTYPE)
-        call(out)
-    return out[:min(len(out), int(n.value))], counts, int(n.value)
+    return _tracts_host("trew_repeats_host", REPEAT_DTYPE, reads_or_packed, min_period, max_period, penalty, min_score, cap)
 
 
 def refine_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24):
@@ -608,22 +611,7 @@ def tandems_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sc
     definition (the refined record of a piece, then what lies in front of its tract and behind it).  reads_or_packed as for
     annotate_host.  Returns (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,), found); with `cap` at most
     that many records."""
-    lib = load()
-    words, offsets, lengths = _packed(reads_or_packed)
-    counts = np.zeros(len(offsets), dtype=np.uint32)
-    n = C.c_uint64(0)
-
-    def call(out):
-        if lib.trew_tandems_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
-                                 int(penalty), int(min_score), out.ctypes.data if len(out) else None, len(out), C.byref(n), counts.ctypes.data) != 0:
-            raise TrewHipError("trew_tandems_host failed: %s" % lib.trew_hip_last_error(None).decode())
-
-    out = np.zeros(0 if cap is None else int(cap), dtype=TANDEM_DTYPE)
-    call(out)
-    if cap is None and n.value:
-        out = np.zeros(int(n.value), dtype=TANDEM_DTYPE)
-        call(out)
-    return out[:min(len(out), int(n.value))], counts, int(n.value)
+    return _tracts_host("trew_tandems_host", TANDEM_DTYPE, reads_or_packed, min_period, max_period, penalty, min_score, cap)
 
 
 def refine_columns(record, penalty):
@@ -646,23 +634,7 @@ def satellites_host(reads_or_packed, min_period=1, max_period=SATELLITE_MAX_PERI
     """trew_satellites_host: repeats_host with periods up to 256 and SATELLITE_DTYPE records (unit: sixteen words, see
     satellite_unit_text).  Returns (records sorted by (read, start), counts of shape (n_reads,), found); with `cap` at most that
     many records."""
-    lib = load()
-    words, offsets, lengths = _packed(reads_or_packed)
-    counts = np.zeros(len(offsets), dtype=np.uint32)
-    n = C.c_uint64(0)
-
-    def call(out):
-        if lib.trew_satellites_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
-                                    int(penalty), int(min_score), out.ctypes.data if len(out) else None, len(out), C.byref(n),
-                                    counts.ctypes.data) != 0:
-            raise TrewHipError("trew_satellites_host failed: %s" % lib.trew_hip_last_error(None).decode())
-
-    out = np.zeros(0 if cap is None else int(cap), dtype=SATELLITE_DTYPE)
-    call(out)
-    if cap is None and n.value:
-        out = np.zeros(int(n.value), dtype=SATELLITE_DTYPE)
-        call(out)
-    return out[:min(len(out), int(n.value))], counts, int(n.value)
+    return _tracts_host("trew_satellites_host", SATELLITE_DTYPE, reads_or_packed, min_period, max_period, penalty, min_score, cap)
 
 
 def satellite_unit_text(unit, period):
@@ -731,6 +703,22 @@ def synth_long_ascii(seed, first_read, n_reads):
     st_u64 = np.ascontiguousarray(st, dtype=np.uint64)  # keep the array alive across the call
     lib.trew_synth_long_ascii(seed, first_read, n_reads, st_u64.ctypes.data, out.ctypes.data)
     return out.tobytes(), st, st + lens - 1
+
+
+def _trace_room(batch, nm, max_items, max_rows):
+    """(max_items, max_rows) of a trace call with the defaults of TrewHip.trace filled in"""
+    if max_items is None:
+        max_items = max(4 * int(batch.n_reads) * nm, 1)
+    if max_rows is None:
+        n = int(batch.n_reads)
+        if not batch.lengths:  # uniform reads
+            bases = n * int(batch.uniform_length)
+        elif not batch.on_device:
+            bases = int(np.ctypeslib.as_array(C.cast(batch.lengths, C.POINTER(C.c_uint32)), shape=(n,)).sum(dtype=np.uint64)) if n else 0
+        else:
+            bases = 256 * n  # lengths in device memory: a guess, the results say when it was too small
+        max_rows = max(bases * nm, 1)
+    return int(max_items), int(max_rows)
 
 
 class TrewHip:
@@ -852,6 +840,31 @@ class TrewHip:
             raise TrewHipError("%s: %d records, expected %d" % (what, n.value, n_reads * nm))
         return (out,) + extra + ((ms.value,) if want_ms else ())
 
+    def _fetch_log(self, measure, slot, dtype, want_ms, counts_shape=lambda n_reads, nm: (n_reads,), partial=False):
+        """The append log of the slot's last intervals, repeats, tandems or satellites: (records, counts, found [, kernel ms]).
+        The log is read once, into a buffer of exactly what it holds: a first call for `found` and the counts, a second one for the
+        records.  found > the call's capacity: no records, or with `partial` (intervals) as many as the log held."""
+        n = C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm, cap = self._queued.get((measure, slot), (0, 1, 0))
+        counts = np.zeros(counts_shape(n_reads, nm), dtype=np.uint32)
+        what = "trew_hip_%s_results" % measure
+        results = getattr(self.lib, what)
+        self._chk(results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None), what)
+        found = int(n.value)
+        out = np.zeros(found if found <= cap else cap if partial else 0, dtype=dtype)
+        if len(out):
+            self._chk(results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), what)
+        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+
+    def _queue_tracts(self, measure, batch, min_period, max_period, penalty, min_score, max_records, slot):
+        """the queue call of repeats, tandems and satellites; max_records: default the batch's read count, at least 1"""
+        if max_records is None:
+            max_records = max(int(batch.n_reads), 1)
+        self._queue(measure, slot, batch, None, 1, shape=(int(max_records),))
+        what = "trew_hip_%s" % measure
+        self._chk(getattr(self.lib, what)(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score), int(max_records)), what)
+
     def annotate(self, batch, motifs, slot=0):
         """Queue the annotation of every read of `batch` against `motifs` (texts or Motif, at most 8) on the slot's stream."""
         arr, nm = _motif_array(motifs)
@@ -938,18 +951,7 @@ class TrewHip:
         """Results of the slot's last intervals: (INTERVAL_DTYPE records sorted by (read, motif, strand, start), counts of
         shape (n_reads, n_motifs, 2), found [, kernel ms]).  found > max_intervals: the records are a subset (as many as the
         log held), counts and found are exact; repeat the call with max_intervals >= found."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, nm, cap = self._queued.get(("intervals", slot), (0, 1, 0))
-        counts = np.zeros((n_reads, nm, 2), dtype=np.uint32)
-        # the log is read once, into a buffer of its capacity or of the sum of the counts, whichever is smaller
-        self._chk(self.lib.trew_hip_intervals_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
-                  "trew_hip_intervals_results")
-        found = int(n.value)
-        out = np.zeros(min(found, cap), dtype=INTERVAL_DTYPE)
-        if len(out):
-            self._chk(self.lib.trew_hip_intervals_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_intervals_results")
-        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+        return self._fetch_log("intervals", slot, INTERVAL_DTYPE, want_ms, lambda n_reads, nm: (n_reads, nm, 2), partial=True)
 
     def chain(self, batch, motifs, max_events=None, slot=0):
         """Queue the ordered unit chain of every read of `batch` for `motifs` (texts or Motif, at most 8, taken as typed) on
@@ -985,17 +987,7 @@ class TrewHip:
         is the default where the lengths are known on the host (256 per read and motif for ragged device-resident batches); a
         tract whose rows do not fit costs time quadratic in its length."""
         arr, nm = _motif_array(motifs)
-        if max_items is None:
-            max_items = max(4 * int(batch.n_reads) * nm, 1)
-        if max_rows is None:
-            n = int(batch.n_reads)
-            if not batch.lengths:  # uniform reads
-                bases = n * int(batch.uniform_length)
-            elif not batch.on_device:
-                bases = int(np.ctypeslib.as_array(C.cast(batch.lengths, C.POINTER(C.c_uint32)), shape=(n,)).sum(dtype=np.uint64)) if n else 0
-            else:
-                bases = 256 * n  # lengths in device memory: a guess, the results say when it was too small
-            max_rows = max(bases * nm, 1)
+        max_items, max_rows = _trace_room(batch, nm, max_items, max_rows)
         self._queue("trace", slot, batch, arr, nm, shape=(int(max_items), int(max_rows)))
         self._chk(self.lib.trew_hip_trace(self.ctx, C.byref(batch), slot, arr, nm, int(penalty), int(min_score), int(max_items), int(max_rows)),
                   "trew_hip_trace")
@@ -1021,78 +1013,35 @@ class TrewHip:
     def repeats(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract of every read of `batch` on the slot's stream (no motifs).  max_records: the
         capacity of the log for this call (default: the batch's read count, at least 1)."""
-        if max_records is None:
-            max_records = max(int(batch.n_reads), 1)
-        self._queue("repeats", slot, batch, None, 1, shape=(int(max_records),))
-        self._chk(self.lib.trew_hip_repeats(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
-                                            int(max_records)), "trew_hip_repeats")
+        self._queue_tracts("repeats", batch, min_period, max_period, penalty, min_score, max_records, slot)
 
     def repeats_results(self, slot=0, want_ms=False):
         """Results of the slot's last repeats: (REPEAT_DTYPE records sorted by (read, start), counts of shape (n_reads,), found
         [, kernel ms]).  found > max_records: no records, counts and found are exact; repeat the call with max_records >=
         found."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, _, cap = self._queued.get(("repeats", slot), (0, 1, 0))
-        counts = np.zeros(n_reads, dtype=np.uint32)
-        self._chk(self.lib.trew_hip_repeats_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
-                  "trew_hip_repeats_results")
-        found = int(n.value)
-        out = np.zeros(found if found <= cap else 0, dtype=REPEAT_DTYPE)
-        if len(out):
-            self._chk(self.lib.trew_hip_repeats_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_repeats_results")
-        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+        return self._fetch_log("repeats", slot, REPEAT_DTYPE, want_ms)
 
     def tandems(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract under indels of every read of `batch` on the slot's stream (no motifs).
         max_records: the capacity of the log for this call (default: the batch's read count, at least 1)."""
-        if max_records is None:
-            max_records = max(int(batch.n_reads), 1)
-        self._queue("tandems", slot, batch, None, 1, shape=(int(max_records),))
-        self._chk(self.lib.trew_hip_tandems(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
-                                            int(max_records)), "trew_hip_tandems")
+        self._queue_tracts("tandems", batch, min_period, max_period, penalty, min_score, max_records, slot)
 
     def tandems_results(self, slot=0, want_ms=False):
         """Results of the slot's last tandems: (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,), found
         [, kernel ms]).  found > max_records: no records, counts and found are exact; repeat the call with max_records >=
         found."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, _, cap = self._queued.get(("tandems", slot), (0, 1, 0))
-        counts = np.zeros(n_reads, dtype=np.uint32)
-        self._chk(self.lib.trew_hip_tandems_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
-                  "trew_hip_tandems_results")
-        found = int(n.value)
-        out = np.zeros(found if found <= cap else 0, dtype=TANDEM_DTYPE)
-        if len(out):
-            self._chk(self.lib.trew_hip_tandems_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), "trew_hip_tandems_results")
-        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+        return self._fetch_log("tandems", slot, TANDEM_DTYPE, want_ms)
 
     def satellites(self, batch, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract with a period of up to 256 of every read of `batch` on the slot's stream (no
         motifs).  max_records: the capacity of the log for this call (default: the batch's read count, at least 1)."""
-        if max_records is None:
-            max_records = max(int(batch.n_reads), 1)
-        self._queue("satellites", slot, batch, None, 1, shape=(int(max_records),))
-        self._chk(self.lib.trew_hip_satellites(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
-                                               int(max_records)), "trew_hip_satellites")
+        self._queue_tracts("satellites", batch, min_period, max_period, penalty, min_score, max_records, slot)
 
     def satellites_results(self, slot=0, want_ms=False):
         """Results of the slot's last satellites: (SATELLITE_DTYPE records sorted by (read, start), counts of shape (n_reads,),
         found [, kernel ms]).  found > max_records: no records, counts and found are exact; repeat the call with max_records
         >= found."""
-        n = C.c_uint64(0)
-        ms = C.c_float(0)
-        n_reads, _, cap = self._queued.get(("satellites", slot), (0, 1, 0))
-        counts = np.zeros(n_reads, dtype=np.uint32)
-        self._chk(self.lib.trew_hip_satellites_results(self.ctx, slot, None, 0, C.byref(n), counts.ctypes.data, C.byref(ms) if want_ms else None),
-                  "trew_hip_satellites_results")
-        found = int(n.value)
-        out = np.zeros(found if found <= cap else 0, dtype=SATELLITE_DTYPE)
-        if len(out):
-            self._chk(self.lib.trew_hip_satellites_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None),
-                      "trew_hip_satellites_results")
-        return (out, counts, found, ms.value) if want_ms else (out, counts, found)
+        return self._fetch_log("satellites", slot, SATELLITE_DTYPE, want_ms)
 
     def submit_reads(self, reads, slot=0):
         b = self.host_batch(*pack_reads(reads))
@@ -1262,23 +1211,41 @@ def k_mer_check(seq, min_mer=5, max_mer=32, low=0.5, high=0.8, flags=0, device=0
                 hist_high=tabs["forward_high"], hist_low=tabs["forward_low"])
 
 
+def _one_batch(reads, device):
+    """(a context sized for `reads`, their batch) of the one-shot wrappers below; the caller closes the context"""
+    words, offsets, lengths = pack_reads(reads)
+    t = TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
+                max_batch_reads=max(len(offsets), 16), table_log2_slots=12)
+    return t, t.host_batch(words, offsets, lengths)
+
+
+def _fetch_with_retry(queue, fetch, room, found_at):
+    """queue(*room) and fetch(); when what the call found -- fetch()[i] for i in found_at, exact also when it did not fit --
+    exceeds `room`, once more with the larger of the two, which always suffices.  Returns what the last fetch returned."""
+    queue(*room)
+    res = fetch()
+    need = tuple(res[i] for i in found_at)
+    if any(n > r for n, r in zip(need, room)):
+        queue(*(max(n, r) for n, r in zip(need, room)))
+        res = fetch()
+    return res
+
+
 def annotate(reads, motifs, device=0):
     """Per-read motif annotation on the GPU: for every read (bytes / str) and motif (text) the matching windows and the
     longest tract on each strand, as ANNOT_DTYPE records of shape (n_reads, n_motifs)."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        t.annotate(t.host_batch(words, offsets, lengths), motifs)
+    t, b = _one_batch(reads, device)
+    with t:
+        t.annotate(b, motifs)
         return t.annotate_results()
 
 
 def tracts(reads, motifs, penalty=3, device=0):
     """Error-tolerant terminal motif tracts on the GPU: for every read (bytes / str) and motif (text) the covered bases and
     the head (5') and tail (3') tract on each strand, as TRACT_DTYPE records of shape (n_reads, n_motifs)."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        t.tracts(t.host_batch(words, offsets, lengths), motifs, penalty)
+    t, b = _one_batch(reads, device)
+    with t:
+        t.tracts(b, motifs, penalty)
         return t.tracts_results()
 
 
@@ -1286,20 +1253,18 @@ def align(reads, motifs, penalty=3, device=0):
     """Indel-aware motif tracts on the GPU: for every read (bytes / str) and motif (text) the best local alignment against the
     motif repeated without end on each strand -- score, start, end, motif bases consumed and matches -- as ALIGN_DTYPE records
     of shape (n_reads, n_motifs); align_columns gives the copies, mismatches, insertions and deletions."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        t.align(t.host_batch(words, offsets, lengths), motifs, penalty)
+    t, b = _one_batch(reads, device)
+    with t:
+        t.align(b, motifs, penalty)
         return t.align_results()
 
 
 def periods(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0):
     """De novo repeat period and unit on the GPU: for every read (bytes / str) the period, the consensus unit and the
     position of its best-scoring repeat tract, as PERIOD_DTYPE records of shape (n_reads,); no motif is given."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        t.periods(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score)
+    t, b = _one_batch(reads, device)
+    with t:
+        t.periods(b, min_period, max_period, penalty, min_score)
         return t.periods_results()
 
 
@@ -1308,10 +1273,9 @@ def refine(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0
     taken from the read, the wraparound alignment against it and the unit re-voted from that alignment -- unit, tract, motif
     bases consumed and matches -- as REFINE_DTYPE records of shape (n_reads,); refine_columns gives the copies, mismatches,
     insertions and deletions.  No motif is given."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        t.refine(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score)
+    t, b = _one_batch(reads, device)
+    with t:
+        t.refine(b, min_period, max_period, penalty, min_score)
         return t.refine_results()
 
 
@@ -1319,10 +1283,9 @@ def variants(reads, motifs, device=0):
     """In-phase variant units on the GPU: for every read (bytes / str) and motif (text, taken as typed) the exact units, the
     anchored units with one substituted base and the commonest substitution on each strand, and the histogram of the
     substitutions over all reads.  Returns (VARIANT_DTYPE records of shape (n_reads, n_motifs), hist, reads_with)."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        t.variants(t.host_batch(words, offsets, lengths), motifs)
+    t, b = _one_batch(reads, device)
+    with t:
+        t.variants(b, motifs)
         return t.variants_results()
 
 
@@ -1332,17 +1295,10 @@ def intervals(reads, motifs, max_gap=None, min_len=None, device=0, max_intervals
     strand.  Returns (INTERVAL_DTYPE records sorted by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2)).
     The first call's log holds max_intervals records (default: one per read); when more are found the call is repeated once
     with the exact number."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        b = t.host_batch(words, offsets, lengths)
-        cap = max(len(offsets), 1) if max_intervals is None else int(max_intervals)
-        t.intervals(b, motifs, max_gap, min_len, cap)
-        out, counts, found = t.intervals_results()
-        if found > cap:
-            t.intervals(b, motifs, max_gap, min_len, found)
-            out, counts, found = t.intervals_results()
-        return out, counts
+    t, b = _one_batch(reads, device)
+    with t:
+        room = (max(int(b.n_reads), 1) if max_intervals is None else int(max_intervals),)
+        return _fetch_with_retry(lambda cap: t.intervals(b, motifs, max_gap, min_len, cap), t.intervals_results, room, (2,))[:2]
 
 
 def chain(reads, motifs, device=0, max_events=None):
@@ -1351,17 +1307,10 @@ def chain(reads, motifs, device=0, max_events=None):
     sorted by (read, motif, strand, start), counts of shape (n_reads, n_motifs, 2, 2) = [read][motif][strand]{runs,
     variants}).  The first call's log holds max_events events (default: four per read); when more are found the call is
     repeated once with the exact number."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        b = t.host_batch(words, offsets, lengths)
-        cap = max(4 * len(offsets), 1) if max_events is None else int(max_events)
-        t.chain(b, motifs, cap)
-        out, counts, items, events = t.chain_results()
-        if events > cap:
-            t.chain(b, motifs, events)
-            out, counts, items, events = t.chain_results()
-        return out, counts
+    t, b = _one_batch(reads, device)
+    with t:
+        room = (max(4 * int(b.n_reads), 1) if max_events is None else int(max_events),)
+        return _fetch_with_retry(lambda cap: t.chain(b, motifs, cap), t.chain_results, room, (3,))[:2]
 
 
 def trace(reads, motifs, penalty=3, min_score=24, device=0, max_items=None, max_rows=None):
@@ -1372,17 +1321,10 @@ def trace(reads, motifs, penalty=3, min_score=24, device=0, max_items=None, max_
     n_motifs)); trace_signature turns a key's items into text.  The first call's log and workspace hold max_items items
     and max_rows rows (defaults: TrewHip.trace's; its max_rows, a row per base and motif, always suffices); when more are found
     the call is repeated once with the exact numbers."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        b = t.host_batch(words, offsets, lengths)
-        t.trace(b, motifs, penalty, min_score, max_items, max_rows)
-        out, counts, records, items, rows = t.trace_results()
-        cap_items, cap_rows = t._queued[("trace", 0)][2:]
-        if items > cap_items or rows > cap_rows:
-            t.trace(b, motifs, penalty, min_score, max(items, cap_items), max(rows, cap_rows))
-            out, counts, records, items, rows = t.trace_results()
-        return out, counts, records
+    t, b = _one_batch(reads, device)
+    with t:
+        room = _trace_room(b, _motif_array(motifs)[1], max_items, max_rows)
+        return _fetch_with_retry(lambda items, rows: t.trace(b, motifs, penalty, min_score, items, rows), t.trace_results, room, (3, 4))[:3]
 
 
 def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):
@@ -1391,17 +1333,10 @@ def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=
     until nothing scores min_score.  Returns (REPEAT_DTYPE records sorted by (read, start), counts of shape (n_reads,)).  The
     first call's log holds max_records records (default: one per read); when more are found the call is repeated once with
     the exact number."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        b = t.host_batch(words, offsets, lengths)
-        cap = max(len(offsets), 1) if max_records is None else int(max_records)
-        t.repeats(b, min_period, max_period, penalty, min_score, cap)
-        out, counts, found = t.repeats_results()
-        if found > cap:
-            t.repeats(b, min_period, max_period, penalty, min_score, found)
-            out, counts, found = t.repeats_results()
-        return out, counts
+    t, b = _one_batch(reads, device)
+    with t:
+        room = (max(int(b.n_reads), 1) if max_records is None else int(max_records),)
+        return _fetch_with_retry(lambda cap: t.repeats(b, min_period, max_period, penalty, min_score, cap), t.repeats_results, room, (2,))[:2]
 
 
 def tandems(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):
@@ -1411,17 +1346,10 @@ def tandems(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=
     Returns (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,)); tandem_columns gives the copies,
     mismatches, insertions and deletions.  The first call's log holds max_records records (default: one per read); when more
     are found the call is repeated once with the exact number."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        b = t.host_batch(words, offsets, lengths)
-        cap = max(len(offsets), 1) if max_records is None else int(max_records)
-        t.tandems(b, min_period, max_period, penalty, min_score, cap)
-        out, counts, found = t.tandems_results()
-        if found > cap:
-            t.tandems(b, min_period, max_period, penalty, min_score, found)
-            out, counts, found = t.tandems_results()
-        return out, counts
+    t, b = _one_batch(reads, device)
+    with t:
+        room = (max(int(b.n_reads), 1) if max_records is None else int(max_records),)
+        return _fetch_with_retry(lambda cap: t.tandems(b, min_period, max_period, penalty, min_score, cap), t.tandems_results, room, (2,))[:2]
 
 
 def satellites(reads, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, device=0, max_records=None):
@@ -1429,14 +1357,7 @@ def satellites(reads, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, 
     sorted by (read, start), counts of shape (n_reads,)); satellite_unit_text turns a record's unit into text.  The first
     call's log holds max_records records (default: one per read); when more are found the call is repeated once with the
     exact number."""
-    words, offsets, lengths = pack_reads(reads)
-    with TrewHip(mode=MODE_SEGMENT, device=device, n_slots=1, max_batch_words=max(len(words), 1 << 12),
-                 max_batch_reads=max(len(offsets), 16), table_log2_slots=12) as t:
-        b = t.host_batch(words, offsets, lengths)
-        cap = max(len(offsets), 1) if max_records is None else int(max_records)
-        t.satellites(b, min_period, max_period, penalty, min_score, cap)
-        out, counts, found = t.satellites_results()
-        if found > cap:
-            t.satellites(b, min_period, max_period, penalty, min_score, found)
-            out, counts, found = t.satellites_results()
-        return out, counts
+    t, b = _one_batch(reads, device)
+    with t:
+        room = (max(int(b.n_reads), 1) if max_records is None else int(max_records),)
+        return _fetch_with_retry(lambda cap: t.satellites(b, min_period, max_period, penalty, min_score, cap), t.satellites_results, room, (2,))[:2]

@@ -55,6 +55,30 @@ std::string canonical(const std::string &p) {  // std::filesystem::canonical, tr
     return p;
 }
 
+void period_options(MotifCli &cli, PeriodOptions &o, int bound) {
+    static_assert(TREW_SATELLITE_MAX_PERIOD == 256, "the text below");
+    o.max_period = bound;
+    cli.motif_less = true;
+    cli.options = {{"--min_period", [&o](const char *s) { return parse_int(s, &o.min_period); }, "MIN_PERIOD must be a number."},
+                   {"--max_period", [&o](const char *s) { return parse_int(s, &o.max_period); }, "MAX_PERIOD must be a number."},
+                   {"--penalty", [&o](const char *s) { return parse_int(s, &o.penalty); }, "PENALTY must be a number."},
+                   {"--min_score", [&o](const char *s) { return parse_int(s, &o.min_score); }, "MIN_SCORE must be a number."}};
+    cli.check = [&o, bound]() -> const char * {
+        if (o.min_period < 1 || o.max_period > bound)
+            return bound == 32 ? "MIN_PERIOD and MAX_PERIOD must be in range 1 to 32." : "MIN_PERIOD and MAX_PERIOD must be in range 1 to 256.";
+        if (o.min_period > o.max_period) return "MIN_PERIOD must not be greater than MAX_PERIOD.";
+        if (o.penalty < 1 || o.penalty > 64) return "PENALTY must be in range 1 to 64.";
+        return o.min_score < 1 ? "MIN_SCORE must be greater than or equal to 1." : nullptr;
+    };
+    cli.per_motif = [](AnnotRequest &, int, uint32_t) {};
+    cli.fill = [&o](AnnotRequest &rq) {
+        rq.min_period = o.min_period;
+        rq.max_period = o.max_period;
+        rq.penalty = o.penalty;
+        rq.min_score = (uint32_t) o.min_score;
+    };
+}
+
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
     Config cfg;
     std::vector<std::string> positional;

@@ -25,27 +25,10 @@ static void periods_usage() {
 }
 
 int periods_main(int argc, char **argv) {
-    int min_period = 1, max_period = 32, penalty = 3, min_score = 24;
+    PeriodOptions o;
     MotifCli cli;
     cli.usage = periods_usage;
-    cli.motif_less = true;
-    cli.options = {{"--min_period", [&](const char *s) { return parse_int(s, &min_period); }, "MIN_PERIOD must be a number."},
-                   {"--max_period", [&](const char *s) { return parse_int(s, &max_period); }, "MAX_PERIOD must be a number."},
-                   {"--penalty", [&](const char *s) { return parse_int(s, &penalty); }, "PENALTY must be a number."},
-                   {"--min_score", [&](const char *s) { return parse_int(s, &min_score); }, "MIN_SCORE must be a number."}};
-    cli.check = [&]() -> const char * {
-        if (min_period < 1 || max_period > 32) return "MIN_PERIOD and MAX_PERIOD must be in range 1 to 32.";
-        if (min_period > max_period) return "MIN_PERIOD must not be greater than MAX_PERIOD.";
-        if (penalty < 1 || penalty > 64) return "PENALTY must be in range 1 to 64.";
-        return min_score < 1 ? "MIN_SCORE must be greater than or equal to 1." : nullptr;
-    };
-    cli.per_motif = [](AnnotRequest &, int, uint32_t) {};
-    cli.fill = [&](AnnotRequest &rq) {
-        rq.min_period = min_period;
-        rq.max_period = max_period;
-        rq.penalty = penalty;
-        rq.min_score = (uint32_t) min_score;
-    };
+    period_options(cli, o, 32);
     cli.print_rows = [](const AnnotFileResult &r, const std::vector<std::string> &) {
         printf("read,length,period,unit,canonical,start,end,score,matches,support,scored_period\n");
         char unit[33], canon[33];

@@ -27,6 +27,7 @@
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -34,6 +35,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
+#include <type_traits>
 
 #include "bgzf_reader.hpp"
 #include "fastq_blocks.hpp"
@@ -1188,21 +1190,12 @@ struct Annotator {
     struct Worker {
         int dev_index = 0, slot = 0;
         uint32_t *h_buf = nullptr;  // pinned: [offsets n][lengths n][words]
-        std::vector<trew_hip_annot> recs;
-        std::vector<trew_hip_tract> trecs;  // trew tracts
-        std::vector<trew_hip_interval> irecs;  // trew intervals
-        std::vector<uint32_t> icounts;
-        std::vector<trew_hip_variant> vrecs;  // trew variants
-        std::vector<uint64_t> vhist;          // hist, then reads_with, of one batch
-        std::vector<trew_hip_period> precs;   // trew periods
-        std::vector<trew_hip_chain_item> crecs;  // trew chain
-        std::vector<uint32_t> ccounts;
-        std::vector<trew_hip_repeat> rrecs;  // trew repeats
-        std::vector<trew_hip_satellite> srecs;  // trew satellites
-        std::vector<trew_hip_alignment> arecs;  // trew align
-        std::vector<trew_hip_refined> frecs;    // trew refine
-        std::vector<trew_hip_tandem> tdrecs;    // trew tandems
-        std::vector<trew_hip_trace_item> xrecs; // trew trace
+        // One buffer per role, not per measure: a request names one measure, so a worker holds one kind of record at a time.
+        void *recs = nullptr;                  // the fixed-size records or the log of the batch at hand (records<T>), malloc'ed
+        size_t recs_bytes = 0;
+        std::vector<uint32_t> counts;          // intervals, chain: the counts per (read, motif, strand)
+        std::vector<uint64_t> vhist;           // variants: hist, then reads_with, of one batch
+        std::vector<trew_hip_alignment> arecs; // trace: the alignment records that come with its items
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1252,7 +1245,10 @@ Annotator *annotator_create(const Config &cfg) {
 
 void annotator_destroy(Annotator *a) {
     if (!a) return;
-    for (auto &w : a->workers) trew_hip_host_free(a->ctx[(size_t) w.dev_index], w.h_buf);
+    for (auto &w : a->workers) {
+        trew_hip_host_free(a->ctx[(size_t) w.dev_index], w.h_buf);
+        free(w.recs);
+    }
     for (auto c : a->ctx) trew_hip_destroy(c);
     delete a;
 }
@@ -1268,6 +1264,39 @@ struct AnnotBatch {
     const char *text;        // the chunk: read r is text[w->st[r] .. w->nd[r]]
 };
 
+// The worker's record buffer as room for n records of T.  It only grows, and nothing of an earlier batch is kept: every fold
+// reads only what the results call of its batch wrote.
+template <class T>
+static T *records(Annotator::Worker *w, uint64_t n) {
+    static_assert(std::is_trivially_copyable<T>::value && alignof(T) <= alignof(std::max_align_t), "plain records of the C ABI");
+    if (w->recs_bytes < n * sizeof(T)) {
+        free(w->recs);
+        w->recs_bytes = 0;
+        if (!(w->recs = malloc(n * sizeof(T)))) die("out of memory");
+        w->recs_bytes = n * sizeof(T);
+    }
+    return static_cast<T *>(w->recs);
+}
+
+// The "queue, size the buffer, fetch, retry once with the exact numbers or die" loop of the six measures with a log.  queue(room)
+// queues the measure with a log (and, trace, a workspace) of `room`; fetch(room) fetches into buffers of that size and returns
+// what the batch needs, which the library reports exactly also when it did not fit -- so one retry always suffices, and a
+// second overflow is a bug (`twice`).  Returns what was found.
+struct LogRoom {
+    uint64_t log, rows;  // records (chain: events) of the log; rows of trace's workspace, 0 for the others
+};
+template <class Queue, class Fetch>
+static LogRoom fetch_with_retry(AnnotFileResult &p, LogRoom room, const char *twice, Queue queue, Fetch fetch) {
+    for (int attempt = 0;; attempt++) {
+        queue(room);
+        const LogRoom need = fetch(room);
+        if (need.log <= room.log && need.rows <= room.rows) return need;
+        if (attempt) die(twice);
+        room = LogRoom{std::max(room.log, need.log), std::max(room.rows, need.rows)};
+        p.interval_retries++;
+    }
+}
+
 static AnnotRow annot_row(const AnnotBatch &x, uint64_t r, int m) {
     AnnotRow row;
     row.read = x.first_read + r;
@@ -1282,12 +1311,12 @@ static void fold_annotate(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const int nm = x.rq->n_motifs;
     if (trew_hip_annotate(x.c, &x.b, w->slot, x.rq->motifs, nm)) hip_die(x.c, "trew_hip_annotate");
-    if (w->recs.size() < x.n * (size_t) nm) w->recs.resize(x.n * (size_t) nm);
+    trew_hip_annot *recs = records<trew_hip_annot>(w, x.n * (uint64_t) nm);
     uint64_t got = 0;
-    if (trew_hip_annotate_results(x.c, w->slot, w->recs.data(), x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_annotate_results");
+    if (trew_hip_annotate_results(x.c, w->slot, recs, x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_annotate_results");
     for (uint64_t r = 0; r < x.n; r++)
         for (int m = 0; m < nm; m++) {
-            const trew_hip_annot &rec = w->recs[r * (size_t) nm + (size_t) m];
+            const trew_hip_annot &rec = recs[r * (size_t) nm + (size_t) m];
             const uint32_t longest = std::max(rec.tract_len_fwd, rec.tract_len_rev);
             p.windows_fwd[m] += rec.windows_fwd;
             p.windows_rev[m] += rec.windows_rev;
@@ -1306,12 +1335,12 @@ static void fold_tracts(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const int nm = x.rq->n_motifs;
     if (trew_hip_tracts(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty)) hip_die(x.c, "trew_hip_tracts");
-    if (w->trecs.size() < x.n * (size_t) nm) w->trecs.resize(x.n * (size_t) nm);
+    trew_hip_tract *recs = records<trew_hip_tract>(w, x.n * (uint64_t) nm);
     uint64_t got = 0;
-    if (trew_hip_tracts_results(x.c, w->slot, w->trecs.data(), x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_tracts_results");
+    if (trew_hip_tracts_results(x.c, w->slot, recs, x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_tracts_results");
     for (uint64_t r = 0; r < x.n; r++)
         for (int m = 0; m < nm; m++) {
-            const trew_hip_tract &rec = w->trecs[r * (size_t) nm + (size_t) m];
+            const trew_hip_tract &rec = recs[r * (size_t) nm + (size_t) m];
             const uint32_t head = std::max(rec.head_len_fwd, rec.head_len_rev), tail = std::max(rec.tail_len_fwd, rec.tail_len_rev);
             p.windows_fwd[m] += rec.covered_fwd;
             p.windows_rev[m] += rec.covered_rev;
@@ -1332,22 +1361,24 @@ static void fold_tracts(const AnnotBatch &x, AnnotFileResult &p) {
 static void fold_intervals(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const int nm = x.rq->n_motifs;
-    uint64_t cap = x.n, found = 0;
-    for (int attempt = 0;; attempt++) {
-        if (trew_hip_intervals(x.c, &x.b, w->slot, x.rq->motifs, x.rq->rules, nm, cap)) hip_die(x.c, "trew_hip_intervals");
-        if (w->irecs.size() < cap) w->irecs.resize(cap);
-        if (w->icounts.size() < x.n * (size_t) nm * 2) w->icounts.resize(x.n * (size_t) nm * 2);
-        if (trew_hip_intervals_results(x.c, w->slot, w->irecs.data(), cap, &found, w->icounts.data(), nullptr)) hip_die(x.c, "trew_hip_intervals_results");
-        if (found <= cap) break;
-        if (attempt) die("internal error: the interval log overflowed twice");
-        cap = found;  // the exact number: one retry always suffices
-        p.interval_retries++;
-    }
+    if (w->counts.size() < x.n * (size_t) nm * 2) w->counts.resize(x.n * (size_t) nm * 2);
+    const uint64_t found = fetch_with_retry(
+        p, LogRoom{x.n, 0}, "internal error: the interval log overflowed twice",
+        [&](LogRoom room) {
+            if (trew_hip_intervals(x.c, &x.b, w->slot, x.rq->motifs, x.rq->rules, nm, room.log)) hip_die(x.c, "trew_hip_intervals");
+        },
+        [&](LogRoom room) {
+            uint64_t n = 0;
+            if (trew_hip_intervals_results(x.c, w->slot, records<trew_hip_interval>(w, room.log), room.log, &n, w->counts.data(), nullptr))
+                hip_die(x.c, "trew_hip_intervals_results");
+            return LogRoom{n, 0};
+        }).log;
+    const trew_hip_interval *recs = static_cast<const trew_hip_interval *>(w->recs);
     for (uint64_t r = 0; r < x.n; r++)
         for (int m = 0; m < nm; m++)
-            if (w->icounts[(r * (size_t) nm + (size_t) m) * 2] + w->icounts[(r * (size_t) nm + (size_t) m) * 2 + 1]) p.reported[m]++;
+            if (w->counts[(r * (size_t) nm + (size_t) m) * 2] + w->counts[(r * (size_t) nm + (size_t) m) * 2 + 1]) p.reported[m]++;
     for (uint64_t i = 0; i < found; i++) {
-        const trew_hip_interval &rec = w->irecs[i];
+        const trew_hip_interval &rec = recs[i];
         const uint32_t len = x.lengths[rec.read];
         const bool terminal = rec.start == 0 || rec.end == len;
         if (rec.strand) {
@@ -1372,10 +1403,10 @@ static void fold_variants(const AnnotBatch &x, AnnotFileResult &p) {
     const int nm = x.rq->n_motifs;
     const size_t hl = (size_t) nm * 2 * TREW_VARIANT_BINS;
     if (trew_hip_variants(x.c, &x.b, w->slot, x.rq->motifs, nm)) hip_die(x.c, "trew_hip_variants");
-    if (w->vrecs.size() < x.n * (size_t) nm) w->vrecs.resize(x.n * (size_t) nm);
+    trew_hip_variant *recs = records<trew_hip_variant>(w, x.n * (uint64_t) nm);
     w->vhist.resize(2 * hl);
     uint64_t got = 0;
-    if (trew_hip_variants_results(x.c, w->slot, w->vrecs.data(), x.n * (uint64_t) nm, &got, w->vhist.data(), w->vhist.data() + hl, nullptr))
+    if (trew_hip_variants_results(x.c, w->slot, recs, x.n * (uint64_t) nm, &got, w->vhist.data(), w->vhist.data() + hl, nullptr))
         hip_die(x.c, "trew_hip_variants_results");
     p.var_hist.resize(hl);
     p.var_reads_with.resize(hl);
@@ -1385,7 +1416,7 @@ static void fold_variants(const AnnotBatch &x, AnnotFileResult &p) {
     }
     for (uint64_t r = 0; r < x.n; r++)
         for (int m = 0; m < nm; m++) {
-            const trew_hip_variant &rec = w->vrecs[r * (size_t) nm + (size_t) m];
+            const trew_hip_variant &rec = recs[r * (size_t) nm + (size_t) m];
             p.windows_fwd[m] += rec.units_fwd;
             p.windows_rev[m] += rec.units_rev;
             p.variants_fwd[m] += rec.variants_fwd;
@@ -1409,11 +1440,11 @@ static void fold_periods(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const AnnotRequest &rq = *x.rq;
     if (trew_hip_periods(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score)) hip_die(x.c, "trew_hip_periods");
-    if (w->precs.size() < x.n) w->precs.resize(x.n);
+    trew_hip_period *recs = records<trew_hip_period>(w, x.n);
     uint64_t got = 0;
-    if (trew_hip_periods_results(x.c, w->slot, w->precs.data(), x.n, &got, nullptr)) hip_die(x.c, "trew_hip_periods_results");
+    if (trew_hip_periods_results(x.c, w->slot, recs, x.n, &got, nullptr)) hip_die(x.c, "trew_hip_periods_results");
     for (uint64_t r = 0; r < x.n; r++) {
-        const trew_hip_period &rec = w->precs[r];
+        const trew_hip_period &rec = recs[r];
         if (rec.period == 0) continue;
         auto &u = p.period_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
         u.first++;
@@ -1431,25 +1462,28 @@ static void fold_periods(const AnnotBatch &x, AnnotFileResult &p) {
 static void fold_chain(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const int nm = x.rq->n_motifs;
-    uint64_t cap = 4 * x.n, items = 0, events = 0;
-    if (w->ccounts.size() < x.n * (size_t) nm * 4) w->ccounts.resize(x.n * (size_t) nm * 4);
-    for (int attempt = 0;; attempt++) {
-        if (trew_hip_chain(x.c, &x.b, w->slot, x.rq->motifs, nm, cap)) hip_die(x.c, "trew_hip_chain");
-        // an item takes at least one event, so a log that fitted holds at most `cap` items
-        if (w->crecs.size() < cap) w->crecs.resize(cap);
-        if (trew_hip_chain_results(x.c, w->slot, w->crecs.data(), cap, &items, &events, w->ccounts.data(), nullptr)) hip_die(x.c, "trew_hip_chain_results");
-        if (events <= cap) break;
-        if (attempt) die("internal error: the chain log overflowed twice");
-        cap = events;  // the exact number: one retry always suffices
-        p.interval_retries++;
-    }
+    uint64_t items = 0;
+    if (w->counts.size() < x.n * (size_t) nm * 4) w->counts.resize(x.n * (size_t) nm * 4);
+    fetch_with_retry(
+        p, LogRoom{4 * x.n, 0}, "internal error: the chain log overflowed twice",
+        [&](LogRoom room) {
+            if (trew_hip_chain(x.c, &x.b, w->slot, x.rq->motifs, nm, room.log)) hip_die(x.c, "trew_hip_chain");
+        },
+        [&](LogRoom room) {
+            // an item takes at least one event, so a log that fitted holds at most room.log items
+            uint64_t events = 0;
+            if (trew_hip_chain_results(x.c, w->slot, records<trew_hip_chain_item>(w, room.log), room.log, &items, &events, w->counts.data(), nullptr))
+                hip_die(x.c, "trew_hip_chain_results");
+            return LogRoom{events, 0};
+        });
+    const trew_hip_chain_item *recs = static_cast<const trew_hip_chain_item *>(w->recs);
     // the items are sorted by (read, motif, strand, start): a key's items are consecutive
     for (uint64_t i = 0; i < items;) {
-        const trew_hip_chain_item &first = w->crecs[i];
+        const trew_hip_chain_item &first = recs[i];
         uint64_t j = i, units = 0, nvar = 0;
         uint32_t longest = 0;
-        for (; j < items && w->crecs[j].read == first.read && w->crecs[j].motif == first.motif && w->crecs[j].strand == first.strand; j++) {
-            const trew_hip_chain_item &it = w->crecs[j];
+        for (; j < items && recs[j].read == first.read && recs[j].motif == first.motif && recs[j].strand == first.strand; j++) {
+            const trew_hip_chain_item &it = recs[j];
             if (it.bin == TREW_VARIANT_NONE) {
                 units += it.count;
                 longest = std::max(longest, it.count);
@@ -1465,87 +1499,91 @@ static void fold_chain(const AnnotBatch &x, AnnotFileResult &p) {
         lg = std::max(lg, longest);
         if (units + nvar >= x.rq->min_tract[m]) {
             (first.strand ? p.reported_rev : p.reported)[m]++;
-            for (uint64_t q = i; q < j; q++) p.crows.push_back(ChainRow{x.first_read + first.read, x.lengths[first.read], w->crecs[q]});
+            for (uint64_t q = i; q < j; q++) p.crows.push_back(ChainRow{x.first_read + first.read, x.lengths[first.read], recs[q]});
         }
         i = j;
     }
 }
 
-// trew repeats: a variable number of records and no motif; every record is a row.  repeat_units counts per (period,
-// strand-canonical unit) the reads that have such a tract, the tracts and their bases.  The log starts at one record per read;
-// a batch whose log overflows is resubmitted once, with the exact number.
-static void fold_repeats(const AnnotBatch &x, AnnotFileResult &p) {
-    Annotator::Worker *w = x.w;
-    const AnnotRequest &rq = *x.rq;
-    uint64_t cap = x.n, found = 0;
-    for (int attempt = 0;; attempt++) {
-        if (trew_hip_repeats(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, cap)) hip_die(x.c, "trew_hip_repeats");
-        if (w->rrecs.size() < cap) w->rrecs.resize(cap);
-        if (trew_hip_repeats_results(x.c, w->slot, w->rrecs.data(), cap, &found, nullptr, nullptr)) hip_die(x.c, "trew_hip_repeats_results");
-        if (found <= cap) break;
-        if (attempt) die("internal error: the repeat log overflowed twice");
-        cap = found;  // the exact number: one retry always suffices
-        p.interval_retries++;
-    }
-    // the records are sorted by (read, start): a read's tracts are consecutive
-    std::vector<std::pair<uint32_t, uint64_t>> seen;  // the keys of the read at hand
+// The unit tally of repeats, satellites and tandems: per key -- key_of(record): (period, strand-canonical unit) -- the reads
+// that have such a tract, the tracts and their bases.  The records are sorted by (read, start), so a read's tracts are
+// consecutive and `seen` holds the keys of the read at hand.  each(record, unit): what the measure does with a record besides
+// (its row; tandems: the copies).
+template <class Rec, class Map, class KeyOf, class Each>
+static void tally_units(const Rec *recs, uint64_t found, Map &units, KeyOf key_of, Each each) {
+    std::vector<typename Map::key_type> seen;
     for (uint64_t i = 0; i < found; i++) {
-        const trew_hip_repeat &rec = w->rrecs[i];
-        if (i == 0 || w->rrecs[i - 1].read != rec.read) seen.clear();
-        const std::pair<uint32_t, uint64_t> key{rec.period, canonical_unit(rec.unit, (int) rec.period)};
-        RepeatUnit &u = p.repeat_units[key];
+        const Rec &rec = recs[i];
+        if (i == 0 || recs[i - 1].read != rec.read) seen.clear();
+        const typename Map::key_type key = key_of(rec);
+        auto &u = units[key];
         if (std::find(seen.begin(), seen.end(), key) == seen.end()) {
             seen.push_back(key);
             u.reads++;
         }
         u.tracts++;
         u.bases += rec.end - rec.start;
-        p.rrows.push_back(RepeatRow{x.first_read + rec.read, x.lengths[rec.read], rec});
+        each(rec, u);
     }
+}
+
+// What repeats, satellites and tandems share: their queue and results calls differ in the record type only.  The log starts at
+// one record per read; a batch whose log overflows is resubmitted once, with the exact number.  Then tally_units.
+template <class Rec, class Map, class KeyOf, class Each>
+static void fold_tract_log(const AnnotBatch &x, AnnotFileResult &p, const char *queue_name, const char *results_name, const char *twice,
+                           int (*queue)(trew_hip_ctx *, const trew_hip_batch *, int, int, int, int, uint32_t, uint64_t),
+                           int (*results)(trew_hip_ctx *, int, Rec *, uint64_t, uint64_t *, uint32_t *, float *), Map &units, KeyOf key_of, Each each) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    const uint64_t found = fetch_with_retry(
+        p, LogRoom{x.n, 0}, twice,
+        [&](LogRoom room) {
+            if (queue(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.log)) hip_die(x.c, queue_name);
+        },
+        [&](LogRoom room) {
+            uint64_t n = 0;
+            if (results(x.c, w->slot, records<Rec>(w, room.log), room.log, &n, nullptr, nullptr)) hip_die(x.c, results_name);
+            return LogRoom{n, 0};
+        }).log;
+    tally_units(static_cast<const Rec *>(w->recs), found, units, key_of, each);
+}
+
+// trew repeats: a variable number of records and no motif; every record is a row.  repeat_units counts per (period,
+// strand-canonical unit) the reads that have such a tract, the tracts and their bases.
+static void fold_repeats(const AnnotBatch &x, AnnotFileResult &p) {
+    fold_tract_log<trew_hip_repeat>(
+        x, p, "trew_hip_repeats", "trew_hip_repeats_results", "internal error: the repeat log overflowed twice", trew_hip_repeats, trew_hip_repeats_results, p.repeat_units,
+        [](const trew_hip_repeat &rec) { return std::pair<uint32_t, uint64_t>{rec.period, canonical_unit(rec.unit, (int) rec.period)}; },
+        [&](const trew_hip_repeat &rec, RepeatUnit &) { p.rrows.push_back(RepeatRow{x.first_read + rec.read, x.lengths[rec.read], rec}); });
 }
 
 // trew satellites: fold_repeats with the wide record; the key's unit is a string of codes.
 static void fold_satellites(const AnnotBatch &x, AnnotFileResult &p) {
-    Annotator::Worker *w = x.w;
-    const AnnotRequest &rq = *x.rq;
-    uint64_t cap = x.n, found = 0;
-    for (int attempt = 0;; attempt++) {
-        if (trew_hip_satellites(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, cap)) hip_die(x.c, "trew_hip_satellites");
-        if (w->srecs.size() < cap) w->srecs.resize(cap);
-        if (trew_hip_satellites_results(x.c, w->slot, w->srecs.data(), cap, &found, nullptr, nullptr)) hip_die(x.c, "trew_hip_satellites_results");
-        if (found <= cap) break;
-        if (attempt) die("internal error: the satellite log overflowed twice");
-        cap = found;  // the exact number: one retry always suffices
-        p.interval_retries++;
-    }
-    // the records are sorted by (read, start): a read's tracts are consecutive
-    std::vector<std::pair<uint32_t, std::string>> seen;  // the keys of the read at hand
-    for (uint64_t i = 0; i < found; i++) {
-        const trew_hip_satellite &rec = w->srecs[i];
-        if (i == 0 || w->srecs[i - 1].read != rec.read) seen.clear();
-        const std::pair<uint32_t, std::string> key{rec.period, satellite_canonical(satellite_codes(rec))};
-        RepeatUnit &u = p.satellite_units[key];
-        if (std::find(seen.begin(), seen.end(), key) == seen.end()) {
-            seen.push_back(key);
-            u.reads++;
-        }
-        u.tracts++;
-        u.bases += rec.end - rec.start;
-        p.srows.push_back(SatelliteRow{x.first_read + rec.read, x.lengths[rec.read], rec});
-    }
+    fold_tract_log<trew_hip_satellite>(
+        x, p, "trew_hip_satellites", "trew_hip_satellites_results", "internal error: the satellite log overflowed twice", trew_hip_satellites, trew_hip_satellites_results,
+        p.satellite_units, [](const trew_hip_satellite &rec) { return std::pair<uint32_t, std::string>{rec.period, satellite_canonical(satellite_codes(rec))}; },
+        [&](const trew_hip_satellite &rec, RepeatUnit &) { p.srows.push_back(SatelliteRow{x.first_read + rec.read, x.lengths[rec.read], rec}); });
 }
 
-// trew align: a row per (read, motif, strand) whose score reaches MIN_SCORE; align_sums: the sums over those rows.
-static void fold_align(const AnnotBatch &x, AnnotFileResult &p) {
-    Annotator::Worker *w = x.w;
+// trew tandems: fold_repeats with the refined record; every record is a row (the kernel stores only those that reach MIN_SCORE).
+// tandem_units counts per (period, strand-canonical unit) the reads that have such a tract, the tracts, their bases and copies.
+static void fold_tandems(const AnnotBatch &x, AnnotFileResult &p) {
+    fold_tract_log<trew_hip_tandem>(
+        x, p, "trew_hip_tandems", "trew_hip_tandems_results", "internal error: the tandem log overflowed twice", trew_hip_tandems, trew_hip_tandems_results, p.tandem_units,
+        [](const trew_hip_tandem &rec) { return std::pair<uint32_t, uint64_t>{rec.period, canonical_unit(rec.unit, (int) rec.period)}; },
+        [&](const trew_hip_tandem &rec, TandemUnit &u) {
+            u.copies += rec.consumed / rec.period;
+            p.trows.push_back(TandemRow{x.first_read + rec.read, x.lengths[rec.read], rec});
+        });
+}
+
+// A row per (read, motif, strand) of `recs` whose score reaches MIN_SCORE; align_sums: the sums over those rows.  What trew
+// align prints, and trew trace from the records that come with its items.
+static void align_rows(const AnnotBatch &x, const trew_hip_alignment *recs, AnnotFileResult &p) {
     const int nm = x.rq->n_motifs;
-    if (trew_hip_align(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty)) hip_die(x.c, "trew_hip_align");
-    if (w->arecs.size() < x.n * (size_t) nm) w->arecs.resize(x.n * (size_t) nm);
-    uint64_t got = 0;
-    if (trew_hip_align_results(x.c, w->slot, w->arecs.data(), x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_align_results");
     for (uint64_t r = 0; r < x.n; r++)
         for (int m = 0; m < nm; m++) {
-            const trew_hip_alignment &rec = w->arecs[r * (size_t) nm + (size_t) m];
+            const trew_hip_alignment &rec = recs[r * (size_t) nm + (size_t) m];
             for (int s = 0; s < 2; s++) {
                 const uint32_t *f = s ? &rec.score_rev : &rec.score_fwd;  // five consecutive u32
                 if (f[0] < x.rq->min_score) continue;
@@ -1563,17 +1601,28 @@ static void fold_align(const AnnotBatch &x, AnnotFileResult &p) {
         }
 }
 
+// trew align: align_rows of one record per (read, motif).
+static void fold_align(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    if (trew_hip_align(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty)) hip_die(x.c, "trew_hip_align");
+    trew_hip_alignment *recs = records<trew_hip_alignment>(w, x.n * (uint64_t) nm);
+    uint64_t got = 0;
+    if (trew_hip_align_results(x.c, w->slot, recs, x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_align_results");
+    align_rows(x, recs, p);
+}
+
 // trew refine: one record per read and no motif.  A read whose final score reaches MIN_SCORE is a row; refine_units counts
 // the rows, the bases of their tracts and their copies per (period, strand-canonical unit).
 static void fold_refine(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const AnnotRequest &rq = *x.rq;
     if (trew_hip_refine(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score)) hip_die(x.c, "trew_hip_refine");
-    if (w->frecs.size() < x.n) w->frecs.resize(x.n);
+    trew_hip_refined *recs = records<trew_hip_refined>(w, x.n);
     uint64_t got = 0;
-    if (trew_hip_refine_results(x.c, w->slot, w->frecs.data(), x.n, &got, nullptr)) hip_die(x.c, "trew_hip_refine_results");
+    if (trew_hip_refine_results(x.c, w->slot, recs, x.n, &got, nullptr)) hip_die(x.c, "trew_hip_refine_results");
     for (uint64_t r = 0; r < x.n; r++) {
-        const trew_hip_refined &rec = w->frecs[r];
+        const trew_hip_refined &rec = recs[r];
         if (rec.period == 0 || rec.score < rq.min_score) continue;
         RefineUnit &u = p.refine_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
         u.reads++;
@@ -1583,40 +1632,7 @@ static void fold_refine(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
-// trew tandems: fold_repeats with the refined record; every record is a row (the kernel stores only those that reach MIN_SCORE).
-// tandem_units counts per (period, strand-canonical unit) the reads that have such a tract, the tracts, their bases and copies.
-static void fold_tandems(const AnnotBatch &x, AnnotFileResult &p) {
-    Annotator::Worker *w = x.w;
-    const AnnotRequest &rq = *x.rq;
-    uint64_t cap = x.n, found = 0;
-    for (int attempt = 0;; attempt++) {
-        if (trew_hip_tandems(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, cap)) hip_die(x.c, "trew_hip_tandems");
-        if (w->tdrecs.size() < cap) w->tdrecs.resize(cap);
-        if (trew_hip_tandems_results(x.c, w->slot, w->tdrecs.data(), cap, &found, nullptr, nullptr)) hip_die(x.c, "trew_hip_tandems_results");
-        if (found <= cap) break;
-        if (attempt) die("internal error: the tandem log overflowed twice");
-        cap = found;  // the exact number: one retry always suffices
-        p.interval_retries++;
-    }
-    // the records are sorted by (read, start): a read's tracts are consecutive
-    std::vector<std::pair<uint32_t, uint64_t>> seen;  // the keys of the read at hand
-    for (uint64_t i = 0; i < found; i++) {
-        const trew_hip_tandem &rec = w->tdrecs[i];
-        if (i == 0 || w->tdrecs[i - 1].read != rec.read) seen.clear();
-        const std::pair<uint32_t, uint64_t> key{rec.period, canonical_unit(rec.unit, (int) rec.period)};
-        TandemUnit &u = p.tandem_units[key];
-        if (std::find(seen.begin(), seen.end(), key) == seen.end()) {
-            seen.push_back(key);
-            u.reads++;
-        }
-        u.tracts++;
-        u.bases += rec.end - rec.start;
-        u.copies += rec.consumed / rec.period;
-        p.trows.push_back(TandemRow{x.first_read + rec.read, x.lengths[rec.read], rec});
-    }
-}
-
-// trew trace: fold_align's rows and sums from the records that come with the items, and the items of those keys with the read
+// trew trace: align_rows from the records that come with the items, and the items of those keys with the read
 // bases of every item that is no run (the signature prints them).  trace_sums: units (the copies of the items with consumed =
 // k count), edited (the items with an error), items.  The workspace holds a row for every base and motif, which no batch
 // exceeds; the log starts at sixteen items per read and motif, and a batch whose log overflows is resubmitted once, with the
@@ -1626,38 +1642,22 @@ static void fold_trace(const AnnotBatch &x, AnnotFileResult &p) {
     const int nm = x.rq->n_motifs;
     uint64_t bases = 0;
     for (uint64_t r = 0; r < x.n; r++) bases += x.lengths[r];
-    uint64_t cap = 16 * x.n * (uint64_t) nm + 1024, rows_cap = std::max<uint64_t>(bases * (uint64_t) nm, 1), items = 0, rows = 0;
     if (w->arecs.size() < x.n * (size_t) nm) w->arecs.resize(x.n * (size_t) nm);
-    for (int attempt = 0;; attempt++) {
-        if (trew_hip_trace(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty, x.rq->min_score, cap, rows_cap)) hip_die(x.c, "trew_hip_trace");
-        if (w->xrecs.size() < cap) w->xrecs.resize(cap);
-        if (trew_hip_trace_results(x.c, w->slot, w->xrecs.data(), cap, &items, &rows, nullptr, w->arecs.data(), nullptr)) hip_die(x.c, "trew_hip_trace_results");
-        if (items <= cap && rows <= rows_cap) break;
-        if (attempt) die("internal error: the trace log overflowed twice");
-        cap = std::max(cap, items);  // the exact numbers: one retry always suffices
-        rows_cap = std::max(rows_cap, rows);
-        p.interval_retries++;
-    }
-    for (uint64_t r = 0; r < x.n; r++)
-        for (int m = 0; m < nm; m++) {
-            const trew_hip_alignment &rec = w->arecs[r * (size_t) nm + (size_t) m];
-            for (int s = 0; s < 2; s++) {
-                const uint32_t *f = s ? &rec.score_rev : &rec.score_fwd;  // five consecutive u32
-                if (f[0] < x.rq->min_score) continue;
-                AlignRow row;
-                row.read = x.first_read + r;
-                row.length = x.lengths[r];
-                row.motif = m;
-                row.strand = s;
-                for (int i = 0; i < 5; i++) row.rec[i] = f[i];
-                p.arows.push_back(row);
-                const AlignColumns c = align_columns(row.rec, (uint32_t) x.rq->motifs[m].k, x.rq->penalty);
-                const uint64_t add[kAlignSums] = {1, (uint64_t) f[2] - f[1], f[0], c.copies, f[3], f[4], c.mismatches, c.insertions, c.deletions};
-                for (int i = 0; i < kAlignSums; i++) p.align_sums[m][s][i] += add[i];
-            }
-        }
+    const uint64_t items = fetch_with_retry(
+        p, LogRoom{16 * x.n * (uint64_t) nm + 1024, std::max<uint64_t>(bases * (uint64_t) nm, 1)}, "internal error: the trace log overflowed twice",
+        [&](LogRoom room) {
+            if (trew_hip_trace(x.c, &x.b, w->slot, x.rq->motifs, nm, x.rq->penalty, x.rq->min_score, room.log, room.rows)) hip_die(x.c, "trew_hip_trace");
+        },
+        [&](LogRoom room) {
+            LogRoom need{0, 0};
+            if (trew_hip_trace_results(x.c, w->slot, records<trew_hip_trace_item>(w, room.log), room.log, &need.log, &need.rows, nullptr, w->arecs.data(), nullptr))
+                hip_die(x.c, "trew_hip_trace_results");
+            return need;
+        }).log;
+    align_rows(x, w->arecs.data(), p);
+    const trew_hip_trace_item *recs = static_cast<const trew_hip_trace_item *>(w->recs);
     for (uint64_t i = 0; i < items; i++) {
-        const trew_hip_trace_item &it = w->xrecs[i];
+        const trew_hip_trace_item &it = recs[i];
         const uint32_t k = (uint32_t) x.rq->motifs[it.motif].k;
         const bool errors = it.mismatches || it.insertions || it.deletions;
         uint64_t *sums = p.trace_sums[it.motif][it.strand];
@@ -1718,6 +1718,12 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
     }
 }
 
+// one (period, unit) map into another: add(into's entry, from's entry)
+template <class Map, class Add>
+static void merge_units(Map &into, const Map &from, Add add) {
+    for (const auto &kv : from) add(into[kv.first], kv.second);
+}
+
 void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     into.reads += from.reads;
     into.bases += from.bases;
@@ -1749,36 +1755,28 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     }
     into.interval_retries += from.interval_retries;
     into.batches += from.batches;
-    for (const auto &kv : from.refine_units) {
-        RefineUnit &u = into.refine_units[kv.first];
-        u.reads += kv.second.reads;
-        u.bases += kv.second.bases;
-        u.copies += kv.second.copies;
-    }
-    for (const auto &kv : from.tandem_units) {
-        TandemUnit &u = into.tandem_units[kv.first];
-        u.reads += kv.second.reads;
-        u.tracts += kv.second.tracts;
-        u.bases += kv.second.bases;
-        u.copies += kv.second.copies;
-    }
-    for (const auto &kv : from.period_units) {
-        auto &u = into.period_units[kv.first];
-        u.first += kv.second.first;
-        u.second += kv.second.second;
-    }
-    for (const auto &kv : from.repeat_units) {
-        RepeatUnit &u = into.repeat_units[kv.first];
-        u.reads += kv.second.reads;
-        u.tracts += kv.second.tracts;
-        u.bases += kv.second.bases;
-    }
-    for (const auto &kv : from.satellite_units) {
-        RepeatUnit &u = into.satellite_units[kv.first];
-        u.reads += kv.second.reads;
-        u.tracts += kv.second.tracts;
-        u.bases += kv.second.bases;
-    }
+    auto add_repeat_unit = [](RepeatUnit &u, const RepeatUnit &v) {
+        u.reads += v.reads;
+        u.tracts += v.tracts;
+        u.bases += v.bases;
+    };
+    merge_units(into.period_units, from.period_units, [](std::pair<uint64_t, uint64_t> &u, const std::pair<uint64_t, uint64_t> &v) {
+        u.first += v.first;
+        u.second += v.second;
+    });
+    merge_units(into.repeat_units, from.repeat_units, add_repeat_unit);
+    merge_units(into.satellite_units, from.satellite_units, add_repeat_unit);
+    merge_units(into.refine_units, from.refine_units, [](RefineUnit &u, const RefineUnit &v) {
+        u.reads += v.reads;
+        u.bases += v.bases;
+        u.copies += v.copies;
+    });
+    merge_units(into.tandem_units, from.tandem_units, [](TandemUnit &u, const TandemUnit &v) {
+        u.reads += v.reads;
+        u.tracts += v.tracts;
+        u.bases += v.bases;
+        u.copies += v.copies;
+    });
 }
 
 static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"};  // in the order of Measure
@@ -1792,6 +1790,28 @@ static int measure_chunk_bytes() {
         if (parse_int(e, &v) && v >= 64 && v <= LENGTH) return v;
     }
     return LENGTH;
+}
+
+// The rows `rows` of every worker's part, in the order `less`: the same for any number of workers.
+template <class Row, class Less>
+static void merge_rows(Annotator *a, std::vector<Row> AnnotFileResult::*rows, AnnotFileResult &out, Less less) {
+    for (auto &w : a->workers) (out.*rows).insert((out.*rows).end(), (w.part.*rows).begin(), (w.part.*rows).end());
+    std::sort((out.*rows).begin(), (out.*rows).end(), less);
+}
+// the sort keys: (read, motif, strand, start) and (read, start) of the record `rec` of a row
+template <class Row, class Rec>
+static auto by_read_motif_strand_start(Rec Row::*rec) {
+    return [rec](const Row &x, const Row &y) {
+        const Rec &a = x.*rec, &b = y.*rec;
+        if (x.read != y.read) return x.read < y.read;
+        if (a.motif != b.motif) return a.motif < b.motif;
+        if (a.strand != b.strand) return a.strand < b.strand;
+        return a.start < b.start;
+    };
+}
+template <class Row, class Rec>
+static auto by_read_start(Rec Row::*rec) {
+    return [rec](const Row &x, const Row &y) { return x.read != y.read ? x.read < y.read : (x.*rec).start < (y.*rec).start; };
 }
 
 AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *file_name, bool is_gz, const AnnotRequest &rq) {
@@ -1811,65 +1831,36 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     }
     for (auto &t : th) t.join();
     AnnotFileResult out;
-    for (auto &w : a->workers) {
-        add_totals(out, w.part);
-        out.rows.insert(out.rows.end(), w.part.rows.begin(), w.part.rows.end());
-        out.irows.insert(out.irows.end(), w.part.irows.begin(), w.part.irows.end());
-        out.crows.insert(out.crows.end(), w.part.crows.begin(), w.part.crows.end());
-        out.rrows.insert(out.rrows.end(), w.part.rrows.begin(), w.part.rrows.end());
-        out.srows.insert(out.srows.end(), w.part.srows.begin(), w.part.srows.end());
-        out.arows.insert(out.arows.end(), w.part.arows.begin(), w.part.arows.end());
-        out.frows.insert(out.frows.end(), w.part.frows.begin(), w.part.frows.end());
-        out.trows.insert(out.trows.end(), w.part.trows.begin(), w.part.trows.end());
-        out.xrows.insert(out.xrows.end(), w.part.xrows.begin(), w.part.xrows.end());
-    }
-    std::sort(out.irows.begin(), out.irows.end(), [](const IntervalRow &x, const IntervalRow &y) {
-        if (x.read != y.read) return x.read < y.read;
-        if (x.iv.motif != y.iv.motif) return x.iv.motif < y.iv.motif;
-        if (x.iv.strand != y.iv.strand) return x.iv.strand < y.iv.strand;
-        return x.iv.start < y.iv.start;
-    });
-    std::sort(out.crows.begin(), out.crows.end(), [](const ChainRow &x, const ChainRow &y) {
-        if (x.read != y.read) return x.read < y.read;
-        if (x.it.motif != y.it.motif) return x.it.motif < y.it.motif;
-        if (x.it.strand != y.it.strand) return x.it.strand < y.it.strand;
-        return x.it.start < y.it.start;
-    });
-    std::sort(out.rrows.begin(), out.rrows.end(),
-              [](const RepeatRow &x, const RepeatRow &y) { return x.read != y.read ? x.read < y.read : x.rp.start < y.rp.start; });
-    std::sort(out.srows.begin(), out.srows.end(),
-              [](const SatelliteRow &x, const SatelliteRow &y) { return x.read != y.read ? x.read < y.read : x.st.start < y.st.start; });
-    std::sort(out.arows.begin(), out.arows.end(), [](const AlignRow &x, const AlignRow &y) {
+    for (auto &w : a->workers) add_totals(out, w.part);
+    merge_rows(a, &AnnotFileResult::rows, out, [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
+    merge_rows(a, &AnnotFileResult::irows, out, by_read_motif_strand_start(&IntervalRow::iv));
+    merge_rows(a, &AnnotFileResult::crows, out, by_read_motif_strand_start(&ChainRow::it));
+    merge_rows(a, &AnnotFileResult::xrows, out, by_read_motif_strand_start(&TraceRow::it));
+    merge_rows(a, &AnnotFileResult::rrows, out, by_read_start(&RepeatRow::rp));
+    merge_rows(a, &AnnotFileResult::srows, out, by_read_start(&SatelliteRow::st));
+    merge_rows(a, &AnnotFileResult::trows, out, by_read_start(&TandemRow::td));
+    merge_rows(a, &AnnotFileResult::frows, out, [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
+    merge_rows(a, &AnnotFileResult::arows, out, [](const AlignRow &x, const AlignRow &y) {
         if (x.read != y.read) return x.read < y.read;
         return x.motif != y.motif ? x.motif < y.motif : x.strand < y.strand;
     });
-    std::sort(out.xrows.begin(), out.xrows.end(), [](const TraceRow &x, const TraceRow &y) {
-        if (x.read != y.read) return x.read < y.read;
-        if (x.it.motif != y.it.motif) return x.it.motif < y.it.motif;
-        if (x.it.strand != y.it.strand) return x.it.strand < y.it.strand;
-        return x.it.start < y.it.start;
-    });
-    std::sort(out.frows.begin(), out.frows.end(), [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
-    std::sort(out.trows.begin(), out.trows.end(),
-              [](const TandemRow &x, const TandemRow &y) { return x.read != y.read ? x.read < y.read : x.td.start < y.td.start; });
-    std::sort(out.rows.begin(), out.rows.end(), [](const AnnotRow &x, const AnnotRow &y) { return x.read != y.read ? x.read < y.read : x.motif < y.motif; });
     if (cfg.stats) {
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         fprintf(stderr, "[trew] %s: %llu reads, %llu bases, %.3f s, %.3f Gbases/s end-to-end (decode + pack + %s; serial reader, %d worker(s))\n", file_name,
                 (unsigned long long) out.reads, (unsigned long long) out.bases, sec, out.bases / sec / 1e9, kMeasureNames[(int) rq.kind], (int) a->workers.size());
         fprintf(stderr, "[trew] %s: %llu batch(es) submitted, chunk length %d bytes\n", file_name, (unsigned long long) out.batches, chunk);
-        if (rq.kind == Measure::Intervals) fprintf(stderr, "[trew] %s: %llu intervals, %llu batch(es) resubmitted with a larger log\n", file_name,
-                                  (unsigned long long) out.irows.size(), (unsigned long long) out.interval_retries);
-        if (rq.kind == Measure::Chain) fprintf(stderr, "[trew] %s: %llu items, %llu batch(es) resubmitted with a larger log\n", file_name,
-                                  (unsigned long long) out.crows.size(), (unsigned long long) out.interval_retries);
-        if (rq.kind == Measure::Repeats) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
-                                  (unsigned long long) out.rrows.size(), (unsigned long long) out.interval_retries);
-        if (rq.kind == Measure::Tandems) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
-                                  (unsigned long long) out.trows.size(), (unsigned long long) out.interval_retries);
-        if (rq.kind == Measure::Trace) fprintf(stderr, "[trew] %s: %llu items, %llu batch(es) resubmitted with a larger log\n", file_name,
-                                  (unsigned long long) out.xrows.size(), (unsigned long long) out.interval_retries);
-        if (rq.kind == Measure::Satellites) fprintf(stderr, "[trew] %s: %llu tracts, %llu batch(es) resubmitted with a larger log\n", file_name,
-                                  (unsigned long long) out.srows.size(), (unsigned long long) out.interval_retries);
+        // the kinds with a log: what their rows are called, and how many there are
+        const struct {
+            Measure kind;
+            const char *noun;
+            size_t rows;
+        } logs[] = {{Measure::Intervals, "intervals", out.irows.size()}, {Measure::Chain, "items", out.crows.size()},
+                    {Measure::Repeats, "tracts", out.rrows.size()},      {Measure::Satellites, "tracts", out.srows.size()},
+                    {Measure::Tandems, "tracts", out.trows.size()},      {Measure::Trace, "items", out.xrows.size()}};
+        for (const auto &l : logs)
+            if (rq.kind == l.kind)
+                fprintf(stderr, "[trew] %s: %llu %s, %llu batch(es) resubmitted with a larger log\n", file_name, (unsigned long long) l.rows, l.noun,
+                        (unsigned long long) out.interval_retries);
     }
     return out;
 }

@@ -29,27 +29,10 @@ static void refine_usage() {
 }
 
 int refine_main(int argc, char **argv) {
-    int min_period = 1, max_period = 32, penalty = 3, min_score = 24;
+    PeriodOptions o;
     MotifCli cli;
     cli.usage = refine_usage;
-    cli.motif_less = true;
-    cli.options = {{"--min_period", [&](const char *s) { return parse_int(s, &min_period); }, "MIN_PERIOD must be a number."},
-                   {"--max_period", [&](const char *s) { return parse_int(s, &max_period); }, "MAX_PERIOD must be a number."},
-                   {"--penalty", [&](const char *s) { return parse_int(s, &penalty); }, "PENALTY must be a number."},
-                   {"--min_score", [&](const char *s) { return parse_int(s, &min_score); }, "MIN_SCORE must be a number."}};
-    cli.check = [&]() -> const char * {
-        if (min_period < 1 || max_period > 32) return "MIN_PERIOD and MAX_PERIOD must be in range 1 to 32.";
-        if (min_period > max_period) return "MIN_PERIOD must not be greater than MAX_PERIOD.";
-        if (penalty < 1 || penalty > 64) return "PENALTY must be in range 1 to 64.";
-        return min_score < 1 ? "MIN_SCORE must be greater than or equal to 1." : nullptr;
-    };
-    cli.per_motif = [](AnnotRequest &, int, uint32_t) {};
-    cli.fill = [&](AnnotRequest &rq) {
-        rq.min_period = min_period;
-        rq.max_period = max_period;
-        rq.penalty = penalty;
-        rq.min_score = (uint32_t) min_score;
-    };
+    period_options(cli, o, 32);
     cli.print_rows = [&](const AnnotFileResult &r, const std::vector<std::string> &) {
         printf("read,length,period,unit,canonical,start,end,score,copies,consumed,matches,mismatches,insertions,deletions,seed_period,seed_unit,seed_score,"
                "changed,scored_period\n");
@@ -57,7 +40,7 @@ int refine_main(int argc, char **argv) {
         for (const auto &row : r.frows) {
             const trew_hip_refined &f = row.rf;
             const uint32_t rec[5] = {f.score, f.start, f.end, f.consumed, f.matches};
-            const AlignColumns c = align_columns(rec, f.period, penalty);
+            const AlignColumns c = align_columns(rec, f.period, o.penalty);
             int_to_four(unit, f.unit, (int) f.period);
             int_to_four(canon, canonical_unit(f.unit, (int) f.period), (int) f.period);
             int_to_four(seed, f.seed_unit, (int) f.seed_period);

@@ -187,7 +187,9 @@ struct RepeatUnit {
     uint64_t reads = 0, tracts = 0, bases = 0;  // reads with such a tract, the tracts, the sum of their end - start
 };
 // What one file (or, summed, all files) came to.  What the per-motif counters count depends on the kind: see the function
-// of process.cpp that folds the kind's records into them.
+// of process.cpp that folds the kind's records into them (fold_<kind>).  What the folds share is there once: the six with a log
+// size and fetch it through fetch_with_retry, repeats, satellites and tandems tally their units through tally_units, align and
+// trace make their rows through align_rows; process_annotate merges and sorts every row vector through merge_rows.
 struct AnnotFileResult {
     std::vector<AnnotRow> rows;      // annotate, tracts, variants: sorted by read, then motif
     std::vector<IntervalRow> irows;  // intervals: sorted by read, motif, strand, start
@@ -248,6 +250,13 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
+// The command line the measures without motifs share (periods, repeats, refine, tandems: bound 32; satellites: 256):
+// --min_period, --max_period (default: bound), --penalty and --min_score with their check, and the request filled from them.
+// `o` must outlive `cli`.
+struct PeriodOptions {
+    int min_period = 1, max_period = 32, penalty = 3, min_score = 24;
+};
+void period_options(MotifCli &cli, PeriodOptions &o, int bound);
 int annotate_main(int argc, char **argv);
 int tracts_main(int argc, char **argv);
 int intervals_main(int argc, char **argv);

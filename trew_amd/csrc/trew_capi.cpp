@@ -28,6 +28,8 @@ namespace {
 // The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace) and what a slot keeps of each.
 enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kMeasures };
 const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"};
+// whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -39,7 +41,7 @@ struct MeasureState {
     unsigned long long *hist = nullptr;     // variants: the batch histograms hist, then reads_with, kVarHistLen values each
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
-    // the numbers of the last call
+    // the numbers of the last call, set in one place each: queue_records (the fixed-size records), queue_log (the append logs)
     u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods, refine: n_reads
     u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites, tandems: their max_records
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites, tandems: n_reads
@@ -1226,6 +1228,9 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
 // ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace
 // The twelve measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
+// That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
+// fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
+// check, what it asks of the helper (record size, capacities) and the launch of its kernel.
 // Their definitions on the CPU are in trew_measures_host.cpp; the wrappers here only keep the error text.
 extern "C" int trew_motif_parse(const char *text, trew_hip_motif *out) {
     const std::string e = motif_parse(text, out);
@@ -1340,21 +1345,20 @@ static int stage_motifs(trew_hip_ctx *ctx, Slot &s, const trew_hip_motif *motifs
 
 // What every queue call does before anything of its own: the argument checks in the order callers see them (`own` holds
 // the measure's own checks; it runs behind the motifs' check and in front of the first HIP call), the batch and the motifs onto the slot's stream, and the measure's two events on its first use.
-// The measures without motifs (periods, repeats, satellites, refine, tandems) are known by `which`, not by their arguments: for them there is no motif check
+// The measures without motifs are known by kMeasureHasMotifs, not by their arguments: for them there is no motif check
 // and no pattern table, and they pass no motifs.  For the others, no motifs stays the argument error it always was.
 template <class Own>
 static int measure_begin(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
                          Own own, Slot **slot_out, DevBatch *db) {
     if (!ctx || !batch) return -1;
     if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
-    const bool motif_less = which == kPeriods || which == kRepeats || which == kSatellites || which == kRefine || which == kTandems;
-    if (!motif_less)
+    if (kMeasureHasMotifs[which])
         if (const char *e = motifs_error(motifs, n_motifs)) return fail(ctx, e);
     if (const char *e = own()) return fail(ctx, e);
     HIPCHK(ctx, hipSetDevice(ctx->p.device));
     Slot &s = ctx->slots[(size_t) slot];
     if (int rc = stage_batch(ctx, batch, s, db)) return rc;  // also: the read index fits a record's u32
-    if (!motif_less)
+    if (kMeasureHasMotifs[which])
         if (int rc = stage_motifs(ctx, s, motifs, n_motifs)) return rc;
     for (auto &e : s.measure[which].ev)
         if (!e) HIPCHK(ctx, hipEventCreate(&e));
@@ -1386,6 +1390,70 @@ static int timed_launch(trew_hip_ctx *ctx, Slot &s, MeasureState &st, Launch lau
     return 0;
 }
 
+// The queue call of the measures with one fixed-size record per (read, motif) or per read (annotate, tracts, align, periods,
+// refine, variants; per_read: n_motifs or 1): measure_begin, room for the records, `setup` (what else the measure keeps on the
+// device: the histograms of variants), then the numbers of the call, all in one place, and `launch` between the events unless
+// the batch is empty.  Every call starts from zero, and one that fails on the way can simply be repeated.
+template <class Own, class Setup, class Launch>
+static int queue_records(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
+                         int per_read, size_t rec_bytes, Own own, Setup setup, Launch launch) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, which, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[which];
+    const u64 need = db.n_reads * (u64) per_read;
+    if (int rc = grow(ctx, s, st.records, need * rec_bytes)) return rc;
+    if (int rc = setup(s, st)) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = need;
+    if (need == 0) return 0;
+    return timed_launch(ctx, s, st, [&]() -> int { return launch(s, st, db); });
+}
+static int no_setup(Slot &, MeasureState &) { return 0; }
+
+// What a measure with an append log asks of queue_log besides its kernel.
+struct LogShape {
+    size_t rec_bytes;        // of one record of the log (chain: one event)
+    u64 max_log;             // the capacity of the log for this call
+    u64 counts_per_read;     // u32 counts: n_motifs * 2 (intervals, trace), n_motifs * 4 (chain), 1 (repeats, satellites, tandems)
+    bool zero_counts;        // the kernel adds to its counts (repeats, satellites, tandems); the others store every one of them
+    u64 max_rows;            // trace: the rows of the direction workspace for this call, and a second counter for them; else 0
+    u64 aligned_per_read;    // trace: n_motifs alignment records; else 0
+};
+
+// The queue call of the measures with an append log (intervals, chain, repeats, satellites, tandems, trace): measure_begin, the
+// counter (one word, trace two: a fixed size, allocated on first use), room for the counts, the log and trace's two buffers,
+// then the numbers of the call, all in one place, the counter back to zero -- every call starts from zero, also one without
+// reads, whose results then report nothing found -- and `launch` between the events unless the batch is empty.
+template <class Own, class Launch>
+static int queue_log(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
+                     const LogShape &shape, Own own, Launch launch) {
+    Slot *sp = nullptr;
+    DevBatch db;
+    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, which, own, &sp, &db)) return rc;
+    Slot &s = *sp;
+    MeasureState &st = s.measure[which];
+    const size_t counter_bytes = (shape.max_rows ? 2 : 1) * sizeof(unsigned long long);
+    const u64 n_counts = db.n_reads * shape.counts_per_read, n_aligned = db.n_reads * shape.aligned_per_read;
+    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, counter_bytes));
+    if (int rc = grow(ctx, s, st.aligned, n_aligned * sizeof(trew_hip_alignment))) return rc;
+    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
+    if (int rc = grow(ctx, s, st.records, shape.max_log * shape.rec_bytes)) return rc;
+    if (int rc = grow(ctx, s, st.rows, shape.max_rows * 64ull)) return rc;
+    st.valid = true;
+    st.timed = false;
+    st.n = n_aligned;
+    st.n_counts = n_counts;
+    st.max_log = shape.max_log;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
+    st.max_rows = shape.max_rows;
+    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, counter_bytes, s.stream));
+    if (n_counts == 0) return 0;
+    if (shape.zero_counts) HIPCHK(ctx, hipMemsetAsync(st.counts.p, 0, n_counts * sizeof(u32), s.stream));
+    return timed_launch(ctx, s, st, [&]() -> int { return launch(s, st, db); });
+}
+
 // What every results call does first: the checks (`arg_error`: the text of the measure's own argument check, which comes
 // behind the slot's), then the wait for the slot's stream.
 static int fetch_begin(trew_hip_ctx *ctx, int slot, Measure which, const char *arg_error, Slot **slot_out) {
@@ -1398,7 +1466,7 @@ static int fetch_begin(trew_hip_ctx *ctx, int slot, Measure which, const char *a
     return trew_hip_wait(ctx, slot);
 }
 
-// the fixed-size records of annotate, tracts and variants: min(n, cap) of them; without `out` none (no error)
+// the fixed-size records of a measure: min(n, cap) of them; without `out` none (no error)
 static int fetch_records(trew_hip_ctx *ctx, const MeasureState &st, void *out, u64 cap, size_t rec_bytes, uint64_t *n) {
     if (n) *n = st.n;
     const u64 take = std::min<u64>(st.n, cap);
@@ -1410,6 +1478,44 @@ static int fetch_end(trew_hip_ctx *ctx, const MeasureState &st, float *ms_kernel
     if (ms_kernel) {
         *ms_kernel = 0.0f;
         if (st.timed) HIPCHK(ctx, hipEventElapsedTime(ms_kernel, st.ev[0], st.ev[1]));
+    }
+    return 0;
+}
+
+// the results call of annotate, tracts, align, periods and refine, whole
+static int results_records(trew_hip_ctx *ctx, int slot, Measure which, void *out, u64 cap, size_t rec_bytes, uint64_t *n, float *ms_kernel) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, which, nullptr, &sp)) return rc;
+    const MeasureState &st = sp->measure[which];
+    if (int rc = fetch_records(ctx, st, out, cap, rec_bytes, n)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// what the kernel of a log measure counted: `words` counter values (trace: two), and the counts where the caller wants them
+static int fetch_counted(trew_hip_ctx *ctx, const MeasureState &st, unsigned long long *found, int words, uint32_t *counts) {
+    HIPCHK(ctx, hipMemcpy(found, st.counter, (size_t) words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// an overflowed log holds an unspecified subset: nothing of it is copied (only intervals, whose records stand each for itself,
+// hands out what its log holds)
+static u64 whole_log(const MeasureState &st, u64 found) { return found <= st.max_log ? found : 0; }
+
+// min(cap, n_in_log) records of the log, the first ones in the order of `sort`: sorted on the host, so the records do not depend
+// on the order in which the waves appended them.  A buffer smaller than the log gets the first `cap` of the sorted log.
+template <class Rec>
+static int fetch_log(trew_hip_ctx *ctx, const MeasureState &st, Rec *out, u64 cap, u64 n_in_log, void (*sort)(Rec *, uint64_t)) {
+    const u64 take = std::min<u64>(n_in_log, cap);
+    if (!take) return 0;
+    if (take == n_in_log) {
+        HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(Rec), hipMemcpyDeviceToHost));
+        sort(out, take);
+    } else {
+        std::vector<Rec> all((size_t) n_in_log);
+        HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, n_in_log * sizeof(Rec), hipMemcpyDeviceToHost));
+        sort(all.data(), n_in_log);
+        memcpy(out, all.data(), take * sizeof(Rec));
     }
     return 0;
 }
@@ -1429,93 +1535,50 @@ extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch,
     } else {
         general = true;  // unknown
     }
-    Slot *sp = nullptr;
-    DevBatch db;
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kAnnotate, no_own_checks, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kAnnotate];
-    const u64 need = db.n_reads * (u64) n_motifs;
-    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_annot))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    if (need == 0) return 0;
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_annotate(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, max_len, general, (trew_hip_annot *) st.records.p));
-        return 0;
-    });
+    return queue_records(ctx, batch, slot, motifs, n_motifs, kAnnotate, n_motifs, sizeof(trew_hip_annot), no_own_checks, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_annotate(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, max_len, general, (trew_hip_annot *) st.records.p));
+                             return 0;
+                         });
 }
 
 extern "C" int trew_hip_annotate_results(trew_hip_ctx *ctx, int slot, trew_hip_annot *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kAnnotate, nullptr, &sp)) return rc;
-    const MeasureState &st = sp->measure[kAnnotate];
-    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_annot), n)) return rc;
-    return fetch_end(ctx, st, ms_kernel);
+    return results_records(ctx, slot, kAnnotate, out, cap, sizeof(trew_hip_annot), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- per-read error-tolerant terminal tracts
 extern "C" int trew_hip_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * { return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr; };
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kTracts, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kTracts];
-    const u64 need = db.n_reads * (u64) n_motifs;
-    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_tract))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    if (need == 0) return 0;
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_tracts(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_tract *) st.records.p));
-        return 0;
-    });
+    return queue_records(ctx, batch, slot, motifs, n_motifs, kTracts, n_motifs, sizeof(trew_hip_tract), own, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_tracts(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_tract *) st.records.p));
+                             return 0;
+                         });
 }
 
 extern "C" int trew_hip_tracts_results(trew_hip_ctx *ctx, int slot, trew_hip_tract *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kTracts, nullptr, &sp)) return rc;
-    const MeasureState &st = sp->measure[kTracts];
-    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_tract), n)) return rc;
-    return fetch_end(ctx, st, ms_kernel);
+    return results_records(ctx, slot, kTracts, out, cap, sizeof(trew_hip_tract), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- indel-aware motif tract per read (wraparound alignment)
 extern "C" int trew_hip_align(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * { return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr; };
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kAlign, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kAlign];
-    const u64 need = db.n_reads * (u64) n_motifs;
-    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_alignment))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    if (need == 0) return 0;
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_align(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_alignment *) st.records.p));
-        return 0;
-    });
+    return queue_records(ctx, batch, slot, motifs, n_motifs, kAlign, n_motifs, sizeof(trew_hip_alignment), own, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_align(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_alignment *) st.records.p));
+                             return 0;
+                         });
 }
 
 extern "C" int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kAlign, nullptr, &sp)) return rc;
-    const MeasureState &st = sp->measure[kAlign];
-    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_alignment), n)) return rc;
-    return fetch_end(ctx, st, ms_kernel);
+    return results_records(ctx, slot, kAlign, out, cap, sizeof(trew_hip_alignment), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- units in place under indels: the traceback of the alignment
+// `records` is the item log, `counter` two values (items, rows), `aligned` the trew_hip_alignment of every (read, motif).
 static_assert(sizeof(trew_hip_trace_item) == 48, "twelve words: what trace_wave_kernel stores");
 extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, int penalty,
                               uint32_t min_score, uint64_t max_items, uint64_t max_rows) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * {
         return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]"
                : min_score < 1             ? "min_score must be at least 1"
@@ -1523,32 +1586,9 @@ extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
                : max_rows < 1              ? "max_rows must be at least 1"
                                            : nullptr;
     };
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kTrace, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kTrace];
-    const u64 need = db.n_reads * (u64) n_motifs;
-    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, 2 * sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.aligned, need * sizeof(trew_hip_alignment))) return rc;
-    if (int rc = grow(ctx, s, st.counts, need * 2ull * sizeof(u32))) return rc;
-    if (int rc = grow(ctx, s, st.records, max_items * sizeof(trew_hip_trace_item))) return rc;
-    if (int rc = grow(ctx, s, st.rows, max_rows * 64ull)) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    st.n_counts = need * 2ull;
-    st.max_log = max_items;
-    st.max_rows = max_rows;
-    // both counters start every call at zero, also a call without reads (its results then report no item and no row)
-    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, 2 * sizeof(unsigned long long), s.stream));
-    if (need == 0) return 0;
-    TraceLog lg;
-    lg.counter = st.counter;
-    lg.recs = (u32 *) st.records.p;
-    lg.cap = max_items;  // this call's capacities, not the (possibly larger) buffers': the overflow contract is per call
-    lg.row_counter = st.counter + 1;
-    lg.rows = (unsigned char *) st.rows.p;
-    lg.max_rows = max_rows;
-    return timed_launch(ctx, s, st, [&]() -> int {
+    const LogShape shape = {sizeof(trew_hip_trace_item), max_items, (u64) n_motifs * 2ull, false, max_rows, (u64) n_motifs};
+    return queue_log(ctx, batch, slot, motifs, n_motifs, kTrace, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         HIPCHK(ctx, launch_trace(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
                                  (u32 *) st.counts.p));
         return 0;
@@ -1564,61 +1604,31 @@ extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trac
     if (int rc = fetch_begin(ctx, slot, kTrace, arg_error, &sp)) return rc;
     const MeasureState &st = sp->measure[kTrace];
     unsigned long long found[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpy(found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
+    if (int rc = fetch_counted(ctx, st, found, 2, counts)) return rc;
     *n_items = found[0];
     *n_rows = found[1];
-    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
     if (records && st.n) HIPCHK(ctx, hipMemcpy(records, st.aligned.p, st.n * sizeof(trew_hip_alignment), hipMemcpyDeviceToHost));
-    const u64 take = std::min<u64>(found[0], cap);
-    if (found[0] <= st.max_log && found[1] <= st.max_rows && take) {  // an overflowed log holds an unspecified subset: nothing is copied
-        // sorted on the host, so the items do not depend on the order in which the waves appended them
-        if (take == found[0]) {
-            HIPCHK(ctx, hipMemcpy(items, st.records.p, take * sizeof(trew_hip_trace_item), hipMemcpyDeviceToHost));
-            sort_trace_items(items, take);
-        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
-            std::vector<trew_hip_trace_item> all((size_t) found[0]);
-            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found[0] * sizeof(trew_hip_trace_item), hipMemcpyDeviceToHost));
-            sort_trace_items(all.data(), found[0]);
-            memcpy(items, all.data(), take * sizeof(trew_hip_trace_item));
-        }
-    }
+    // a workspace that overflowed did not stop the walk, but the contract is one: both fit, or no items
+    if (int rc = fetch_log(ctx, st, items, cap, found[1] <= st.max_rows ? whole_log(st, found[0]) : 0, sort_trace_items)) return rc;
     return fetch_end(ctx, st, ms_kernel);
 }
 
 // ---------------------------------------------------------------- gap-tolerant motif intervals anywhere in a read
 extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs,
                                   const trew_hip_interval_rule *rules, int n_motifs, uint64_t max_intervals) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * {
         if (const char *e = rules_error(rules, n_motifs)) return e;
         return max_intervals < 1 ? "max_intervals must be at least 1" : nullptr;
     };
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kIntervals, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kIntervals];
-    const u64 keys = db.n_reads * (u64) n_motifs * 2ull;
-    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.counts, keys * sizeof(u32))) return rc;
-    if (int rc = grow(ctx, s, st.records, max_intervals * sizeof(trew_hip_interval))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.max_log = max_intervals;
-    st.n_counts = keys;
-    // the counter starts every call at zero, also a call without reads (its results then report no interval)
-    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
-    if (keys == 0) return 0;
-    IntervalRulesDev rd;
-    memset(&rd, 0, sizeof(rd));
-    for (int m = 0; m < n_motifs; m++) {
-        rd.max_gap[m] = rules[m].max_gap;
-        rd.min_len[m] = rules[m].min_len;
-    }
-    IntervalLog lg;
-    lg.counter = st.counter;
-    lg.recs = (u32 *) st.records.p;
-    lg.cap = max_intervals;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
-    return timed_launch(ctx, s, st, [&]() -> int {
+    const LogShape shape = {sizeof(trew_hip_interval), max_intervals, (u64) n_motifs * 2ull, false, 0, 0};
+    return queue_log(ctx, batch, slot, motifs, n_motifs, kIntervals, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        IntervalRulesDev rd;
+        memset(&rd, 0, sizeof(rd));
+        for (int m = 0; m < n_motifs; m++) {
+            rd.max_gap[m] = rules[m].max_gap;
+            rd.min_len[m] = rules[m].min_len;
+        }
+        const IntervalLog lg = {st.counter, (u32 *) st.records.p, st.max_log};
         HIPCHK(ctx, launch_intervals(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, rd, lg, (u32 *) st.counts.p));
         return 0;
     });
@@ -1626,30 +1636,16 @@ extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch
 
 extern "C" int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_interval *out, uint64_t cap, uint64_t *n, uint32_t *counts,
                                           float *ms_kernel) {
-    // unlike the other three, this call needs `n` (the only way to learn of an overflow), and like variants it refuses a
+    // unlike the fixed-size ones, this call needs `n` (the only way to learn of an overflow), and like variants it refuses a
     // capacity without a buffer
     const char *arg_error = !n ? "trew_hip_intervals_results: n must not be null" : cap && !out ? "trew_hip_intervals_results: out must not be null" : nullptr;
     Slot *sp = nullptr;
     if (int rc = fetch_begin(ctx, slot, kIntervals, arg_error, &sp)) return rc;
     const MeasureState &st = sp->measure[kIntervals];
     unsigned long long found = 0;
-    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
+    if (int rc = fetch_counted(ctx, st, &found, 1, counts)) return rc;
     *n = found;
-    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
-    const u64 in_log = std::min<u64>(found, st.max_log);
-    const u64 take = std::min<u64>(in_log, cap);
-    if (take) {
-        // sorted on the host, so the records do not depend on the order in which the waves appended them
-        if (take == in_log) {
-            HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
-            sort_intervals(out, take);
-        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
-            std::vector<trew_hip_interval> all((size_t) in_log);
-            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, in_log * sizeof(trew_hip_interval), hipMemcpyDeviceToHost));
-            sort_intervals(all.data(), in_log);
-            memcpy(out, all.data(), take * sizeof(trew_hip_interval));
-        }
-    }
+    if (int rc = fetch_log(ctx, st, out, cap, std::min<u64>(found, st.max_log), sort_intervals)) return rc;
     return fetch_end(ctx, st, ms_kernel);
 }
 
@@ -1657,25 +1653,18 @@ extern "C" int trew_hip_intervals_results(trew_hip_ctx *ctx, int slot, trew_hip_
 constexpr u64 kVarHistLen = (u64) kAnnotMaxMotifs * 2ull * TREW_VARIANT_BINS;  // values of one histogram of a slot
 
 extern "C" int trew_hip_variants(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs) {
-    Slot *sp = nullptr;
-    DevBatch db;
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kVariants, no_own_checks, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kVariants];
-    const u64 need = db.n_reads * (u64) n_motifs;
-    if (!st.hist) HIPCHK(ctx, hipMalloc((void **) &st.hist, 2ull * kVarHistLen * sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_variant))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    st.n_motifs = n_motifs;
-    // both histograms start every call at zero, also a call without reads
-    HIPCHK(ctx, hipMemsetAsync(st.hist, 0, 2ull * kVarHistLen * sizeof(unsigned long long), s.stream));
-    if (need == 0) return 0;
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_variants(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, (trew_hip_variant *) st.records.p, st.hist, st.hist + kVarHistLen));
+    // both histograms (a fixed size: allocated on first use, never grown) start every call at zero, also a call without reads
+    auto hists = [&](Slot &s, MeasureState &st) -> int {
+        if (!st.hist) HIPCHK(ctx, hipMalloc((void **) &st.hist, 2ull * kVarHistLen * sizeof(unsigned long long)));
+        HIPCHK(ctx, hipMemsetAsync(st.hist, 0, 2ull * kVarHistLen * sizeof(unsigned long long), s.stream));
+        st.n_motifs = n_motifs;
         return 0;
-    });
+    };
+    return queue_records(ctx, batch, slot, motifs, n_motifs, kVariants, n_motifs, sizeof(trew_hip_variant), no_own_checks, hists,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_variants(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, (trew_hip_variant *) st.records.p, st.hist, st.hist + kVarHistLen));
+                             return 0;
+                         });
 }
 
 extern "C" int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_variant *out, uint64_t cap, uint64_t *n, uint64_t *hist,
@@ -1694,86 +1683,40 @@ extern "C" int trew_hip_variants_results(trew_hip_ctx *ctx, int slot, trew_hip_v
 
 // ---------------------------------------------------------------- de novo repeat period and unit per read
 extern "C" int trew_hip_periods(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * { return periods_error(min_period, max_period, penalty, min_score); };
-    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kPeriods, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kPeriods];
-    const u64 need = db.n_reads;
-    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_period))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    if (need == 0) return 0;
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_periods(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_period *) st.records.p));
-        return 0;
-    });
+    return queue_records(ctx, batch, slot, nullptr, 0, kPeriods, 1, sizeof(trew_hip_period), own, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_periods(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_period *) st.records.p));
+                             return 0;
+                         });
 }
 
 extern "C" int trew_hip_periods_results(trew_hip_ctx *ctx, int slot, trew_hip_period *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kPeriods, nullptr, &sp)) return rc;
-    const MeasureState &st = sp->measure[kPeriods];
-    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_period), n)) return rc;
-    return fetch_end(ctx, st, ms_kernel);
+    return results_records(ctx, slot, kPeriods, out, cap, sizeof(trew_hip_period), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- de novo repeats under indels: seed, align, re-vote
 extern "C" int trew_hip_refine(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * { return periods_error(min_period, max_period, penalty, min_score); };
-    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kRefine, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kRefine];
-    const u64 need = db.n_reads;
-    if (int rc = grow(ctx, s, st.records, need * sizeof(trew_hip_refined))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.n = need;
-    if (need == 0) return 0;
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_refine(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_refined *) st.records.p));
-        return 0;
-    });
+    return queue_records(ctx, batch, slot, nullptr, 0, kRefine, 1, sizeof(trew_hip_refined), own, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_refine(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_refined *) st.records.p));
+                             return 0;
+                         });
 }
 
 extern "C" int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_refined *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kRefine, nullptr, &sp)) return rc;
-    const MeasureState &st = sp->measure[kRefine];
-    if (int rc = fetch_records(ctx, st, out, cap, sizeof(trew_hip_refined), n)) return rc;
-    return fetch_end(ctx, st, ms_kernel);
+    return results_records(ctx, slot, kRefine, out, cap, sizeof(trew_hip_refined), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- ordered unit chain per read
+// The log holds events, not items; the results call pairs them, for which it keeps the motifs' lengths.
 extern "C" int trew_hip_chain(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, uint64_t max_events) {
-    Slot *sp = nullptr;
-    DevBatch db;
     auto own = [&]() -> const char * { return max_events < 1 ? "max_events must be at least 1" : nullptr; };
-    if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, kChain, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kChain];
-    const u64 n_counts = db.n_reads * (u64) n_motifs * 4ull;
-    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
-    if (int rc = grow(ctx, s, st.records, max_events * sizeof(uint4))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.max_log = max_events;
-    st.n_counts = n_counts;
-    st.n_motifs = n_motifs;
-    for (int m = 0; m < n_motifs; m++) st.k[m] = (u32) motifs[m].k;
-    // the counter starts every call at zero, also a call without reads (its results then report no event)
-    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
-    if (n_counts == 0) return 0;
-    ChainLog lg;
-    lg.counter = st.counter;
-    lg.events = (uint4 *) st.records.p;
-    lg.cap = max_events;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
-    return timed_launch(ctx, s, st, [&]() -> int {
+    const LogShape shape = {sizeof(uint4), max_events, (u64) n_motifs * 4ull, false, 0, 0};
+    return queue_log(ctx, batch, slot, motifs, n_motifs, kChain, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        for (int m = 0; m < n_motifs; m++) st.k[m] = (u32) motifs[m].k;  // a batch without reads has no events to pair
+        const ChainLog lg = {st.counter, (uint4 *) st.records.p, st.max_log};
         HIPCHK(ctx, launch_chain(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, lg, (u32 *) st.counts.p));
         return 0;
     });
@@ -1787,16 +1730,15 @@ extern "C" int trew_hip_chain_results(trew_hip_ctx *ctx, int slot, trew_hip_chai
     Slot *sp = nullptr;
     if (int rc = fetch_begin(ctx, slot, kChain, arg_error, &sp)) return rc;
     const MeasureState &st = sp->measure[kChain];
-    unsigned long long found = 0;
-    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
-    *n_events = found;
     // the number of items is the sum of the counts, which the kernel stores whether or not the log fitted
     std::vector<u32> own_counts;
     if (!counts && st.n_counts) {
         own_counts.resize((size_t) st.n_counts);
         counts = own_counts.data();
     }
-    if (st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
+    unsigned long long found = 0;
+    if (int rc = fetch_counted(ctx, st, &found, 1, counts)) return rc;
+    *n_events = found;
     u64 items = 0;
     for (u64 i = 0; i < st.n_counts; i++) items += counts[i];
     *n_items = items;
@@ -1831,98 +1773,57 @@ extern "C" int trew_hip_chain_results(trew_hip_ctx *ctx, int slot, trew_hip_chai
     return fetch_end(ctx, st, ms_kernel);
 }
 
-// ---------------------------------------------------------------- de novo repeats: every tract of a read
-extern "C" int trew_hip_repeats(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
-                                uint64_t max_records) {
-    Slot *sp = nullptr;
-    DevBatch db;
+// ---------------------------------------------------------------- de novo repeats: every tract of a read (repeats), with periods up to 256 (satellites), under indels (tandems)
+// Three kernels, three record types and one host path: a log of one record per tract, one count per read that the kernel adds
+// to, and a MeasureState each.
+template <class Own, class Launch>
+static int queue_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, Measure which, size_t rec_bytes, uint64_t max_records, Own error,
+                        Launch launch) {
     auto own = [&]() -> const char * {
-        if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+        if (const char *e = error()) return e;
         return max_records < 1 ? "max_records must be at least 1" : nullptr;
     };
-    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kRepeats, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kRepeats];
-    const u64 n_counts = db.n_reads;
-    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
-    if (int rc = grow(ctx, s, st.records, max_records * sizeof(trew_hip_repeat))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.max_log = max_records;
-    st.n_counts = n_counts;
-    // the counter and the counts start every call at zero, also a call without reads (its results then report no tract)
-    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
-    if (n_counts == 0) return 0;
-    HIPCHK(ctx, hipMemsetAsync(st.counts.p, 0, n_counts * sizeof(u32), s.stream));
-    RepeatLog lg;
-    lg.counter = st.counter;
-    lg.recs = (u32 *) st.records.p;
-    lg.cap = max_records;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_repeats(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, (u32 *) st.counts.p));
+    const LogShape shape = {rec_bytes, max_records, 1, true, 0, 0};
+    return queue_log(ctx, batch, slot, nullptr, 0, which, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        return launch(s, db, RepeatLog{st.counter, (u32 *) st.records.p, st.max_log}, (u32 *) st.counts.p);
+    });
+}
+
+// like intervals, their results call needs `n` (the only way to learn of an overflow) and refuses a capacity without a buffer:
+// `arg_error` is the text of that check
+template <class Rec>
+static int results_tracts(trew_hip_ctx *ctx, int slot, Measure which, const char *arg_error, Rec *out, uint64_t cap, uint64_t *n, uint32_t *counts,
+                          float *ms_kernel, void (*sort)(Rec *, uint64_t)) {
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, which, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[which];
+    unsigned long long found = 0;
+    if (int rc = fetch_counted(ctx, st, &found, 1, counts)) return rc;
+    *n = found;
+    if (int rc = fetch_log(ctx, st, out, cap, whole_log(st, found), sort)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+extern "C" int trew_hip_repeats(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                                uint64_t max_records) {
+    auto error = [&]() { return periods_error(min_period, max_period, penalty, min_score); };
+    return queue_tracts(ctx, batch, slot, kRepeats, sizeof(trew_hip_repeat), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
+        HIPCHK(ctx, launch_repeats(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, counts));
         return 0;
     });
 }
 
 extern "C" int trew_hip_repeats_results(trew_hip_ctx *ctx, int slot, trew_hip_repeat *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel) {
-    // like intervals, this call needs `n` (the only way to learn of an overflow) and refuses a capacity without a buffer
     const char *arg_error = !n ? "trew_hip_repeats_results: n must not be null" : cap && !out ? "trew_hip_repeats_results: out must not be null" : nullptr;
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kRepeats, arg_error, &sp)) return rc;
-    const MeasureState &st = sp->measure[kRepeats];
-    unsigned long long found = 0;
-    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
-    *n = found;
-    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
-    const u64 take = std::min<u64>(found, cap);
-    if (found <= st.max_log && take) {  // an overflowed log holds an unspecified subset: nothing is copied
-        // sorted on the host, so the records do not depend on the order in which the waves appended them
-        if (take == found) {
-            HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(trew_hip_repeat), hipMemcpyDeviceToHost));
-            sort_repeats(out, take);
-        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
-            std::vector<trew_hip_repeat> all((size_t) found);
-            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found * sizeof(trew_hip_repeat), hipMemcpyDeviceToHost));
-            sort_repeats(all.data(), found);
-            memcpy(out, all.data(), take * sizeof(trew_hip_repeat));
-        }
-    }
-    return fetch_end(ctx, st, ms_kernel);
+    return results_tracts(ctx, slot, kRepeats, arg_error, out, cap, n, counts, ms_kernel, sort_repeats);
 }
 
-// ---------------------------------------------------------------- de novo repeats with periods up to 256
-// trew_hip_repeats with the wider check, the wider record and its own kernel; a MeasureState of its own.
 static_assert(sizeof(trew_hip_satellite) == 104, "26 words: what satellites_wave_kernel stores");
 extern "C" int trew_hip_satellites(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
                                    uint32_t min_score, uint64_t max_records) {
-    Slot *sp = nullptr;
-    DevBatch db;
-    auto own = [&]() -> const char * {
-        if (const char *e = satellites_error(min_period, max_period, penalty, min_score)) return e;
-        return max_records < 1 ? "max_records must be at least 1" : nullptr;
-    };
-    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kSatellites, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kSatellites];
-    const u64 n_counts = db.n_reads;
-    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
-    if (int rc = grow(ctx, s, st.records, max_records * sizeof(trew_hip_satellite))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.max_log = max_records;
-    st.n_counts = n_counts;
-    // the counter and the counts start every call at zero, also a call without reads (its results then report no tract)
-    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
-    if (n_counts == 0) return 0;
-    HIPCHK(ctx, hipMemsetAsync(st.counts.p, 0, n_counts * sizeof(u32), s.stream));
-    RepeatLog lg;
-    lg.counter = st.counter;
-    lg.recs = (u32 *) st.records.p;
-    lg.cap = max_records;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_satellites(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, (u32 *) st.counts.p));
+    auto error = [&]() { return satellites_error(min_period, max_period, penalty, min_score); };
+    return queue_tracts(ctx, batch, slot, kSatellites, sizeof(trew_hip_satellite), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
+        HIPCHK(ctx, launch_satellites(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, counts));
         return 0;
     });
 }
@@ -1930,88 +1831,22 @@ extern "C" int trew_hip_satellites(trew_hip_ctx *ctx, const trew_hip_batch *batc
 extern "C" int trew_hip_satellites_results(trew_hip_ctx *ctx, int slot, trew_hip_satellite *out, uint64_t cap, uint64_t *n, uint32_t *counts,
                                            float *ms_kernel) {
     const char *arg_error = !n ? "trew_hip_satellites_results: n must not be null" : cap && !out ? "trew_hip_satellites_results: out must not be null" : nullptr;
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kSatellites, arg_error, &sp)) return rc;
-    const MeasureState &st = sp->measure[kSatellites];
-    unsigned long long found = 0;
-    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
-    *n = found;
-    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
-    const u64 take = std::min<u64>(found, cap);
-    if (found <= st.max_log && take) {  // an overflowed log holds an unspecified subset: nothing is copied
-        // sorted on the host, so the records do not depend on the order in which the waves appended them
-        if (take == found) {
-            HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(trew_hip_satellite), hipMemcpyDeviceToHost));
-            sort_satellites(out, take);
-        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
-            std::vector<trew_hip_satellite> all((size_t) found);
-            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found * sizeof(trew_hip_satellite), hipMemcpyDeviceToHost));
-            sort_satellites(all.data(), found);
-            memcpy(out, all.data(), take * sizeof(trew_hip_satellite));
-        }
-    }
-    return fetch_end(ctx, st, ms_kernel);
+    return results_tracts(ctx, slot, kSatellites, arg_error, out, cap, n, counts, ms_kernel, sort_satellites);
 }
 
-// ---------------------------------------------------------------- de novo repeats under indels: every tract of a read
-// trew_hip_repeats with the record and the kernel of its own; a MeasureState of its own.
 static_assert(sizeof(trew_hip_tandem) == 72, "18 words: what tandems_wave_kernel stores");
 extern "C" int trew_hip_tandems(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
                                 uint64_t max_records) {
-    Slot *sp = nullptr;
-    DevBatch db;
-    auto own = [&]() -> const char * {
-        if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-        return max_records < 1 ? "max_records must be at least 1" : nullptr;
-    };
-    if (int rc = measure_begin(ctx, batch, slot, nullptr, 0, kTandems, own, &sp, &db)) return rc;
-    Slot &s = *sp;
-    MeasureState &st = s.measure[kTandems];
-    const u64 n_counts = db.n_reads;
-    if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, sizeof(unsigned long long)));  // a fixed size: never grows
-    if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
-    if (int rc = grow(ctx, s, st.records, max_records * sizeof(trew_hip_tandem))) return rc;
-    st.valid = true;
-    st.timed = false;
-    st.max_log = max_records;
-    st.n_counts = n_counts;
-    // the counter and the counts start every call at zero, also a call without reads (its results then report no tract)
-    HIPCHK(ctx, hipMemsetAsync(st.counter, 0, sizeof(unsigned long long), s.stream));
-    if (n_counts == 0) return 0;
-    HIPCHK(ctx, hipMemsetAsync(st.counts.p, 0, n_counts * sizeof(u32), s.stream));
-    RepeatLog lg;
-    lg.counter = st.counter;
-    lg.recs = (u32 *) st.records.p;
-    lg.cap = max_records;  // this call's capacity, not the (possibly larger) buffer's: the overflow contract is per call
-    return timed_launch(ctx, s, st, [&]() -> int {
-        HIPCHK(ctx, launch_tandems(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, (u32 *) st.counts.p));
+    auto error = [&]() { return periods_error(min_period, max_period, penalty, min_score); };
+    return queue_tracts(ctx, batch, slot, kTandems, sizeof(trew_hip_tandem), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
+        HIPCHK(ctx, launch_tandems(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, counts));
         return 0;
     });
 }
 
 extern "C" int trew_hip_tandems_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts, float *ms_kernel) {
     const char *arg_error = !n ? "trew_hip_tandems_results: n must not be null" : cap && !out ? "trew_hip_tandems_results: out must not be null" : nullptr;
-    Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kTandems, arg_error, &sp)) return rc;
-    const MeasureState &st = sp->measure[kTandems];
-    unsigned long long found = 0;
-    HIPCHK(ctx, hipMemcpy(&found, st.counter, sizeof(found), hipMemcpyDeviceToHost));
-    *n = found;
-    if (counts && st.n_counts) HIPCHK(ctx, hipMemcpy(counts, st.counts.p, st.n_counts * sizeof(u32), hipMemcpyDeviceToHost));
-    const u64 take = std::min<u64>(found, cap);
-    if (found <= st.max_log && take) {  // an overflowed log holds an unspecified subset: nothing is copied
-        // sorted on the host, so the records do not depend on the order in which the waves appended them
-        if (take == found) {
-            HIPCHK(ctx, hipMemcpy(out, st.records.p, take * sizeof(trew_hip_tandem), hipMemcpyDeviceToHost));
-            sort_tandems(out, take);
-        } else {  // a buffer smaller than the log: the first `cap` of the sorted log
-            std::vector<trew_hip_tandem> all((size_t) found);
-            HIPCHK(ctx, hipMemcpy(all.data(), st.records.p, found * sizeof(trew_hip_tandem), hipMemcpyDeviceToHost));
-            sort_tandems(all.data(), found);
-            memcpy(out, all.data(), take * sizeof(trew_hip_tandem));
-        }
-    }
-    return fetch_end(ctx, st, ms_kernel);
+    return results_tracts(ctx, slot, kTandems, arg_error, out, cap, n, counts, ms_kernel, sort_tandems);
 }
 
 // ---------------------------------------------------------------- host packing
