@@ -35,8 +35,9 @@ extern "C" {
  * trew_hip_periods_results, trew_periods_host), the satellite entry points (trew_hip_satellites,
  * trew_hip_satellites_results, trew_satellites_host), the alignment entry points (trew_hip_align, trew_hip_align_results,
  * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host), the tandem
- * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host) and the traceback entry points (trew_hip_trace,
- * trew_hip_trace_results, trew_trace_host): they are purely additive -- no existing
+ * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host), the traceback entry points (trew_hip_trace,
+ * trew_hip_trace_results, trew_trace_host) and the decomposition entry points (trew_hip_decompose, trew_hip_decompose_results,
+ * trew_decompose_host): they are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
@@ -759,6 +760,53 @@ int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *ite
 int trew_trace_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                     int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
                     trew_hip_alignment *records);
+
+/* ---- units in place with no motif given: trew_hip_refine's unit, anchored at a fixed rotation, and trew_hip_trace against it ----
+ * (what is this telomere made of, and in which order, when nobody knows its motif?)  Integer-exact (DESIGN 4.7i;
+ * tests/decompose_ref.py is the reference).  The arguments are min_period, max_period (<= 32), the penalty P and min_score: those
+ * of trew_hip_refine, with the same checks and error texts.  max_items and max_rows are those of trew_hip_trace; both must be
+ * >= 1.
+ * 1. Refine.  R is the read's trew_hip_refined record, field for field.
+ * 2. Anchor.  If R is zero or R.score < min_score, the read has no items and anchor is 0.  Otherwise k = R.period and U =
+ *    R.unit.  U is primitive, so its k rotations are distinct.  M is the smallest rotation of U, in the order in which the
+ *    scan compares rotations (as packed words, first base most significant).  No reverse complement is taken here.  anchor =
+ *    rho, the one offset with M[j] = U[(j + rho) mod k].
+ * 3. Trace.  The items are those of trew_hip_trace_item's definition for the forward strand of the read against the motif M:
+ *    the tuples, the three tie rules, the walk, the segments and the merging of complete exact copies are all unchanged.  Unit
+ *    lengths 1 and 2 are included: the lower limit of 3 in trew_hip_trace is a check on typed motifs and not a property of the
+ *    table.  The item is a trew_hip_trace_item with motif = 0 and strand = 0.
+ * 4. Outputs per read: the record R, with its reserved word carrying anchor, and the number of items.
+ * Items come sorted by (read, start).  Consequences: the record equals trew_hip_refine's in every field but reserved; a read has
+ * items if and only if R.period > 0 and R.score >= min_score; the alignment record of the traced table equals R ((score, start,
+ * end, consumed, matches) is the same for every rotation of a unit, only the end phase depends on the rotation); the items tile
+ * [R.start, R.end) without a gap; bases sums to end - start, consumed to R.consumed, and the errors to those that follow from R
+ * and P; only the first item has phase != 0; for k >= 3 the items equal the forward-strand items of trew_hip_trace with motif
+ * M; a perfect repeat begun at each of its k rotations gives the same M, and its first item's phase follows the rotation; a
+ * read's items do not depend on the rest of the batch.  Limits: those of trew_hip_refine (one tract per read, periods <= 32,
+ * linear gaps, a wrong scored_period not repaired); the items are in read orientation and cut at M, and a read of the other
+ * strand is cut at the smallest rotation of the reverse complement, so items compare directly only between reads of one
+ * strand.  Also additive: TREW_HIP_ABI_VERSION stays 4.
+ *
+ * Like trew_hip_refine in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, no motifs, the checks and their error texts), with buffers of its own and independent of
+ * the scan and of the other twelve kernels.  Further argument errors: "max_items must be at least 1", "max_rows must be at
+ * least 1".  The log of max_items items, the workspace of max_rows rows -- here of 32 bytes, one strand -- and the two counters
+ * are as in trew_hip_trace; a read claims end - start rows when it has items, else none.  At most 2^32 - 1 reads a batch.  One
+ * kernel, a wave per read, for every read length. */
+int trew_hip_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                       uint64_t max_items, uint64_t max_rows);
+/* The contract of trew_hip_trace_results: *n_items and *n_rows (neither may be NULL) are exact also beyond max_items, max_rows
+ * or cap; counts (n_reads values; may be NULL) the items of every read, always exact; records (n_reads; may be NULL) the
+ * trew_hip_refined of every read with reserved = anchor.  min(cap, *n_items) items sorted by (read, start) go to `items` when
+ * *n_items <= max_items and *n_rows <= max_rows; otherwise nothing is copied into `items` and the call returns 0: repeat
+ * trew_hip_decompose with both at least what was reported -- one retry always suffices. */
+int trew_hip_decompose_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                               uint32_t *counts, trew_hip_refined *records, float *ms_kernel);
+/* The definition on the host with the full table, over packed planes: *n_items = items found, min(cap, *n_items) items (the
+ * first ones of the sorted order), counts and records as above (each may be NULL). */
+int trew_decompose_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                        int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
+                        trew_hip_refined *records);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -27,6 +27,7 @@ from .capi import (  # noqa: F401
     align,
     annotate,
     chain,
+    decompose,
     intervals,
     k_mer_check,
     pack_reads,

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_refine", "trew_hip_refine_results", "trew_refine_host",
     "trew_hip_tandems", "trew_hip_tandems_results", "trew_tandems_host",
     "trew_hip_trace", "trew_hip_trace_results", "trew_trace_host",
+    "trew_hip_decompose", "trew_hip_decompose_results", "trew_decompose_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain")
@@ -291,6 +292,9 @@ def load():
     lib.trew_hip_trace.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, i32, C.c_uint32, u64, u64]
     lib.trew_hip_trace_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(C.c_float)]
     lib.trew_trace_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
+    lib.trew_hip_decompose.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64, u64]
+    lib.trew_hip_decompose_results.argtypes = lib.trew_hip_trace_results.argtypes
+    lib.trew_decompose_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
     lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
     lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
@@ -541,6 +545,33 @@ def trace_host(reads_or_packed, motifs, penalty=3, min_score=24, cap=None):
 
     out, found = _sized_call(call, TRACE_DTYPE, cap)
     return out, counts[:, :nm], records[:, :nm], found
+
+
+def decompose_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
+    """trew_decompose_host: refine_host's record of every read, its unit turned to its smallest rotation (the record's
+    `reserved` word is the anchor, the offset of that rotation in the unit) and the traceback of the read's forward strand
+    against it, computed on the host with the full table.  reads_or_packed as for annotate_host.  Returns (TRACE_DTYPE items
+    sorted by (read, start), motif = strand = 0, counts of shape (n_reads,), REFINE_DTYPE records of shape (n_reads,), n_items);
+    with `cap` at most that many items."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    counts = np.zeros(len(offsets), dtype=np.uint32)
+    records = np.zeros(len(offsets), dtype=REFINE_DTYPE)
+
+    def call(ptr, room, n):
+        if lib.trew_decompose_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                                   int(penalty), int(min_score), ptr, room, C.byref(n), counts.ctypes.data, records.ctypes.data) != 0:
+            _host_fail("trew_decompose_host")
+
+    out, found = _sized_call(call, TRACE_DTYPE, cap)
+    return out, counts, records, found
+
+
+def decompose_anchor(record):
+    """The anchored unit M of a REFINE_DTYPE record of decompose as a packed word: rotation `reserved` of `unit`, M[j] = U[(j +
+    anchor) mod period], first base most significant."""
+    k, unit, sh = int(record["period"]), int(record["unit"]), 2 * int(record["reserved"])
+    return ((unit << sh) | (unit >> (2 * k - sh))) & ((1 << (2 * k)) - 1) if k else 0
 
 
 _TRACE_COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
@@ -1010,6 +1041,32 @@ class TrewHip:
                       "trew_hip_trace_results")
         return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
 
+    def decompose(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_items=None, max_rows=None, slot=0):
+        """Queue refine's unit of every read of `batch`, anchored at its smallest rotation, and the traceback of the read against
+        it on the slot's stream (no motifs).  max_items, max_rows: as for trace with one motif; a row has 32 bytes here."""
+        max_items, max_rows = _trace_room(batch, 1, max_items, max_rows)
+        self._queue("decompose", slot, batch, None, 1, shape=(int(max_items), int(max_rows)))
+        self._chk(self.lib.trew_hip_decompose(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
+                                              int(max_items), int(max_rows)), "trew_hip_decompose")
+
+    def decompose_results(self, slot=0, want_ms=False):
+        """Results of the slot's last decompose: (TRACE_DTYPE items sorted by (read, start), counts of shape (n_reads,),
+        REFINE_DTYPE records of shape (n_reads,) with reserved = anchor, n_items, n_rows [, kernel ms]).  n_items > max_items or
+        n_rows > max_rows: no items, everything else is exact; repeat the call with both at least what was reported."""
+        n_items, n_rows = C.c_uint64(0), C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, _, max_items, max_rows = self._queued.get(("decompose", slot), (0, 1, 0, 0))
+        counts = np.zeros(n_reads, dtype=np.uint32)
+        records = np.zeros(n_reads, dtype=REFINE_DTYPE)
+        self._chk(self.lib.trew_hip_decompose_results(self.ctx, slot, None, 0, C.byref(n_items), C.byref(n_rows), counts.ctypes.data, records.ctypes.data,
+                                                      C.byref(ms) if want_ms else None), "trew_hip_decompose_results")
+        items, rows = int(n_items.value), int(n_rows.value)
+        out = np.zeros(items if items <= max_items and rows <= max_rows else 0, dtype=TRACE_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_decompose_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n_items), C.byref(n_rows), None, None, None),
+                      "trew_hip_decompose_results")
+        return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
+
     def repeats(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract of every read of `batch` on the slot's stream (no motifs).  max_records: the
         capacity of the log for this call (default: the batch's read count, at least 1)."""
@@ -1325,6 +1382,21 @@ def trace(reads, motifs, penalty=3, min_score=24, device=0, max_items=None, max_
     with t:
         room = _trace_room(b, _motif_array(motifs)[1], max_items, max_rows)
         return _fetch_with_retry(lambda items, rows: t.trace(b, motifs, penalty, min_score, items, rows), t.trace_results, room, (3, 4))[:3]
+
+
+def decompose(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_items=None, max_rows=None):
+    """Units in place with no motif given on the GPU: for every read (bytes / str) `refine`'s record, its unit turned to its
+    smallest rotation (the record's `reserved` word is the anchor; decompose_anchor gives the rotation) and, when the score
+    reaches min_score, the traceback of the read against it cut into copies -- `trace`'s items for that unit, in read
+    orientation.  Returns (TRACE_DTYPE items sorted by (read, start), counts of shape (n_reads,), REFINE_DTYPE records of shape
+    (n_reads,)); trace_signature turns a read's items into text with k = period.  The first call's log and workspace hold
+    max_items items and max_rows rows (defaults: TrewHip.trace's for one motif); when more are found the call is repeated once
+    with the exact numbers."""
+    t, b = _one_batch(reads, device)
+    with t:
+        room = _trace_room(b, 1, max_items, max_rows)
+        return _fetch_with_retry(lambda items, rows: t.decompose(b, min_period, max_period, penalty, min_score, items, rows), t.decompose_results, room,
+                                 (3, 4))[:3]
 
 
 def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):

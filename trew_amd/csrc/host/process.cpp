@@ -1196,6 +1196,7 @@ struct Annotator {
         std::vector<uint32_t> counts;          // intervals, chain: the counts per (read, motif, strand)
         std::vector<uint64_t> vhist;           // variants: hist, then reads_with, of one batch
         std::vector<trew_hip_alignment> arecs; // trace: the alignment records that come with its items
+        std::vector<trew_hip_refined> drecs;   // decompose: the refined records that come with its items
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1670,6 +1671,54 @@ static void fold_trace(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew decompose: fold_refine's rows from the records that come with the items (reserved: the anchor), and fold_trace's items
+// of those reads, against each read's own unit.  decompose_units counts per (period, strand-canonical unit) the rows, their
+// bases and copies, and the units, edited items and items of their signatures.  The workspace holds a row of 32 bytes for every
+// base of the batch, which no batch exceeds; the log starts at sixteen items per read, and a batch whose log overflows is
+// resubmitted once, with the exact numbers.
+static void fold_decompose(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    uint64_t bases = 0;
+    for (uint64_t r = 0; r < x.n; r++) bases += x.lengths[r];
+    if (w->drecs.size() < x.n) w->drecs.resize(x.n);
+    const uint64_t items = fetch_with_retry(
+        p, LogRoom{16 * x.n, std::max<uint64_t>(bases, 1)}, "internal error: the decompose log overflowed twice",
+        [&](LogRoom room) {
+            if (trew_hip_decompose(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.log, room.rows))
+                hip_die(x.c, "trew_hip_decompose");
+        },
+        [&](LogRoom room) {
+            LogRoom need{0, 0};
+            if (trew_hip_decompose_results(x.c, w->slot, records<trew_hip_trace_item>(w, room.log), room.log, &need.log, &need.rows, nullptr, w->drecs.data(), nullptr))
+                hip_die(x.c, "trew_hip_decompose_results");
+            return need;
+        }).log;
+    for (uint64_t r = 0; r < x.n; r++) {
+        const trew_hip_refined &rec = w->drecs[r];
+        if (rec.period == 0 || rec.score < rq.min_score) continue;
+        DecomposeUnit &u = p.decompose_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
+        u.reads++;
+        u.bases += rec.end - rec.start;
+        u.copies += rec.consumed / rec.period;
+        p.frows.push_back(RefineRow{x.first_read + r, x.lengths[r], rec});
+    }
+    const trew_hip_trace_item *recs = static_cast<const trew_hip_trace_item *>(w->recs);
+    for (uint64_t i = 0; i < items; i++) {
+        const trew_hip_trace_item &it = recs[i];
+        const trew_hip_refined &rec = w->drecs[it.read];
+        const uint32_t k = rec.period;
+        const bool errors = it.mismatches || it.insertions || it.deletions;
+        DecomposeUnit &u = p.decompose_units[{k, canonical_unit(rec.unit, (int) k)}];
+        if (it.consumed == k * it.count) u.units += it.count;
+        u.edited += errors;
+        u.items++;
+        const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
+        p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
+                                   run ? std::string() : std::string(x.text + w->st[it.read] + it.start, (size_t) it.bases)});
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1711,6 +1760,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Refine: fold_refine(x, p); break;
             case Measure::Tandems: fold_tandems(x, p); break;
             case Measure::Trace: fold_trace(x, p); break;
+            case Measure::Decompose: fold_decompose(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1777,9 +1827,17 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         u.bases += v.bases;
         u.copies += v.copies;
     });
+    merge_units(into.decompose_units, from.decompose_units, [](DecomposeUnit &u, const DecomposeUnit &v) {
+        u.reads += v.reads;
+        u.bases += v.bases;
+        u.copies += v.copies;
+        u.units += v.units;
+        u.edited += v.edited;
+        u.items += v.items;
+    });
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -1856,7 +1914,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
             size_t rows;
         } logs[] = {{Measure::Intervals, "intervals", out.irows.size()}, {Measure::Chain, "items", out.crows.size()},
                     {Measure::Repeats, "tracts", out.rrows.size()},      {Measure::Satellites, "tracts", out.srows.size()},
-                    {Measure::Tandems, "tracts", out.trows.size()},      {Measure::Trace, "items", out.xrows.size()}};
+                    {Measure::Tandems, "tracts", out.trows.size()},      {Measure::Trace, "items", out.xrows.size()},
+                    {Measure::Decompose, "items", out.xrows.size()}};
         for (const auto &l : logs)
             if (rq.kind == l.kind)
                 fprintf(stderr, "[trew] %s: %llu %s, %llu batch(es) resubmitted with a larger log\n", file_name, (unsigned long long) l.rows, l.noun,

@@ -99,10 +99,10 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems FASTQ...: the per-read measures.
-// One file path for all twelve (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp and trace.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace };
+// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose FASTQ...: the per-read measures.
+// One file path for all thirteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp and decompose.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
@@ -183,6 +183,10 @@ struct TandemRow {
 struct TandemUnit {
     uint64_t reads = 0, tracts = 0, bases = 0, copies = 0;  // reads with such a tract, the tracts, the sums of their end - start and of their copies
 };
+struct DecomposeUnit {
+    uint64_t reads = 0, bases = 0, copies = 0;  // as RefineUnit
+    uint64_t units = 0, edited = 0, items = 0;  // over the rows' items: the copies of the items with consumed = period count, the items with an error, the items
+};
 struct RepeatUnit {
     uint64_t reads = 0, tracts = 0, bases = 0;  // reads with such a tract, the tracts, the sum of their end - start
 };
@@ -198,9 +202,9 @@ struct AnnotFileResult {
     std::vector<SatelliteRow> srows; // satellites: sorted by read, start
     std::vector<AlignRow> arows;     // align: sorted by read, motif, strand
     uint64_t align_sums[TREW_ANNOT_MAX_MOTIFS][2][kAlignSums] = {};  // align: [motif][strand], over the rows
-    std::vector<TraceRow> xrows;     // trace: the items of its arows' keys, sorted by read, motif, strand, start
+    std::vector<TraceRow> xrows;     // trace: the items of its arows' keys, sorted by read, motif, strand, start; decompose: the items of its frows (motif = strand = 0)
     uint64_t trace_sums[TREW_ANNOT_MAX_MOTIFS][2][kTraceSums] = {};  // trace: [motif][strand], over the rows
-    std::vector<RefineRow> frows;    // refine: sorted by read
+    std::vector<RefineRow> frows;    // refine, decompose (rf.reserved: the anchor): sorted by read
     std::vector<TandemRow> trows;    // tandems: sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
@@ -215,6 +219,8 @@ struct AnnotFileResult {
     std::map<std::pair<uint32_t, uint64_t>, std::pair<uint64_t, uint64_t>> period_units;
     // refine: (period, strand-canonical unit) -> its rows, bases and copies
     std::map<std::pair<uint32_t, uint64_t>, RefineUnit> refine_units;
+    // decompose: (period, strand-canonical unit) -> its rows, bases and copies, and the units, edited items and items of their signatures
+    std::map<std::pair<uint32_t, uint64_t>, DecomposeUnit> decompose_units;
     // tandems: (period, strand-canonical unit) -> its reads, tracts, bases and copies
     std::map<std::pair<uint32_t, uint64_t>, TandemUnit> tandem_units;
     // repeats: (period, strand-canonical unit) -> its reads, tracts and bases
@@ -246,7 +252,7 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
-    bool motif_less = false;                      // periods, repeats, satellites, refine, tandems: every positional argument is a file, `names` stays empty
+    bool motif_less = false;                      // periods, repeats, satellites, refine, tandems, decompose: every positional argument is a file, `names` stays empty
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
@@ -269,6 +275,7 @@ int align_main(int argc, char **argv);
 int refine_main(int argc, char **argv);
 int tandems_main(int argc, char **argv);
 int trace_main(int argc, char **argv);
+int decompose_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement

@@ -25,11 +25,11 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose"};
 // whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
-const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true};
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -48,8 +48,9 @@ struct MeasureState {
     int n_motifs = 0;  // variants
     u32 k[kAnnotMaxMotifs] = {};  // chain: the motifs' lengths (pairing a run's events needs start mod k)
     // trace: `records` is its item log, `counter` two values (items, rows), `counts` one u32 per (read, motif, strand); beside them
-    DevBuf rows;       // the direction workspace, 64 bytes a row, grown on demand
-    DevBuf aligned;    // the trew_hip_alignment of every (read, motif)
+    // (decompose: the same, `counts` one u32 per read)
+    DevBuf rows;       // the direction workspace, 64 bytes a row (decompose: 32), grown on demand
+    DevBuf aligned;    // the trew_hip_alignment of every (read, motif) (decompose: the trew_hip_refined of every read)
     u64 max_rows = 0;  // the max_rows of the last call (max_log: its max_items; n: its alignment records)
 };
 
@@ -1225,8 +1226,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace
-// The twelve measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose
+// The thirteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
 // fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
@@ -1305,6 +1306,12 @@ extern "C" int trew_trace_host(const uint32_t *words, const uint32_t *offsets, c
                                int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items,
                                uint32_t *counts, trew_hip_alignment *records) {
     return host_status(trace_host(words, offsets, lengths, n_reads, motifs, n_motifs, penalty, min_score, items, cap, n_items, counts, records));
+}
+
+extern "C" int trew_decompose_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                   int max_period, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items,
+                                   uint32_t *counts, trew_hip_refined *records) {
+    return host_status(decompose_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, items, cap, n_items, counts, records));
 }
 
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
@@ -1419,12 +1426,14 @@ struct LogShape {
     u64 max_log;             // the capacity of the log for this call
     u64 counts_per_read;     // u32 counts: n_motifs * 2 (intervals, trace), n_motifs * 4 (chain), 1 (repeats, satellites, tandems)
     bool zero_counts;        // the kernel adds to its counts (repeats, satellites, tandems); the others store every one of them
-    u64 max_rows;            // trace: the rows of the direction workspace for this call, and a second counter for them; else 0
-    u64 aligned_per_read;    // trace: n_motifs alignment records; else 0
+    u64 max_rows;            // trace, decompose: the rows of the direction workspace for this call, and a second counter for them; else 0
+    u64 aligned_per_read;    // trace: n_motifs alignment records; decompose: one refined record; else 0
+    size_t row_bytes;        // trace: 64, decompose: 32; else 0
+    size_t aligned_bytes;    // of one of the records beside the log; else 0
 };
 
-// The queue call of the measures with an append log (intervals, chain, repeats, satellites, tandems, trace): measure_begin, the
-// counter (one word, trace two: a fixed size, allocated on first use), room for the counts, the log and trace's two buffers,
+// The queue call of the measures with an append log (intervals, chain, repeats, satellites, tandems, trace, decompose): measure_begin, the
+// counter (one word, trace and decompose two: a fixed size, allocated on first use), room for the counts, the log and trace's two buffers,
 // then the numbers of the call, all in one place, the counter back to zero -- every call starts from zero, also one without
 // reads, whose results then report nothing found -- and `launch` between the events unless the batch is empty.
 template <class Own, class Launch>
@@ -1438,10 +1447,10 @@ static int queue_log(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, c
     const size_t counter_bytes = (shape.max_rows ? 2 : 1) * sizeof(unsigned long long);
     const u64 n_counts = db.n_reads * shape.counts_per_read, n_aligned = db.n_reads * shape.aligned_per_read;
     if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, counter_bytes));
-    if (int rc = grow(ctx, s, st.aligned, n_aligned * sizeof(trew_hip_alignment))) return rc;
+    if (int rc = grow(ctx, s, st.aligned, n_aligned * shape.aligned_bytes)) return rc;
     if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
     if (int rc = grow(ctx, s, st.records, shape.max_log * shape.rec_bytes)) return rc;
-    if (int rc = grow(ctx, s, st.rows, shape.max_rows * 64ull)) return rc;
+    if (int rc = grow(ctx, s, st.rows, shape.max_rows * shape.row_bytes)) return rc;
     st.valid = true;
     st.timed = false;
     st.n = n_aligned;
@@ -1586,7 +1595,7 @@ extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
                : max_rows < 1              ? "max_rows must be at least 1"
                                            : nullptr;
     };
-    const LogShape shape = {sizeof(trew_hip_trace_item), max_items, (u64) n_motifs * 2ull, false, max_rows, (u64) n_motifs};
+    const LogShape shape = {sizeof(trew_hip_trace_item), max_items, (u64) n_motifs * 2ull, false, max_rows, (u64) n_motifs, 64, sizeof(trew_hip_alignment)};
     return queue_log(ctx, batch, slot, motifs, n_motifs, kTrace, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         HIPCHK(ctx, launch_trace(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
@@ -1613,6 +1622,42 @@ extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trac
     return fetch_end(ctx, st, ms_kernel);
 }
 
+// ---------------------------------------------------------------- units in place with no motif given: refine's unit, anchored, traced
+// As trace: `records` is the item log, `counter` two values (items, rows); `counts` one u32 per read, `aligned` the
+// trew_hip_refined of every read (its reserved word the anchor), `rows` 32 bytes a row.
+extern "C" int trew_hip_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                                  uint32_t min_score, uint64_t max_items, uint64_t max_rows) {
+    auto own = [&]() -> const char * {
+        if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+        return max_items < 1 ? "max_items must be at least 1" : max_rows < 1 ? "max_rows must be at least 1" : nullptr;
+    };
+    const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 1, false, max_rows, 1, 32, sizeof(trew_hip_refined)};
+    return queue_log(ctx, batch, slot, nullptr, 0, kDecompose, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
+        HIPCHK(ctx, launch_decompose(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, (trew_hip_refined *) st.aligned.p,
+                                     (u32 *) st.counts.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_decompose_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                                          uint32_t *counts, trew_hip_refined *records, float *ms_kernel) {
+    const char *arg_error = !n_items || !n_rows ? "trew_hip_decompose_results: n_items and n_rows must not be null"
+                            : cap && !items     ? "trew_hip_decompose_results: items must not be null"
+                                                : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kDecompose, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kDecompose];
+    unsigned long long found[2] = {0, 0};
+    if (int rc = fetch_counted(ctx, st, found, 2, counts)) return rc;
+    *n_items = found[0];
+    *n_rows = found[1];
+    if (records && st.n) HIPCHK(ctx, hipMemcpy(records, st.aligned.p, st.n * sizeof(trew_hip_refined), hipMemcpyDeviceToHost));
+    // trace's contract: both fit, or no items
+    if (int rc = fetch_log(ctx, st, items, cap, found[1] <= st.max_rows ? whole_log(st, found[0]) : 0, sort_trace_items)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
 // ---------------------------------------------------------------- gap-tolerant motif intervals anywhere in a read
 extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs,
                                   const trew_hip_interval_rule *rules, int n_motifs, uint64_t max_intervals) {
@@ -1620,7 +1665,7 @@ extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch
         if (const char *e = rules_error(rules, n_motifs)) return e;
         return max_intervals < 1 ? "max_intervals must be at least 1" : nullptr;
     };
-    const LogShape shape = {sizeof(trew_hip_interval), max_intervals, (u64) n_motifs * 2ull, false, 0, 0};
+    const LogShape shape = {sizeof(trew_hip_interval), max_intervals, (u64) n_motifs * 2ull, false, 0, 0, 0, 0};
     return queue_log(ctx, batch, slot, motifs, n_motifs, kIntervals, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         IntervalRulesDev rd;
         memset(&rd, 0, sizeof(rd));
@@ -1713,7 +1758,7 @@ extern "C" int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_ref
 // The log holds events, not items; the results call pairs them, for which it keeps the motifs' lengths.
 extern "C" int trew_hip_chain(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, uint64_t max_events) {
     auto own = [&]() -> const char * { return max_events < 1 ? "max_events must be at least 1" : nullptr; };
-    const LogShape shape = {sizeof(uint4), max_events, (u64) n_motifs * 4ull, false, 0, 0};
+    const LogShape shape = {sizeof(uint4), max_events, (u64) n_motifs * 4ull, false, 0, 0, 0, 0};
     return queue_log(ctx, batch, slot, motifs, n_motifs, kChain, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         for (int m = 0; m < n_motifs; m++) st.k[m] = (u32) motifs[m].k;  // a batch without reads has no events to pair
         const ChainLog lg = {st.counter, (uint4 *) st.records.p, st.max_log};
@@ -1783,7 +1828,7 @@ static int queue_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot
         if (const char *e = error()) return e;
         return max_records < 1 ? "max_records must be at least 1" : nullptr;
     };
-    const LogShape shape = {rec_bytes, max_records, 1, true, 0, 0};
+    const LogShape shape = {rec_bytes, max_records, 1, true, 0, 0, 0, 0};
     return queue_log(ctx, batch, slot, nullptr, 0, which, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         return launch(s, db, RepeatLog{st.counter, (u32 *) st.records.p, st.max_log}, (u32 *) st.counts.p);
     });

@@ -172,7 +172,7 @@ struct RepeatLog {
 };
 
 // trew_hip_trace's item log and direction workspace (kernels/trace.inc): items of twelve u32 (trew_hip_trace_item), rows of 64
-// bytes (a direction byte a lane)
+// bytes (a direction byte a lane); trew_hip_decompose's as well (kernels/decompose.inc), whose rows have one strand and 32 bytes
 struct TraceLog {
     unsigned long long *counter;      // items found; keeps counting past cap
     u32 *recs;                        // cap items

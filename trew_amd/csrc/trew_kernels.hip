@@ -49,6 +49,7 @@
 //   refine.inc         refine_wave_kernel (de novo repeats under indels: periods.inc's period and tract, a seed unit from the longest run of eq_k, align.inc's row step for the alignment, the vote and the re-voted unit)
 //   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: repeats.inc's recursion over pieces with refine.inc's refine_piece per piece)
 //   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
+//   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -92,6 +93,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/refine.inc"
 #include "kernels/tandems.inc"
 #include "kernels/trace.inc"
+#include "kernels/decompose.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -456,6 +458,15 @@ hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const Annot
     if (B.n_reads == 0) return hipSuccess;
     const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
     hipLaunchKernelGGL(trace_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, min_score, lg, (u32 *) d_out, d_counts);
+    return hipGetLastError();
+}
+
+// Units in place with no motif given: one kernel, a wave per read, for every read length (the grid of launch_tracts).
+hipError_t launch_decompose(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const TraceLog &lg,
+                            trew_hip_refined *d_out, u32 *d_counts) {
+    if (B.n_reads == 0) return hipSuccess;
+    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
+    hipLaunchKernelGGL(decompose_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts);
     return hipGetLastError();
 }
 

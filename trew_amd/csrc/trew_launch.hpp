@@ -64,6 +64,10 @@ hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const Annot
 // when the kernel starts; d_out: the alignment records, d_counts: the items of every (read, motif, strand)
 hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, u32 min_score,
                         const TraceLog &lg, trew_hip_alignment *d_out, u32 *d_counts);
+// trew_hip_decompose: the wave-per-read kernel of kernels/decompose.inc on the grid of launch_tracts; no motifs; both counters
+// of `lg` are zero when it starts, its rows have 32 bytes
+hipError_t launch_decompose(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const TraceLog &lg,
+                            trew_hip_refined *d_out, u32 *d_counts);
 // trew_hip_refine: the wave-per-read kernel of kernels/refine.inc on the grid of launch_tracts; no motifs
 hipError_t launch_refine(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined *d_out);
 // trew_hip_tandems: the wave-per-read kernel of kernels/tandems.inc on the grid of launch_tracts; no motifs; `lg` holds records

@@ -1008,4 +1008,50 @@ const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths,
     return nullptr;
 }
 
+// ---------------------------------------------------------------- units in place with no motif given: refine's unit, anchored, traced
+//  refine_read_host's record, the rotations of its unit compared as packed words, and trace_codes_host's full table
+// for the forward strand against the smallest one, for any unit length >= 1.
+const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                           u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_refined *records) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    if (!n_items || (cap && !items)) return "trew_decompose_host: null argument";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_decompose_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_decompose_host: more than 2^32 - 1 reads";
+    std::vector<unsigned char> base, dirs;
+    std::vector<trew_hip_trace_item> mine;
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        trew_hip_refined R;
+        trew_hip_period periods;
+        refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, R, periods);
+        mine.clear();
+        if (R.period && R.score >= min_score) {
+            const u32 k = R.period;
+            u32 u[32], t[32], rho = 0;
+            for (u32 j = 0; j < k; j++) u[j] = (u32) (R.unit >> (2 * (k - 1 - j))) & 3u;  // first base most significant
+            u64 smallest = R.unit;
+            for (u32 q = 1; q < k; q++) {  // rotation q: its base j is U[(j + q) mod k]
+                u32 rot[32];
+                for (u32 j = 0; j < k; j++) rot[j] = u[(j + q) % k];
+                const u64 w = pack_unit(rot, k);
+                if (w < smallest) smallest = w, rho = q;  // U is primitive: the rotations are distinct
+            }
+            for (u32 j = 0; j < k; j++) t[j] = u[(j + rho) % k];
+            u32 rec[5];
+            trace_codes_host(base.data(), lengths[r], t, (int) k, penalty, min_score, rec, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                             mine);
+            R.reserved = rho;
+        }
+        for (size_t q = mine.size(); q-- > 0;) {  // last to first: ascending starts
+            if (found < cap) items[found] = mine[q];
+            found++;
+        }
+        if (counts) counts[r] = (u32) mine.size();
+        if (records) records[r] = R;
+    }
+    *n_items = found;
+    return nullptr;
+}
+
 }  // namespace trew

@@ -1,5 +1,5 @@
 // trew_measures_host.hpp -- the per-read measures computed on the CPU, straight from their definitions
-// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite, trew_hip_alignment, trew_hip_refined, trew_hip_trace_item), and the argument checks the
+// (include/trew_hip.h: trew_hip_annot, trew_hip_tract, trew_hip_interval, trew_hip_variant, trew_hip_period, trew_hip_chain_item, trew_hip_repeat, trew_hip_satellite, trew_hip_alignment, trew_hip_refined, trew_hip_trace_item; trew_hip_decompose uses the last two), and the argument checks the
 // device entry points share with them.  Plain C++17: no HIP, no context.  trew_capi.cpp wraps these into the extern "C"
 // trew_*_host functions and keeps the error strings; tests/harness/measures_host_harness.cpp runs them under sanitizers.
 //
@@ -63,5 +63,9 @@ const char *trace_host(const uint32_t *words, const uint32_t *offsets, const uin
                        int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
                        trew_hip_alignment *records);
 void sort_trace_items(trew_hip_trace_item *v, uint64_t n);  // by (read, motif, strand, start)
+// units in place with no motif given: refine_host's record, its unit's smallest rotation and trace_host's table for one strand
+const char *decompose_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                           int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
+                           trew_hip_refined *records);
 
 }  // namespace trew
