@@ -89,6 +89,10 @@ enum {
     TREW_FLAG_DEBUG_SMALL_BOUNDS = 16384, /* tests: the buffer in which the bounds pass hands the packed bounds of the flagged short reads
                                 to the exact kernel holds 64 worklist entries instead of a share of max_batch_reads, so that a small
                                 batch has reads on either side of it (stored bounds / bounds in row layout); results are identical */
+    TREW_FLAG_DEBUG_NO_LIVE_LIST = 32768, /* tests and A/B runs: the bounds pass neither sharpens the bound of halves with an N on sixteen
+                                buckets nor drops the worklist entries no k of which can still count; the exact kernel reads the
+                                prefilter's worklist and the 8-bucket words (trew_hip_debug_live_list then returns the worklist,
+                                and no entry is counted dead); results are identical */
     TREW_FLAG_TRACK_PRESSURE = 256 /* every batch ends with a copy of the table's fill counters into pinned host memory, and
                                 trew_hip_table_pressure answers from those copies (and from what collect / add_rows /
                                 reset read since) instead of asking the device: for hosts that ask before every batch.
@@ -254,14 +258,23 @@ int trew_hip_table_pressure(trew_hip_ctx *ctx, uint64_t *used_slots, uint64_t *t
  * out[8] prefilter, uniform batches of short or paired reads: units of which only one half had to be judged after the fast
  *        loop (an N in it, or a 4-bucket pass) and was, a lane per half; out[9] units judged whole by the same drain (two or
  *        more such halves).  Both count items drained, flagged or not.
+ * out[10] worklist entries the bounds pass of the most recent submit found dead (both halves bounded, no k of either with a pass
+ *        bit, no whole-read segment) and kept from the exact kernel; unlike the others a figure of ONE launch, and zero after
+ *        trew_hip_reset_tables, without a bounds pass and with TREW_FLAG_DEBUG_NO_LIVE_LIST.
  * n <= TREW_DEBUG_COUNTERS entries are written. */
-#define TREW_DEBUG_COUNTERS 10
+#define TREW_DEBUG_COUNTERS 11
 int trew_hip_debug_counters(trew_hip_ctx *ctx, uint64_t *out, int n);
 
 /* Diagnostic: the unit indices (reads, or pairs in pair mode) the prefilter of the last submit on `slot` handed to the exact
  * kernel, in worklist order (after trew_hip_wait).  *n receives their number even when it exceeds cap.  Tests use it to assert
  * that the prefilter is sound: every read with a (segment, k) that k_mer_check accepts (kmer.cpp:2221-2258) must be there. */
 int trew_hip_debug_worklist(trew_hip_ctx *ctx, int slot, uint32_t *units, uint64_t cap, uint64_t *n);
+
+/* Diagnostic: the unit indices the exact kernel of the last submit on `slot` walked, in its order (after trew_hip_wait): the live
+ * entries the bounds pass kept of the worklist's leading ones, then the worklist's entries beyond the hand-over buffer, which that
+ * pass does not look at.  A subset of trew_hip_debug_worklist as a multiset; equal to it where no bounds pass ran (other modes,
+ * MAX_MER > 32, TREW_FLAG_DEBUG_NO_GROUP) and with TREW_FLAG_DEBUG_NO_LIVE_LIST.  Arguments as trew_hip_debug_worklist. */
+int trew_hip_debug_live_list(trew_hip_ctx *ctx, int slot, uint32_t *units, uint64_t cap, uint64_t *n);
 
 /* Per-read results of the last submit on `slot` (after trew_hip_wait): for
  * TREW_MODE_SEGMENT the (k_high, k_low, MAX_SEQ at k_high, MAX_SEQ at k_low)

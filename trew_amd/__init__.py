@@ -16,6 +16,7 @@ from .capi import (  # noqa: F401
     FLAG_DEBUG_NO_JOINT,
     FLAG_DEBUG_NO_UNI_DRAIN,
     FLAG_DEBUG_SMALL_BOUNDS,
+    FLAG_DEBUG_NO_LIVE_LIST,
     FLAG_DEBUG_WIDE_NO_WAIT,
     MODE_LONG,
     MODE_PAIR,

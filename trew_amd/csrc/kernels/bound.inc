@@ -198,3 +198,61 @@ __device__ __forceinline__ u32 class_links(const u32 (&V)[NW], const u32 (&E)[NW
     }
     return links;
 }
+
+// ------------------------------------------------------------------ the fourth invariant: adjacent equal bases
+// The number of cyclically adjacent equal bases of a k-mer (base t == base t+1, and base k-1 == base 0) is the same for every
+// rotation of it, so its parity is one more feature that is constant on a rotation class: it splits each of the eight parity
+// buckets in two.  For window i at length k the parity is PD[i] ^ PD[i+k-1] ^ [base i == base i+k-1], with PD the exclusive prefix
+// parity of D[t] = [base t == base t+1] over valid neighbours.  A window that counts has no N, so every adjacent pair inside it
+// is a valid one and D says the truth about it; windows with an N are in no bucket, as in the 8-bucket split.
+// Only the bounds pass uses it (bounds_pass.inc): inline in the prefilter it cost the fast loop its registers.
+
+// PD of a segment: lo / hi = its planes from bit 0, v1 = its valid bases (segment_setup)
+template <int NW>
+__device__ __forceinline__ void adjacency_parity(const u32 (&lo)[NW], const u32 (&hi)[NW], const u32 (&v1)[NW], u32 (&PD)[NW]) {
+    u32 D[NW];
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+        const int jn = j + 1 < NW ? j + 1 : 0;
+        const u32 nlo = alignbit(j + 1 < NW ? lo[jn] : 0u, lo[j], 1u), nhi = alignbit(j + 1 < NW ? hi[jn] : 0u, hi[j], 1u);
+        const u32 nv = alignbit(j + 1 < NW ? v1[jn] : 0u, v1[j], 1u);
+        D[j] = ~((lo[j] ^ nlo) | (hi[j] ^ nhi)) & v1[j] & nv;
+    }
+    prefix_parity<NW>(D, PD);
+}
+
+// word j of the feature at length k, s = k - 1 in [0, 31] (wave-uniform); bits outside the windows that count are not defined
+template <int NW>
+__device__ __forceinline__ u32 adjacency_feature_word(const u32 (&PD)[NW], const u32 (&lo)[NW], const u32 (&hi)[NW], int j, u32 s) {
+    const int jn = j + 1 < NW ? j + 1 : 0;
+    const u32 pd = alignbit(j + 1 < NW ? PD[jn] : 0u, PD[j], s);
+    const u32 sl = alignbit(j + 1 < NW ? lo[jn] : 0u, lo[j], s), sh = alignbit(j + 1 < NW ? hi[jn] : 0u, hi[j], s);
+    return PD[j] ^ pd ^ ~((lo[j] ^ sl) | (hi[j] ^ sh));
+}
+
+// The 16-bucket split of one k: Buckets8's masked form (F1, F2 hold no bit outside V) with every bucket split once more by F4.
+// The largest of the sixteen is at most the largest of the eight, and still an upper bound of MAX.  Written plainly, a popcount
+// a bucket: its only caller runs it where a half with an N passed on eight buckets, which is rare.
+template <int N>
+__device__ __forceinline__ u32 max_bucket16(const u32 (&F1)[N], const u32 (&F2)[N], const u32 (&F3)[N], const u32 (&F4)[N], const u32 (&V)[N]) {
+    u32 c[16];
+#pragma unroll
+    for (int b = 0; b < 16; b++) c[b] = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const u32 a[4] = {V[j] & ~(F1[j] | F2[j]), ~F1[j] & F2[j], F1[j] & ~F2[j], F1[j] & F2[j]};
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const u32 b1 = a[q] & F3[j], b0 = a[q] ^ b1;
+            const u32 d11 = b1 & F4[j], d01 = b0 & F4[j];
+            c[4 * q + 0] += __popc(b0 ^ d01);
+            c[4 * q + 1] += __popc(d01);
+            c[4 * q + 2] += __popc(b1 ^ d11);
+            c[4 * q + 3] += __popc(d11);
+        }
+    }
+    u32 m = 0;
+#pragma unroll
+    for (int b = 0; b < 16; b++) m = max(m, c[b]);
+    return m;
+}

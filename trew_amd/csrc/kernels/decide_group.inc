@@ -592,8 +592,8 @@ __device__ __forceinline__ WT strand_flip(WT w, int k) {
 // more than 16 runs -- goes through decide_halves / run_short_routed / target as before.
 // rdA / rdB: reads whose triples are staged in LDS, both with valid halves (n >= 4 MIN_MER); haveB = false: rdA alone (rows 2
 // and 3 idle).  Only instantiated where the k range fits 32 indices.
-// SB: the worklist positions of the two reads, by which the packed bounds the bounds pass (bounds_pass.inc) left for them are
-// found -- StoredBounds (positions at or beyond the buffer's capacity have none), or NoStoredBounds in the instantiations that
+// SB: the positions of the two reads in the kernel's list, by which the packed bounds the bounds pass (bounds_pass.inc) left for them are
+// found -- StoredBounds (positions at or beyond the stored prefix have none), or NoStoredBounds in the instantiations that
 // never have any.  Where both reads have stored bounds, lane (row g, j) loads word j and word 16 + j of its half and the row needs
 // no parities; otherwise the rows bound their k themselves (row_prepare, bound_at_k).
 constexpr u32 kBoundWords = 32;                   // packed words per half, index k - MIN_MER: every k of a run the group pass takes
@@ -619,6 +619,7 @@ struct ExactKernArgs {
     u32 cap, rawwords;
     const u32 *bnd;  // the packed bounds of the first bnd_cap worklist entries (bounds_pass.inc), bnd_cap = 0: none
     u32 bnd_cap;
+    const u32 *live;  // the leading entries of the list exact_kernel<3, short, u64> works on (exact_kernel.inc)
 };
 template <int NW, typename WT, typename SB>
 __device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, const ReadRef rdA, const ReadRef rdB, bool haveB, const SB sb) {
@@ -633,7 +634,8 @@ __device__ void run_short_group(ExactSmem sm, const DevParams &P, TableRef T, co
         typedef const __attribute__((address_space(4))) u64 *c64;
         typedef const __attribute__((address_space(4))) u32 *c32;
         const u64 ka = (u64) __builtin_amdgcn_kernarg_segment_ptr();
-        const u32 bcap = *(c32) (ka + offsetof(ExactKernArgs, bnd_cap));
+        // the positions with stored bounds: the leading wl_count[kStoredPrefixWord] of the kernel's list (bounds_pass.inc)
+        const u32 bcap = *(c32) (*(c64) (ka + offsetof(ExactKernArgs, wl_count)) + 4u * kStoredPrefixWord);
         const u32 posA = rfl(sb.posA), posB = rfl(sb.posB);  // (wave-uniform, see rfl_i)
         stored = posA < bcap && posB < bcap;  // both reads of the pass have stored bounds
         if (stored && (lane < 32u || haveB)) {

@@ -22,9 +22,10 @@ constexpr int exact_waves(bool narrow) {
 template <int NW, int MODE, typename WT>
 __global__ __launch_bounds__(64, (exact_waves<NW, MODE>(sizeof(WT) == 8))) void exact_kernel(DevParams P, DevBatch B, DevTableG1 TG, const u32 *wl,
                                                    u32 *wl_count, u32 *wl_count_next, u32 wl_cap, SegResults R, u32 cap, u32 rawwords,
-                                                   const u32 *bnd, u32 bnd_cap) {
+                                                   const u32 *bnd, u32 bnd_cap, const u32 *live) {
     // bnd / bnd_cap: the packed bounds the bounds pass left for the first bnd_cap worklist entries (kernels/bounds_pass.inc; 0: none --
     // only the short-read kernel on 3-word masks is ever given any)
+    // live: the list that kernel reads in front of the worklist (kLive below); everywhere else it is not looked at
     // The table descriptor is a by-value kernel argument that the kernel never touches as such: it hands a POINTER to it --
     // into the kernarg segment of this very dispatch -- down to the functions that add rows (TableRef, exact_core.inc), which
     // read its fields with scalar loads when they need them.  (A device-resident copy of the descriptor, written once at
@@ -56,6 +57,12 @@ __global__ __launch_bounds__(64, (exact_waves<NW, MODE>(sizeof(WT) == 8))) void 
     sm.rw = nullptr;
     u32 n = wl_count[0];
     n = n < wl_cap ? n : wl_cap;
+    // The short-read kernel on 3-word masks works on the list the bounds pass left (bounds_pass.inc): `live`, whose
+    // wl_count[kStoredPrefixWord] entries have their packed bounds stored at their positions, and behind them the worklist's
+    // entries from bnd_cap on, which have none.  Where that pass dropped nothing (TREW_FLAG_DEBUG_NO_LIVE_LIST: live = wl, the word =
+    // min(n, bnd_cap)) or did not run (the word and bnd_cap are zero) this is the worklist itself.
+    constexpr bool kLive = MODE == TREW_MODE_SHORT && NW == 3 && sizeof(WT) == 8;
+    if constexpr (kLive) n = wl_count[kStoredPrefixWord] + (n > bnd_cap ? n - bnd_cap : 0u);
 #ifdef TREW_PHASE_PROFILE
     if (lane_id() < 32) ph_lds()[lane_id()] = 0;
     __syncthreads();
@@ -134,7 +141,16 @@ __global__ __launch_bounds__(64, (exact_waves<NW, MODE>(sizeof(WT) == 8))) void 
         auto chunk_items = [&](u64 w0l) __attribute__((always_inline)) -> u32 { return (u32) ((w0l + kUnits < n ? w0l + kUnits : n) - w0l); };
         // step A: the chunk's worklist entries -> unit[] of buffer bf
         auto fetch_units = [&](u32 bf, u64 w0l, u32 nit) __attribute__((always_inline)) {
-            if (lane < nit) __builtin_amdgcn_global_load_lds(wl + w0l + lane, (__attribute__((address_space(3))) u32 *) (meta_base + bf * kMetaWords), 4, 0, 0);
+            const u32 *src = wl + w0l + lane;
+            if constexpr (kLive) {  // (all three from memory: scalar loads a chunk, no register held across the passes)
+                typedef const __attribute__((address_space(4))) u64 *c64;
+                typedef const __attribute__((address_space(4))) u32 *c32;
+                const u64 ka = (u64) __builtin_amdgcn_kernarg_segment_ptr();
+                const u32 pre = *(c32) (*(c64) (ka + offsetof(KernArgs, wl_count)) + 4u * kStoredPrefixWord);
+                const u32 p = (u32) w0l + lane;  // (positions fit 32 bits: n <= wl_cap)
+                src = p < pre ? (const u32 *) *(c64) (ka + offsetof(KernArgs, live)) + p : wl + (p - pre) + *(c32) (ka + offsetof(KernArgs, bnd_cap));
+            }
+            if (lane < nit) __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) u32 *) (meta_base + bf * kMetaWords), 4, 0, 0);
         };
         // step B (unit[] has landed): descriptors, then the reads' words -> raw[] of buffer bf
         auto fetch_words = [&](u32 bf, u32 nit) __attribute__((always_inline)) {

@@ -65,6 +65,10 @@ struct Slot {
     // slot's batch, written between its prefilter and its exact kernel (nullptr / 0: a context whose batches never take that pass)
     u32 *d_bnd = nullptr;
     u32 bnd_cap = 0;
+    // the live worklist of the same pass: those of the first bnd_cap entries the exact kernel can still record something for
+    // (bnd_cap words; nullptr with TREW_FLAG_DEBUG_NO_LIVE_LIST).  live_launch: the slot's last launch read it.
+    u32 *d_live = nullptr;
+    bool live_launch = false;
     int2 *d_thr = nullptr;   // pass thresholds of the prefilter's uniform-geometry path (kThrRows * kThrRow)
     int2 *h_thr = nullptr;   // pinned staging of the same
     hipEvent_t ev_tail = nullptr, ev_copied = nullptr;  // order the context's copy stream behind / in front of this slot's stream (BatchCopy)
@@ -144,6 +148,8 @@ struct trew_hip_ctx {
     // between resets); trew_hip_table_pressure answers from these
     std::atomic<u32> seen[kDiagWords];
     std::atomic<int> last_slot{-1};  // slot of the most recent submit (launch_batch: is another slot's batch still running?)
+    u32 *d_bound_need = nullptr;  // integer pass thresholds of the bounds pass (fill_bound_needs); nullptr: it keeps its doubles
+    std::atomic<int> dead_slot{-1};  // the slot whose counter block holds the dead entries of the most recent launch (-1: it had no live list, or the tables were reset since)
     std::mutex seen_mu;  // keeps a reset (which zeroes the copies) apart from a query that folds them
 };
 
@@ -326,6 +332,13 @@ extern "C" int trew_hip_init(const trew_hip_params *params, trew_hip_ctx **out) 
     }
 
     if ((e = hipMalloc((void **) &ctx->d_row_flags, kRowFlagWords * 4)) != hipSuccess) return bail("hipMalloc(row flags)", e);
+    if (bounds_pass_applies(ctx->dp, 1)) {
+        u32 need[kBoundNeedWords];
+        if (fill_bound_needs(ctx->dp, need)) {  // LOW and HIGH are the context's: once
+            if ((e = hipMalloc((void **) &ctx->d_bound_need, sizeof(need))) != hipSuccess) return bail("hipMalloc(bound thresholds)", e);
+            if ((e = hipMemcpy(ctx->d_bound_need, need, sizeof(need), hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(bound thresholds)", e);
+        }
+    }
     if ((e = hipEventCreateWithFlags(&ctx->ev_producer, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     ctx->slots.resize((size_t) p.n_slots);
     for (auto &s : ctx->slots) {
@@ -358,6 +371,8 @@ extern "C" int trew_hip_init(const trew_hip_params *params, trew_hip_ctx **out) 
             const u64 share = std::min<u64>(std::max<u64>(p.max_batch_reads / 32, std::min<u64>(p.max_batch_reads, 1ull << 16)), 1ull << 22);
             s.bnd_cap = (p.flags & TREW_FLAG_DEBUG_SMALL_BOUNDS) ? 64u : (u32) share;
             if ((e = hipMalloc((void **) &s.d_bnd, (size_t) s.bnd_cap * bounds_entry_bytes())) != hipSuccess) return bail("hipMalloc(bounds)", e);
+            if (!(p.flags & TREW_FLAG_DEBUG_NO_LIVE_LIST) && (e = hipMalloc((void **) &s.d_live, (size_t) s.bnd_cap * sizeof(u32))) != hipSuccess)
+                return bail("hipMalloc(live worklist)", e);
         }
         if ((e = hipMalloc((void **) &s.d_wl_count, 2 * kWlCountBytes)) != hipSuccess) return bail("hipMalloc(wl_count)", e);
         if ((e = hipMemsetAsync(s.d_wl_count, 0, 2 * kWlCountBytes, ctx->fill_stream)) != hipSuccess) return bail("hipMemsetAsync", e);
@@ -394,6 +409,7 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
         if (s.h_thr) (void) hipHostFree(s.h_thr);
         if (s.d_wl) (void) hipFree(s.d_wl);
         if (s.d_bnd) (void) hipFree(s.d_bnd);
+        if (s.d_live) (void) hipFree(s.d_live);
         if (s.d_wl_count) (void) hipFree(s.d_wl_count);
         if (s.res.k_high) (void) hipFree(s.res.k_high);
         if (s.res.k_low) (void) hipFree(s.res.k_low);
@@ -437,6 +453,7 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
     if (ctx->d_collect_rows) (void) hipFree(ctx->d_collect_rows);
     if (ctx->d_add_rows) (void) hipFree(ctx->d_add_rows);
     if (ctx->d_row_flags) (void) hipFree(ctx->d_row_flags);
+    if (ctx->d_bound_need) (void) hipFree(ctx->d_bound_need);
     if (ctx->ev_producer) (void) hipEventDestroy(ctx->ev_producer);
     delete ctx;
 }
@@ -682,9 +699,11 @@ static int launch_batch(trew_hip_ctx *ctx, Slot &s, const DevBatch &db, u32 max_
     }
     // the bounds pass, on the slot's stream between the two kernels (exact_ms of last_timing includes it); no stream of its own
     const bool with_bounds = s.d_bnd != nullptr && bounds_pass_applies(ctx->dp, max_seg);
-    if (with_bounds) SUBMIT_CHK(launch_bounds(s.stream, (u32) ctx->n_cu, db.n_units, ctx->dp, db, s.d_wl, wl_count, wl_cap, s.d_bnd, s.bnd_cap));
+    if (with_bounds) SUBMIT_CHK(launch_bounds(s.stream, (u32) ctx->n_cu, db.n_units, ctx->dp, db, s.d_wl, wl_count, wl_cap, s.d_bnd, s.bnd_cap, s.d_live, ctx->d_bound_need));
     SUBMIT_CHK(launch_exact(s.stream, (u32) ctx->n_cu, db.n_units, ctx->dp, db, ctx->table_g1, s.d_wl, wl_count, wl_count_next, wl_cap, s.res, cap, rawwords, max_seg, share,
-                            with_bounds ? s.d_bnd : nullptr, s.bnd_cap));
+                            with_bounds ? s.d_bnd : nullptr, s.bnd_cap, with_bounds ? s.d_live : nullptr));
+    s.live_launch = with_bounds && s.d_live != nullptr;
+    ctx->dead_slot.store(s.live_launch ? me : -1, std::memory_order_relaxed);
     if (timed) SUBMIT_CHK(hipEventRecord(ev[2], s.stream));
     if (compat_g1) {  // the stale rows of this batch's pairs (and of the previous batch's tail) are added again, in file order
         SUBMIT_CHK(launch_g1_apply(s.stream, ctx->table, ctx->g1, db, ctx->dp.min_mer, ctx->g1_carry[ctx->g1_batches & 1], ctx->g1_carry[(ctx->g1_batches + 1) & 1],
@@ -1000,6 +1019,7 @@ extern "C" int trew_hip_reset_tables(trew_hip_ctx *ctx) {
     if (!ctx) return -1;
     std::lock_guard<std::mutex> lk(ctx->table_mu);
     if (int rc = sync_all(ctx)) return rc;
+    ctx->dead_slot.store(-1, std::memory_order_relaxed);  // trew_hip_debug_counters starts from zero in every slot
     return reset_locked(ctx);
 }
 
@@ -1112,13 +1132,38 @@ extern "C" int trew_hip_debug_worklist(trew_hip_ctx *ctx, int slot, uint32_t *un
     return 0;
 }
 
+extern "C" int trew_hip_debug_live_list(trew_hip_ctx *ctx, int slot, uint32_t *units, uint64_t cap, uint64_t *n) {
+    if (!ctx || !n) return -1;
+    if (slot < 0 || slot >= (int) ctx->slots.size()) return fail(ctx, "slot out of range");
+    HIPCHK(ctx, hipSetDevice(ctx->p.device));
+    Slot &s = ctx->slots[(size_t) slot];
+    if (!s.live_launch) return trew_hip_debug_worklist(ctx, slot, units, cap, n);  // the exact kernel read the worklist itself
+    HIPCHK(ctx, hipStreamSynchronize(s.stream));
+    u32 blk[3] = {0, 0, 0};  // worklist size, stored prefix, dead entries (trew_common.hpp)
+    HIPCHK(ctx, hipMemcpy(blk, s.d_wl_count + ((s.n_launches - 1) & 1) * kWlCountWords, sizeof(blk), hipMemcpyDeviceToHost));
+    const u64 flagged = std::min<u64>(blk[0], ctx->p.max_batch_reads);
+    const u64 pre = std::min<u64>(blk[kStoredPrefixWord], s.bnd_cap), tail = flagged > s.bnd_cap ? flagged - s.bnd_cap : 0;
+    *n = pre + tail;
+    // the live entries, then the worklist's entries the bounds pass did not look at: what the exact kernel walked, in its order
+    const u64 take_pre = std::min<u64>(pre, cap), take_tail = std::min<u64>(tail, cap - take_pre);
+    if (units && take_pre) HIPCHK(ctx, hipMemcpy(units, s.d_live, take_pre * 4, hipMemcpyDeviceToHost));
+    if (units && take_tail) HIPCHK(ctx, hipMemcpy(units + take_pre, s.d_wl + s.bnd_cap, take_tail * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int trew_hip_debug_counters(trew_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0) return -1;
     if (int rc = sync_all(ctx)) return rc;
     u32 diag[kDiagWords], fb[kFallbackWords];
     HIPCHK(ctx, hipMemcpy(diag, ctx->table.overflow, sizeof(diag), hipMemcpyDeviceToHost));
     HIPCHK(ctx, fallback_counters_read(fb));
-    const u32 v[TREW_DEBUG_COUNTERS] = {fb[kFallbackStrictRerun], fb[kFallbackWindows], fb[kFallbackWideSpin], diag[kDiagInserted], diag[kDiagInsertedWide], fb[kFallbackGroupPunt], fb[kFallbackGroupRouted], fb[kFallbackGroupTarget], fb[kFallbackHalfDrain], fb[kFallbackUnitDrain]};
+    u32 dead = 0;  // of the most recent launch: in the counter block that launch used
+    const int ds = ctx->dead_slot.load(std::memory_order_relaxed);
+    if (ds >= 0) {
+        const Slot &s = ctx->slots[(size_t) ds];
+        if (s.n_launches) HIPCHK(ctx, hipMemcpy(&dead, s.d_wl_count + ((s.n_launches - 1) & 1) * kWlCountWords + kDeadEntriesWord, 4, hipMemcpyDeviceToHost));
+    }
+    const u32 v[TREW_DEBUG_COUNTERS] = {fb[kFallbackStrictRerun], fb[kFallbackWindows], fb[kFallbackWideSpin], diag[kDiagInserted], diag[kDiagInsertedWide], fb[kFallbackGroupPunt], fb[kFallbackGroupRouted], fb[kFallbackGroupTarget], fb[kFallbackHalfDrain], fb[kFallbackUnitDrain], dead};
     for (int i = 0; i < n; i++) out[i] = i < TREW_DEBUG_COUNTERS ? v[i] : 0;
     return 0;
 }

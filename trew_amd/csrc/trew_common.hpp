@@ -47,6 +47,13 @@ struct DevBatch {
 // One counter block per launch (a slot owns two and alternates, trew_capi.cpp): word 0 = worklist size, then eight 32-word
 // lines: word 0 of line s = the exact kernel's queue head of shard s, word kChunkCounterWord = the prefilter's chunk counter of shard s.
 constexpr int kChunkCounterWord = 16;
+// Two more words of the block's first line belong to the bounds pass (kernels/bounds_pass.inc), which runs between the two kernels:
+// the number of leading positions of the exact kernel's list whose packed bounds are stored (the live entries, or with
+// TREW_FLAG_DEBUG_NO_LIVE_LIST the worklist entries inside the hand-over buffer), and the entries it found dead.  Both are zero
+// where no bounds pass ran: the exact kernel of the launch before cleared the block.
+constexpr int kStoredPrefixWord = 1;
+constexpr int kDeadEntriesWord = 2;
+constexpr int kBoundNeedWords = 97;  // the integer pass thresholds of the bounds pass: one word for every COUNT 0..96 (fill_bound_needs)
 
 // words of DevTable::overflow (one 64-byte line of device counters, cleared by trew_hip_reset_tables)
 enum {

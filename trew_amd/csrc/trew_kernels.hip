@@ -220,22 +220,52 @@ bool bounds_pass_applies(const DevParams &P, u32 max_seg_len) {
 }
 size_t bounds_entry_bytes() { return kBoundItemWords * sizeof(u32); }
 
+// The pass bits of the bounds pass as integer thresholds (pack_bound_word, kernels/bounds_pass.inc): table[c] = need_lo | need_hi
+// << 16 for COUNT = c, the smallest largest-bucket m that passes LOW / HIGH (c + 1: none does).  The kernel's doubles decide by the
+// product m > t * c unless SOME lane of the wave is within 1e-9 of a threshold, and then every lane of it by the division
+// m / c >= t; so a table can stand for them only if the two forms agree on every (m, c) that is not itself that close, and then it
+// holds the division form.  Both are evaluated here as the device evaluates them (one IEEE multiplication, division and
+// comparison each).  false: they disagree somewhere for this LOW / HIGH, and the kernel keeps the doubles.
+bool fill_bound_needs(const DevParams &P, u32 *table) {
+    bool usable = true;
+    for (int c = 0; c < kBoundNeedWords; c++) {
+        u32 need_lo = (u32) c + 1u, need_hi = (u32) c + 1u;
+        for (int m = c; m >= 0; m--) {
+            const double dm = (double) m, dc = (double) c;
+            const double tl = P.low * dc, th = P.high * dc;
+            const bool prod_lo = dm > tl, prod_hi = dm > th;
+            const bool amb = fabs(dm - tl) <= 1e-9 || fabs(dm - th) <= 1e-9;
+            const double ub = c ? dm / dc : 0.0;
+            const bool div_lo = ub >= P.low, div_hi = ub >= P.high;
+            if (!amb && (prod_lo != div_lo || prod_hi != div_hi)) usable = false;
+            // (thresholds only if passing is monotonic in m, which a division by a positive c is)
+            if (div_lo) { if (need_lo != (u32) m + 1u) usable = false; need_lo = (u32) m; }
+            if (div_hi) { if (need_hi != (u32) m + 1u) usable = false; need_hi = (u32) m; }
+        }
+        table[c] = need_lo | (need_hi << 16);
+    }
+    return usable;
+}
+
 // The bounds pass over the worklist of one batch, between its prefilter and its exact kernel: bnd gets kBoundItemWords words for
-// each of the first bnd_cap worklist entries.  A fixed grid: the worklist's length is on the device only.
-hipError_t launch_bounds(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const u32 *wl, const u32 *wl_count,
-                         u32 wl_cap, u32 *bnd, u32 bnd_cap) {
+// each live one of the first bnd_cap worklist entries and `live` those entries (bnd_cap words); live == nullptr
+// (TREW_FLAG_DEBUG_NO_LIVE_LIST): words for every one of them, at its worklist position.  A fixed grid: the worklist's length is on
+// the device only.
+hipError_t launch_bounds(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const u32 *wl, u32 *wl_count, u32 wl_cap,
+                         u32 *bnd, u32 bnd_cap, u32 *live, const u32 *need) {
     if (n_units == 0 || bnd_cap == 0) return hipSuccess;
-    // a lane per half, a wave per block; sixteen waves a CU hold every wave the kernel's 8.4 KB of LDS lets a CU keep, and a small
-    // batch starts no more waves than its reads could fill
-    const u64 most = (std::min<u64>(n_units, bnd_cap) * 2 + 63) / 64;
-    const u32 grid = (u32) std::min<u64>((u64) n_cu * 16ull, most);
-    hipLaunchKernelGGL(bounds_kernel<3>, dim3(grid), dim3(64), 0, st, P, B, wl, wl_count, wl_cap, bnd, bnd_cap);
+    // a lane per half, four waves a block (one atomic on the live count each); four blocks a CU hold every wave the kernel's 34 KB
+    // of LDS a block lets a CU keep, and a small batch starts no more blocks than its reads could fill
+    const u64 per_block = 64ull * kBoundsWaves;
+    const u64 most = (std::min<u64>(n_units, bnd_cap) * 2 + per_block - 1) / per_block;
+    const u32 grid = (u32) std::min<u64>((u64) n_cu * 4ull, most);
+    hipLaunchKernelGGL(bounds_kernel<3>, dim3(grid), dim3((u32) per_block), 0, st, P, B, wl, wl_count, wl_cap, bnd, bnd_cap, live, need);
     return hipGetLastError();
 }
 
 hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const DevTableG1 &T,
                         const u32 *wl, u32 *wl_count, u32 *wl_count_next, u32 wl_cap, const SegResults &R, u32 cap, u32 rawwords,
-                        u32 max_seg_len, bool share, const u32 *bnd, u32 bnd_cap) {
+                        u32 max_seg_len, bool share, const u32 *bnd, u32 bnd_cap, const u32 *live) {
     // lane_bounds needs every staged segment (< cap) to fit its NW words
     const bool wide = P.max_mer > 32;  // 128-bit words, k_mer_check_128 (kmer.cpp:100, 180)
     const u32 lds = exact_lds_bytes(cap, rawwords, wide ? 16u : 8u);
@@ -247,9 +277,10 @@ hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &
     // 0: no lane bounds -- NO_FILTER, and segments above 319 bases (pick_nw's 32, which the switches below map to 0)
     const int nw = (P.flags & TREW_FLAG_NO_FILTER) ? 0 : pick_nw(bound_len);
     // one block = one wave; fill the chip exactly once (persistent, self-scheduling waves)
-    typedef void (*kern_t)(DevParams, DevBatch, DevTableG1, const u32 *, u32 *, u32 *, u32, SegResults, u32, u32, const u32 *, u32);
+    typedef void (*kern_t)(DevParams, DevBatch, DevTableG1, const u32 *, u32 *, u32 *, u32, SegResults, u32, u32, const u32 *, u32, const u32 *);
     kern_t fn = nullptr;
     if (!bounds_pass_applies(P, max_seg_len)) bnd = nullptr;  // no other instantiation reads stored bounds
+    if (!bnd || !live) live = wl;  // no live list: the leading entries of the exact kernel's list are the worklist's own
 #define TREW_PICK_MODE(NWV, WTV)                                                      \
     switch (P.mode) {                                                                 \
     case TREW_MODE_SHORT: fn = exact_kernel<NWV, TREW_MODE_SHORT, WTV>; break;        \
@@ -302,7 +333,7 @@ hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &
     // prefilter) one wave per 16 units, so that a launch does not start thousands of waves that find the queue empty.
     const u64 full = (u64) n_cu * (u64) per_cu;
     const u32 grid = (u32) std::min<u64>(full, std::max<u64>(n_units / 16, 64));
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, st, P, B, T, wl, wl_count, wl_count_next, wl_cap, R, cap, rawwords, bnd, bnd ? bnd_cap : 0u);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, st, P, B, T, wl, wl_count, wl_count_next, wl_cap, R, cap, rawwords, bnd, bnd ? bnd_cap : 0u, live);
     return hipGetLastError();
 }
 

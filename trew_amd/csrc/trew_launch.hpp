@@ -13,12 +13,15 @@ hipError_t launch_filter(hipStream_t st, u32 n_cu, u32 max_seg_len, const DevPar
 void fill_thresholds(const DevParams &P, u32 uniform_length, int2 *table);  // kThrTableBytes
 hipError_t launch_exact(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const DevTableG1 &T,
                         const u32 *wl, u32 *wl_count, u32 *wl_count_next, u32 wl_cap, const SegResults &R, u32 cap, u32 rawwords,
-                        u32 max_seg_len, bool share, const u32 *bnd, u32 bnd_cap);  // share: leave half of the wave slots to a prefilter on another stream
-// the bounds pass (kernels/bounds_pass.inc): bnd = what launch_bounds left for the first bnd_cap worklist entries, or nullptr
+                        u32 max_seg_len, bool share, const u32 *bnd, u32 bnd_cap, const u32 *live);  // share: leave half of the wave slots to a prefilter on another stream
+// the bounds pass (kernels/bounds_pass.inc): bnd = what launch_bounds left for the first bnd_cap worklist entries, or nullptr;
+// live = the live worklist it wrote (the exact kernel reads it in front of the worklist entries from bnd_cap on), or nullptr
 bool bounds_pass_applies(const DevParams &P, u32 max_seg_len);  // this batch's exact kernel reads stored bounds
 size_t bounds_entry_bytes();                                    // of one worklist entry in bnd
-hipError_t launch_bounds(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const u32 *wl, const u32 *wl_count,
-                         u32 wl_cap, u32 *bnd, u32 bnd_cap);
+hipError_t launch_bounds(hipStream_t st, u32 n_cu, u64 n_units, const DevParams &P, const DevBatch &B, const u32 *wl, u32 *wl_count, u32 wl_cap,
+                         u32 *bnd, u32 bnd_cap, u32 *live, const u32 *need);
+// need: the device copy of what fill_bound_needs wrote (kBoundNeedWords words), or nullptr where it returned false
+bool fill_bound_needs(const DevParams &P, u32 *table);
 u32 exact_lds_bytes_host(u32 cap, u32 rawwords, u32 wordbytes);
 hipError_t launch_g1_apply(hipStream_t st, const DevTable &T, const DevG1 &G, const DevBatch &B, int min_mer, const trew_hip_row *carry_in,
                            trew_hip_row *carry_out, u32 carry_cap);
