@@ -112,12 +112,9 @@ __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min
             u32 blk_lo = i;  // the block holds the rows blk_lo + 1 .. : none yet
             auto emit = [&](u32 e_start, u32 e_bases, u32 e_count, u32 e_phase, u32 e_consumed, u32 e_sub, u32 e_ins, u32 e_del) {
                 found++;
-                u64 idx = 0;
-                if (lane == 0) idx = atomicAdd(lg.counter, 1ull);
-                idx = rfl64(idx);
                 const u32 v = lane == 0u ? (u32) r : lane == 3u ? e_start : lane == 4u ? e_bases : lane == 5u ? e_count : lane == 6u ? e_phase
                             : lane == 7u ? e_consumed : lane == 8u ? e_sub : lane == 9u ? e_ins : lane == 10u ? e_del : 0u;  // motif = strand = 0
-                if (idx < lg.cap && lane < kTraceWords) lg.recs[idx * (u64) kTraceWords + lane] = v;
+                log_append<kTraceWords>(lg.counter, lg.recs, lg.cap, v);
             };
             auto flush_run = [&]() {
                 if (run) emit(run_start, run * k, run, 0, run * k, 0, 0, 0);

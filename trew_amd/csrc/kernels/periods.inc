@@ -315,9 +315,7 @@ __global__ void __launch_bounds__(256) periods_wave_kernel(DevBatch B, int min_p
         const ReadRef rd = uni(get_read(B, r));
         u32 rec[10];
         period_record(rd, Piece{0u, rd.len}, kmin, kmax, P, min_score, h, rec);  // the whole read
-        u32 x = rec[9];
-#pragma unroll
-        for (int i = 8; i >= 0; i--) x = lane == (u32) i ? rec[i] : x;
+        const u32 x = lane_words(rec, rec[9]);
         if (lane < 10) out[r * 10ull + lane] = x;
     }
 }

@@ -279,9 +279,7 @@ __global__ void __launch_bounds__(256) refine_wave_kernel(DevBatch B, int min_pe
         u32 rec[16], r_start, r_end;  // the periods tract and the returned flag are for kernels/tandems.inc: not used here
         refine_piece(rd, Piece{0u, rd.len}, kmin, kmax, P, min_score, h, rec, r_start, r_end);  // the whole read; all zero without a record
         // sixteen lanes write the record's sixteen words (trew_hip_refined): one vector store
-        u32 x = rec[15];
-#pragma unroll
-        for (int i = 14; i >= 0; i--) x = lane == (u32) i ? rec[i] : x;
+        const u32 x = lane_words(rec, rec[15]);
         if (lane < 16) out[r * 16ull + lane] = x;
     }
 }

@@ -15,7 +15,7 @@
 //                reaches phase (j + d) mod k*; the proper divisors d of k* in ascending order.
 //   record       26 words from 26 lanes with one vector store: lanes 0 .. 9 the header, lane 10 + i unit word i, packed from
 //                the sixteen codes 16 i .. 16 i + 15 in LDS (no carry between words; nothing at or above base `period`).
-//   recursion    the stack in the lanes of three VGPRs, the pruning (repeat_worth) and the append of kernels/repeats.inc.
+//   recursion    the stack in the lanes of three VGPRs, the pruning (repeat_worth) and the append are kernels/pieces.inc's.
 
 constexpr u32 kSatelliteMaxPeriod = 256;                  // the one place the upper limit of a period is written down
 constexpr u32 kSatelliteBins = 4u * kSatelliteMaxPeriod;  // u32 per wave
@@ -161,57 +161,11 @@ __global__ void __launch_bounds__(256, 5) satellites_wave_kernel(DevBatch B, int
     const u32 smin = rfl(min_score);
     for (u64 r = wave; r < B.n_reads; r += n_waves) {
         const ReadRef rd = uni(get_read(B, r));
-        u32 st_lo = 0, st_hi = 0, st_d = 0;  // the stack of kernels/repeats.inc: entry i in lane i, at most 32 pending
-        u32 sp = 0;
-        u32 lo = 0, hi = rd.len, depth = 0;  // the piece at hand
-        u32 found = 0;
-        bool have = repeat_worth(lo, hi, kmin, smin);
-        while (have) {  // wave-uniform
-            u32 rec[8], unit_word;
-            bool split = satellite_record(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, unit_word);
-            // a tract lies inside its piece; the pieces below are formed from it, so nothing else may ever reach them
-            if (split && !(rec[3] >= lo && rec[4] <= hi && rec[3] < rec[4])) break;
-            u32 a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // the children; a the shorter
-            if (split) {
-                found++;
-                u64 idx = 0;
-                if (lane == 0) idx = atomicAdd(lg.counter, 1ull);
-                idx = rfl64(idx);
-                u32 x = unit_word;  // lanes 10 .. 25
-#pragma unroll
-                for (int i = 7; i >= 0; i--) x = lane == (u32) (i + 2) ? rec[i] : x;
-                x = lane == 1u ? depth : x;
-                x = lane == 0u ? (u32) r : x;
-                if (idx < lg.cap && lane < kSatelliteWords) lg.recs[idx * (u64) kSatelliteWords + lane] = x;
-                const u32 start = rfl(rec[3]), end = rfl(rec[4]);
-                const bool left_short = start - lo <= hi - end;
-                a_lo = left_short ? lo : end;
-                a_hi = left_short ? start : hi;
-                b_lo = left_short ? end : lo;
-                b_hi = left_short ? hi : start;
-                depth++;
-                if (repeat_worth(b_lo, b_hi, kmin, smin)) {  // push the longer child
-                    if (lane == sp) {
-                        st_lo = b_lo;
-                        st_hi = b_hi;
-                        st_d = depth;
-                    }
-                    sp++;
-                }
-            }
-            if (split && repeat_worth(a_lo, a_hi, kmin, smin)) {  // go on with the shorter child
-                lo = a_lo;
-                hi = a_hi;
-            } else if (sp != 0u) {  // pop
-                sp--;
-                sp = rfl(sp);
-                lo = (u32) __builtin_amdgcn_readlane((int) st_lo, sp);
-                hi = (u32) __builtin_amdgcn_readlane((int) st_hi, sp);
-                depth = (u32) __builtin_amdgcn_readlane((int) st_d, sp);
-            } else {
-                have = false;
-            }
-        }
+        const u32 found = walk_pieces<kSatelliteWords>(r, rd.len, kmin, smin, lg, [&](u32 lo, u32 hi) __attribute__((always_inline)) {
+            u32 rec[8], unit_word;  // unit_word: lanes 10 .. 25
+            const bool split = satellite_record(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, unit_word);
+            return PieceEval{split, rec[3], rec[4], lane_words<8, 2>(rec, unit_word)};
+        });
         if (lane == 0) counts[r] = found;
     }
 }

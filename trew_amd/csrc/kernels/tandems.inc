@@ -11,9 +11,13 @@
 // record, then tandems([lo, R.start)) and tandems([R.end, hi)) around the periods tract R, which is used up.  The tracts of a
 // read are tandems([0, n)); depth is 0 for the read's own piece and parent + 1 below it, whether the parent gave a record or not.
 //
-// The piece loop is that of repeats.inc: the wave-uniform stack of (lo, hi, depth) across the lanes of three VGPRs, the LONGER
-// child pushed and the SHORTER continued (both children of a weak piece as well: R is not empty, so they shrink), hence at
-// most 32 entries pending; a piece that repeat_worth rules out can have no periods record and is neither pushed nor walked.
+// The piece loop is that of walk_pieces (kernels/pieces.inc): the wave-uniform stack of (lo, hi, depth) across the lanes of three
+// VGPRs, the LONGER child pushed and the SHORTER continued (both children of a weak piece as well: R is not empty, so they
+// shrink), hence at most 32 entries pending; a piece that repeat_worth rules out can have no periods record and is neither
+// pushed nor walked.  It is written out here and does not call walk_pieces, lane_words or log_append: with any of them this
+// kernel's registers come out differently (113 VGPRs instead of 119 with the walk, the hot loops of refine_piece the same
+// instructions on other registers) and long reads take 2.1 to 2.9 % longer on the MI355X (profiles/piece_walk/README.md).  A fix
+// to the walk there has to be made here as well.
 //
 // Append.  One returning 64-bit vector-memory atomic per record on the log's counter, wave-uniform (lane 0 adds, the others
 // get the index through readfirstlane); the record's eighteen words go out from eighteen lanes, those of a record at or beyond

@@ -190,13 +190,10 @@ __global__ void __launch_bounds__(256) trace_wave_kernel(DevBatch B, const Annot
                     u32 found = 0;
                     auto emit = [&](u32 e_start, u32 e_bases, u32 e_count, u32 e_phase, u32 e_consumed, u32 e_sub, u32 e_ins, u32 e_del) {
                         found++;
-                        u64 idx = 0;
-                        if (lane == 0) idx = atomicAdd(lg.counter, 1ull);
-                        idx = rfl64(idx);
                         const u32 v = lane == 0u ? (u32) r : lane == 1u ? (u32) m : lane == 2u ? s : lane == 3u ? e_start : lane == 4u ? e_bases
                                     : lane == 5u ? e_count : lane == 6u ? e_phase : lane == 7u ? e_consumed : lane == 8u ? e_sub
                                     : lane == 9u ? e_ins : lane == 10u ? e_del : 0u;
-                        if (idx < lg.cap && lane < kTraceWords) lg.recs[idx * (u64) kTraceWords + lane] = v;
+                        log_append<kTraceWords>(lg.counter, lg.recs, lg.cap, v);
                     };
                     auto flush_run = [&]() {
                         if (run) emit(run_start, run * k, run, 0, run * k, 0, 0, 0);

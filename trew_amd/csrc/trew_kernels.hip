@@ -41,13 +41,14 @@
 //   tracts.inc         tracts_wave_kernel (per-read error-tolerant terminal tracts; shares annotate.inc's match word)
 //   intervals.inc      intervals_wave_kernel (gap-tolerant motif intervals anywhere in a read; shares tracts.inc's coverage word)
 //   variants.inc       variants_wave_kernel (in-phase variant units per read and their batch histogram; Hamming distance 1)
+//   pieces.inc         lane_words, log_append, repeat_worth, walk_pieces (what the every-tract measures share: a record's words over lanes, the append of a record to a log, the recursion over the pieces of a read inside the wave)
 //   periods.inc        periods_wave_kernel (de novo repeat period and consensus unit per read; no motif, the shifted self-comparison)
 //   chain.inc          chain_wave_kernel (ordered unit chain per read: run and variant events into an append log; shares variants.inc's words)
-//   repeats.inc        repeats_wave_kernel (de novo repeats: every tract of a read, the recursion over pieces inside the wave; shares periods.inc's functions)
-//   satellites.inc     satellites_wave_kernel (de novo repeats with periods up to 256: the wide eq word, 1024 consensus bins and a 16-word unit; shares periods.inc's and repeats.inc's functions)
+//   repeats.inc        repeats_wave_kernel (de novo repeats: every tract of a read: pieces.inc's recursion over pieces with periods.inc's period_record per piece)
+//   satellites.inc     satellites_wave_kernel (de novo repeats with periods up to 256: the wide eq word, 1024 consensus bins and a 16-word unit; shares periods.inc's and pieces.inc's functions)
 //   align.inc          align_wave_kernel (indel-aware motif tract per read: wraparound alignment, the row of the table in registers, a phase per lane)
 //   refine.inc         refine_wave_kernel (de novo repeats under indels: periods.inc's period and tract, a seed unit from the longest run of eq_k, align.inc's row step for the alignment, the vote and the re-voted unit)
-//   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: repeats.inc's recursion over pieces with refine.inc's refine_piece per piece)
+//   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: the recursion of pieces.inc over pieces, written out in the kernel, with refine.inc's refine_piece per piece)
 //   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
 //   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
 // The launchers (host code) follow the includes.
@@ -85,6 +86,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/tracts.inc"
 #include "kernels/intervals.inc"
 #include "kernels/variants.inc"
+#include "kernels/pieces.inc"
 #include "kernels/periods.inc"
 #include "kernels/chain.inc"
 #include "kernels/repeats.inc"
@@ -379,126 +381,85 @@ hipError_t launch_slice_finish(hipStream_t st, trew_hip_row *d_slice, u64 slice_
     return hipGetLastError();
 }
 
+// The grid of every wave-per-read kernel: persistent waves, grid-strided over the reads; four waves a block, up to eight blocks a CU.
+static u32 wave_per_read_blocks(u32 n_cu, u64 n_reads) { return (u32) std::min<u64>((n_reads + 3ull) / 4ull, (u64) n_cu * 8ull); }
+
+// One wave-per-read kernel over the batch, for every read length: nothing for an empty batch, else kernel(B, args...) on that grid.
+template <class Kernel, class... Args>
+static hipError_t launch_wave_per_read(hipStream_t st, u32 n_cu, const DevBatch &B, Kernel kernel, const Args &...args) {
+    if (B.n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3(wave_per_read_blocks(n_cu, B.n_reads)), dim3(256), 0, st, B, args...);
+    return hipGetLastError();
+}
+
 // Per-read annotation.  Reads of up to 160 bases keep their planes in 15 registers (NW = 5), up to 256 in 24 (NW = 8); anything
 // longer, or of unknown length, gets a wave per read.
 hipError_t launch_annotate(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, u32 max_len, bool general,
                            trew_hip_annot *d_out) {
+    if (general || max_len > 256u) return launch_wave_per_read(st, n_cu, B, annotate_wave_kernel, d_motifs, n_motifs, (u32 *) d_out);
     if (B.n_reads == 0) return hipSuccess;
-    if (general || max_len > 256u) {
-        // persistent waves, grid-strided over the reads; four waves a block, up to eight blocks a CU
-        const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-        hipLaunchKernelGGL(annotate_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, (u32 *) d_out);
-    } else {
-        const dim3 grid((u32) ((B.n_reads + 255ull) / 256ull));
-        if (max_len <= 160u)
-            hipLaunchKernelGGL(annotate_lane_kernel<5>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
-        else
-            hipLaunchKernelGGL(annotate_lane_kernel<8>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
-    }
+    const dim3 grid((u32) ((B.n_reads + 255ull) / 256ull));
+    if (max_len <= 160u)
+        hipLaunchKernelGGL(annotate_lane_kernel<5>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
+    else
+        hipLaunchKernelGGL(annotate_lane_kernel<8>, grid, dim3(256), 0, st, B, d_motifs, n_motifs, (uint2 *) d_out);
     return hipGetLastError();
 }
 
-// Per-read terminal tracts: one kernel, a wave per read, for every read length (same grid as the annotation's wave kernel).
+// The eleven measures below: one kernel each, a wave per read (launch_wave_per_read).
 hipError_t launch_tracts(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_tract *d_out) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(tracts_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, (u32 *) d_out);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, tracts_wave_kernel, d_motifs, n_motifs, penalty, (u32 *) d_out);
 }
 
-// Gap-tolerant intervals: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_intervals(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const IntervalRulesDev &rules,
                             const IntervalLog &lg, u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(intervals_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, rules, lg, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, intervals_wave_kernel, d_motifs, n_motifs, rules, lg, d_counts);
 }
 
-// Variant repeats: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_variants(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, trew_hip_variant *d_out,
                            unsigned long long *d_hist, unsigned long long *d_reads_with) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(variants_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, (u32 *) d_out, d_hist, d_reads_with);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, variants_wave_kernel, d_motifs, n_motifs, (u32 *) d_out, d_hist, d_reads_with);
 }
 
-// De novo periods: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_periods(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_period *d_out) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(periods_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, (u32 *) d_out);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, periods_wave_kernel, min_period, max_period, penalty, min_score, (u32 *) d_out);
 }
 
-// Unit chain: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_chain(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, const ChainLog &lg, u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(chain_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, lg, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, chain_wave_kernel, d_motifs, n_motifs, lg, d_counts);
 }
 
-// De novo repeats, every tract: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_repeats(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &lg,
                           u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(repeats_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, repeats_wave_kernel, min_period, max_period, penalty, min_score, lg, d_counts);
 }
 
-// De novo repeats with periods up to 256: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_satellites(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score,
                              const RepeatLog &lg, u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(satellites_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, satellites_wave_kernel, min_period, max_period, penalty, min_score, lg, d_counts);
 }
 
-// Indel-aware motif tract: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, trew_hip_alignment *d_out) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(align_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, (u32 *) d_out);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, align_wave_kernel, d_motifs, n_motifs, penalty, (u32 *) d_out);
 }
 
-// De novo repeats under indels: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_refine(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined *d_out) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(refine_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, (u32 *) d_out);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, refine_wave_kernel, min_period, max_period, penalty, min_score, (u32 *) d_out);
 }
 
-// De novo repeats under indels, every tract: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &lg,
                           u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(tandems_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, tandems_wave_kernel, min_period, max_period, penalty, min_score, lg, d_counts);
 }
 
-// Units in place under indels: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, u32 min_score,
                         const TraceLog &lg, trew_hip_alignment *d_out, u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(trace_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, d_motifs, n_motifs, penalty, min_score, lg, (u32 *) d_out, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, trace_wave_kernel, d_motifs, n_motifs, penalty, min_score, lg, (u32 *) d_out, d_counts);
 }
 
-// Units in place with no motif given: one kernel, a wave per read, for every read length (the grid of launch_tracts).
 hipError_t launch_decompose(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const TraceLog &lg,
                             trew_hip_refined *d_out, u32 *d_counts) {
-    if (B.n_reads == 0) return hipSuccess;
-    const u64 blocks = std::min<u64>((B.n_reads + 3ull) / 4ull, (u64) n_cu * 8ull);
-    hipLaunchKernelGGL(decompose_wave_kernel, dim3((u32) blocks), dim3(256), 0, st, B, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts);
-    return hipGetLastError();
+    return launch_wave_per_read(st, n_cu, B, decompose_wave_kernel, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts);
 }
 
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words) {

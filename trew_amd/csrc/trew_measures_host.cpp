@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 namespace trew {
@@ -536,6 +537,66 @@ const char *periods_host(const u32 *words, const u32 *offsets, const u32 *length
     return nullptr;
 }
 
+// ---------------------------------------------------------------- the every-tract measures: one walk over the pieces of a read
+// "<name>: <what>", kept for the calling thread until its next failed check
+static const char *named_error(const char *name, const char *what) {
+    static thread_local std::string text;
+    text = std::string(name) + ": " + what;
+    return text.c_str();
+}
+
+// what a measure's `piece` says of a piece [lo, hi)
+enum class PieceResult {
+    none,        // no tract: the branch ends here
+    split_only,  // a tract [start, end) that is used up without a record: the pieces around it are walked
+    record,      // a tract with its record
+};
+
+// The part of trew_hip_repeats, trew_hip_satellites and trew_hip_tandems that is one definition: tracts([lo, hi)) is what
+// piece(base, read, lo, hi, depth, rec, start, end) gives [lo, hi), then tracts([lo, start)) and tracts([end, hi)) one level
+// deeper; the tracts of a read are tracts([0, n)) at depth 0.  No piece is pruned; a piece without a tract ends its branch.
+// A read's records go out in the order of their starts (they are disjoint); *n counts them all, out holds the first cap.
+// `name` is the entry point's, for the texts of the argument checks.
+template <class Rec, class PieceFn>
+static const char *every_tract_host(const char *name, const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, Rec *out, u64 cap, u64 *n,
+                                    u32 *counts, PieceFn piece) {
+    if (!n) return named_error(name, "n must not be null");
+    if (cap && !out) return named_error(name, "out must not be null");
+    if (n_reads && (!words || !offsets || !lengths)) return named_error(name, "null argument");
+    if (n_reads > 0xffffffffull) return named_error(name, "a batch holds at most 2^32 - 1 reads");
+    struct Todo {
+        u32 lo, hi, depth;
+    };
+    std::vector<unsigned char> base;  // per base: code, or 4 with its nmask bit set
+    std::vector<Todo> todo;
+    std::vector<Rec> mine;  // the tracts of one read
+    u64 found = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        mine.clear();
+        todo.assign(1, Todo{0, lengths[r], 0});
+        while (!todo.empty()) {
+            const Todo t = todo.back();
+            todo.pop_back();
+            Rec rec;
+            u32 start = 0, end = 0;
+            const PieceResult what = piece(base.data(), (u32) r, t.lo, t.hi, t.depth, rec, start, end);
+            if (what == PieceResult::none) continue;
+            if (what == PieceResult::record) mine.push_back(rec);
+            todo.push_back(Todo{end, t.hi, t.depth + 1});
+            todo.push_back(Todo{t.lo, start, t.depth + 1});
+        }
+        std::sort(mine.begin(), mine.end(), [](const Rec &a, const Rec &b) { return a.start < b.start; });
+        for (const Rec &x : mine) {
+            if (found < cap) out[found] = x;
+            found++;
+        }
+        if (counts) counts[r] = (u32) mine.size();
+    }
+    *n = found;
+    return nullptr;
+}
+
 // ---------------------------------------------------------------- de novo repeats: every tract of a read
 void sort_repeats(trew_hip_repeat *v, u64 n) {
     std::sort(v, v + n, [](const trew_hip_repeat &a, const trew_hip_repeat &b) { return a.read != b.read ? a.read < b.read : a.start < b.start; });
@@ -544,40 +605,15 @@ void sort_repeats(trew_hip_repeat *v, u64 n) {
 const char *repeats_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
                          u32 min_score, trew_hip_repeat *out, u64 cap, u64 *n, u32 *counts) {
     if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-    if (!n) return "trew_repeats_host: n must not be null";
-    if (cap && !out) return "trew_repeats_host: out must not be null";
-    if (n_reads && (!words || !offsets || !lengths)) return "trew_repeats_host: null argument";
-    if (n_reads > 0xffffffffull) return "trew_repeats_host: a batch holds at most 2^32 - 1 reads";
-    struct Todo {
-        u32 lo, hi, depth;
-    };
-    std::vector<unsigned char> base;
-    std::vector<Todo> todo;
-    std::vector<trew_hip_repeat> mine;  // the tracts of one read
-    u64 found = 0;
-    for (u64 r = 0; r < n_reads; r++) {
-        unpack_bases(words + offsets[r], lengths[r], base);
-        mine.clear();
-        todo.assign(1, Todo{0, lengths[r], 0});
-        while (!todo.empty()) {  // the definition piece by piece; no piece is pruned, a piece without a record ends its branch
-            const Todo t = todo.back();
-            todo.pop_back();
-            trew_hip_period p;
-            period_piece(base.data(), t.lo, t.hi, min_period, max_period, penalty, min_score, p);
-            if (p.scored_period == 0) continue;
-            mine.push_back(trew_hip_repeat{(u32) r, t.depth, p.period, p.scored_period, p.score, p.start, p.end, p.matches, p.support, 0, p.unit});
-            todo.push_back(Todo{p.end, t.hi, t.depth + 1});
-            todo.push_back(Todo{t.lo, p.start, t.depth + 1});
-        }
-        sort_repeats(mine.data(), mine.size());  // disjoint, so by start
-        for (const trew_hip_repeat &x : mine) {
-            if (found < cap) out[found] = x;
-            found++;
-        }
-        if (counts) counts[r] = (u32) mine.size();
-    }
-    *n = found;
-    return nullptr;
+    return every_tract_host("trew_repeats_host", words, offsets, lengths, n_reads, out, cap, n, counts,
+                            [&](const unsigned char *base, u32 r, u32 lo, u32 hi, u32 depth, trew_hip_repeat &rec, u32 &start, u32 &end) {
+                                trew_hip_period p;
+                                period_piece(base, lo, hi, min_period, max_period, penalty, min_score, p);
+                                if (p.scored_period == 0) return PieceResult::none;
+                                rec = trew_hip_repeat{r, depth, p.period, p.scored_period, p.score, p.start, p.end, p.matches, p.support, 0, p.unit};
+                                start = p.start, end = p.end;
+                                return PieceResult::record;
+                            });
 }
 
 // ---------------------------------------------------------------- de novo repeats with periods up to 256
@@ -588,42 +624,15 @@ void sort_satellites(trew_hip_satellite *v, u64 n) {
 const char *satellites_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
                             u32 min_score, trew_hip_satellite *out, u64 cap, u64 *n, u32 *counts) {
     if (const char *e = satellites_error(min_period, max_period, penalty, min_score)) return e;
-    if (!n) return "trew_satellites_host: n must not be null";
-    if (cap && !out) return "trew_satellites_host: out must not be null";
-    if (n_reads && (!words || !offsets || !lengths)) return "trew_satellites_host: null argument";
-    if (n_reads > 0xffffffffull) return "trew_satellites_host: a batch holds at most 2^32 - 1 reads";
-    struct Todo {
-        u32 lo, hi, depth;
-    };
-    std::vector<unsigned char> base;
-    std::vector<Todo> todo;
-    std::vector<trew_hip_satellite> mine;  // the tracts of one read
-    u64 found = 0;
-    for (u64 r = 0; r < n_reads; r++) {
-        unpack_bases(words + offsets[r], lengths[r], base);
-        mine.clear();
-        todo.assign(1, Todo{0, lengths[r], 0});
-        while (!todo.empty()) {  // the definition piece by piece, as in repeats_host: no piece is pruned
-            const Todo t = todo.back();
-            todo.pop_back();
-            trew_hip_satellite p;
-            satellite_piece(base.data(), t.lo, t.hi, min_period, max_period, penalty, min_score, p);
-            if (p.scored_period == 0) continue;
-            p.read = (u32) r;
-            p.depth = t.depth;
-            mine.push_back(p);
-            todo.push_back(Todo{p.end, t.hi, t.depth + 1});
-            todo.push_back(Todo{t.lo, p.start, t.depth + 1});
-        }
-        sort_satellites(mine.data(), mine.size());  // disjoint, so by start
-        for (const trew_hip_satellite &x : mine) {
-            if (found < cap) out[found] = x;
-            found++;
-        }
-        if (counts) counts[r] = (u32) mine.size();
-    }
-    *n = found;
-    return nullptr;
+    return every_tract_host("trew_satellites_host", words, offsets, lengths, n_reads, out, cap, n, counts,
+                            [&](const unsigned char *base, u32 r, u32 lo, u32 hi, u32 depth, trew_hip_satellite &rec, u32 &start, u32 &end) {
+                                satellite_piece(base, lo, hi, min_period, max_period, penalty, min_score, rec);
+                                if (rec.scored_period == 0) return PieceResult::none;
+                                rec.read = r;
+                                rec.depth = depth;
+                                start = rec.start, end = rec.end;
+                                return PieceResult::record;
+                            });
 }
 
 // ---------------------------------------------------------------- indel-aware motif tract per read (wraparound alignment)
@@ -817,46 +826,19 @@ void sort_tandems(trew_hip_tandem *v, u64 n) {
 const char *tandems_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
                          u32 min_score, trew_hip_tandem *out, u64 cap, u64 *n, u32 *counts) {
     if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-    if (!n) return "trew_tandems_host: n must not be null";
-    if (cap && !out) return "trew_tandems_host: out must not be null";
-    if (n_reads && (!words || !offsets || !lengths)) return "trew_tandems_host: null argument";
-    if (n_reads > 0xffffffffull) return "trew_tandems_host: a batch holds at most 2^32 - 1 reads";
-    struct Todo {
-        u32 lo, hi, depth;
-    };
-    std::vector<unsigned char> base;
-    std::vector<Todo> todo;
-    std::vector<trew_hip_tandem> mine;  // the tracts of one read
-    u64 found = 0;
-    for (u64 r = 0; r < n_reads; r++) {
-        unpack_bases(words + offsets[r], lengths[r], base);
-        mine.clear();
-        todo.assign(1, Todo{0, lengths[r], 0});
-        while (!todo.empty()) {  // the definition piece by piece, as in repeats_host: no piece is pruned
-            const Todo t = todo.back();
-            todo.pop_back();
-            trew_hip_refined x;
-            trew_hip_period R;
-            refine_read_host(base.data() + t.lo, t.hi - t.lo, min_period, max_period, penalty, min_score, x, R);  // the piece as a read of its own
-            if (R.scored_period == 0) continue;
-            u32 start = t.lo + R.start, end = t.lo + R.end;  // a weak piece: around the periods tract
-            if (x.score >= min_score) {
-                start = t.lo + x.start, end = t.lo + x.end;
-                mine.push_back(trew_hip_tandem{(u32) r, t.depth, x.period, x.seed_period, x.scored_period, x.changed, x.score, start, end, x.consumed,
-                                               x.matches, x.seed_score, x.support, 0, x.unit, x.seed_unit});
-            }
-            todo.push_back(Todo{end, t.hi, t.depth + 1});
-            todo.push_back(Todo{t.lo, start, t.depth + 1});
-        }
-        sort_tandems(mine.data(), mine.size());  // disjoint, so by start
-        for (const trew_hip_tandem &x : mine) {
-            if (found < cap) out[found] = x;
-            found++;
-        }
-        if (counts) counts[r] = (u32) mine.size();
-    }
-    *n = found;
-    return nullptr;
+    return every_tract_host("trew_tandems_host", words, offsets, lengths, n_reads, out, cap, n, counts,
+                            [&](const unsigned char *base, u32 r, u32 lo, u32 hi, u32 depth, trew_hip_tandem &rec, u32 &start, u32 &end) {
+                                trew_hip_refined x;
+                                trew_hip_period R;
+                                refine_read_host(base + lo, hi - lo, min_period, max_period, penalty, min_score, x, R);  // the piece as a read of its own
+                                if (R.scored_period == 0) return PieceResult::none;
+                                start = lo + R.start, end = lo + R.end;  // a weak piece: around the periods tract
+                                if (x.score < min_score) return PieceResult::split_only;
+                                start = lo + x.start, end = lo + x.end;
+                                rec = trew_hip_tandem{r, depth, x.period, x.seed_period, x.scored_period, x.changed, x.score, start, end, x.consumed,
+                                                      x.matches, x.seed_score, x.support, 0, x.unit, x.seed_unit};
+                                return PieceResult::record;
+                            });
 }
 
 // ---------------------------------------------------------------- units in place under indels: the traceback of the alignment
