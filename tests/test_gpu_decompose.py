@@ -236,6 +236,21 @@ def test_overflow_of_the_log_and_of_the_workspace(fuzz):
         ni, nr = C.c_uint64(0), C.c_uint64(0)
         assert t.lib.trew_hip_decompose_results(t.ctx, 0, buf.ctypes.data, 5, C.byref(ni), C.byref(nr), None, None, None) == 0
         assert ni.value == n_items and (buf == want[0][:5]).all()
+    # the refused workspace on the tracts around the row block: the walk fills every block by computing the rows again
+    for unit in (TEL, UNITS[17], UNITS[2]):
+        reads = block_reads(unit)
+        want = host(reads, 3, 20)
+        n_rows = int((want[2]["end"].astype(np.int64) - want[2]["start"])[want[1] > 0].sum())  # the definition's: a traced read's tract
+        assert (want[1] > 0).sum() >= 9 and n_rows > 1
+        words, offsets, lengths = capi.pack_reads(reads)
+        with ctx(words=len(words) + 64, reads=len(reads)) as t:
+            b = t.host_batch(words, offsets, lengths)
+            t.decompose(b, 1, 32, 3, 20, 1 << 20, 1)
+            got = t.decompose_results()
+            assert len(got[0]) == 0 and (got[3], got[4]) == (want[3], n_rows)
+            assert (got[1] == want[1]).all() and (got[2] == want[2]).all()
+            t.decompose(b, 1, 32, 3, 20, got[3], got[4])
+            same(t.decompose_results(), want)
 
 
 def long_reads(n):

@@ -208,6 +208,25 @@ def test_overflow_of_the_log_and_of_the_workspace():
         ni, nr = C.c_uint64(0), C.c_uint64(0)
         assert t.lib.trew_hip_trace_results(t.ctx, 0, buf.ctypes.data, 5, C.byref(ni), C.byref(nr), None, None, None) == 0
         assert ni.value == n_items and (buf == want[0][:5]).all()
+    # the refused workspace on the tracts around the row block: the walk fills every block by computing the rows again
+    for unit in (TEL, UNITS[17]):
+        reads = block_reads(unit)
+        want = host(reads, [unit], 3, 24)
+        a = want[2].astype([(f, "<i8") for f in capi.ALIGN_DTYPE.names])
+        fwd, rev = a["score_fwd"] >= 24, a["score_rev"] >= 24
+        lo = np.minimum(np.where(fwd, a["start_fwd"], 1 << 40), np.where(rev, a["start_rev"], 1 << 40))
+        hi = np.maximum(np.where(fwd, a["end_fwd"], 0), np.where(rev, a["end_rev"], 0))
+        n_rows = int((hi - lo)[fwd | rev].sum())  # the definition's: from the first start to the last end of the traced strands
+        assert (want[1][:, 0, 0] > 0).any() and (want[1][:, 0, 1] > 0).any() and n_rows > 1
+        words, offsets, lengths = capi.pack_reads(reads)
+        with ctx(words=len(words) + 64, reads=len(reads)) as t:
+            b = t.host_batch(words, offsets, lengths)
+            t.trace(b, [unit], 3, 24, 1 << 20, 1)
+            got = t.trace_results()
+            assert len(got[0]) == 0 and (got[3], got[4]) == (want[3], n_rows)
+            assert (got[1] == want[1]).all() and (got[2] == want[2]).all()
+            t.trace(b, [unit], 3, 24, got[3], got[4])
+            same(t.trace_results(), want)
 
 
 def long_reads(n):

@@ -2,8 +2,9 @@
 // Units in place with no motif given (trew_hip_decompose): refine.inc's unit of the read, anchored at its smallest rotation,
 // and trace.inc's traceback of the read against that rotation on the one strand the unit was found on.  A kernel beside the scan
 // and beside the other twelve measures: it reads the same bit planes, takes no pattern table and writes its own records,
-// counts, item log and direction workspace.  refine_piece, the cells and the lane reads of align.inc and trace_row are used,
-// not changed; the fill is written again here because a row has one strand.
+// counts, item log and direction workspace.  refine_piece is refine.inc's; the rows and the walk are wrap_fill<32>, wrap_fetch<32>
+// and wrap_walk<32> of kernels/wraparound.inc, which trace.inc calls with 64 bytes a row; this file is the anchor, the claim of
+// the rows, the end phase and one walk.
 //
 // Definition (DESIGN 4.7i, include/trew_hip.h).  R is the read's trew_hip_refined record.  Without one, or with R.score <
 // min_score, the read has no items and anchor 0.  Otherwise M is the smallest of the k = R.period rotations of U = R.unit as
@@ -25,25 +26,6 @@
 // are not stored; the walk then fills its block by computing the rows from `start` again, as in trace.inc.  No scalar
 // stores, no inline assembly.
 
-// Rows from + 1 .. to of the table that starts from (0, from, 0, 0) in every phase at row from; lanes 0 .. 31 store the byte of
-// row i > keep at dst[(i - keep - 1) * 32 + lane].  Returns H of row `to`.
-__device__ __forceinline__ AlignCell decompose_fill(const ReadRef &rd, u32 from, u32 to, u32 tb, int P, u32 k, const u32 (&src)[5], unsigned char *dst,
-                                                    u32 keep, u32 lane) {
-    AlignCell H{0, from, 0, 0};
-    u32 lo = 0, hi = 0, nm = 0;
-    for (u32 i = from + 1u; i <= to; i++) {
-        const u32 p = i - 1u, b = p & 31u;
-        if (b == 0u || p == from) {
-            const u64 w = p >> 5;
-            lo = rfl(rd.w[3ull * w + 0]), hi = rfl(rd.w[3ull * w + 1]), nm = rfl(rd.w[3ull * w + 2]);
-        }
-        const u32 c = ((lo >> b) & 1u) | (((hi >> b) & 1u) << 1) | (((nm >> b) & 1u) << 2);
-        const u32 byte = trace_row(H, c, tb, i, P, k, src);
-        if (i > keep && lane < 32u) dst[(u64) (i - keep - 1u) * 32ull + lane] = (unsigned char) byte;
-    }
-    return H;
-}
-
 __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, TraceLog lg,
                                                              u32 *__restrict__ out, u32 *__restrict__ counts) {
     __shared__ u32 bins[4][kPeriodBins];
@@ -59,7 +41,7 @@ __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min
     const int P = rfl_i(penalty);
     const u32 kmin = (u32) rfl_i(min_period), kmax = (u32) rfl_i(max_period);
     const u32 smin = rfl(min_score);
-    const u32 j = lane & 31u, half = lane & 32u;
+    const u32 j = lane & 31u;
     uint4 *const blk4 = dec_lds[(threadIdx.x >> 6) & 3u];
     unsigned char *const blk = (unsigned char *) blk4;
     for (u64 r = wave; r < B.n_reads; r += n_waves) {
@@ -83,12 +65,7 @@ __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min
             const u32 at = j >= k ? 0u : j + rho >= k ? j + rho - k : j + rho;  // (j + rho) mod k for the lanes j < k
             const u32 tb = j < k ? (u32) (unit >> (2u * (k - 1u - at))) & 3u : 8u;  // M[j]; both halves alike, an idle lane matches nothing
             u32 src[5];
-#pragma unroll
-            for (int t = 0; t < 5; t++) {
-                int q = ((int) j - (1 << t)) % (int) k;
-                q = q < 0 ? q + (int) k : q;
-                src[t] = (half | (u32) q) << 2;
-            }
+            wrap_sources(k, src);
             // ---- rows
             const u32 rows = en - start;  // >= 1
             u64 first = 0;
@@ -104,78 +81,18 @@ __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min
             };
             u32 jj = 0;
             if (fits) {
-                jj = end_phase(decompose_fill(rd, start, en, tb, P, k, src, ws, start, lane));
+                jj = end_phase(wrap_fill<32>(rd, start, en, start, tb, P, k, src, ws, start));
                 __threadfence();  // other lanes of this wave read the rows back
             }
-            // ---- the walk and the items: trace.inc's, one strand
-            u32 i = en, seg_end = i, consumed = 0, sub = 0, ins = 0, del = 0, phase = 0, cols = 0, run = 0, run_start = 0;
-            u32 blk_lo = i;  // the block holds the rows blk_lo + 1 .. : none yet
-            auto emit = [&](u32 e_start, u32 e_bases, u32 e_count, u32 e_phase, u32 e_consumed, u32 e_sub, u32 e_ins, u32 e_del) {
-                found++;
-                const u32 v = lane == 0u ? (u32) r : lane == 3u ? e_start : lane == 4u ? e_bases : lane == 5u ? e_count : lane == 6u ? e_phase
-                            : lane == 7u ? e_consumed : lane == 8u ? e_sub : lane == 9u ? e_ins : lane == 10u ? e_del : 0u;  // motif = strand = 0
-                log_append<kTraceWords>(lg.counter, lg.recs, lg.cap, v);
-            };
-            auto flush_run = [&]() {
-                if (run) emit(run_start, run * k, run, 0, run * k, 0, 0, 0);
-                run = 0;
-            };
-            auto close = [&]() {  // the running segment begins at read base i
-                if (phase == 0 && consumed == k && (sub | ins | del) == 0) {
-                    run++;
-                    run_start = i;
+            // ---- the walk and the items, one strand
+            found = wrap_walk<32>(lg, (u32) r, 0u, 0u, k, start, en, jj, blk, [&](u32 blk_lo, u32 i) {
+                if (fits) {
+                    wrap_fetch<32>(ws, start, blk4, blk_lo, i);
                 } else {
-                    flush_run();
-                    emit(i, seg_end - i, 1, phase, consumed, sub, ins, del);
+                    const AlignCell H = wrap_fill<32>(rd, start, i, start, tb, P, k, src, blk, blk_lo);
+                    if (i == en) jj = end_phase(H);  // the first block ends at row `end`
                 }
-                seg_end = i;
-                consumed = sub = ins = del = phase = cols = 0;
-            };
-            while (i > start) {
-                if (i <= blk_lo) {  // the next block: the rows blk_lo + 1 .. i
-                    blk_lo = i - start > kTraceBlock ? i - kTraceBlock : start;
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    if (fits) {
-                        const u32 row = blk_lo + 1u + lane;
-                        if (row <= i) {
-                            const uint4 *g = (const uint4 *) (ws + (u64) (row - start - 1u) * 32ull);
-                            const uint4 a = g[0], b = g[1];
-                            blk4[lane * 2u + 0u] = a;
-                            blk4[lane * 2u + 1u] = b;
-                        }
-                    } else {
-                        const AlignCell H = decompose_fill(rd, start, i, tb, P, k, src, blk, blk_lo, lane);
-                        if (i == en) jj = end_phase(H);  // the first block ends at row `end`
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                }
-                const unsigned char *row = blk + (i - blk_lo - 1u) * 32u;
-                const u32 d = rfl((u32) row[jj]) >> 2 & 31u;
-                for (u32 q = 0; q < d; q++) {
-                    phase = jj;
-                    consumed++, del++, cols++;
-                    if (jj == 0) close();
-                    jj = jj ? jj - 1u : k - 1u;
-                }
-                const u32 cell = rfl((u32) row[jj]);
-                const u32 op = cell & 3u;
-                if (op == 0) break;  // never: the fresh start lies in row `start`
-                i--;
-                cols++;
-                if (op == 1) {
-                    phase = jj;
-                    consumed++;
-                    sub += (cell >> 7) ^ 1u;
-                    if (jj == 0) close();
-                    jj = jj ? jj - 1u : k - 1u;
-                } else {
-                    ins++;
-                }
-            }
-            if (cols) close();
-            flush_run();
+            });
         }
         // sixteen lanes write the record's sixteen words (trew_hip_refined), its reserved word the anchor: one vector store
         u32 x = rec[15];

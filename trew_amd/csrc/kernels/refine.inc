@@ -17,7 +17,8 @@
 // never wins.  The longest run, the smallest start among the longest: two wave maxima an iteration; a later iteration must be
 // strictly longer.
 //
-// Stages 3 to 6 (align, vote, align) are align.inc's row step: the row in registers, a phase per lane, the cyclic neighbour
+// Stages 3 to 6 (align, vote, align) are the row step of kernels/wraparound.inc, kept written out in refine_pass because the
+// shared form was 3 % slower on long reads (profiles/wraparound/README.md): the row in registers, a phase per lane, the cyclic neighbour
 // by ds_bpermute, the doubling steps below the unit length only, everything selects.  The unit length is wave-uniform per
 // read, so the source-lane tables are computed per pass.  Only one strand is needed: lanes 32 .. 63 mirror lanes 0 .. 31
 // (same phase, same unit, same cells), which keeps every lane read inside its half as in align.inc and costs nothing.  The
@@ -86,6 +87,7 @@ __device__ __forceinline__ u32 refine_longest_run(const ReadRef &rd, Piece pc, u
 // One pass of the wraparound recurrence over the bases [lo, hi) of the read, taken as a read of their own, against the unit
 // whose base j is tb in the lanes with (lane & 31) = j < k (8 in the others): the best cell of the row's lanes as
 // align_wave_kernel finds it, in every lane; start and end count from lo.  kVote: the forward decode into cnt.
+// Repeats wrap_sources, base_code, wrap_row<false> (the vote where its `mid` runs), wrap_keep_best and wrap_reduce_half<false>.
 template <bool kVote>
 __device__ __forceinline__ void refine_pass(const ReadRef &rd, u32 lo_pos, u32 hi_pos, u32 tb, u32 k, int P, AlignCell &best, u32 &best_end,
                                             u32 (&cnt)[4]) {

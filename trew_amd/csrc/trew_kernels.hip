@@ -91,6 +91,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/chain.inc"
 #include "kernels/repeats.inc"
 #include "kernels/satellites.inc"
+#include "kernels/wraparound.inc"
 #include "kernels/align.inc"
 #include "kernels/refine.inc"
 #include "kernels/tandems.inc"

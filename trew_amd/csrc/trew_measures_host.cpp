@@ -648,23 +648,32 @@ struct AlignCell {
     }
 };
 
-// the alignment of a read against the unit t[0 .. k - 1] repeated without end (1 <= k <= 32): o = {score, start, end,
-// consumed, matches}.  base[i]: the read's codes, 4: an N, which matches nothing.  With cnt (trew_hip_refined's vote) also the
-// forward decode: at every row the phase j* with the largest V, the smallest on a tie, and cnt[j*][base] += 1 when the base is
-// valid and the diagonal is that cell.
-static void align_codes_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5], u32 (*cnt)[4] = nullptr) {
+// The table of the alignment of a read against the unit t[0 .. k - 1] repeated without end (1 <= k <= 32): o = {score,
+// start, end, consumed, matches}.  base[i]: the read's codes, 4: an N, which matches nothing.  With cnt (trew_hip_refined's
+// vote) also the forward decode: at every row the phase j* with the largest V, the smallest on a tie, and cnt[j*][base] += 1
+// when the base is valid and the diagonal is that cell.  With dirs (trew_hip_trace_item) also a direction byte a cell, n + 1
+// rows of k (op of V in bits 0 .. 1: 0 fresh, 1 diagonal, 2 inserted read base; d of H above them), and the end cell's phase,
+// under the three tie rules; without dirs nothing is allocated.  The cells are the same either way: equal tuples are equal.
+static void wrap_table_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5], u32 (*cnt)[4] = nullptr,
+                            std::vector<unsigned char> *dirs = nullptr, int *end_phase = nullptr) {
     AlignCell H[32], V[32], D[32];
     for (int j = 0; j < k; j++) H[j] = AlignCell{0, 0, 0, 0};
+    if (dirs) dirs->assign(((size_t) n + 1) * (size_t) k, 0);
+    unsigned char unkept[32];
     AlignCell best{0, 0, 0, 0};
     u32 best_end = 0;
+    int best_j = 0;
     for (u32 i = 1; i <= n; i++) {
         const u32 c = base[i - 1];
+        unsigned char *row = dirs ? dirs->data() + (size_t) i * (size_t) k : unkept;
         for (int j = 0; j < k; j++) {
             const AlignCell &d = H[(j + k - 1) % k];
             D[j] = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
                              : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
             const AlignCell ins{H[j].score - penalty, H[j].start, H[j].consumed, H[j].matches};
-            V[j] = std::max(AlignCell{0, i, 0, 0}, std::max(D[j], ins));
+            V[j] = AlignCell{0, i, 0, 0}, row[j] = 0;  // rule 1: the fresh start, then the diagonal, then the inserted read base
+            if (V[j] < D[j]) V[j] = D[j], row[j] = 1;
+            if (V[j] < ins) V[j] = ins, row[j] = 2;
         }
         if (cnt) {
             int js = 0;
@@ -674,18 +683,21 @@ static void align_codes_host(const unsigned char *base, u32 n, const u32 *t, int
         }
         for (int j = 0; j < k; j++) {
             H[j] = V[j];
-            for (int d = 1; d < k; d++) {
+            for (int d = 1; d < k; d++) {  // rule 2: the smallest d
                 const AlignCell &v = V[(j + k - d) % k];
-                H[j] = std::max(H[j], AlignCell{v.score - (long long) penalty * d, v.start, v.consumed + (u32) d, v.matches});
+                const AlignCell cand{v.score - (long long) penalty * d, v.start, v.consumed + (u32) d, v.matches};
+                if (H[j] < cand) H[j] = cand, row[j] = (unsigned char) ((row[j] & 3) | (d << 2));
             }
         }
-        // the largest (score, -end, start, consumed, matches): rows come in the order of their end
+        // the largest (score, -end, start, consumed, matches): rows come in the order of their end; rule 3: the smallest j
         for (int j = 0; j < k; j++)
             if (H[j].score > best.score || (H[j].score == best.score && best_end == i && best < H[j])) {
                 best = H[j];
                 best_end = i;
+                best_j = j;
             }
     }
+    if (end_phase) *end_phase = best_j;
     if (best.score <= 0) {
         for (u32 &x : o) x = 0;
         return;
@@ -697,13 +709,17 @@ static void align_codes_host(const unsigned char *base, u32 n, const u32 *t, int
     o[4] = best.matches;
 }
 
-// one strand of one motif over one read: o = {score, start, end, consumed, matches}
-static void align_strand_host(const unsigned char *base, u32 n, const trew_hip_motif &motif, int s, int penalty, u32 (&o)[5]) {
+// the codes of strand s of a motif, first base most significant
+static void target_codes(const trew_hip_motif &motif, int s, u32 (&t)[32]) {
     const int k = motif.k;
     const u64 target = s ? motif_revcomp(motif.word, k) : motif.word;
-    u32 t[32];
-    for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;  // first base most significant
-    align_codes_host(base, n, t, k, penalty, o);
+    for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;
+}
+
+// two strands' {score, start, end, consumed, matches} as a record
+static void spread_alignment(const u32 (&f)[5], const u32 (&v)[5], trew_hip_alignment &o) {
+    o.score_fwd = f[0], o.start_fwd = f[1], o.end_fwd = f[2], o.consumed_fwd = f[3], o.matches_fwd = f[4];
+    o.score_rev = v[0], o.start_rev = v[1], o.end_rev = v[2], o.consumed_rev = v[3], o.matches_rev = v[4];
 }
 
 const char *align_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
@@ -715,12 +731,12 @@ const char *align_host(const u32 *words, const u32 *offsets, const u32 *lengths,
     for (u64 r = 0; r < n_reads; r++) {
         unpack_bases(words + offsets[r], lengths[r], base);
         for (int m = 0; m < n_motifs; m++) {
-            u32 f[5], v[5];
-            align_strand_host(base.data(), lengths[r], motifs[m], 0, penalty, f);
-            align_strand_host(base.data(), lengths[r], motifs[m], 1, penalty, v);
-            trew_hip_alignment &o = out[r * (u64) n_motifs + (u64) m];
-            o.score_fwd = f[0], o.start_fwd = f[1], o.end_fwd = f[2], o.consumed_fwd = f[3], o.matches_fwd = f[4];
-            o.score_rev = v[0], o.start_rev = v[1], o.end_rev = v[2], o.consumed_rev = v[3], o.matches_rev = v[4];
+            u32 rec[2][5], t[32];
+            for (int s = 0; s < 2; s++) {
+                target_codes(motifs[m], s, t);
+                wrap_table_host(base.data(), lengths[r], t, motifs[m].k, penalty, rec[s]);
+            }
+            spread_alignment(rec[0], rec[1], out[r * (u64) n_motifs + (u64) m]);
         }
     }
     return nullptr;
@@ -768,10 +784,10 @@ static void refine_read_host(const unsigned char *base, u32 n, int min_period, i
     const u32 ks = primitive_root(S, k);
     // 3. align against the seed
     u32 a1[5], a2[5];
-    align_codes_host(base, n, S, (int) ks, penalty, a1);
+    wrap_table_host(base, n, S, (int) ks, penalty, a1);
     // 4. vote over the tract alone
     u32 cnt[32][4] = {};
-    align_codes_host(base + a1[1], a1[2] - a1[1], S, (int) ks, penalty, a2, cnt);
+    wrap_table_host(base + a1[1], a1[2] - a1[1], S, (int) ks, penalty, a2, cnt);
     // 5. re-vote
     u32 changed = 0, support = 0;
     for (u32 j = 0; j < ks; j++) {
@@ -786,7 +802,7 @@ static void refine_read_host(const unsigned char *base, u32 n, int min_period, i
     // 6. final
     for (int i = 0; i < 5; i++) a2[i] = a1[i];
     if (changed) {
-        align_codes_host(base, n, U, (int) ku, penalty, a2);
+        wrap_table_host(base, n, U, (int) ku, penalty, a2);
         if (a2[0] < a1[0]) {  // the seed is kept
             for (int i = 0; i < 5; i++) a2[i] = a1[i];
             for (u32 j = 0; j < ks; j++) U[j] = S[j];
@@ -851,58 +867,13 @@ void sort_trace_items(trew_hip_trace_item *v, u64 n) {
     });
 }
 
-// One strand of one motif over one read (trew_hip_trace_item, include/trew_hip.h): the full table with a direction byte a cell
-// (op of V in bits 0 .. 1: 0 fresh, 1 diagonal, 2 inserted read base; d of H above them), o = the record as in
-// align_codes_host, and the walk from the end cell when the score reaches min_score.  The walk meets the columns last to
-// first, so a segment closes at its first column, an item is known when its segment closes, and a run of complete exact
-// copies when a segment that is none closes behind it; the items are appended to `items` last to first.
-static void trace_codes_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 min_score, u32 (&o)[5],
-                             std::vector<unsigned char> &dirs, trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &items) {
-    AlignCell H[32], V[32];
-    for (int j = 0; j < k; j++) H[j] = AlignCell{0, 0, 0, 0};
-    dirs.assign(((size_t) n + 1) * (size_t) k, 0);
-    AlignCell best{0, 0, 0, 0};
-    u32 best_end = 0;
-    int best_j = 0;
-    for (u32 i = 1; i <= n; i++) {
-        const u32 c = base[i - 1];
-        unsigned char *row = dirs.data() + (size_t) i * (size_t) k;
-        for (int j = 0; j < k; j++) {
-            const AlignCell &d = H[(j + k - 1) % k];
-            const AlignCell diag = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
-                                             : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
-            const AlignCell ins{H[j].score - penalty, H[j].start, H[j].consumed, H[j].matches};
-            V[j] = AlignCell{0, i, 0, 0};  // rule 1: the fresh start, then the diagonal, then the inserted read base
-            if (V[j] < diag) V[j] = diag, row[j] = 1;
-            if (V[j] < ins) V[j] = ins, row[j] = 2;
-        }
-        for (int j = 0; j < k; j++) {
-            H[j] = V[j];
-            for (int d = 1; d < k; d++) {  // rule 2: the smallest d
-                const AlignCell &v = V[(j + k - d) % k];
-                const AlignCell cand{v.score - (long long) penalty * d, v.start, v.consumed + (u32) d, v.matches};
-                if (H[j] < cand) H[j] = cand, row[j] = (unsigned char) ((row[j] & 3) | (d << 2));
-            }
-        }
-        for (int j = 0; j < k; j++)  // rule 3: the smallest j
-            if (H[j].score > best.score || (H[j].score == best.score && best_end == i && best < H[j])) {
-                best = H[j];
-                best_end = i;
-                best_j = j;
-            }
-    }
-    if (best.score <= 0) {
-        for (u32 &x : o) x = 0;
-        return;
-    }
-    o[0] = (u32) best.score;
-    o[1] = best.start;
-    o[2] = best_end;
-    o[3] = best.consumed;
-    o[4] = best.matches;
-    if (o[0] < min_score) return;
-    u32 i = best_end, seg_end = best_end, consumed = 0, sub = 0, ins = 0, del = 0, phase = 0, cols = 0, run = 0, run_start = 0;
-    int j = best_j;
+// The walk over the direction bytes of wrap_table_host from the end cell (row end, phase j) to the fresh start, against the
+// unit t[0 .. k - 1].  It meets the columns last to first, so a segment closes at its first column, an item is known when
+// its segment closes, and a run of complete exact copies when a segment that is none closes behind it; the items, proto with
+// their own fields filled in, are appended to `items` last to first.
+static void wrap_walk_host(const unsigned char *base, const u32 *t, int k, const std::vector<unsigned char> &dirs, u32 end, int j,
+                           trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &items) {
+    u32 i = end, seg_end = end, consumed = 0, sub = 0, ins = 0, del = 0, phase = 0, cols = 0, run = 0, run_start = 0;
     auto flush_run = [&]() {
         if (!run) return;
         trew_hip_trace_item it = proto;
@@ -950,6 +921,22 @@ static void trace_codes_host(const unsigned char *base, u32 n, const u32 *t, int
     flush_run();
 }
 
+// one unit over one read: the record o of wrap_table_host and, from min_score (>= 1) on, the items of its path, last to first
+static void trace_unit_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 min_score, u32 (&o)[5],
+                            std::vector<unsigned char> &dirs, trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &items) {
+    int j;
+    wrap_table_host(base, n, t, k, penalty, o, nullptr, &dirs, &j);
+    if (o[0] >= min_score) wrap_walk_host(base, t, k, dirs, o[2], j, proto, items);
+}
+
+// `mine`, which a walk left last to first, behind items[found ..] in ascending starts; nothing at or beyond cap while found counts on
+static void append_reversed(const std::vector<trew_hip_trace_item> &mine, trew_hip_trace_item *items, u64 cap, u64 &found) {
+    for (size_t q = mine.size(); q-- > 0;) {
+        if (found < cap) items[found] = mine[q];
+        found++;
+    }
+}
+
 const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_motif *motifs, int n_motifs,
                        int penalty, u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_alignment *records) {
     if (const char *e = motifs_error(motifs, n_motifs)) return e;
@@ -965,25 +952,16 @@ const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths,
         unpack_bases(words + offsets[r], lengths[r], base);
         for (int m = 0; m < n_motifs; m++) {
             const int k = motifs[m].k;
-            u32 rec[2][5];
+            u32 rec[2][5], t[32];
             for (int s = 0; s < 2; s++) {
-                const u64 target = s ? motif_revcomp(motifs[m].word, k) : motifs[m].word;
-                u32 t[32];
-                for (int j = 0; j < k; j++) t[j] = (u32) (target >> (2 * (k - 1 - j))) & 3u;  // first base most significant
+                target_codes(motifs[m], s, t);
                 mine.clear();
-                trace_codes_host(base.data(), lengths[r], t, k, penalty, min_score, rec[s], dirs,
-                                 trew_hip_trace_item{(u32) r, (u32) m, (u32) s, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mine);
-                for (size_t q = mine.size(); q-- > 0;) {  // last to first: ascending starts
-                    if (found < cap) items[found] = mine[q];
-                    found++;
-                }
+                trace_unit_host(base.data(), lengths[r], t, k, penalty, min_score, rec[s], dirs, trew_hip_trace_item{(u32) r, (u32) m, (u32) s, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                mine);
+                append_reversed(mine, items, cap, found);
                 if (counts) counts[(r * (u64) n_motifs + (u64) m) * 2ull + (u64) s] = (u32) mine.size();
             }
-            if (records) {
-                trew_hip_alignment &o = records[r * (u64) n_motifs + (u64) m];
-                o.score_fwd = rec[0][0], o.start_fwd = rec[0][1], o.end_fwd = rec[0][2], o.consumed_fwd = rec[0][3], o.matches_fwd = rec[0][4];
-                o.score_rev = rec[1][0], o.start_rev = rec[1][1], o.end_rev = rec[1][2], o.consumed_rev = rec[1][3], o.matches_rev = rec[1][4];
-            }
+            if (records) spread_alignment(rec[0], rec[1], records[r * (u64) n_motifs + (u64) m]);
         }
     }
     *n_items = found;
@@ -991,7 +969,7 @@ const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths,
 }
 
 // ---------------------------------------------------------------- units in place with no motif given: refine's unit, anchored, traced
-//  refine_read_host's record, the rotations of its unit compared as packed words, and trace_codes_host's full table
+//  refine_read_host's record, the rotations of its unit compared as packed words, and trace_unit_host's table and walk
 // for the forward strand against the smallest one, for any unit length >= 1.
 const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
                            u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_refined *records) {
@@ -1021,14 +999,11 @@ const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *leng
             }
             for (u32 j = 0; j < k; j++) t[j] = u[(j + rho) % k];
             u32 rec[5];
-            trace_codes_host(base.data(), lengths[r], t, (int) k, penalty, min_score, rec, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                             mine);
+            trace_unit_host(base.data(), lengths[r], t, (int) k, penalty, min_score, rec, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                            mine);
             R.reserved = rho;
         }
-        for (size_t q = mine.size(); q-- > 0;) {  // last to first: ascending starts
-            if (found < cap) items[found] = mine[q];
-            found++;
-        }
+        append_reversed(mine, items, cap, found);
         if (counts) counts[r] = (u32) mine.size();
         if (records) records[r] = R;
     }
