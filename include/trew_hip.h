@@ -36,8 +36,9 @@ extern "C" {
  * trew_hip_satellites_results, trew_satellites_host), the alignment entry points (trew_hip_align, trew_hip_align_results,
  * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host), the tandem
  * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host), the traceback entry points (trew_hip_trace,
- * trew_hip_trace_results, trew_trace_host) and the decomposition entry points (trew_hip_decompose, trew_hip_decompose_results,
- * trew_decompose_host): they are purely additive -- no existing
+ * trew_hip_trace_results, trew_trace_host), the decomposition entry points (trew_hip_decompose, trew_hip_decompose_results,
+ * trew_decompose_host) and the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host): they
+ * are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
 
@@ -820,6 +821,54 @@ int trew_hip_decompose_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item 
 int trew_decompose_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                         int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
                         trew_hip_refined *records);
+
+/* ---- units in place for every tract of a read, no motif given: trew_hip_tandems with trew_hip_decompose's traceback per tract ----
+ * (a long read with a satellite beside a telomere, or two telomeric arrays around a junction: what is each of them made of?)
+ * Integer-exact (tests/dissect_ref.py is the reference).  The arguments are those of trew_hip_tandems and
+ * trew_hip_decompose, with the same checks and error texts; max_records, max_items and max_rows must each be >= 1.
+ * 1. Pieces.  The pieces of a read, their depths, and which pieces give a record are exactly those of trew_hip_tandems,
+ *    the weak-piece rule and the pieces too short to repeat included.
+ * 2. Records.  A piece [lo, hi) with a record X (score >= min_score) yields a trew_hip_tandem record that equals
+ *    trew_hip_tandems' record in every field but reserved, which carries the anchor rho of X.unit as trew_hip_decompose
+ *    defines it: M is the smallest rotation of the unit as packed words, no reverse complement taken, M[j] = U[(j + rho) mod k].
+ * 3. Items.  The items of that record are those of trew_hip_decompose for the bases lo .. hi - 1 taken as a read of their own,
+ *    with lo added to start: trew_hip_trace_items with strand = 0.  motif holds the index of the item's tract among the
+ *    read's records in the order of their starts, counting from 0.  Unit lengths 1 and 2 are traced.
+ * 4. A weak piece gives no record, no items and claims no rows; its children are walked as in trew_hip_tandems.
+ * Records come sorted by (read, start), items by (read, start).  Consequences: the records equal trew_hip_tandems' but for
+ * reserved; the depth-0 record and its items equal trew_hip_decompose's record and items of the read whenever that record
+ * reaches min_score; the items of a tract tile [start, end) of its record without a gap; their bases, consumed and errors sum
+ * to the record's; only the first item of a tract can have phase != 0; a read's output does not depend on the rest of the batch;
+ * the rows claimed are the sum of end - start over all records.  Limits: those of trew_hip_tandems and trew_hip_decompose --
+ * periods <= 32; linear gaps; a wrong scored_period is not repaired; a weak piece is dropped; signatures compare directly
+ * only within one strand value (a tract of the other strand is cut at the smallest rotation of the reverse complement).  Also
+ * additive: TREW_HIP_ABI_VERSION stays 4.
+ *
+ * Like trew_hip_tandems in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, no motifs, the checks and their error texts), with buffers of its own and independent of
+ * the scan and of the other thirteen kernels.  Further argument errors: "max_records must be at least 1", "max_items must be at
+ * least 1", "max_rows must be at least 1".  The kernel appends records to a log of max_records records and items to a log of
+ * max_items items and keeps the directions of the traced tracts in a workspace of max_rows rows of 32 bytes; all grow only.  A
+ * tract claims end - start rows.  At most 2^32 - 1 reads a batch.  One kernel launch, a wave per read, for every read length;
+ * the recursion runs inside the wave. */
+int trew_hip_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                     uint64_t max_records, uint64_t max_items, uint64_t max_rows);
+/* Waits for the slot.  *n_records, *n_items and *n_rows (none may be NULL) are the records and items found and the rows claimed,
+ * exact also beyond max_records, max_items, max_rows, rec_cap or item_cap; counts (n_reads * 2 values, (tracts, items) of every
+ * read; may be NULL) is always exact.  min(rec_cap, *n_records) records and min(item_cap, *n_items) items, each sorted by (read,
+ * start), go to `records` and `items` when *n_records <= max_records, *n_items <= max_items and *n_rows <= max_rows; if any of
+ * the three capacities is exceeded nothing is copied into `records` or `items` and the call returns 0: repeat trew_hip_dissect
+ * with all three at least what was reported -- one retry always suffices.  (A tract whose rows did not fit is still traced, by
+ * recomputing its rows block after block: the decision is taken per tract.)  "no trew_hip_dissect on this slot yet" without a
+ * call. */
+int trew_hip_dissect_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items, uint64_t item_cap,
+                             uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts, float *ms_kernel);
+/* The definition on the host, piece by piece with the full table of every traced piece, over packed planes: *n_records and
+ * *n_items (neither may be NULL) as above, *n_rows (may be NULL) the sum of end - start over the records, the first
+ * min(rec_cap, *n_records) records and min(item_cap, *n_items) items of the sorted orders, counts as above (may be NULL). */
+int trew_dissect_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                      int penalty, uint32_t min_score, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items, uint64_t item_cap,
+                      uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -1,0 +1,58 @@
+// dissect_host_harness.cpp -- runs the CPU definition of units in place for every tract of a read (dissect_host of
+// trew_measures_host.cpp) on its own, so that it can be built with sanitizers: no HIP, no library.
+//
+//   dissect_host_harness MIN_PERIOD MAX_PERIOD PENALTY MIN_SCORE REC_CAP ITEM_CAP  < reads (one per line; an empty line is a read of no bases)
+//
+// Prints the numbers of records, items and rows on one line, then every copied record (at most REC_CAP) in the order of the
+// fields of trew_hip_tandem, then every copied item (at most ITEM_CAP) in the order of the fields of trew_hip_trace_item, one
+// line each, then the counts on one line (tests/test_dissect_cpu.py compares it with what trew_amd.capi returns through
+// libtrew_hip.so).
+#include <cstdio>
+#include <cstdlib>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "../../trew_amd/csrc/trew_measures_host.hpp"
+
+int main(int argc, char **argv) {
+    if (argc != 7) return fprintf(stderr, "usage: dissect_host_harness MIN_PERIOD MAX_PERIOD PENALTY MIN_SCORE REC_CAP ITEM_CAP\n"), 2;
+    // the packed layout of trew_hip.h, base by base: three words {lo, hi, nmask} per 32 bases, T=0 G=1 C=2 A=3
+    std::vector<uint32_t> words, offsets, lengths;
+    words.reserve(64);  // reads of no bases only: still a buffer
+    for (std::string line; std::getline(std::cin, line);) {
+        offsets.push_back((uint32_t) words.size());
+        lengths.push_back((uint32_t) line.size());
+        words.resize(words.size() + 3 * ((line.size() + 31) / 32), 0);
+        for (size_t i = 0; i < line.size(); i++) {
+            uint32_t *w = &words[offsets.back() + 3 * (i / 32)];
+            const std::string::size_type c = std::string("TGCA").find(line[i]);
+            if (c == std::string::npos) w[2] |= 1u << (i % 32);
+            else w[0] |= (uint32_t) (c & 1) << (i % 32), w[1] |= (uint32_t) (c >> 1) << (i % 32);
+        }
+    }
+    const uint64_t n = offsets.size();
+    const uint64_t rec_cap = strtoull(argv[5], nullptr, 10), item_cap = strtoull(argv[6], nullptr, 10);
+    std::vector<trew_hip_tandem> recs(rec_cap);      // exactly the capacities: a write beyond one is the sanitizer's to find
+    std::vector<trew_hip_trace_item> items(item_cap);
+    std::vector<uint32_t> counts(2 * n);
+    uint64_t n_recs = 0, n_items = 0, n_rows = 0;
+    if (const char *e = trew::dissect_host(words.data(), offsets.data(), lengths.data(), n, atoi(argv[1]), atoi(argv[2]), atoi(argv[3]),
+                                           (uint32_t) strtoul(argv[4], nullptr, 10), rec_cap ? recs.data() : nullptr, rec_cap,
+                                           item_cap ? items.data() : nullptr, item_cap, &n_recs, &n_items, &n_rows, counts.data()))
+        return fprintf(stderr, "%s\n", e), 3;
+    printf("%llu %llu %llu\n", (unsigned long long) n_recs, (unsigned long long) n_items, (unsigned long long) n_rows);
+    for (uint64_t i = 0; i < n_recs && i < rec_cap; i++) {
+        const trew_hip_tandem &x = recs[i];
+        printf("%u %u %u %u %u %u %u %u %u %u %u %u %u %u %llu %llu\n", x.read, x.depth, x.period, x.seed_period, x.scored_period, x.changed, x.score, x.start,
+               x.end, x.consumed, x.matches, x.seed_score, x.support, x.reserved, (unsigned long long) x.unit, (unsigned long long) x.seed_unit);
+    }
+    for (uint64_t i = 0; i < n_items && i < item_cap; i++) {
+        const trew_hip_trace_item &x = items[i];
+        printf("%u %u %u %u %u %u %u %u %u %u %u %u\n", x.read, x.motif, x.strand, x.start, x.bases, x.count, x.phase, x.consumed, x.mismatches, x.insertions,
+               x.deletions, x.reserved);
+    }
+    for (uint32_t c : counts) printf("%u ", c);
+    printf("\n");
+    return 0;
+}

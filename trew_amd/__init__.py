@@ -29,6 +29,7 @@ from .capi import (  # noqa: F401
     annotate,
     chain,
     decompose,
+    dissect,
     intervals,
     k_mer_check,
     pack_reads,

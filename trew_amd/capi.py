@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_tandems", "trew_hip_tandems_results", "trew_tandems_host",
     "trew_hip_trace", "trew_hip_trace_results", "trew_trace_host",
     "trew_hip_decompose", "trew_hip_decompose_results", "trew_decompose_host",
+    "trew_hip_dissect", "trew_hip_dissect_results", "trew_dissect_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain", "dead_entries")
@@ -297,6 +298,9 @@ def load():
     lib.trew_hip_decompose.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64, u64]
     lib.trew_hip_decompose_results.argtypes = lib.trew_hip_trace_results.argtypes
     lib.trew_decompose_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
+    lib.trew_hip_dissect.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64, u64, u64]
+    lib.trew_hip_dissect_results.argtypes = [vp, i32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(C.c_float)]
+    lib.trew_dissect_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
     lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
     lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
@@ -567,6 +571,35 @@ def decompose_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_
 
     out, found = _sized_call(call, TRACE_DTYPE, cap)
     return out, counts, records, found
+
+
+def dissect_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, rec_cap=None, item_cap=None):
+    """trew_dissect_host: tandems_host's records of every read, each with its unit's anchor in `reserved`, and for every record
+    decompose_host's items of its piece taken as a read of its own, in read coordinates, computed on the host.  reads_or_packed
+    as for annotate_host.  Returns (TANDEM_DTYPE records sorted by (read, start), TRACE_DTYPE items sorted by (read, start) with
+    motif = the index of the item's tract among its read's records and strand = 0, counts of shape (n_reads, 2) = (tracts,
+    items), n_records, n_items, n_rows); with rec_cap / item_cap at most that many records / items."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    counts = np.zeros((len(offsets), 2), dtype=np.uint32)
+    nr, ni, nw = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(recs, items):
+        if lib.trew_dissect_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                                 int(penalty), int(min_score), recs.ctypes.data if len(recs) else None, len(recs),
+                                 items.ctypes.data if len(items) else None, len(items), C.byref(nr), C.byref(ni), C.byref(nw), counts.ctypes.data) != 0:
+            _host_fail("trew_dissect_host")
+
+    recs = np.zeros(0 if rec_cap is None else int(rec_cap), dtype=TANDEM_DTYPE)
+    items = np.zeros(0 if item_cap is None else int(item_cap), dtype=TRACE_DTYPE)
+    call(recs, items)
+    if (rec_cap is None and nr.value) or (item_cap is None and ni.value):
+        if rec_cap is None:
+            recs = np.zeros(int(nr.value), dtype=TANDEM_DTYPE)
+        if item_cap is None:
+            items = np.zeros(int(ni.value), dtype=TRACE_DTYPE)
+        call(recs, items)
+    return recs[:min(len(recs), int(nr.value))], items[:min(len(items), int(ni.value))], counts, int(nr.value), int(ni.value), int(nw.value)
 
 
 def decompose_anchor(record):
@@ -1069,6 +1102,37 @@ class TrewHip:
                       "trew_hip_decompose_results")
         return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
 
+    def dissect(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, max_items=None, max_rows=None, slot=0):
+        """Queue every de novo repeat tract under indels of every read of `batch`, each with its unit anchored and the traceback
+        of its piece against it, on the slot's stream (no motifs).  max_records: as for tandems; max_items, max_rows: as for
+        decompose."""
+        if max_records is None:
+            max_records = max(int(batch.n_reads), 1)
+        max_items, max_rows = _trace_room(batch, 1, max_items, max_rows)
+        self._queue("dissect", slot, batch, None, 1, shape=(int(max_records), int(max_items), int(max_rows)))
+        self._chk(self.lib.trew_hip_dissect(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
+                                            int(max_records), int(max_items), int(max_rows)), "trew_hip_dissect")
+
+    def dissect_results(self, slot=0, want_ms=False):
+        """Results of the slot's last dissect: (TANDEM_DTYPE records sorted by (read, start) with reserved = anchor, TRACE_DTYPE
+        items sorted by (read, start) with motif = the index of the item's tract in its read, counts of shape (n_reads, 2) =
+        (tracts, items), n_records, n_items, n_rows [, kernel ms]).  Any of the three beyond its capacity: no records and no
+        items, everything else is exact; repeat the call with all three at least what was reported."""
+        nr, ni, nw = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, _, max_records, max_items, max_rows = self._queued.get(("dissect", slot), (0, 1, 0, 0, 0))
+        counts = np.zeros((n_reads, 2), dtype=np.uint32)
+        self._chk(self.lib.trew_hip_dissect_results(self.ctx, slot, None, 0, None, 0, C.byref(nr), C.byref(ni), C.byref(nw), counts.ctypes.data,
+                                                    C.byref(ms) if want_ms else None), "trew_hip_dissect_results")
+        found, items, rows = int(nr.value), int(ni.value), int(nw.value)
+        fits = found <= max_records and items <= max_items and rows <= max_rows
+        recs = np.zeros(found if fits else 0, dtype=TANDEM_DTYPE)
+        out = np.zeros(items if fits else 0, dtype=TRACE_DTYPE)
+        if len(recs):
+            self._chk(self.lib.trew_hip_dissect_results(self.ctx, slot, recs.ctypes.data, len(recs), out.ctypes.data if len(out) else None, len(out),
+                                                        C.byref(nr), C.byref(ni), C.byref(nw), None, None), "trew_hip_dissect_results")
+        return (recs, out, counts, found, items, rows, ms.value) if want_ms else (recs, out, counts, found, items, rows)
+
     def repeats(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
         """Queue every de novo repeat tract of every read of `batch` on the slot's stream (no motifs).  max_records: the
         capacity of the log for this call (default: the batch's read count, at least 1)."""
@@ -1407,6 +1471,21 @@ def decompose(reads, min_period=1, max_period=32, penalty=3, min_score=24, devic
         room = _trace_room(b, 1, max_items, max_rows)
         return _fetch_with_retry(lambda items, rows: t.decompose(b, min_period, max_period, penalty, min_score, items, rows), t.decompose_results, room,
                                  (3, 4))[:3]
+
+
+def dissect(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None, max_items=None, max_rows=None):
+    """Units in place for every tract of a read with no motif given on the GPU: `tandems`' records of every read (bytes / str),
+    each with its unit turned to its smallest rotation (`reserved` is the anchor; decompose_anchor gives the rotation), and for
+    every record `decompose`'s items of its piece, in read coordinates.  Returns (TANDEM_DTYPE records sorted by (read, start),
+    TRACE_DTYPE items sorted by (read, start) with motif = the index of the item's tract in its read, counts of shape (n_reads,
+    2) = (tracts, items)); trace_signature turns a tract's items into text with k = period, tandem_columns gives a record's
+    columns.  The first call's logs and workspace hold max_records records, max_items items and max_rows rows (defaults:
+    TrewHip.dissect's); when more are found the call is repeated once with the exact numbers."""
+    t, b = _one_batch(reads, device)
+    with t:
+        room = (max(int(b.n_reads), 1) if max_records is None else int(max_records),) + _trace_room(b, 1, max_items, max_rows)
+        return _fetch_with_retry(lambda recs, items, rows: t.dissect(b, min_period, max_period, penalty, min_score, recs, items, rows), t.dissect_results,
+                                 room, (3, 4, 5))[:3]
 
 
 def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):

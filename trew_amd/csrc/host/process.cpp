@@ -1178,11 +1178,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1197,6 +1197,7 @@ struct Annotator {
         std::vector<uint64_t> vhist;           // variants: hist, then reads_with, of one batch
         std::vector<trew_hip_alignment> arecs; // trace: the alignment records that come with its items
         std::vector<trew_hip_refined> drecs;   // decompose: the refined records that come with its items
+        std::vector<trew_hip_tandem> trecs;    // dissect: the records that come with its items
         AnnotFileResult part;
         std::vector<uint32_t> nl;
         std::vector<int64_t> st, nd;
@@ -1284,16 +1285,17 @@ static T *records(Annotator::Worker *w, uint64_t n) {
 // what the batch needs, which the library reports exactly also when it did not fit -- so one retry always suffices, and a
 // second overflow is a bug (`twice`).  Returns what was found.
 struct LogRoom {
-    uint64_t log, rows;  // records (chain: events) of the log; rows of trace's workspace, 0 for the others
+    uint64_t log, rows;   // records (chain: events) of the log; rows of trace's workspace, 0 for the others
+    uint64_t tracts = 0;  // dissect: the records of its second log, 0 for the others
 };
 template <class Queue, class Fetch>
 static LogRoom fetch_with_retry(AnnotFileResult &p, LogRoom room, const char *twice, Queue queue, Fetch fetch) {
     for (int attempt = 0;; attempt++) {
         queue(room);
         const LogRoom need = fetch(room);
-        if (need.log <= room.log && need.rows <= room.rows) return need;
+        if (need.log <= room.log && need.rows <= room.rows && need.tracts <= room.tracts) return need;
         if (attempt) die(twice);
-        room = LogRoom{std::max(room.log, need.log), std::max(room.rows, need.rows)};
+        room = LogRoom{std::max(room.log, need.log), std::max(room.rows, need.rows), std::max(room.tracts, need.tracts)};
         p.interval_retries++;
     }
 }
@@ -1719,6 +1721,57 @@ static void fold_decompose(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew dissect: fold_tandems' rows and tally from the records (reserved: the anchor), and fold_decompose's items of those tracts,
+// each against its tract's own unit (it.motif: the tract's index among its read's records).  dissect_units counts per (period,
+// strand-canonical unit) what tandem_units counts, and the units, edited items and items of the tracts' signatures.  The
+// workspace holds a row of 32 bytes for every base of the batch, which no batch exceeds; the logs start at sixteen items and four
+// records per read, and a batch of which either overflows is resubmitted once, with the exact numbers.
+static void fold_dissect(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    uint64_t bases = 0;
+    for (uint64_t r = 0; r < x.n; r++) bases += x.lengths[r];
+    const LogRoom found = fetch_with_retry(
+        p, LogRoom{16 * x.n, std::max<uint64_t>(bases, 1), 4 * x.n + 16}, "internal error: the dissect logs overflowed twice",
+        [&](LogRoom room) {
+            if (trew_hip_dissect(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.tracts, room.log, room.rows))
+                hip_die(x.c, "trew_hip_dissect");
+        },
+        [&](LogRoom room) {
+            LogRoom need{0, 0, 0};
+            if (w->trecs.size() < room.tracts) w->trecs.resize(room.tracts);
+            if (trew_hip_dissect_results(x.c, w->slot, w->trecs.data(), room.tracts, records<trew_hip_trace_item>(w, room.log), room.log, &need.tracts, &need.log,
+                                         &need.rows, nullptr, nullptr))
+                hip_die(x.c, "trew_hip_dissect_results");
+            return need;
+        });
+    const trew_hip_tandem *trecs = w->trecs.data();
+    tally_units(
+        trecs, found.tracts, p.dissect_units,
+        [](const trew_hip_tandem &rec) { return std::pair<uint32_t, uint64_t>{rec.period, canonical_unit(rec.unit, (int) rec.period)}; },
+        [&](const trew_hip_tandem &rec, DissectUnit &u) {
+            u.copies += rec.consumed / rec.period;
+            p.trows.push_back(TandemRow{x.first_read + rec.read, x.lengths[rec.read], rec});
+        });
+    const trew_hip_trace_item *recs = static_cast<const trew_hip_trace_item *>(w->recs);
+    uint64_t q = 0;  // items and records are sorted alike: the record of an item is found going forward
+    for (uint64_t i = 0; i < found.log; i++) {
+        const trew_hip_trace_item &it = recs[i];
+        while (q < found.tracts && (trecs[q].read < it.read || (trecs[q].read == it.read && trecs[q].end <= it.start))) q++;
+        if (q >= found.tracts) die("internal error: a dissect item without its record");
+        const trew_hip_tandem &rec = trecs[q];
+        const uint32_t k = rec.period;
+        const bool errors = it.mismatches || it.insertions || it.deletions;
+        DissectUnit &u = p.dissect_units[{k, canonical_unit(rec.unit, (int) k)}];
+        if (it.consumed == k * it.count) u.units += it.count;
+        u.edited += errors;
+        u.items++;
+        const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
+        p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
+                                   run ? std::string() : std::string(x.text + w->st[it.read] + it.start, (size_t) it.bases)});
+    }
+}
+
 static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue *q, const AnnotRequest *rq) {
     trew_hip_ctx *c = a->ctx[(size_t) w->dev_index];
     for (;;) {
@@ -1761,6 +1814,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Tandems: fold_tandems(x, p); break;
             case Measure::Trace: fold_trace(x, p); break;
             case Measure::Decompose: fold_decompose(x, p); break;
+            case Measure::Dissect: fold_dissect(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1827,6 +1881,15 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         u.bases += v.bases;
         u.copies += v.copies;
     });
+    merge_units(into.dissect_units, from.dissect_units, [](DissectUnit &u, const DissectUnit &v) {
+        u.reads += v.reads;
+        u.tracts += v.tracts;
+        u.bases += v.bases;
+        u.copies += v.copies;
+        u.units += v.units;
+        u.edited += v.edited;
+        u.items += v.items;
+    });
     merge_units(into.decompose_units, from.decompose_units, [](DecomposeUnit &u, const DecomposeUnit &v) {
         u.reads += v.reads;
         u.bases += v.bases;
@@ -1837,7 +1900,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     });
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -1915,7 +1978,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         } logs[] = {{Measure::Intervals, "intervals", out.irows.size()}, {Measure::Chain, "items", out.crows.size()},
                     {Measure::Repeats, "tracts", out.rrows.size()},      {Measure::Satellites, "tracts", out.srows.size()},
                     {Measure::Tandems, "tracts", out.trows.size()},      {Measure::Trace, "items", out.xrows.size()},
-                    {Measure::Decompose, "items", out.xrows.size()}};
+                    {Measure::Decompose, "items", out.xrows.size()},     {Measure::Dissect, "items", out.xrows.size()}};
         for (const auto &l : logs)
             if (rq.kind == l.kind)
                 fprintf(stderr, "[trew] %s: %llu %s, %llu batch(es) resubmitted with a larger log\n", file_name, (unsigned long long) l.rows, l.noun,

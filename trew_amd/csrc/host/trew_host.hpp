@@ -99,10 +99,10 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose FASTQ...: the per-read measures.
-// One file path for all thirteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp and decompose.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose };
+// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect FASTQ...: the per-read measures.
+// One file path for all fourteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp and dissect.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
@@ -187,6 +187,10 @@ struct DecomposeUnit {
     uint64_t reads = 0, bases = 0, copies = 0;  // as RefineUnit
     uint64_t units = 0, edited = 0, items = 0;  // over the rows' items: the copies of the items with consumed = period count, the items with an error, the items
 };
+struct DissectUnit {
+    uint64_t reads = 0, tracts = 0, bases = 0, copies = 0;  // as TandemUnit
+    uint64_t units = 0, edited = 0, items = 0;              // over the tracts' items, as DecomposeUnit
+};
 struct RepeatUnit {
     uint64_t reads = 0, tracts = 0, bases = 0;  // reads with such a tract, the tracts, the sum of their end - start
 };
@@ -202,10 +206,10 @@ struct AnnotFileResult {
     std::vector<SatelliteRow> srows; // satellites: sorted by read, start
     std::vector<AlignRow> arows;     // align: sorted by read, motif, strand
     uint64_t align_sums[TREW_ANNOT_MAX_MOTIFS][2][kAlignSums] = {};  // align: [motif][strand], over the rows
-    std::vector<TraceRow> xrows;     // trace: the items of its arows' keys, sorted by read, motif, strand, start; decompose: the items of its frows (motif = strand = 0)
+    std::vector<TraceRow> xrows;     // trace: the items of its arows' keys, sorted by read, motif, strand, start; decompose: the items of its frows (motif = strand = 0); dissect: the items of its trows (motif: the tract's index in its read)
     uint64_t trace_sums[TREW_ANNOT_MAX_MOTIFS][2][kTraceSums] = {};  // trace: [motif][strand], over the rows
     std::vector<RefineRow> frows;    // refine, decompose (rf.reserved: the anchor): sorted by read
-    std::vector<TandemRow> trows;    // tandems: sorted by read, start
+    std::vector<TandemRow> trows;    // tandems, dissect (td.reserved: the anchor): sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
     uint32_t longest[TREW_ANNOT_MAX_MOTIFS] = {}, longest_tail[TREW_ANNOT_MAX_MOTIFS] = {};
@@ -223,6 +227,8 @@ struct AnnotFileResult {
     std::map<std::pair<uint32_t, uint64_t>, DecomposeUnit> decompose_units;
     // tandems: (period, strand-canonical unit) -> its reads, tracts, bases and copies
     std::map<std::pair<uint32_t, uint64_t>, TandemUnit> tandem_units;
+    // dissect: the same, and the units, edited items and items of the tracts' signatures
+    std::map<std::pair<uint32_t, uint64_t>, DissectUnit> dissect_units;
     // repeats: (period, strand-canonical unit) -> its reads, tracts and bases
     std::map<std::pair<uint32_t, uint64_t>, RepeatUnit> repeat_units;
     // satellites: the same, the canonical unit as its codes (one char a base, T 0, G 1, C 2, A 3; see satellite_canonical)
@@ -252,7 +258,7 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
-    bool motif_less = false;                      // periods, repeats, satellites, refine, tandems, decompose: every positional argument is a file, `names` stays empty
+    bool motif_less = false;                      // periods, repeats, satellites, refine, tandems, decompose, dissect: every positional argument is a file, `names` stays empty
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
@@ -276,6 +282,7 @@ int refine_main(int argc, char **argv);
 int tandems_main(int argc, char **argv);
 int trace_main(int argc, char **argv);
 int decompose_main(int argc, char **argv);
+int dissect_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement

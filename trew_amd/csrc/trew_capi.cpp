@@ -25,11 +25,11 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect"};
 // whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
-const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false};
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -52,6 +52,8 @@ struct MeasureState {
     DevBuf rows;       // the direction workspace, 64 bytes a row (decompose: 32), grown on demand
     DevBuf aligned;    // the trew_hip_alignment of every (read, motif) (decompose: the trew_hip_refined of every read)
     u64 max_rows = 0;  // the max_rows of the last call (max_log: its max_items; n: its alignment records)
+    // dissect: as decompose, with `aligned` its log of trew_hip_tandem records, `counter` three values (items, rows, records),
+    // `counts` two u32 per read; n: the max_records of the last call
 };
 
 struct Slot {
@@ -1271,8 +1273,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose
-// The thirteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect
+// The fourteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
 // fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
@@ -1357,6 +1359,14 @@ extern "C" int trew_decompose_host(const uint32_t *words, const uint32_t *offset
                                    int max_period, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items,
                                    uint32_t *counts, trew_hip_refined *records) {
     return host_status(decompose_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, items, cap, n_items, counts, records));
+}
+
+extern "C" int trew_dissect_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                 int max_period, int penalty, uint32_t min_score, trew_hip_tandem *records, uint64_t rec_cap,
+                                 trew_hip_trace_item *items, uint64_t item_cap, uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows,
+                                 uint32_t *counts) {
+    return host_status(dissect_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, records, rec_cap, items, item_cap,
+                                    n_records, n_items, n_rows, counts));
 }
 
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
@@ -1475,10 +1485,11 @@ struct LogShape {
     u64 aligned_per_read;    // trace: n_motifs alignment records; decompose: one refined record; else 0
     size_t row_bytes;        // trace: 64, decompose: 32; else 0
     size_t aligned_bytes;    // of one of the records beside the log; else 0
+    u64 max_tracts;          // dissect: the capacity of its second log, the records kept in `aligned`, and a third counter for them; else 0
 };
 
 // The queue call of the measures with an append log (intervals, chain, repeats, satellites, tandems, trace, decompose): measure_begin, the
-// counter (one word, trace and decompose two: a fixed size, allocated on first use), room for the counts, the log and trace's two buffers,
+// counter (one word, trace and decompose two, dissect three: a fixed size, allocated on first use), room for the counts, the log and trace's two buffers,
 // then the numbers of the call, all in one place, the counter back to zero -- every call starts from zero, also one without
 // reads, whose results then report nothing found -- and `launch` between the events unless the batch is empty.
 template <class Own, class Launch>
@@ -1489,8 +1500,8 @@ static int queue_log(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, c
     if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, which, own, &sp, &db)) return rc;
     Slot &s = *sp;
     MeasureState &st = s.measure[which];
-    const size_t counter_bytes = (shape.max_rows ? 2 : 1) * sizeof(unsigned long long);
-    const u64 n_counts = db.n_reads * shape.counts_per_read, n_aligned = db.n_reads * shape.aligned_per_read;
+    const size_t counter_bytes = (shape.max_tracts ? 3 : shape.max_rows ? 2 : 1) * sizeof(unsigned long long);
+    const u64 n_counts = db.n_reads * shape.counts_per_read, n_aligned = shape.max_tracts ? shape.max_tracts : db.n_reads * shape.aligned_per_read;
     if (!st.counter) HIPCHK(ctx, hipMalloc((void **) &st.counter, counter_bytes));
     if (int rc = grow(ctx, s, st.aligned, n_aligned * shape.aligned_bytes)) return rc;
     if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
@@ -1700,6 +1711,58 @@ extern "C" int trew_hip_decompose_results(trew_hip_ctx *ctx, int slot, trew_hip_
     if (records && st.n) HIPCHK(ctx, hipMemcpy(records, st.aligned.p, st.n * sizeof(trew_hip_refined), hipMemcpyDeviceToHost));
     // trace's contract: both fit, or no items
     if (int rc = fetch_log(ctx, st, items, cap, found[1] <= st.max_rows ? whole_log(st, found[0]) : 0, sort_trace_items)) return rc;
+    return fetch_end(ctx, st, ms_kernel);
+}
+
+// ---------------------------------------------------------------- units in place for every tract of a read, no motif given
+// As decompose: `records` is the item log, `rows` 32 bytes a row; `aligned` is the log of trew_hip_tandem records (reserved: the
+// anchor), `counter` three values (items, rows, records), `counts` two u32 per read (tracts, items).
+extern "C" int trew_hip_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                                uint64_t max_records, uint64_t max_items, uint64_t max_rows) {
+    auto own = [&]() -> const char * {
+        if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+        return max_records < 1 ? "max_records must be at least 1"
+               : max_items < 1 ? "max_items must be at least 1"
+               : max_rows < 1  ? "max_rows must be at least 1"
+                               : nullptr;
+    };
+    const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 2, false, max_rows, 0, 32, sizeof(trew_hip_tandem), max_records};
+    return queue_log(ctx, batch, slot, nullptr, 0, kDissect, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
+        const RepeatLog rl = {st.counter + 2, (u32 *) st.aligned.p, st.n};
+        HIPCHK(ctx, launch_dissect(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, rl, lg, (u32 *) st.counts.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_dissect_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items,
+                                        uint64_t item_cap, uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts,
+                                        float *ms_kernel) {
+    const char *arg_error = !n_records || !n_items || !n_rows ? "trew_hip_dissect_results: n_records, n_items and n_rows must not be null"
+                            : rec_cap && !records             ? "trew_hip_dissect_results: records must not be null"
+                            : item_cap && !items              ? "trew_hip_dissect_results: items must not be null"
+                                                              : nullptr;
+    Slot *sp = nullptr;
+    if (int rc = fetch_begin(ctx, slot, kDissect, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[kDissect];
+    unsigned long long found[3] = {0, 0, 0};
+    if (int rc = fetch_counted(ctx, st, found, 3, counts)) return rc;
+    *n_items = found[0];
+    *n_rows = found[1];
+    *n_records = found[2];
+    // one contract for the three: all fit, or nothing is copied.  The items are numbered against all the records, so both logs
+    // come whole to the host whatever the caller's buffers hold.
+    if (found[0] <= st.max_log && found[1] <= st.max_rows && found[2] <= st.n && (rec_cap || item_cap) && found[2]) {
+        std::vector<trew_hip_tandem> recs((size_t) found[2]);
+        std::vector<trew_hip_trace_item> its((size_t) found[0]);
+        HIPCHK(ctx, hipMemcpy(recs.data(), st.aligned.p, recs.size() * sizeof(trew_hip_tandem), hipMemcpyDeviceToHost));
+        if (!its.empty()) HIPCHK(ctx, hipMemcpy(its.data(), st.records.p, its.size() * sizeof(trew_hip_trace_item), hipMemcpyDeviceToHost));
+        sort_tandems(recs.data(), recs.size());
+        sort_dissect_items(its.data(), its.size());
+        number_dissect_items(recs.data(), recs.size(), its.data(), its.size());
+        if (const u64 take = std::min<u64>(rec_cap, recs.size())) memcpy(records, recs.data(), take * sizeof(trew_hip_tandem));
+        if (const u64 take = std::min<u64>(item_cap, its.size())) memcpy(items, its.data(), take * sizeof(trew_hip_trace_item));
+    }
     return fetch_end(ctx, st, ms_kernel);
 }
 

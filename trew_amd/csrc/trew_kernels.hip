@@ -51,6 +51,7 @@
 //   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: the recursion of pieces.inc over pieces, written out in the kernel, with refine.inc's refine_piece per piece)
 //   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
 //   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
+//   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: tandems.inc's piece loop, written out once more, with decompose.inc's anchor, rows and walk for every piece that gives a record)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -97,6 +98,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/tandems.inc"
 #include "kernels/trace.inc"
 #include "kernels/decompose.inc"
+#include "kernels/dissect.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -461,6 +463,11 @@ hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const Annot
 hipError_t launch_decompose(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const TraceLog &lg,
                             trew_hip_refined *d_out, u32 *d_counts) {
     return launch_wave_per_read(st, n_cu, B, decompose_wave_kernel, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts);
+}
+
+hipError_t launch_dissect(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &rl,
+                          const TraceLog &lg, u32 *d_counts) {
+    return launch_wave_per_read(st, n_cu, B, dissect_wave_kernel, min_period, max_period, penalty, min_score, rl, lg, d_counts);
 }
 
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words) {

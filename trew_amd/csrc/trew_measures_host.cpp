@@ -971,6 +971,27 @@ const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths,
 // ---------------------------------------------------------------- units in place with no motif given: refine's unit, anchored, traced
 //  refine_read_host's record, the rotations of its unit compared as packed words, and trace_unit_host's table and walk
 // for the forward strand against the smallest one, for any unit length >= 1.
+// steps 2 and 3 of 4.7i for the read `base` of n bases with the refined record R: R.reserved becomes the anchor and the items of
+// the forward strand against the smallest rotation are appended to `mine`, last to first; nothing without a record of min_score
+static void anchor_and_trace_host(const unsigned char *base, u32 n, trew_hip_refined &R, int penalty, u32 min_score, std::vector<unsigned char> &dirs,
+                                  trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &mine) {
+    if (!R.period || R.score < min_score) return;
+    const u32 k = R.period;
+    u32 u[32], t[32], rho = 0;
+    for (u32 j = 0; j < k; j++) u[j] = (u32) (R.unit >> (2 * (k - 1 - j))) & 3u;  // first base most significant
+    u64 smallest = R.unit;
+    for (u32 q = 1; q < k; q++) {  // rotation q: its base j is U[(j + q) mod k]
+        u32 rot[32];
+        for (u32 j = 0; j < k; j++) rot[j] = u[(j + q) % k];
+        const u64 w = pack_unit(rot, k);
+        if (w < smallest) smallest = w, rho = q;  // U is primitive: the rotations are distinct
+    }
+    for (u32 j = 0; j < k; j++) t[j] = u[(j + rho) % k];
+    u32 rec[5];
+    trace_unit_host(base, n, t, (int) k, penalty, min_score, rec, dirs, proto, mine);
+    R.reserved = rho;
+}
+
 const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
                            u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_refined *records) {
     if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
@@ -986,29 +1007,98 @@ const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *leng
         trew_hip_period periods;
         refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, R, periods);
         mine.clear();
-        if (R.period && R.score >= min_score) {
-            const u32 k = R.period;
-            u32 u[32], t[32], rho = 0;
-            for (u32 j = 0; j < k; j++) u[j] = (u32) (R.unit >> (2 * (k - 1 - j))) & 3u;  // first base most significant
-            u64 smallest = R.unit;
-            for (u32 q = 1; q < k; q++) {  // rotation q: its base j is U[(j + q) mod k]
-                u32 rot[32];
-                for (u32 j = 0; j < k; j++) rot[j] = u[(j + q) % k];
-                const u64 w = pack_unit(rot, k);
-                if (w < smallest) smallest = w, rho = q;  // U is primitive: the rotations are distinct
-            }
-            for (u32 j = 0; j < k; j++) t[j] = u[(j + rho) % k];
-            u32 rec[5];
-            trace_unit_host(base.data(), lengths[r], t, (int) k, penalty, min_score, rec, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                            mine);
-            R.reserved = rho;
-        }
+        anchor_and_trace_host(base.data(), lengths[r], R, penalty, min_score, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mine);
         append_reversed(mine, items, cap, found);
         if (counts) counts[r] = (u32) mine.size();
         if (records) records[r] = R;
     }
     *n_items = found;
     return nullptr;
+}
+
+// ---------------------------------------------------------------- units in place for every tract of a read, no motif given
+//  tandems_host's piece walk, and for every piece that gives a record decompose_host's anchor and traceback of the
+// piece's bases as a read of their own, its items shifted into read coordinates and numbered by the tract's place in the read.
+const char *dissect_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, trew_hip_tandem *records, u64 rec_cap, trew_hip_trace_item *items, u64 item_cap, u64 *n_records, u64 *n_items,
+                         u64 *n_rows, u32 *counts) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    if (!n_records || !n_items || (rec_cap && !records) || (item_cap && !items)) return "trew_dissect_host: null argument";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_dissect_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_dissect_host: more than 2^32 - 1 reads";
+    struct Tract {
+        trew_hip_tandem rec;
+        std::vector<trew_hip_trace_item> items;  // last to first
+    };
+    struct Todo {
+        u32 lo, hi, depth;
+    };
+    std::vector<unsigned char> base, dirs;
+    std::vector<Todo> todo;
+    std::vector<Tract> mine;
+    u64 found = 0, found_items = 0, rows = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        mine.clear();
+        todo.assign(1, Todo{0, lengths[r], 0});
+        while (!todo.empty()) {
+            const Todo t = todo.back();
+            todo.pop_back();
+            trew_hip_refined x;
+            trew_hip_period R;
+            refine_read_host(base.data() + t.lo, t.hi - t.lo, min_period, max_period, penalty, min_score, x, R);  // the piece as a read of its own
+            if (R.scored_period == 0) continue;
+            u32 start = t.lo + R.start, end = t.lo + R.end;  // a weak piece: around the periods tract
+            if (x.score >= min_score) {
+                Tract tr;
+                anchor_and_trace_host(base.data() + t.lo, t.hi - t.lo, x, penalty, min_score, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+                                      tr.items);
+                start = t.lo + x.start, end = t.lo + x.end;
+                tr.rec = trew_hip_tandem{(u32) r, t.depth, x.period, x.seed_period, x.scored_period, x.changed, x.score, start, end, x.consumed,
+                                         x.matches, x.seed_score, x.support, x.reserved, x.unit, x.seed_unit};
+                for (trew_hip_trace_item &it : tr.items) it.start += t.lo;
+                mine.push_back(std::move(tr));
+            }
+            todo.push_back(Todo{end, t.hi, t.depth + 1});
+            todo.push_back(Todo{t.lo, start, t.depth + 1});
+        }
+        std::sort(mine.begin(), mine.end(), [](const Tract &a, const Tract &b) { return a.rec.start < b.rec.start; });
+        u32 my_items = 0;
+        for (size_t q = 0; q < mine.size(); q++) {
+            if (found < rec_cap) records[found] = mine[q].rec;
+            found++;
+            rows += mine[q].rec.end - mine[q].rec.start;
+            for (trew_hip_trace_item &it : mine[q].items) it.motif = (u32) q;
+            append_reversed(mine[q].items, items, item_cap, found_items);
+            my_items += (u32) mine[q].items.size();
+        }
+        if (counts) counts[2 * r] = (u32) mine.size(), counts[2 * r + 1] = my_items;
+    }
+    *n_records = found;
+    *n_items = found_items;
+    if (n_rows) *n_rows = rows;
+    return nullptr;
+}
+
+// `items` sorted by (read, start) with `motif` still the start of each item's tract, `records` sorted by (read, start): motif
+// becomes the index of that tract among its read's records.  The tracts of a read are disjoint and an item starts inside its own.
+void number_dissect_items(const trew_hip_tandem *records, u64 n_records, trew_hip_trace_item *items, u64 n_items) {
+    u64 q = 0, first = 0;  // the record at hand, the first record of its read
+    for (u64 i = 0; i < n_items; i++) {
+        while (q < n_records && (records[q].read < items[i].read || (records[q].read == items[i].read && records[q].start < items[i].motif))) {
+            q++;
+            if (q < n_records && records[q].read != records[first].read) first = q;
+        }
+        if (q >= n_records) break;  // never: every item has its record
+        items[i].motif = (u32) (q - first);
+    }
+}
+
+void sort_dissect_items(trew_hip_trace_item *v, u64 n) {
+    std::sort(v, v + n, [](const trew_hip_trace_item &a, const trew_hip_trace_item &b) {
+        if (a.read != b.read) return a.read < b.read;
+        return a.start < b.start;
+    });
 }
 
 }  // namespace trew

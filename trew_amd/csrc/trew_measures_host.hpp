@@ -67,5 +67,12 @@ void sort_trace_items(trew_hip_trace_item *v, uint64_t n);  // by (read, motif, 
 const char *decompose_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                            int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
                            trew_hip_refined *records);
+// units in place for every tract of a read, no motif given: tandems_host's pieces, decompose_host's anchor and items per record
+const char *dissect_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                         int penalty, uint32_t min_score, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items, uint64_t item_cap,
+                         uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts);
+void sort_dissect_items(trew_hip_trace_item *v, uint64_t n);  // by (read, start)
+// items sorted by (read, start) whose motif word is the start of their tract, records sorted by (read, start): motif becomes the tract's index in its read
+void number_dissect_items(const trew_hip_tandem *records, uint64_t n_records, trew_hip_trace_item *items, uint64_t n_items);
 
 }  // namespace trew
