@@ -1,6 +1,7 @@
 """The file of tests/test_gpu_measure_cli.py -- one generated FASTQ of a few hundred KB that is cut into many chunks by a small
-TREW_MEASURE_CHUNK_BYTES -- and what the twelve measure commands must print for it, formatted from the CPU definitions
-(capi.*_host) over the whole file, with file-wide ordinals, by the formatters of the measures' own tests."""
+TREW_MEASURE_CHUNK_BYTES -- and what the fourteen measure commands must print for it, formatted from the CPU definitions
+(capi.*_host) over the whole file, with file-wide ordinals, by the formatters of the measures' own tests; and a second, small
+file of many short tracts a read (make_tract_file), which fills dissect's record log as well."""
 import os
 import random
 
@@ -8,6 +9,8 @@ import numpy as np
 
 import align_ref
 import annot_ref
+import decompose_ref
+import dissect_ref
 import interval_ref
 import period_ref
 import refine_ref
@@ -26,13 +29,17 @@ SEED = 20260117
 CHUNK = 4096
 MOTIFS = ["TTAGGG", "AATGG"]
 SAT_MAX_PERIOD = 180  # keeps satellites_host short; the planted 171-mer is within it
-COMMANDS = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"]
-LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace"]  # the six with an append log that can overflow
+COMMANDS = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace",
+            "decompose", "dissect"]
+LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace", "decompose", "dissect"]  # the eight with an append log that can overflow
+ITEMIZED = ["decompose", "dissect"]  # the two whose --items form is run beside their rows form
 _RC = str.maketrans("ACGTacgt", "TGCAtgca")
 
 
-def command_line(name, paths):
-    """arguments of `trew` for one command at its defaults"""
+def command_line(name, paths, per_item=False):
+    """arguments of `trew` for one command at its defaults; per_item: decompose and dissect with --items"""
+    if name in ITEMIZED:  # in their rows form a row per tract, with the signature printed from the chunk's text
+        return [name, *(["--items"] if per_item else []), *paths]
     if name in ("periods", "repeats", "refine", "tandems"):
         return [name, *paths]
     if name == "trace":  # a row per item: the log's records themselves, in place
@@ -159,7 +166,7 @@ def reads_of(data):
 
 
 def host_results(reads):
-    """the CPU definitions of the twelve commands over the whole file, at the commands' defaults"""
+    """the CPU definitions of the fourteen commands over the whole file, at the commands' defaults"""
     p = capi.pack_reads(reads)
     return {
         "annotate": capi.annotate_host(p, MOTIFS),
@@ -174,6 +181,8 @@ def host_results(reads):
         "refine": capi.refine_host(p),
         "tandems": capi.tandems_host(p),
         "trace": capi.trace_host(p, MOTIFS, 3, 24),
+        "decompose": capi.decompose_host(p),
+        "dissect": capi.dissect_host(p),
     }
 
 
@@ -183,7 +192,7 @@ def _shifted(recs, n):
     return np.concatenate([recs, out])
 
 
-def _one_file(name, path, reads, res):
+def _one_file(name, path, reads, res, per_item=False):
     """(the file's section, the summary section) of a one-file run"""
     real = os.path.realpath(path)
     if name == "annotate":
@@ -206,18 +215,22 @@ def _one_file(name, path, reads, res):
         return tandem_ref.cli_lines(path, reads, res[0], 3)
     elif name == "trace":
         lines = trace_ref.cli_lines(path, reads, MOTIFS, res, 3, per_item=True)
+    elif name == "decompose":
+        return decompose_ref.cli_lines(path, reads, res, 3, per_item=per_item)
+    elif name == "dissect":
+        return dissect_ref.cli_lines(path, reads, res, 3, per_item=per_item)
     at = lines.index(">Summary")
     return lines[:at], lines[at:]
 
 
-def expected(name, paths, reads, res):
+def expected(name, paths, reads, res, per_item=False):
     """stdout of `trew <name>` for the same reads under every path of `paths`: a section per path, with ordinals that start
-    at 0 in each, and one summary over all of them"""
+    at 0 in each, and one summary over all of them; per_item: the --items form of decompose and dissect"""
     if name == "variants":
         return variant_ref.cli_lines([(p, reads) for p in paths], MOTIFS, results=[res] * len(paths))
     if name == "chain":
         return chain_cli_lines([(p, reads) for p in paths], MOTIFS, results=[res] * len(paths))
-    sections = [_one_file(name, p, reads, res) for p in paths]
+    sections = [_one_file(name, p, reads, res, per_item) for p in paths]
     if len(paths) == 1:
         return sections[0][0] + sections[0][1]
     assert len(paths) == 2
@@ -226,11 +239,15 @@ def expected(name, paths, reads, res):
         both = np.concatenate([res, res])
     elif name == "trace":
         both = (_shifted(res[0], n), np.concatenate([res[1], res[1]]), np.concatenate([res[2], res[2]]))
+    elif name == "decompose":  # items, counts, records: the records are one per read, the items name theirs
+        both = (_shifted(res[0], n), np.concatenate([res[1], res[1]]), np.concatenate([res[2], res[2]]))
+    elif name == "dissect":  # records and items both name their read
+        both = (_shifted(res[0], n), _shifted(res[1], n))
     elif name == "intervals":
         both = (_shifted(res[0], n), np.concatenate([res[1], res[1]]))
     else:
         both = (_shifted(res[0], n),)
-    return sections[0][0] + sections[1][0] + _one_file(name, paths[0], reads + reads, both)[1]
+    return sections[0][0] + sections[1][0] + _one_file(name, paths[0], reads + reads, both, per_item)[1]
 
 
 def reported_reads(name, lines):
@@ -240,11 +257,94 @@ def reported_reads(name, lines):
 
 
 def summary_keys(name, lines):
-    """(period, canonical) -> ordinals of the reads with such a row, from the rows of periods, refine, repeats, satellites or
-    tandems"""
-    col = 2 if name in ("periods", "refine") else 3
+    """(period, canonical) -> ordinals of the reads with such a row, from the rows of periods, refine, decompose (a row per
+    read: the period is column 2), repeats, satellites, tandems or dissect (a row per tract, with its depth: column 3)"""
+    col = 2 if name in ("periods", "refine", "decompose") else 3
     out = {}
     for ln in lines[2:lines.index(">Summary")]:
         f = ln.split(",")
         out.setdefault((f[col], f[col + 2]), set()).add(int(f[0]))
     return out
+
+
+def tract_rows(name, lines):
+    """(read, start, end, strand, signature) of every row of decompose or dissect in their rows form"""
+    col = 5 if name == "decompose" else 6
+    out = []
+    for ln in lines[2:lines.index(">Summary")]:
+        f = ln.split(",")
+        out.append((int(f[0]), int(f[col]), int(f[col + 1]), f[-4], f[-1]))
+    return out
+
+
+def log_overflows(name, res, chunk_reads):
+    """(chunks whose items exceed the first item log of fold_decompose / fold_dissect, sixteen a read; chunks whose records
+    exceed dissect's first record log, four a read and sixteen more), from the host definition's result `res`"""
+    n_reads = 1 + max(i for c in chunk_reads for i in c)
+    items, tracts = [0] * n_reads, [0] * n_reads
+    for r in res[0 if name == "decompose" else 1]["read"]:
+        items[int(r)] += 1
+    if name == "dissect":
+        for r in res[0]["read"]:
+            tracts[int(r)] += 1
+    over_items = [n for n, c in enumerate(chunk_reads) if sum(items[i] for i in c) > 16 * len(c)]
+    over_tracts = [n for n, c in enumerate(chunk_reads) if c and sum(tracts[i] for i in c) > 4 * len(c) + 16]
+    return over_items, over_tracts
+
+
+# The second file: about 40 KB of reads with many short tracts each, for the one capacity the first file never fills.  A read
+# of the first file has two tracts at the most, so at any chunk length fold_dissect's record log (4 n + 16 records for n reads)
+# holds every batch.  Here every third read holds 26 exact tracts and the others 10, each of 36 bases of a unit of 2 to 6 bases
+# with 18 random bases in front of it: at chunk 4096 a batch is two or three reads, and its 20 to 46 tracts fall on either side
+# of the 24 or 28 records its log starts with.  A read's recursion splits around one tract at a time, so its depth grows with
+# its tracts.  In front of them stand two reads of 14 tracts that are one item each (whole copies of the unit's anchored
+# rotation, the bases beside them no match): the first chunk is these two, 28 records for a log of 24 and about as many items
+# for a log of 32 -- the one batch that is resubmitted for its records alone.
+TRACT_SEED = 20260330
+TRACT_READS = 2 + 24
+TRACT_BASES, TRACT_GAP = 36, 18
+CLEAN_TRACTS, CLEAN_BASES = 14, 30
+
+
+def _unit(rnd, k, avoid):
+    """a unit of k bases that is no repetition of a shorter one and shares no rotation with `avoid`"""
+    while True:
+        u = _junk(rnd, k)
+        if all(u != u[:d] * (k // d) for d in range(1, k) if k % d == 0) and (avoid is None or len(avoid) != k or u not in avoid + avoid):
+            return u
+
+
+def _anchored(unit):
+    """the rotation of `unit` that decompose traces against: the one with the smallest packed word"""
+    word = period_ref.pack_unit(decompose_ref.anchor(list(align_ref.codes(unit)))[1])
+    return period_ref.unit_text(word, len(unit))
+
+
+def _clean_read(rnd):
+    """CLEAN_TRACTS tracts of CLEAN_BASES bases, whole copies of an anchored unit of 2, 3, 5 or 6 bases, between random bases
+    of which the two beside a tract do not continue it"""
+    seq, unit = "", None
+    for _ in range(CLEAN_TRACTS):
+        unit = _anchored(_unit(rnd, rnd.choice([2, 3, 5, 6]), unit))
+        seq += _junk(rnd, TRACT_GAP - 2) + rnd.choice([c for c in "ACGT" if c != unit[-1]]) + unit * (CLEAN_BASES // len(unit))
+        seq += rnd.choice([c for c in "ACGT" if c != unit[0]])
+    return seq + _junk(rnd, TRACT_GAP)
+
+
+def make_tract_records(seed=TRACT_SEED):
+    rnd = random.Random(seed + 1)
+    recs = [["@c%d" % i, seq, "I" * len(seq)] for i, seq in enumerate(_clean_read(rnd) for _ in range(2))]
+    rnd = random.Random(seed)
+    for i in range(TRACT_READS - 2):
+        seq, unit = "", None
+        for _ in range(26 if i % 3 == 0 else 10):
+            unit = _unit(rnd, rnd.randint(2, 6), unit)
+            phase = rnd.randrange(len(unit))
+            seq += _junk(rnd, TRACT_GAP) + (unit * (TRACT_BASES // len(unit) + 2))[phase:phase + TRACT_BASES]
+        seq += _junk(rnd, TRACT_GAP)
+        recs.append(["@m%d" % i, seq, "I" * len(seq)])
+    return recs
+
+
+def make_tract_file(seed=TRACT_SEED):
+    return render(make_tract_records(seed))

@@ -1,4 +1,4 @@
-"""The per-measure state of a slot (trew_capi.cpp: MeasureState, stage_motifs, grow, the log counters): the twelve per-read
+"""The per-measure state of a slot (trew_capi.cpp: MeasureState, stage_motifs, grow, the log counters): the fourteen per-read
 measures queued back to back on one slot, each with a motif list (or none) and a batch of its own, keep their results apart;
 the pattern tables are restaged exactly when they have to be; every buffer grows when a larger batch comes and carries nothing
 over to the next call; a log that overflowed leaves nothing behind for the next call; a results call without its queue call
@@ -34,11 +34,12 @@ MOTIFS_B = {
     "align": ["TTG", "TTAGGG", "TTAGG", "AATGG"],
     "trace": ["TTAGGG", K32],
 }
-ORDER = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace"]  # of the queue calls in sequence_a
+ORDER = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose",
+         "dissect"]  # of the queue calls in sequence_a
 WITH_MOTIFS = [name for name in ORDER if name in MOTIFS]
-LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace"]  # the measures with an append log and a counter
+LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace", "decompose", "dissect"]  # the measures with an append log and a counter
 ROOMY = 1 << 16  # a log no batch of this file fills
-ROOMY_ROWS = 1 << 18  # a trace workspace (64 bytes a row) no batch of this file fills
+ROOMY_ROWS = 1 << 18  # a trace workspace (64 bytes a row; decompose, dissect: 32) no batch of this file fills
 READS = make_reads()
 SMALL = [READS[i] for i in (23, 29, 17, 11)]  # 65, 2017, 33 and 6 bases
 
@@ -65,8 +66,21 @@ class Expected:
         return self._host[key]
 
     def found(self, name, motifs=None):
-        """the records (chain, trace: items) of a logged measure, as its host definition counts them"""
-        return self.host(name, motifs)[3 if name == "trace" else 2]
+        """the records (chain, trace, decompose, dissect: items) of a logged measure, as its host definition counts them"""
+        return self.host(name, motifs)[{"trace": 3, "decompose": 3, "dissect": 4}.get(name, 2)]
+
+    def dissect_records(self):
+        """the records of dissect's second log"""
+        return self.host("dissect")[3]
+
+    def rows(self, name):
+        """the workspace rows decompose and dissect claim, a row per base of a traced tract: decompose's from its refined
+        records, dissect's as its host definition counts them"""
+        if name == "dissect":
+            return self.host("dissect")[5]
+        r = self.host("decompose")[2]
+        traced = (r["period"] > 0) & (r["score"] >= 24)
+        return int((r["end"].astype(np.int64) - r["start"].astype(np.int64))[traced].sum())
 
     def trace_rows(self, motifs=None):
         """the workspace rows trace claims: for every (read, motif) with a strand whose score reaches min_score, the bases
@@ -94,9 +108,9 @@ def same(got, want, what):
     assert got.tobytes() == want.tobytes(), "%s differs at %s" % (what, np.argwhere(got != want)[:1].tolist())
 
 
-def queue(t, name, e, motifs=None, cap=ROOMY, slot=0, rows=ROOMY_ROWS):
-    """one queue call of measure `name` for the batch of `e`; cap: the log of the six logged measures; rows: the workspace
-    of trace"""
+def queue(t, name, e, motifs=None, cap=ROOMY, slot=0, rows=ROOMY_ROWS, records=ROOMY):
+    """one queue call of measure `name` for the batch of `e`; cap: the log of the eight logged measures (trace, decompose,
+    dissect: the item log); rows: the workspace of trace, decompose and dissect; records: dissect's second log"""
     b = t.host_batch(*e.packed)
     motifs = MOTIFS.get(name) if motifs is None else motifs
     if name == "intervals":
@@ -109,6 +123,10 @@ def queue(t, name, e, motifs=None, cap=ROOMY, slot=0, rows=ROOMY_ROWS):
         getattr(t, name)(b, slot=slot)
     elif name == "trace":
         t.trace(b, motifs, 3, 24, max_items=cap, max_rows=rows, slot=slot)
+    elif name == "decompose":
+        t.decompose(b, 1, 32, 3, 24, max_items=cap, max_rows=rows, slot=slot)
+    elif name == "dissect":
+        t.dissect(b, 1, 32, 3, 24, max_records=records, max_items=cap, max_rows=rows, slot=slot)
     elif name in ("tracts", "align"):
         getattr(t, name)(b, motifs, 3, slot=slot)
     else:
@@ -118,7 +136,9 @@ def queue(t, name, e, motifs=None, cap=ROOMY, slot=0, rows=ROOMY_ROWS):
 def fetch(t, name, e, motifs=None, slot=0, overflowed=False):
     """the results call of `name`, compared with the host definition of the batch of `e`.  overflowed: the log was too small --
     the counts and the numbers found are exact all the same; intervals keeps as many records as the log held, the other five
-    none (trace: its log or its workspace was too small; its alignment records and its rows are exact as well)"""
+    none (trace: its log or its workspace was too small; its alignment records and its rows are exact as well; decompose:
+    likewise, with its refined records; dissect: any of its three capacities was too small -- no records and no items, the
+    counts and the three numbers exact)"""
     want = e.host(name, motifs)
     what = "%s (slot %d)" % (name, slot)
     got = getattr(t, name + "_results")(slot=slot)
@@ -127,6 +147,24 @@ def fetch(t, name, e, motifs=None, slot=0, overflowed=False):
     elif name == "variants":
         for g, w, part in zip(got, want, ("records", "hist", "reads_with")):
             same(g, w, what + " " + part)
+    elif name == "decompose":
+        items, counts, refined, n_items, n_rows = got
+        assert (n_items, n_rows) == (e.found(name), e.rows(name)), what
+        same(counts, want[1], what + " counts")
+        same(refined, want[2], what + " refined records")
+        if overflowed:
+            assert len(items) == 0, what
+        else:
+            same(items, want[0], what + " items")
+    elif name == "dissect":
+        recs, items, counts, n_records, n_items, n_rows = got
+        assert (n_records, n_items, n_rows) == (e.dissect_records(), e.found(name), e.rows(name)) == want[3:], what
+        same(counts, want[2], what + " counts")
+        if overflowed:
+            assert len(recs) == 0 and len(items) == 0, what
+        else:
+            same(recs, want[0], what + " tandem records")
+            same(items, want[1], what + " items")
     else:
         recs, counts = got[:2]
         found = got[3 if name == "trace" else 2]
@@ -147,7 +185,7 @@ def fetch(t, name, e, motifs=None, slot=0, overflowed=False):
 
 
 def sequence_a(t, e):
-    """the twelve measures queued back to back on slot 0, fetched in reverse order; returns the variants histograms"""
+    """the fourteen measures queued back to back on slot 0, fetched in reverse order; returns the variants histograms"""
     found = e.intervals[2]
     for name in ORDER:
         queue(t, name, e, cap=max(found, 1) if name == "intervals" else ROOMY)
@@ -169,7 +207,7 @@ def test_results_call_without_its_queue_call_fails():
     """first in the file: needs a context of its own on which nothing was queued"""
     with capi.TrewHip(mode=capi.MODE_SHORT, n_slots=1, max_batch_words=1 << 12, max_batch_reads=16, table_log2_slots=12) as fresh:
         fetch = {name: getattr(fresh, name + "_results") for name in ORDER}
-        assert len(fetch) == 12
+        assert len(fetch) == 14
         for name, f in fetch.items():
             with pytest.raises(capi.TrewHipError, match="no trew_hip_%s on this slot yet" % name):
                 f()
@@ -199,7 +237,12 @@ def test_the_expected_results_are_not_trivial(expected):
             assert 2 * x.n // 5 < x.found(name) < ROOMY // 8, (key, name)
         assert x.found("tandems") > 1 and x.found("trace") > 1
         assert 1 < x.trace_rows() and max(x.trace_rows(), x.trace_rows(MOTIFS_B["trace"])) < ROOMY_ROWS // 2
+        # decompose and dissect: more than the one item, record or row of the overflow tests, and the rows below the workspace
+        assert x.found("decompose") > 1 and x.found("dissect") > 1 and 1 < x.dissect_records() < ROOMY // 8
+        assert 1 < x.rows("decompose") < ROOMY_ROWS // 2 and 1 < x.rows("dissect") < ROOMY_ROWS // 2
+        assert x.dissect_records() == len(x.host("dissect")[0]) == x.found("tandems") and x.found("dissect") == len(x.host("dissect")[1])
         assert all((x.host("chain")[1][:, m] > 0).any() for m in range(2))
+    assert e.dissect_records() > e.n * 4 // 5 and e.found("dissect") > e.found("decompose") and e.rows("dissect") > e.rows("decompose")  # tracts beside the best one
     assert (e.host("align")["score_fwd"] > 24).any() and (e.host("align")["score_rev"] > 24).any()
     assert len({r["period"] for r in e.host("satellites")[0]}) >= 3 and len({r["period"] for r in e.host("repeats")[0]}) >= 3
     for lists in (MOTIFS, MOTIFS_B):
@@ -208,13 +251,13 @@ def test_the_expected_results_are_not_trivial(expected):
 
 
 def test_four_measures_back_to_back_on_one_slot(t, expected):
-    """(all twelve since the eight newer ones came; the name is the one the test has always had)"""
+    """(all fourteen since the ten newer ones came; the name is the one the test has always had)"""
     sequence_a(t, expected["full"])
 
 
 def test_alternating_batches_and_other_motif_lists(t, expected):
     """consecutive calls use different batches (the small and the full one in turn) and the lists of MOTIFS_B; nothing is
-    fetched until all twelve are queued, then in the order of the queue calls"""
+    fetched until all fourteen are queued, then in the order of the queue calls"""
     batch = {name: expected["small" if i % 2 == 0 else "full"] for i, name in enumerate(ORDER)}
     for name in ORDER:
         queue(t, name, batch[name], MOTIFS_B.get(name))
@@ -290,6 +333,33 @@ def test_a_trace_workspace_that_overflowed_leaves_nothing_behind(t, expected):
     fetch(t, "trace", expected["small"])
 
 
+FURTHER = [("decompose", "rows"), ("dissect", "records"), ("dissect", "cap"), ("dissect", "rows")]
+
+
+@pytest.mark.parametrize("name,short", FURTHER, ids=["%s-%s" % (n, "items" if c == "cap" else c) for n, c in FURTHER])
+def test_a_further_counter_that_overflowed_leaves_nothing_behind(t, expected, name, short):
+    """the overflow test once more for the counters beside the first: decompose's workspace, and each of dissect's three
+    capacities -- records, items, rows -- at 1 alone with the other two roomy.  The call is refused; then a call of a measure
+    that runs the same kernels' code on a state of its own (refine behind decompose, tandems behind dissect); then the refused
+    call again with exactly the numbers it reported"""
+    other = "refine" if name == "decompose" else "tandems"
+    for key in ("full", "small", "full"):
+        e = expected[key]
+        queue(t, name, e, **{short: 1})
+        got = fetch(t, name, e, overflowed=True)
+        queue(t, other, e)
+        if name == "decompose":
+            queue(t, name, e, cap=got[3], rows=got[4])
+        else:
+            queue(t, name, e, records=got[3], cap=got[4], rows=got[5])
+        fetch(t, name, e)
+        fetch(t, other, e)
+    # queued back to back without a fetch in between: every counter of the second call starts at zero
+    queue(t, name, expected["full"], **{short: 1})
+    queue(t, name, expected["small"])
+    fetch(t, name, expected["small"])
+
+
 def test_buffers_grow_and_nothing_accumulates(expected):
     """a context of its own, so that the first round is the first use of every buffer and the second grows each of them"""
     with capi.TrewHip(mode=capi.MODE_SHORT, n_slots=1, max_batch_words=1 << 14, max_batch_reads=64, table_log2_slots=12) as ctx:
@@ -301,7 +371,7 @@ def test_buffers_grow_and_nothing_accumulates(expected):
 
 
 def test_two_slots_interleaved(expected):
-    """the twelve measures on slots 0 and 1, interleaved call by call with different batches and motif lists; slot 1 is fetched
+    """the fourteen measures on slots 0 and 1, interleaved call by call with different batches and motif lists; slot 1 is fetched
     first, in reverse order"""
     with capi.TrewHip(mode=capi.MODE_SHORT, n_slots=2, max_batch_words=1 << 14, max_batch_reads=64, table_log2_slots=12) as ctx:
         for name in ORDER:
