@@ -94,6 +94,10 @@ enum {
                                 buckets nor drops the worklist entries no k of which can still count; the exact kernel reads the
                                 prefilter's worklist and the 8-bucket words (trew_hip_debug_live_list then returns the worklist,
                                 and no entry is counted dead); results are identical */
+    TREW_FLAG_DEBUG_ONE_CU = 65536, /* tests: the wave-per-read kernels of the per-read measures get the grid of a one-CU device, 8 blocks
+                                and 32 waves, so a batch of a few thousand reads gives every wave many reads (the scan's kernels and
+                                annotate's lane-per-read kernel keep their grids; trew_hip_debug_measure_grid tells the blocks);
+                                results are identical */
     TREW_FLAG_TRACK_PRESSURE = 256 /* every batch ends with a copy of the table's fill counters into pinned host memory, and
                                 trew_hip_table_pressure answers from those copies (and from what collect / add_rows /
                                 reset read since) instead of asking the device: for hosts that ask before every batch.
@@ -276,6 +280,12 @@ int trew_hip_debug_worklist(trew_hip_ctx *ctx, int slot, uint32_t *units, uint64
  * pass does not look at.  A subset of trew_hip_debug_worklist as a multiset; equal to it where no bounds pass ran (other modes,
  * MAX_MER > 32, TREW_FLAG_DEBUG_NO_GROUP) and with TREW_FLAG_DEBUG_NO_LIVE_LIST.  Arguments as trew_hip_debug_worklist. */
 int trew_hip_debug_live_list(trew_hip_ctx *ctx, int slot, uint32_t *units, uint64_t cap, uint64_t *n);
+
+/* Diagnostic: the blocks (of four waves, a wave per read) the launcher of the per-read measures below would start for a batch of
+ * n_reads reads on this context -- on the device's compute units, or on one with TREW_FLAG_DEBUG_ONE_CU.  A wave of that grid
+ * works through reads wave, wave + 4 * blocks, ...; tests use it to assert that their batches give every wave a second read.
+ * Touches no device.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+int trew_hip_debug_measure_grid(trew_hip_ctx *ctx, uint64_t n_reads, uint32_t *blocks);
 
 /* Per-read results of the last submit on `slot` (after trew_hip_wait): for
  * TREW_MODE_SEGMENT the (k_high, k_low, MAX_SEQ at k_high, MAX_SEQ at k_low)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from measure_cases import K32, make_reads
+from measure_slots import LOGGED, ORDER, ROOMY, ROOMY_ROWS, Expected, fetch, queue, same  # the queue / fetch / compare machinery, shared with test_gpu_persist.py
 from trew_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -34,154 +35,20 @@ MOTIFS_B = {
     "align": ["TTG", "TTAGGG", "TTAGG", "AATGG"],
     "trace": ["TTAGGG", K32],
 }
-ORDER = ["annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose",
-         "dissect"]  # of the queue calls in sequence_a
-WITH_MOTIFS = [name for name in ORDER if name in MOTIFS]
-LOGGED = ["intervals", "chain", "repeats", "satellites", "tandems", "trace", "decompose", "dissect"]  # the measures with an append log and a counter
-ROOMY = 1 << 16  # a log no batch of this file fills
-ROOMY_ROWS = 1 << 18  # a trace workspace (64 bytes a row; decompose, dissect: 32) no batch of this file fills
+WITH_MOTIFS = [name for name in ORDER if name in MOTIFS]  # ORDER: of the queue calls in sequence_a
 READS = make_reads()
 SMALL = [READS[i] for i in (23, 29, 17, 11)]  # 65, 2017, 33 and 6 bases
 
 
-class Expected:
-    """the CPU definitions of one batch, computed once per (measure, motif list)"""
-
-    def __init__(self, reads):
-        self.packed = capi.pack_reads(reads)
-        self.n = len(reads)
-        self._host = {}
-        self.annotate = self.host("annotate")
-        self.tracts = self.host("tracts")
-        self.intervals = self.host("intervals")
-        self.variants = self.host("variants")
-
-    def host(self, name, motifs=None):
-        motifs = MOTIFS.get(name) if motifs is None else motifs
-        key = (name, tuple(motifs or ()))
-        if key not in self._host:
-            extra = {"tracts": (3,), "align": (3,), "trace": (3, 24)}.get(name, ())
-            f = getattr(capi, name + "_host")
-            self._host[key] = f(self.packed, *(() if motifs is None else (motifs,)), *extra)
-        return self._host[key]
-
-    def found(self, name, motifs=None):
-        """the records (chain, trace, decompose, dissect: items) of a logged measure, as its host definition counts them"""
-        return self.host(name, motifs)[{"trace": 3, "decompose": 3, "dissect": 4}.get(name, 2)]
-
-    def dissect_records(self):
-        """the records of dissect's second log"""
-        return self.host("dissect")[3]
-
-    def rows(self, name):
-        """the workspace rows decompose and dissect claim, a row per base of a traced tract: decompose's from its refined
-        records, dissect's as its host definition counts them"""
-        if name == "dissect":
-            return self.host("dissect")[5]
-        r = self.host("decompose")[2]
-        traced = (r["period"] > 0) & (r["score"] >= 24)
-        return int((r["end"].astype(np.int64) - r["start"].astype(np.int64))[traced].sum())
-
-    def trace_rows(self, motifs=None):
-        """the workspace rows trace claims: for every (read, motif) with a strand whose score reaches min_score, the bases
-        from the first start to the last end of those strands"""
-        a = self.host("trace", motifs)[2].astype([(f, "<i8") for f in capi.ALIGN_DTYPE.names])
-        fwd, rev = a["score_fwd"] >= 24, a["score_rev"] >= 24
-        lo = np.minimum(np.where(fwd, a["start_fwd"], 1 << 40), np.where(rev, a["start_rev"], 1 << 40))
-        hi = np.maximum(np.where(fwd, a["end_fwd"], 0), np.where(rev, a["end_rev"], 0))
-        return int((hi - lo)[fwd | rev].sum())
-
-
 @pytest.fixture(scope="module")
 def expected():
-    return {"small": Expected(SMALL), "full": Expected(READS)}
+    return {"small": Expected(SMALL, MOTIFS), "full": Expected(READS, MOTIFS)}
 
 
 @pytest.fixture(scope="module")
 def t():
     with capi.TrewHip(mode=capi.MODE_SHORT, n_slots=1, max_batch_words=1 << 14, max_batch_reads=64, table_log2_slots=12) as ctx:
         yield ctx
-
-
-def same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    assert got.tobytes() == want.tobytes(), "%s differs at %s" % (what, np.argwhere(got != want)[:1].tolist())
-
-
-def queue(t, name, e, motifs=None, cap=ROOMY, slot=0, rows=ROOMY_ROWS, records=ROOMY):
-    """one queue call of measure `name` for the batch of `e`; cap: the log of the eight logged measures (trace, decompose,
-    dissect: the item log); rows: the workspace of trace, decompose and dissect; records: dissect's second log"""
-    b = t.host_batch(*e.packed)
-    motifs = MOTIFS.get(name) if motifs is None else motifs
-    if name == "intervals":
-        t.intervals(b, motifs, max_intervals=cap, slot=slot)
-    elif name == "chain":
-        t.chain(b, motifs, max_events=cap, slot=slot)
-    elif name in ("repeats", "satellites", "tandems"):
-        getattr(t, name)(b, max_records=cap, slot=slot)
-    elif name in ("periods", "refine"):
-        getattr(t, name)(b, slot=slot)
-    elif name == "trace":
-        t.trace(b, motifs, 3, 24, max_items=cap, max_rows=rows, slot=slot)
-    elif name == "decompose":
-        t.decompose(b, 1, 32, 3, 24, max_items=cap, max_rows=rows, slot=slot)
-    elif name == "dissect":
-        t.dissect(b, 1, 32, 3, 24, max_records=records, max_items=cap, max_rows=rows, slot=slot)
-    elif name in ("tracts", "align"):
-        getattr(t, name)(b, motifs, 3, slot=slot)
-    else:
-        getattr(t, name)(b, motifs, slot=slot)
-
-
-def fetch(t, name, e, motifs=None, slot=0, overflowed=False):
-    """the results call of `name`, compared with the host definition of the batch of `e`.  overflowed: the log was too small --
-    the counts and the numbers found are exact all the same; intervals keeps as many records as the log held, the other five
-    none (trace: its log or its workspace was too small; its alignment records and its rows are exact as well; decompose:
-    likewise, with its refined records; dissect: any of its three capacities was too small -- no records and no items, the
-    counts and the three numbers exact)"""
-    want = e.host(name, motifs)
-    what = "%s (slot %d)" % (name, slot)
-    got = getattr(t, name + "_results")(slot=slot)
-    if name in ("annotate", "tracts", "align", "periods", "refine"):
-        same(got, want, what)
-    elif name == "variants":
-        for g, w, part in zip(got, want, ("records", "hist", "reads_with")):
-            same(g, w, what + " " + part)
-    elif name == "decompose":
-        items, counts, refined, n_items, n_rows = got
-        assert (n_items, n_rows) == (e.found(name), e.rows(name)), what
-        same(counts, want[1], what + " counts")
-        same(refined, want[2], what + " refined records")
-        if overflowed:
-            assert len(items) == 0, what
-        else:
-            same(items, want[0], what + " items")
-    elif name == "dissect":
-        recs, items, counts, n_records, n_items, n_rows = got
-        assert (n_records, n_items, n_rows) == (e.dissect_records(), e.found(name), e.rows(name)) == want[3:], what
-        same(counts, want[2], what + " counts")
-        if overflowed:
-            assert len(recs) == 0 and len(items) == 0, what
-        else:
-            same(recs, want[0], what + " tandem records")
-            same(items, want[1], what + " items")
-    else:
-        recs, counts = got[:2]
-        found = got[3 if name == "trace" else 2]
-        assert found == e.found(name, motifs), what
-        same(counts, want[1], what + " counts")
-        if name == "trace":
-            same(got[2], want[2], what + " alignment records")
-            assert got[4] == e.trace_rows(motifs), what
-        if name == "chain":
-            assert got[3] >= found, what  # an item takes at least one event
-        if not overflowed:
-            same(recs, want[0], what + " records")
-        elif name == "intervals":
-            assert len(recs) == 1 and (want[0] == recs[0]).any(), what
-        else:
-            assert len(recs) == 0, what
-    return got
 
 
 def sequence_a(t, e):

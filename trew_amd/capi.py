@@ -26,6 +26,7 @@ FLAG_DEBUG_NO_GROUP = 1024  # tests / A-B: every segment decided by a wave of it
 FLAG_DEBUG_ANNOT_GENERAL = 8192  # tests: annotate gives every batch a wave per read (the lane-per-read kernel is never picked)
 FLAG_DEBUG_SMALL_BOUNDS = 16384  # tests: the bounds pass hands over 64 worklist entries only (stored bounds and row bounds in one small batch)
 FLAG_DEBUG_NO_LIVE_LIST = 32768  # tests, A/B runs: the bounds pass sharpens no bound and drops no entry; the exact kernel reads the prefilter's worklist
+FLAG_DEBUG_ONE_CU = 65536  # tests: the wave-per-read kernels of the per-read measures get a one-CU grid (8 blocks, 32 waves): every wave loops over many reads
 FLAG_DEBUG_WIDE_NO_WAIT = 128  # tests: the wide table never waits for a slot's ready bit (forces its time-out path)
 TABLE_NAMES = ("forward_high", "forward_low", "backward_high", "backward_low", "both_high", "both_low")
 
@@ -39,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "trew_pack_pairs", "trew_hip_host_alloc", "trew_hip_host_free", "trew_hip_device_count",
     "trew_synth_long_lengths", "trew_synth_long_ascii", "trew_synth_long_device",
     "trew_hip_collect_device", "trew_hip_add_rows_device", "trew_hip_merge", "trew_hip_table_pressure",
-    "trew_hip_add_gathered_device", "trew_hip_collect_slice_device", "trew_hip_debug_counters", "trew_hip_debug_worklist", "trew_hip_debug_live_list", "trew_hip_submit_ascii", "trew_hip_pack_ascii",
+    "trew_hip_add_gathered_device", "trew_hip_collect_slice_device", "trew_hip_debug_counters", "trew_hip_debug_worklist", "trew_hip_debug_live_list", "trew_hip_debug_measure_grid", "trew_hip_submit_ascii", "trew_hip_pack_ascii",
     "trew_motif_parse", "trew_hip_annotate", "trew_hip_annotate_results", "trew_annotate_host",
     "trew_hip_tracts", "trew_hip_tracts_results", "trew_tracts_host",
     "trew_hip_intervals", "trew_hip_intervals_results", "trew_intervals_host",
@@ -260,6 +261,8 @@ def load():
     lib.trew_hip_debug_counters.argtypes = [vp, C.POINTER(u64), i32]
     lib.trew_hip_debug_worklist.argtypes = [vp, i32, vp, u64, C.POINTER(u64)]
     lib.trew_hip_debug_live_list.argtypes = [vp, i32, vp, u64, C.POINTER(u64)]
+    lib.trew_hip_debug_measure_grid.restype = i32
+    lib.trew_hip_debug_measure_grid.argtypes = [vp, u64, C.POINTER(C.c_uint32)]
     lib.trew_hip_table_pressure.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     lib.trew_hip_segment_results.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, u64]
     lib.trew_hip_filter_masks.argtypes = [vp, C.POINTER(Batch), vp, i32]
@@ -1247,6 +1250,12 @@ class TrewHip:
         """Unit indices the exact kernel of the last submit on `slot` walked (numpy uint32, its order): the worklist without the
         entries the bounds pass found dead (debug_counters()["dead_entries"])."""
         return self._debug_units(self.lib.trew_hip_debug_live_list, "trew_hip_debug_live_list", slot)
+
+    def debug_measure_grid(self, n_reads):
+        """The blocks (four waves each, a wave per read) the per-read measures' launcher starts for a batch of n_reads here."""
+        blocks = C.c_uint32(0)
+        self._chk(self.lib.trew_hip_debug_measure_grid(self.ctx, n_reads, C.byref(blocks)), "trew_hip_debug_measure_grid")
+        return int(blocks.value)
 
     def merge_from(self, other):
         """Add every row of `other`'s tables (another context, same or another GPU) into this context's tables."""

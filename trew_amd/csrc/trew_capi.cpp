@@ -1153,6 +1153,16 @@ extern "C" int trew_hip_debug_live_list(trew_hip_ctx *ctx, int slot, uint32_t *u
     return 0;
 }
 
+// the compute units the wave-per-read launchers of the per-read measures size their grid by: the device's, or one
+// (TREW_FLAG_DEBUG_ONE_CU: every wave of a small batch loops over many reads)
+static u32 measure_cu(const trew_hip_ctx *ctx) { return (ctx->p.flags & TREW_FLAG_DEBUG_ONE_CU) ? 1u : (u32) ctx->n_cu; }
+
+extern "C" int trew_hip_debug_measure_grid(trew_hip_ctx *ctx, uint64_t n_reads, uint32_t *blocks) {
+    if (!ctx || !blocks) return -1;
+    *blocks = wave_per_read_blocks(measure_cu(ctx), n_reads);
+    return 0;
+}
+
 extern "C" int trew_hip_debug_counters(trew_hip_ctx *ctx, uint64_t *out, int n) {
     if (!ctx || !out || n < 0) return -1;
     if (int rc = sync_all(ctx)) return rc;
@@ -1602,7 +1612,7 @@ extern "C" int trew_hip_annotate(trew_hip_ctx *ctx, const trew_hip_batch *batch,
     }
     return queue_records(ctx, batch, slot, motifs, n_motifs, kAnnotate, n_motifs, sizeof(trew_hip_annot), no_own_checks, no_setup,
                          [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
-                             HIPCHK(ctx, launch_annotate(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, max_len, general, (trew_hip_annot *) st.records.p));
+                             HIPCHK(ctx, launch_annotate(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, max_len, general, (trew_hip_annot *) st.records.p));
                              return 0;
                          });
 }
@@ -1616,7 +1626,7 @@ extern "C" int trew_hip_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, i
     auto own = [&]() -> const char * { return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr; };
     return queue_records(ctx, batch, slot, motifs, n_motifs, kTracts, n_motifs, sizeof(trew_hip_tract), own, no_setup,
                          [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
-                             HIPCHK(ctx, launch_tracts(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_tract *) st.records.p));
+                             HIPCHK(ctx, launch_tracts(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, penalty, (trew_hip_tract *) st.records.p));
                              return 0;
                          });
 }
@@ -1630,7 +1640,7 @@ extern "C" int trew_hip_align(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
     auto own = [&]() -> const char * { return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr; };
     return queue_records(ctx, batch, slot, motifs, n_motifs, kAlign, n_motifs, sizeof(trew_hip_alignment), own, no_setup,
                          [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
-                             HIPCHK(ctx, launch_align(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, (trew_hip_alignment *) st.records.p));
+                             HIPCHK(ctx, launch_align(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, penalty, (trew_hip_alignment *) st.records.p));
                              return 0;
                          });
 }
@@ -1654,7 +1664,7 @@ extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, (u64) n_motifs * 2ull, false, max_rows, (u64) n_motifs, 64, sizeof(trew_hip_alignment)};
     return queue_log(ctx, batch, slot, motifs, n_motifs, kTrace, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
-        HIPCHK(ctx, launch_trace(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
+        HIPCHK(ctx, launch_trace(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
                                  (u32 *) st.counts.p));
         return 0;
     });
@@ -1690,7 +1700,7 @@ extern "C" int trew_hip_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 1, false, max_rows, 1, 32, sizeof(trew_hip_refined)};
     return queue_log(ctx, batch, slot, nullptr, 0, kDecompose, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
-        HIPCHK(ctx, launch_decompose(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, (trew_hip_refined *) st.aligned.p,
+        HIPCHK(ctx, launch_decompose(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, (trew_hip_refined *) st.aligned.p,
                                      (u32 *) st.counts.p));
         return 0;
     });
@@ -1730,7 +1740,7 @@ extern "C" int trew_hip_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, 
     return queue_log(ctx, batch, slot, nullptr, 0, kDissect, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         const RepeatLog rl = {st.counter + 2, (u32 *) st.aligned.p, st.n};
-        HIPCHK(ctx, launch_dissect(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, rl, lg, (u32 *) st.counts.p));
+        HIPCHK(ctx, launch_dissect(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, rl, lg, (u32 *) st.counts.p));
         return 0;
     });
 }
@@ -1782,7 +1792,7 @@ extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch
             rd.min_len[m] = rules[m].min_len;
         }
         const IntervalLog lg = {st.counter, (u32 *) st.records.p, st.max_log};
-        HIPCHK(ctx, launch_intervals(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, rd, lg, (u32 *) st.counts.p));
+        HIPCHK(ctx, launch_intervals(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, rd, lg, (u32 *) st.counts.p));
         return 0;
     });
 }
@@ -1815,7 +1825,7 @@ extern "C" int trew_hip_variants(trew_hip_ctx *ctx, const trew_hip_batch *batch,
     };
     return queue_records(ctx, batch, slot, motifs, n_motifs, kVariants, n_motifs, sizeof(trew_hip_variant), no_own_checks, hists,
                          [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
-                             HIPCHK(ctx, launch_variants(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, (trew_hip_variant *) st.records.p, st.hist, st.hist + kVarHistLen));
+                             HIPCHK(ctx, launch_variants(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, (trew_hip_variant *) st.records.p, st.hist, st.hist + kVarHistLen));
                              return 0;
                          });
 }
@@ -1839,7 +1849,7 @@ extern "C" int trew_hip_periods(trew_hip_ctx *ctx, const trew_hip_batch *batch, 
     auto own = [&]() -> const char * { return periods_error(min_period, max_period, penalty, min_score); };
     return queue_records(ctx, batch, slot, nullptr, 0, kPeriods, 1, sizeof(trew_hip_period), own, no_setup,
                          [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
-                             HIPCHK(ctx, launch_periods(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_period *) st.records.p));
+                             HIPCHK(ctx, launch_periods(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, (trew_hip_period *) st.records.p));
                              return 0;
                          });
 }
@@ -1853,7 +1863,7 @@ extern "C" int trew_hip_refine(trew_hip_ctx *ctx, const trew_hip_batch *batch, i
     auto own = [&]() -> const char * { return periods_error(min_period, max_period, penalty, min_score); };
     return queue_records(ctx, batch, slot, nullptr, 0, kRefine, 1, sizeof(trew_hip_refined), own, no_setup,
                          [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
-                             HIPCHK(ctx, launch_refine(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, (trew_hip_refined *) st.records.p));
+                             HIPCHK(ctx, launch_refine(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, (trew_hip_refined *) st.records.p));
                              return 0;
                          });
 }
@@ -1870,7 +1880,7 @@ extern "C" int trew_hip_chain(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
     return queue_log(ctx, batch, slot, motifs, n_motifs, kChain, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         for (int m = 0; m < n_motifs; m++) st.k[m] = (u32) motifs[m].k;  // a batch without reads has no events to pair
         const ChainLog lg = {st.counter, (uint4 *) st.records.p, st.max_log};
-        HIPCHK(ctx, launch_chain(s.stream, (u32) ctx->n_cu, db, s.d_motifs, n_motifs, lg, (u32 *) st.counts.p));
+        HIPCHK(ctx, launch_chain(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, lg, (u32 *) st.counts.p));
         return 0;
     });
 }
@@ -1961,7 +1971,7 @@ extern "C" int trew_hip_repeats(trew_hip_ctx *ctx, const trew_hip_batch *batch, 
                                 uint64_t max_records) {
     auto error = [&]() { return periods_error(min_period, max_period, penalty, min_score); };
     return queue_tracts(ctx, batch, slot, kRepeats, sizeof(trew_hip_repeat), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
-        HIPCHK(ctx, launch_repeats(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, counts));
+        HIPCHK(ctx, launch_repeats(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, counts));
         return 0;
     });
 }
@@ -1976,7 +1986,7 @@ extern "C" int trew_hip_satellites(trew_hip_ctx *ctx, const trew_hip_batch *batc
                                    uint32_t min_score, uint64_t max_records) {
     auto error = [&]() { return satellites_error(min_period, max_period, penalty, min_score); };
     return queue_tracts(ctx, batch, slot, kSatellites, sizeof(trew_hip_satellite), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
-        HIPCHK(ctx, launch_satellites(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, counts));
+        HIPCHK(ctx, launch_satellites(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, counts));
         return 0;
     });
 }
@@ -1992,7 +2002,7 @@ extern "C" int trew_hip_tandems(trew_hip_ctx *ctx, const trew_hip_batch *batch, 
                                 uint64_t max_records) {
     auto error = [&]() { return periods_error(min_period, max_period, penalty, min_score); };
     return queue_tracts(ctx, batch, slot, kTandems, sizeof(trew_hip_tandem), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
-        HIPCHK(ctx, launch_tandems(s.stream, (u32) ctx->n_cu, db, min_period, max_period, penalty, min_score, lg, counts));
+        HIPCHK(ctx, launch_tandems(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, counts));
         return 0;
     });
 }

@@ -385,7 +385,7 @@ hipError_t launch_slice_finish(hipStream_t st, trew_hip_row *d_slice, u64 slice_
 }
 
 // The grid of every wave-per-read kernel: persistent waves, grid-strided over the reads; four waves a block, up to eight blocks a CU.
-static u32 wave_per_read_blocks(u32 n_cu, u64 n_reads) { return (u32) std::min<u64>((n_reads + 3ull) / 4ull, (u64) n_cu * 8ull); }
+u32 wave_per_read_blocks(u32 n_cu, u64 n_reads) { return (u32) std::min<u64>((n_reads + 3ull) / 4ull, (u64) n_cu * 8ull); }
 
 // One wave-per-read kernel over the batch, for every read length: nothing for an empty batch, else kernel(B, args...) on that grid.
 template <class Kernel, class... Args>

@@ -35,6 +35,8 @@ hipError_t launch_compact(hipStream_t st, const DevTable &T, u64 n_slots, u32 wi
                           unsigned long long *d_n);
 hipError_t launch_slice_finish(hipStream_t st, trew_hip_row *d_slice, u64 slice_rows, const unsigned long long *d_n, const trew_hip_row *d_spill_rows,
                                const u32 *d_spill_n, u32 spill_cap);
+// the blocks of every wave-per-read launch below for a batch of n_reads (trew_hip_debug_measure_grid reports them)
+u32 wave_per_read_blocks(u32 n_cu, u64 n_reads);
 // trew_hip_annotate: general = the wave-per-read kernel, else the lane-per-read one (max_len <= 256)
 hipError_t launch_annotate(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, u32 max_len, bool general,
                            trew_hip_annot *d_out);
