@@ -37,7 +37,8 @@ extern "C" {
  * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host), the tandem
  * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host), the traceback entry points (trew_hip_trace,
  * trew_hip_trace_results, trew_trace_host), the decomposition entry points (trew_hip_decompose, trew_hip_decompose_results,
- * trew_decompose_host) and the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host): they
+ * trew_decompose_host), the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host) and the
+ * resolution entry points (trew_hip_resolve, trew_hip_resolve_results, trew_resolve_host): they
  * are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
@@ -665,6 +666,7 @@ int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32
  * deletions follow as for trew_hip_alignment with k = period.  Limits: one tract per read, the best one; periods <= 32; linear
  * gap cost; a wrong scored_period (a multiple or a neighbour of the true period) is not repaired; the vote is a forward
  * decode, not a traceback (an indel misplaces the few bases until the penalised path overtakes); one refinement round.
+ * trew_hip_resolve, further below, lets the alignment choose between the few best-scoring periods of step 1.
  * Also additive: TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
     uint32_t period, seed_period, scored_period, changed;
@@ -879,6 +881,52 @@ int trew_hip_dissect_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *recor
 int trew_dissect_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                       int penalty, uint32_t min_score, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items, uint64_t item_cap,
                       uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts);
+
+/* ---- refine's unit with the period chosen by alignment: the few best-scoring periods each refined, the best record kept ----
+ * (step 1 of trew_hip_refine takes the one period with the largest fixed-phase score; on noisy long tracts a multiple or a
+ * neighbour of the true period can win there.  Here the alignment decides between the few periods step 1 cannot separate.)
+ * Integer-exact.  The read x, its codes, min_period, max_period (<= 32), penalty P and min_score are those of trew_hip_refine,
+ * with the same checks and error texts; candidates is C, 1 <= C <= TREW_RESOLVE_MAX_CANDIDATES, anything else is the argument
+ * error "resolve: 1 <= candidates <= 4 is required".
+ * 1. Scores.  For every admissible k (min_period <= k <= min(max_period, n - 1)) s_k is the trew_hip_periods score of the read
+ *    at k.  Order the k by (s_k descending, k ascending); the candidates k_0 .. k_{m-1} are the first C of that order with
+ *    s_k >= min_score, so m <= C.  If m = 0 the record is zero.  k_0 is trew_hip_refine's scored_period.
+ * 2. Per candidate.  For candidate c, (b, e) is the trew_hip_periods segment of k_c (the smallest e, then the largest b),
+ *    start = b and end = e + k_c.  Steps 2 to 6 of trew_hip_refine run with k = k_c and that segment: the seed from the longest
+ *    run of eq_{k_c} in [b, e), an N replaced from the unreduced consensus of [start, end) at k_c; align; vote; re-vote; final.
+ *    This gives the sixteen words R_c of a trew_hip_refined record with scored_period = k_c and reserved = 0.  R_0 is the read's
+ *    trew_hip_refine record word for word.
+ * 3. Choice.  The winner is the candidate with the largest R_c.score; on a tie the smaller R_c.period, then the smaller c.
+ * 4. Record: the sixteen words of the winner's R_c in trew_hip_refined's layout, then candidates = m, rank = the winner's c,
+ *    first_period = R_0.period and first_score = R_0.score.
+ * Consequences: with C = 1 the first sixteen words are trew_hip_refine's; score >= first_score >= the seed_score of R_0;
+ * rank = 0 implies the sixteen words are trew_hip_refine's; the record is zero exactly when trew_hip_refine's is; score ..
+ * matches equal the forward fields of trew_hip_align with the motif `unit` whenever seed_period >= 3; on a perfect repeat
+ * rank = 0 (the multiples of the period are the other candidates, their seeds reduce to the same unit and the tie goes to
+ * candidate 0).  Limits: the candidates come from the fixed-phase score, so a true period outside the best C is not found; the
+ * largest alignment score can prefer a neighbour period over a true-period unit with wrong phases (on one fuzz set of 93 noisy
+ * tracts the period alone was right in 77 reads against trew_hip_refine's 79, while the whole unit was right in 77 against 71);
+ * the cost is up to C times trew_hip_refine's alignment passes; trew_hip_refine's other limits apply.  Also additive:
+ * TREW_HIP_ABI_VERSION stays 4. */
+#define TREW_RESOLVE_MAX_CANDIDATES 4
+typedef struct {
+    uint32_t period, seed_period, scored_period, changed;
+    uint32_t score, start, end, consumed, matches;
+    uint32_t seed_score, support, reserved;
+    uint64_t unit, seed_unit;
+    uint32_t candidates, rank, first_period, first_score;
+} trew_hip_resolved; /* 80 bytes: the sixteen words of trew_hip_refined, then four of its own */
+/* Like trew_hip_refine in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, no motifs, the checks and their error texts), with a result buffer of its own that the
+ * slot's first call allocates and independent of the scan and of the other fourteen kernels.  One record per read.  One kernel,
+ * a wave per read, for every read length. */
+int trew_hip_resolve(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                     int candidates);
+/* Waits for the slot and copies the records of its last trew_hip_resolve; arguments as trew_hip_refine_results. */
+int trew_hip_resolve_results(trew_hip_ctx *ctx, int slot, trew_hip_resolved *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same records on the host, step by step from the definition, over packed planes. */
+int trew_resolve_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                      int penalty, uint32_t min_score, int candidates, trew_hip_resolved *out);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_trace", "trew_hip_trace_results", "trew_trace_host",
     "trew_hip_decompose", "trew_hip_decompose_results", "trew_decompose_host",
     "trew_hip_dissect", "trew_hip_dissect_results", "trew_dissect_host",
+    "trew_hip_resolve", "trew_hip_resolve_results", "trew_resolve_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain", "dead_entries")
@@ -201,6 +202,15 @@ REFINE_DTYPE = np.dtype([(name, "<u8" if name in ("unit", "seed_unit") else "<u4
 assert REFINE_DTYPE.itemsize == C.sizeof(Refined) == 64
 
 
+class Resolved(C.Structure):
+    _fields_ = list(Refined._fields_) + [(name, C.c_uint32) for name in ("candidates", "rank", "first_period", "first_score")]
+
+
+RESOLVE_DTYPE = np.dtype([(name, "<u8" if name in ("unit", "seed_unit") else "<u4") for name, _ in Resolved._fields_])
+assert RESOLVE_DTYPE.itemsize == C.sizeof(Resolved) == 80
+RESOLVE_MAX_CANDIDATES = 4
+
+
 class Tandem(C.Structure):
     _fields_ = [("read", C.c_uint32), ("depth", C.c_uint32)] + list(Refined._fields_)
 
@@ -307,6 +317,9 @@ def load():
     lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
     lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
+    lib.trew_hip_resolve.argtypes = lib.trew_hip_periods.argtypes + [i32]
+    lib.trew_hip_resolve_results.argtypes = lib.trew_hip_periods_results.argtypes
+    lib.trew_resolve_host.argtypes = lib.trew_periods_host.argtypes[:-1] + [i32, vp]
     lib.trew_hip_tandems.argtypes = lib.trew_hip_repeats.argtypes
     lib.trew_hip_tandems_results.argtypes = lib.trew_hip_repeats_results.argtypes
     lib.trew_tandems_host.argtypes = lib.trew_repeats_host.argtypes
@@ -675,6 +688,20 @@ def refine_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sco
     return out
 
 
+def resolve_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, candidates=3):
+    """trew_resolve_host: refine's unit with the period chosen by alignment, computed on the host step by step from the
+    definition: the `candidates` (1 .. 4) best-scoring periods of `periods`' score each refined as refine_host refines its one,
+    the record with the largest final score kept.  reads_or_packed as for annotate_host.  Returns RESOLVE_DTYPE records of
+    shape (n_reads,); their first sixteen words are a REFINE_DTYPE record (refine_columns takes them as they are)."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    out = np.zeros(len(offsets), dtype=RESOLVE_DTYPE)
+    if lib.trew_resolve_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                             int(penalty), int(min_score), int(candidates), out.ctypes.data) != 0:
+        raise TrewHipError("trew_resolve_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out
+
+
 def tandems_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
     """trew_tandems_host: every de novo repeat tract of every read under indels computed on the host, piece by piece from the
     definition (the refined record of a piece, then what lies in front of its tract and behind it).  reads_or_packed as for
@@ -989,6 +1016,17 @@ class TrewHip:
     def refine_results(self, slot=0, want_ms=False):
         """Records of the slot's last refine: REFINE_DTYPE array of shape (n_reads,) [, kernel ms]."""
         res = self._fetch_records("refine", slot, REFINE_DTYPE, want_ms)
+        return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
+
+    def resolve(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, candidates=3, slot=0):
+        """Queue refine's unit with the period chosen by alignment for every read of `batch` on the slot's stream (no motifs)."""
+        self._queue("resolve", slot, batch, None, 1)
+        self._chk(self.lib.trew_hip_resolve(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
+                                            int(candidates)), "trew_hip_resolve")
+
+    def resolve_results(self, slot=0, want_ms=False):
+        """Records of the slot's last resolve: RESOLVE_DTYPE array of shape (n_reads,) [, kernel ms]."""
+        res = self._fetch_records("resolve", slot, RESOLVE_DTYPE, want_ms)
         return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
 
     def variants(self, batch, motifs, slot=0):
@@ -1417,6 +1455,17 @@ def refine(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0
     with t:
         t.refine(b, min_period, max_period, penalty, min_score)
         return t.refine_results()
+
+
+def resolve(reads, min_period=1, max_period=32, penalty=3, min_score=24, candidates=3, device=0):
+    """`refine` with the period chosen by alignment on the GPU: for every read (bytes / str) the `candidates` (1 .. 4)
+    best-scoring periods of `periods`' score are each refined as `refine` refines its one, and the record with the largest
+    final score is kept -- RESOLVE_DTYPE records of shape (n_reads,): a REFINE_DTYPE record, then candidates, rank (0: what
+    `refine` reports), first_period and first_score (of `refine`'s record).  No motif is given."""
+    t, b = _one_batch(reads, device)
+    with t:
+        t.resolve(b, min_period, max_period, penalty, min_score, candidates)
+        return t.resolve_results()
 
 
 def variants(reads, motifs, device=0):

@@ -1178,11 +1178,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1635,6 +1635,26 @@ static void fold_refine(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew resolve: fold_refine with the resolved record; resolve_units also counts the rows with rank > 0.
+static void fold_resolve(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    if (trew_hip_resolve(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, rq.candidates)) hip_die(x.c, "trew_hip_resolve");
+    trew_hip_resolved *recs = records<trew_hip_resolved>(w, x.n);
+    uint64_t got = 0;
+    if (trew_hip_resolve_results(x.c, w->slot, recs, x.n, &got, nullptr)) hip_die(x.c, "trew_hip_resolve_results");
+    for (uint64_t r = 0; r < x.n; r++) {
+        const trew_hip_resolved &rec = recs[r];
+        if (rec.period == 0 || rec.score < rq.min_score) continue;
+        ResolveUnit &u = p.resolve_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
+        u.reads++;
+        u.bases += rec.end - rec.start;
+        u.copies += rec.consumed / rec.period;
+        u.repaired += rec.rank > 0;
+        p.vrows.push_back(ResolveRow{x.first_read + r, x.lengths[r], rec});
+    }
+}
+
 // trew trace: align_rows from the records that come with the items, and the items of those keys with the read
 // bases of every item that is no run (the signature prints them).  trace_sums: units (the copies of the items with consumed =
 // k count), edited (the items with an error), items.  The workspace holds a row for every base and motif, which no batch
@@ -1815,6 +1835,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Trace: fold_trace(x, p); break;
             case Measure::Decompose: fold_decompose(x, p); break;
             case Measure::Dissect: fold_dissect(x, p); break;
+            case Measure::Resolve: fold_resolve(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1875,6 +1896,12 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         u.bases += v.bases;
         u.copies += v.copies;
     });
+    merge_units(into.resolve_units, from.resolve_units, [](ResolveUnit &u, const ResolveUnit &v) {
+        u.reads += v.reads;
+        u.bases += v.bases;
+        u.copies += v.copies;
+        u.repaired += v.repaired;
+    });
     merge_units(into.tandem_units, from.tandem_units, [](TandemUnit &u, const TandemUnit &v) {
         u.reads += v.reads;
         u.tracts += v.tracts;
@@ -1900,7 +1927,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     });
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -1961,6 +1988,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     merge_rows(a, &AnnotFileResult::srows, out, by_read_start(&SatelliteRow::st));
     merge_rows(a, &AnnotFileResult::trows, out, by_read_start(&TandemRow::td));
     merge_rows(a, &AnnotFileResult::frows, out, [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
+    merge_rows(a, &AnnotFileResult::vrows, out, [](const ResolveRow &x, const ResolveRow &y) { return x.read < y.read; });
     merge_rows(a, &AnnotFileResult::arows, out, [](const AlignRow &x, const AlignRow &y) {
         if (x.read != y.read) return x.read < y.read;
         return x.motif != y.motif ? x.motif < y.motif : x.strand < y.strand;

@@ -99,10 +99,10 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect FASTQ...: the per-read measures.
-// One file path for all fourteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp and dissect.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect };
+// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...: the per-read measures.
+// One file path for all fifteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp, dissect.cpp and resolve.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect, Resolve };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
@@ -113,6 +113,7 @@ struct AnnotRequest {
     int min_period = 1, max_period = 32;                  // periods, repeats, satellites, refine, tandems (which take no motifs: n_motifs = 0)
     uint32_t min_score = 24;                              // periods, repeats, satellites, align, refine, tandems, trace
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
+    int candidates = 3;                                   // resolve
 };
 struct AnnotRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
@@ -175,6 +176,15 @@ struct RefineRow {
 struct RefineUnit {
     uint64_t reads = 0, bases = 0, copies = 0;  // rows with such a unit, the sums of their end - start and of their copies
 };
+struct ResolveRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_resolved rv;
+};
+struct ResolveUnit {
+    uint64_t reads = 0, bases = 0, copies = 0;  // as RefineUnit
+    uint64_t repaired = 0;                      // the rows with rank > 0
+};
 struct TandemRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
     uint32_t length;  // bases
@@ -209,6 +219,7 @@ struct AnnotFileResult {
     std::vector<TraceRow> xrows;     // trace: the items of its arows' keys, sorted by read, motif, strand, start; decompose: the items of its frows (motif = strand = 0); dissect: the items of its trows (motif: the tract's index in its read)
     uint64_t trace_sums[TREW_ANNOT_MAX_MOTIFS][2][kTraceSums] = {};  // trace: [motif][strand], over the rows
     std::vector<RefineRow> frows;    // refine, decompose (rf.reserved: the anchor): sorted by read
+    std::vector<ResolveRow> vrows;   // resolve: sorted by read
     std::vector<TandemRow> trows;    // tandems, dissect (td.reserved: the anchor): sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
@@ -223,6 +234,8 @@ struct AnnotFileResult {
     std::map<std::pair<uint32_t, uint64_t>, std::pair<uint64_t, uint64_t>> period_units;
     // refine: (period, strand-canonical unit) -> its rows, bases and copies
     std::map<std::pair<uint32_t, uint64_t>, RefineUnit> refine_units;
+    // resolve: the same, and the rows whose period the alignment chose against step 1
+    std::map<std::pair<uint32_t, uint64_t>, ResolveUnit> resolve_units;
     // decompose: (period, strand-canonical unit) -> its rows, bases and copies, and the units, edited items and items of their signatures
     std::map<std::pair<uint32_t, uint64_t>, DecomposeUnit> decompose_units;
     // tandems: (period, strand-canonical unit) -> its reads, tracts, bases and copies
@@ -258,7 +271,7 @@ struct MotifCli {
     std::function<void(AnnotRequest &rq, int m, uint32_t k)> per_motif;  // the request's parameters of motif m, which has k bases
     std::function<void(const AnnotFileResult &r, const std::vector<std::string> &names)> print_rows;  // header line and rows of one file
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
-    bool motif_less = false;                      // periods, repeats, satellites, refine, tandems, decompose, dissect: every positional argument is a file, `names` stays empty
+    bool motif_less = false;                      // periods, repeats, satellites, refine, tandems, decompose, dissect, resolve: every positional argument is a file, `names` stays empty
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
@@ -283,6 +296,7 @@ int tandems_main(int argc, char **argv);
 int trace_main(int argc, char **argv);
 int decompose_main(int argc, char **argv);
 int dissect_main(int argc, char **argv);
+int resolve_main(int argc, char **argv);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement

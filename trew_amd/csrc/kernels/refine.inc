@@ -162,28 +162,18 @@ __device__ __forceinline__ void refine_pass(const ReadRef &rd, u32 lo_pos, u32 h
     }
 }
 
-// The refined record of one piece (DESIGN 4.7f, all six steps, over the bases [pc.lo, pc.hi) taken as a read of their own; nothing
-// outside the piece is seen): rec[0 .. 15] = the sixteen words of trew_hip_refined, start and end in read coordinates.  False
-// without a periods record (step 1), rec all zero; otherwise r_start and r_end hold the periods tract of step 1, in read
-// coordinates as well (kernels/tandems.inc splits a weak piece there).  Wave-uniform.  h: the wave's bins.
-__device__ __forceinline__ bool refine_piece(const ReadRef &rd, Piece pc, u32 kmin, u32 kmax, int P, u32 min_score, u32 *h, u32 (&rec)[16], u32 &r_start,
-                                             u32 &r_end) {
+// Steps 2 to 6 of DESIGN 4.7f for the period k of the piece pc and its periods score (> 0): the segment of k and its consensus,
+// the seed, align, vote, re-vote, final.  rec[0 .. 15] = the sixteen words of trew_hip_refined with scored_period = k, start and
+// end in read coordinates; r_start and r_end the periods tract of k, in read coordinates as well.  What refine_piece does with the
+// one period of its step 1 and resolve_wave_kernel (kernels/resolve.inc) with each of its candidates.  skip(S): asked once, with
+// the primitive seed in the lanes (base j in the lanes with (lane & 31) = j < seed_period, 8 in the others), in front of the three
+// passes; wave-uniform; true: the passes walk no base (their range is empty: a branch around them cost resolve_wave_kernel 22
+// VGPRs and a wave per SIMD), rec is of no use and the result is false.  Wave-uniform.  h: the wave's bins, all zero on entry and
+// on exit.
+template <class Skip>
+__device__ __forceinline__ bool refine_at(const ReadRef &rd, Piece pc, u32 k, u32 score, int P, u32 *h, u32 (&rec)[16], u32 &r_start, u32 &r_end, Skip skip) {
     const u32 lane = lane_id();
     const u32 j = lane & 31u;
-    // 1. periods: the scored k and its segment
-    u32 score = 0, k = 0;
-    for (u32 kk = kmin; kk <= kmax && kk < pc.hi - pc.lo; kk++) {
-        const u32 sc = period_score(rd, pc, kk, P);
-        if (sc > score) {  // strictly: the smallest k keeps a tie
-            score = sc;
-            k = kk;
-        }
-    }
-    if (k == 0u || score < min_score) {  // wave-uniform: a zero record
-#pragma unroll
-        for (int i = 0; i < 16; i++) rec[i] = 0;
-        return false;
-    }
     u32 b, e;
     period_locate(rd, pc, k, P, score, b, e);
     const u32 start = b, end = e + k;
@@ -206,11 +196,13 @@ __device__ __forceinline__ bool refine_piece(const ReadRef &rd, Piece pc, u32 km
     }
     const u32 ks = refine_root(s0, k);
     const u32 S = j < ks ? lane_read(s0, j << 2) : 8u;  // both halves alike
+    const bool skipped = skip(S);                 // wave-uniform
+    const u32 p_hi = skipped ? pc.lo : pc.hi;    // skipped: the passes walk no base
     u32 cnt[4] = {0, 0, 0, 0};
     // 3. align against the seed
     AlignCell a1;
     u32 a1_end;
-    refine_pass<false>(rd, pc.lo, pc.hi, S, ks, P, a1, a1_end, cnt);
+    refine_pass<false>(rd, pc.lo, p_hi, S, ks, P, a1, a1_end, cnt);
     const u32 a1_start = rfl(a1.start);  // the best cell is in every lane; 0 and 0 without one
     a1_end = rfl(a1_end);
     // 4. vote over the tract alone
@@ -238,7 +230,7 @@ __device__ __forceinline__ bool refine_piece(const ReadRef &rd, Piece pc, u32 km
     if (changed) {  // wave-uniform
         ku = refine_root(U0, ks);
         U = j < ku ? U0 : 8u;
-        refine_pass<false>(rd, pc.lo, pc.hi, U, ku, P, a2, a2_end, cnt);
+        refine_pass<false>(rd, pc.lo, p_hi, U, ku, P, a2, a2_end, cnt);
         if (rfl(a2.score) < rfl(a1.score)) {
             a2 = a1;
             a2_end = a1_end;
@@ -261,7 +253,30 @@ __device__ __forceinline__ bool refine_piece(const ReadRef &rd, Piece pc, u32 km
     rec[11] = 0;
     refine_pack(U, ku, rec[12], rec[13]);
     refine_pack(S, ks, rec[14], rec[15]);
-    return true;
+    return !skipped;
+}
+
+// The refined record of one piece (DESIGN 4.7f, all six steps, over the bases [pc.lo, pc.hi) taken as a read of their own; nothing
+// outside the piece is seen): rec[0 .. 15] = the sixteen words of trew_hip_refined, start and end in read coordinates.  False
+// without a periods record (step 1), rec all zero; otherwise r_start and r_end hold the periods tract of step 1, in read
+// coordinates as well (kernels/tandems.inc splits a weak piece there).  Wave-uniform.  h: the wave's bins.
+__device__ __forceinline__ bool refine_piece(const ReadRef &rd, Piece pc, u32 kmin, u32 kmax, int P, u32 min_score, u32 *h, u32 (&rec)[16], u32 &r_start,
+                                             u32 &r_end) {
+    // 1. periods: the scored k
+    u32 score = 0, k = 0;
+    for (u32 kk = kmin; kk <= kmax && kk < pc.hi - pc.lo; kk++) {
+        const u32 sc = period_score(rd, pc, kk, P);
+        if (sc > score) {  // strictly: the smallest k keeps a tie
+            score = sc;
+            k = kk;
+        }
+    }
+    if (k == 0u || score < min_score) {  // wave-uniform: a zero record
+#pragma unroll
+        for (int i = 0; i < 16; i++) rec[i] = 0;
+        return false;
+    }
+    return refine_at(rd, pc, k, score, P, h, rec, r_start, r_end, [](u32) { return false; });
 }
 
 __global__ void __launch_bounds__(256) refine_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, u32 *__restrict__ out) {

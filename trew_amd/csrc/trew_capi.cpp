@@ -25,11 +25,11 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve"};
 // whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
-const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false};
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false};
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -42,7 +42,7 @@ struct MeasureState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call, set in one place each: queue_records (the fixed-size records), queue_log (the append logs)
-    u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods, refine: n_reads
+    u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods, refine, resolve: n_reads
     u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites, tandems: their max_records
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites, tandems: n_reads
     int n_motifs = 0;  // variants
@@ -1283,8 +1283,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect
-// The fourteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve
+// The fifteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
 // fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
@@ -1379,6 +1379,11 @@ extern "C" int trew_dissect_host(const uint32_t *words, const uint32_t *offsets,
                                     n_records, n_items, n_rows, counts));
 }
 
+extern "C" int trew_resolve_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                 int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_resolved *out) {
+    return host_status(resolve_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, candidates, out));
+}
+
 // the pattern words of one motif (AnnotMotifDev, trew_common.hpp)
 static void fill_motif(const trew_hip_motif &m, AnnotMotifDev *d) {
     memset(d, 0, sizeof(*d));
@@ -1463,7 +1468,7 @@ static int timed_launch(trew_hip_ctx *ctx, Slot &s, MeasureState &st, Launch lau
 }
 
 // The queue call of the measures with one fixed-size record per (read, motif) or per read (annotate, tracts, align, periods,
-// refine, variants; per_read: n_motifs or 1): measure_begin, room for the records, `setup` (what else the measure keeps on the
+// refine, resolve, variants; per_read: n_motifs or 1): measure_begin, room for the records, `setup` (what else the measure keeps on the
 // device: the histograms of variants), then the numbers of the call, all in one place, and `launch` between the events unless
 // the batch is empty.  Every call starts from zero, and one that fails on the way can simply be repeated.
 template <class Own, class Setup, class Launch>
@@ -1557,7 +1562,7 @@ static int fetch_end(trew_hip_ctx *ctx, const MeasureState &st, float *ms_kernel
     return 0;
 }
 
-// the results call of annotate, tracts, align, periods and refine, whole
+// the results call of annotate, tracts, align, periods, refine and resolve, whole
 static int results_records(trew_hip_ctx *ctx, int slot, Measure which, void *out, u64 cap, size_t rec_bytes, uint64_t *n, float *ms_kernel) {
     Slot *sp = nullptr;
     if (int rc = fetch_begin(ctx, slot, which, nullptr, &sp)) return rc;
@@ -1870,6 +1875,22 @@ extern "C" int trew_hip_refine(trew_hip_ctx *ctx, const trew_hip_batch *batch, i
 
 extern "C" int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_refined *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
     return results_records(ctx, slot, kRefine, out, cap, sizeof(trew_hip_refined), n, ms_kernel);
+}
+
+// ---------------------------------------------------------------- refine's unit with the period chosen by alignment
+extern "C" int trew_hip_resolve(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                                int candidates) {
+    auto own = [&]() -> const char * { return resolve_error(min_period, max_period, penalty, min_score, candidates); };
+    return queue_records(ctx, batch, slot, nullptr, 0, kResolve, 1, sizeof(trew_hip_resolved), own, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_resolve(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, candidates,
+                                                        (trew_hip_resolved *) st.records.p));
+                             return 0;
+                         });
+}
+
+extern "C" int trew_hip_resolve_results(trew_hip_ctx *ctx, int slot, trew_hip_resolved *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    return results_records(ctx, slot, kResolve, out, cap, sizeof(trew_hip_resolved), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- ordered unit chain per read

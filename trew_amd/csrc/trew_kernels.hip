@@ -52,6 +52,7 @@
 //   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
 //   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
 //   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: tandems.inc's piece loop, written out once more, with decompose.inc's anchor, rows and walk for every piece that gives a record)
+//   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, refine.inc's refine_at per candidate in a runtime loop, the record with the largest final score)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -99,6 +100,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/trace.inc"
 #include "kernels/decompose.inc"
 #include "kernels/dissect.inc"
+#include "kernels/resolve.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -468,6 +470,11 @@ hipError_t launch_decompose(hipStream_t st, u32 n_cu, const DevBatch &B, int min
 hipError_t launch_dissect(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &rl,
                           const TraceLog &lg, u32 *d_counts) {
     return launch_wave_per_read(st, n_cu, B, dissect_wave_kernel, min_period, max_period, penalty, min_score, rl, lg, d_counts);
+}
+
+hipError_t launch_resolve(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                          trew_hip_resolved *d_out) {
+    return launch_wave_per_read(st, n_cu, B, resolve_wave_kernel, min_period, max_period, penalty, min_score, (u32) candidates, (u32 *) d_out);
 }
 
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words) {

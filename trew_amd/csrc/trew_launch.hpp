@@ -83,6 +83,9 @@ hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_p
 // of 18 u32, `lg` items and rows of 32 bytes; all three counters are zero when it starts; d_counts: (tracts, items) per read
 hipError_t launch_dissect(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &rl,
                           const TraceLog &lg, u32 *d_counts);
+// trew_hip_resolve: the wave-per-read kernel of kernels/resolve.inc on the grid of launch_tracts; no motifs; 1 <= candidates <= 4
+hipError_t launch_resolve(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                          trew_hip_resolved *d_out);
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);
 hipError_t launch_synth_long(hipStream_t st, u64 seed, u64 first, u64 n, const u32 *d_qtable, const u32 *d_offsets, u32 *d_words);
 hipError_t launch_synth_pair(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words);

@@ -443,6 +443,44 @@ const char *satellites_error(int min_period, int max_period, int penalty, u32 mi
     return penalty_score_error(penalty, min_score);
 }
 
+// The best-scoring segment of eq_k of a read of n bases for one k < n: its score, 0 without one, and [b, e), the
+// smallest e and then the largest b.  The per-period entry of piece_record, which trew_resolve_host asks for every k as well.
+static long long period_segment(const unsigned char *base, u32 n, u32 k, int penalty, u32 &b, u32 &e) {
+    long long S = 0, low = 0, score = 0;  // S(e), the smallest S(b) over b <= e, the largest S(e) - low so far
+    u32 b_lo = 0;                         // the latest b at which S is low
+    b = e = 0;
+    for (u32 i = 0; i + k < n; i++) {
+        const bool eq = base[i] < 4 && base[i] == base[i + k];
+        S += eq ? 1 : -(long long) penalty;
+        if (S <= low) {  // the latest b keeps a tie: the shorter segment
+            low = S;
+            b_lo = i + 1;
+        }
+        if (S - low > score) {  // strictly: the earliest e keeps a tie
+            score = S - low;
+            e = i + 1;
+            b = b_lo;
+        }
+    }
+    return score;
+}
+
+// the unreduced consensus u[0 .. k - 1] of [start, end) at period k, the smallest code on a tie; returns the sum of its counts
+template <u32 kMaxK>
+static u32 period_consensus_host(const unsigned char *base, u32 start, u32 end, u32 k, u32 *u) {
+    u32 cnt[kMaxK][4] = {};
+    for (u32 p = start; p < end; p++)
+        if (base[p] < 4) cnt[(p - start) % k][base[p]]++;
+    u32 support = 0;
+    for (u32 j = 0; j < k; j++) {
+        u[j] = 0;
+        for (u32 c = 1; c < 4; c++)
+            if (cnt[j][c] > cnt[j][u[j]]) u[j] = c;  // strictly: the smallest code keeps a tie
+        support += cnt[j][u[j]];
+    }
+    return support;
+}
+
 // The record of the piece [lo, hi) of a read, its bases taken as a read of their own: nothing outside the piece is seen, start
 // and end are in read coordinates.  base: per base of the read its code, or 4 with its nmask bit set.  All zero without a record.
 // What period_piece and satellite_piece share: everything but the packing of the unit.  u: the codes of the primitive unit,
@@ -455,21 +493,8 @@ static bool piece_record(const unsigned char *base, u32 lo, u32 hi, int min_peri
     long long best = 0;
     u32 ks = 0, bs = 0, es = 0;
     for (u32 k = (u32) min_period; k <= (u32) max_period && k < n; k++) {
-        long long S = 0, low = 0, score = 0;  // S(e), the smallest S(b) over b <= e, the largest S(e) - low so far
-        u32 b_lo = 0, b = 0, e = 0;           // the latest b at which S is low; the segment of `score`
-        for (u32 i = 0; i + k < n; i++) {
-            const bool eq = base[i] < 4 && base[i] == base[i + k];
-            S += eq ? 1 : -(long long) penalty;
-            if (S <= low) {  // the latest b keeps a tie: the shorter segment
-                low = S;
-                b_lo = i + 1;
-            }
-            if (S - low > score) {  // strictly: the earliest e keeps a tie
-                score = S - low;
-                e = i + 1;
-                b = b_lo;
-            }
-        }
+        u32 b = 0, e = 0;
+        const long long score = period_segment(base, n, k, penalty, b, e);
         if (score > best) {
             best = score;
             ks = k;
@@ -482,15 +507,7 @@ static bool piece_record(const unsigned char *base, u32 lo, u32 hi, int min_peri
     o.score = (u32) best;
     o.matches = (u32) (((u64) best + (u64) penalty * (u64) (es - bs)) / (u64) (1 + penalty));
     const u32 start = bs, end = es + ks;  // in the piece
-    u32 cnt[kMaxK][4] = {};
-    for (u32 p = start; p < end; p++)
-        if (base[p] < 4) cnt[(p - start) % ks][base[p]]++;
-    for (u32 j = 0; j < ks; j++) {
-        u[j] = 0;
-        for (u32 c = 1; c < 4; c++)
-            if (cnt[j][c] > cnt[j][u[j]]) u[j] = c;  // strictly: the smallest code keeps a tie
-        o.support += cnt[j][u[j]];
-    }
+    o.support += period_consensus_host<kMaxK>(base, start, end, ks, u);
     for (u32 d = 1; d <= ks; d++) {
         if (ks % d) continue;
         bool periodic = true;
@@ -760,6 +777,8 @@ static u64 pack_unit(const u32 *u, u32 k) {
     return w;
 }
 
+static void refine_at_period(const unsigned char *base, u32 n, u32 k, u32 b, u32 e, const u32 *cons, int penalty, trew_hip_refined &o);
+
 // the record of one read, step by step from the definition (trew_hip_refined, include/trew_hip.h); R: the periods record of step 1
 // (scored_period 0 without one), for trew_hip_tandems' weak pieces
 static void refine_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined &o,
@@ -769,7 +788,13 @@ static void refine_read_host(const unsigned char *base, u32 n, int min_period, i
     memset(&R, 0, sizeof(R));
     u32 cons[32];
     if (!piece_record<32>(base, 0, n, min_period, max_period, penalty, min_score, R, cons)) return;
-    const u32 k = R.scored_period, b = R.start, e = R.end - k;
+    refine_at_period(base, n, R.scored_period, R.start, R.end - R.scored_period, cons, penalty, o);
+}
+
+// steps 2 to 6 of the definition for the period k with the segment [b, e) of its eq_k and the unreduced consensus of [b, e + k) at
+// k: what refine_read_host does with the one period of step 1 and trew_resolve_host with each of its candidates
+static void refine_at_period(const unsigned char *base, u32 n, u32 k, u32 b, u32 e, const u32 *cons, int penalty, trew_hip_refined &o) {
+    memset(&o, 0, sizeof(o));
     // 2. seed: the longest run of eq_k in [b, e), the first of the longest
     u32 rs = b, longest = 0, run = 0;
     for (u32 i = b; i < e; i++) {
@@ -780,7 +805,7 @@ static void refine_read_host(const unsigned char *base, u32 n, int min_period, i
         }
     }
     u32 S[32], U[32];
-    for (u32 j = 0; j < k; j++) S[j] = base[rs + j] < 4 ? base[rs + j] : cons[(rs + j - R.start) % k];
+    for (u32 j = 0; j < k; j++) S[j] = base[rs + j] < 4 ? base[rs + j] : cons[(rs + j - b) % k];
     const u32 ks = primitive_root(S, k);
     // 3. align against the seed
     u32 a1[5], a2[5];
@@ -830,6 +855,65 @@ const char *refine_host(const u32 *words, const u32 *offsets, const u32 *lengths
         unpack_bases(words + offsets[r], lengths[r], base);
         trew_hip_period R;
         refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, out[r], R);
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- refine's unit with the period chosen by alignment
+const char *resolve_error(int min_period, int max_period, int penalty, u32 min_score, int candidates) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    static_assert(TREW_RESOLVE_MAX_CANDIDATES == 4, "the text below");
+    return candidates < 1 || candidates > TREW_RESOLVE_MAX_CANDIDATES ? "resolve: 1 <= candidates <= 4 is required" : nullptr;
+}
+
+// the record of one read, step by step from the definition (trew_hip_resolved, include/trew_hip.h)
+static void resolve_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                              trew_hip_resolved &o) {
+    memset(&o, 0, sizeof(o));
+    // 1. scores: the first C of the order (score descending, k ascending) that reach min_score
+    struct Candidate {
+        long long score;
+        u32 k, b, e;
+    };
+    Candidate cand[TREW_RESOLVE_MAX_CANDIDATES];
+    u32 m = 0;
+    for (u32 k = (u32) min_period; k <= (u32) max_period && k < n; k++) {
+        Candidate x{0, k, 0, 0};
+        x.score = period_segment(base, n, k, penalty, x.b, x.e);
+        if (x.score < (long long) min_score) continue;
+        u32 at = m;  // k ascends: strictly greater displaces, so the smaller k keeps a tie
+        while (at > 0 && cand[at - 1].score < x.score) at--;
+        if (at >= (u32) candidates) continue;
+        if (m < (u32) candidates) m++;
+        for (u32 i = m - 1; i > at; i--) cand[i] = cand[i - 1];
+        cand[at] = x;
+    }
+    // 2. per candidate: steps 2 to 6 of refine with its own segment; 3. the largest score, then the smaller period, then the smaller c
+    trew_hip_refined win{};
+    for (u32 c = 0; c < m; c++) {
+        u32 cons[32];
+        period_consensus_host<32>(base, cand[c].b, cand[c].e + cand[c].k, cand[c].k, cons);
+        trew_hip_refined x;
+        refine_at_period(base, n, cand[c].k, cand[c].b, cand[c].e, cons, penalty, x);
+        if (c == 0) o.first_period = x.period, o.first_score = x.score;
+        if (c == 0 || x.score > win.score || (x.score == win.score && x.period < win.period)) {
+            win = x;
+            o.rank = c;
+        }
+    }
+    if (m == 0) return;
+    memcpy(&o, &win, sizeof(win));  // the first sixteen words are trew_hip_refined's
+    o.candidates = m;
+}
+
+const char *resolve_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, int candidates, trew_hip_resolved *out) {
+    if (const char *e = resolve_error(min_period, max_period, penalty, min_score, candidates)) return e;
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_resolve_host: null argument";
+    std::vector<unsigned char> base;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        resolve_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, candidates, out[r]);
     }
     return nullptr;
 }

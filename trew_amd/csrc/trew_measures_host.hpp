@@ -54,6 +54,11 @@ const char *align_host(const uint32_t *words, const uint32_t *offsets, const uin
 // de novo repeats under indels: seed, wraparound alignment, re-vote (include/trew_hip.h); the checks of periods_host
 const char *refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                         int penalty, uint32_t min_score, trew_hip_refined *out);
+// refine's unit with the period chosen by alignment: refine_host's steps 2 to 6 for the best-scoring periods, the best record kept;
+// resolve_error is the argument check the device entry point shares (periods_error, then the candidates)
+const char *resolve_error(int min_period, int max_period, int penalty, uint32_t min_score, int candidates);
+const char *resolve_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                         int penalty, uint32_t min_score, int candidates, trew_hip_resolved *out);
 // de novo repeats under indels, every tract of a read: repeats_host's recursion with the refine definition on a piece
 const char *tandems_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                          int penalty, uint32_t min_score, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts);
