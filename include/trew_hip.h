@@ -37,8 +37,9 @@ extern "C" {
  * trew_align_host), the refinement entry points (trew_hip_refine, trew_hip_refine_results, trew_refine_host), the tandem
  * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host), the traceback entry points (trew_hip_trace,
  * trew_hip_trace_results, trew_trace_host), the decomposition entry points (trew_hip_decompose, trew_hip_decompose_results,
- * trew_decompose_host), the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host) and the
- * resolution entry points (trew_hip_resolve, trew_hip_resolve_results, trew_resolve_host): they
+ * trew_decompose_host), the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host), the
+ * resolution entry points (trew_hip_resolve, trew_hip_resolve_results, trew_resolve_host) and the resolved forms of three
+ * of them (trew_hip_tandems_resolved, trew_hip_decompose_resolved, trew_hip_dissect_resolved and their _host functions): they
  * are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
@@ -666,7 +667,8 @@ int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32
  * deletions follow as for trew_hip_alignment with k = period.  Limits: one tract per read, the best one; periods <= 32; linear
  * gap cost; a wrong scored_period (a multiple or a neighbour of the true period) is not repaired; the vote is a forward
  * decode, not a traceback (an indel misplaces the few bases until the penalised path overtakes); one refinement round.
- * trew_hip_resolve, further below, lets the alignment choose between the few best-scoring periods of step 1.
+ * trew_hip_resolve, further below, lets the alignment choose between the few best-scoring periods of step 1, and
+ * trew_hip_tandems_resolved, trew_hip_decompose_resolved and trew_hip_dissect_resolved do so for every piece.
  * Also additive: TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
     uint32_t period, seed_period, scored_period, changed;
@@ -707,7 +709,8 @@ int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint3
  * repeats with flanks the (period, unit) pairs are those of trew_hip_repeats, and start, end and score those of
  * trew_hip_align against that unit.  NOT a consequence, unlike trew_hip_repeats: "none scores above the first" -- alignment
  * scores are not ordered by the periods score that picks the tract first.
- * Limits: periods <= 32; linear gap cost; a wrong scored_period is not repaired; a weak piece is dropped, with whatever
+ * Limits: periods <= 32; linear gap cost; a wrong scored_period is not repaired (trew_hip_tandems_resolved, further below, takes
+ * trew_hip_resolve's choice of period for every piece); a weak piece is dropped, with whatever
  * shorter tract a unit of its own would have aligned to inside it; the cost is that of trew_hip_refine per piece.  Also
  * additive: TREW_HIP_ABI_VERSION stays 4. */
 typedef struct {
@@ -809,7 +812,8 @@ int trew_trace_host(const uint32_t *words, const uint32_t *offsets, const uint32
  * and P; only the first item has phase != 0; for k >= 3 the items equal the forward-strand items of trew_hip_trace with motif
  * M; a perfect repeat begun at each of its k rotations gives the same M, and its first item's phase follows the rotation; a
  * read's items do not depend on the rest of the batch.  Limits: those of trew_hip_refine (one tract per read, periods <= 32,
- * linear gaps, a wrong scored_period not repaired); the items are in read orientation and cut at M, and a read of the other
+ * linear gaps, a wrong scored_period not repaired -- trew_hip_decompose_resolved, further below, takes trew_hip_resolve's record);
+ * the items are in read orientation and cut at M, and a read of the other
  * strand is cut at the smallest rotation of the reverse complement, so items compare directly only between reads of one
  * strand.  Also additive: TREW_HIP_ABI_VERSION stays 4.
  *
@@ -852,7 +856,8 @@ int trew_decompose_host(const uint32_t *words, const uint32_t *offsets, const ui
  * reaches min_score; the items of a tract tile [start, end) of its record without a gap; their bases, consumed and errors sum
  * to the record's; only the first item of a tract can have phase != 0; a read's output does not depend on the rest of the batch;
  * the rows claimed are the sum of end - start over all records.  Limits: those of trew_hip_tandems and trew_hip_decompose --
- * periods <= 32; linear gaps; a wrong scored_period is not repaired; a weak piece is dropped; signatures compare directly
+ * periods <= 32; linear gaps; a wrong scored_period is not repaired (trew_hip_dissect_resolved, further below, takes
+ * trew_hip_resolve's choice for every piece); a weak piece is dropped; signatures compare directly
  * only within one strand value (a tract of the other strand is cut at the smallest rotation of the reverse complement).  Also
  * additive: TREW_HIP_ABI_VERSION stays 4.
  *
@@ -927,6 +932,52 @@ int trew_hip_resolve_results(trew_hip_ctx *ctx, int slot, trew_hip_resolved *out
 /* The same records on the host, step by step from the definition, over packed planes. */
 int trew_resolve_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                       int penalty, uint32_t min_score, int candidates, trew_hip_resolved *out);
+
+/* ---- tandems, decompose and dissect with resolve's period choice: the winner of trew_hip_resolve per piece ----
+ * (trew_hip_tandems, trew_hip_decompose and trew_hip_dissect work with trew_hip_refine's record of a piece, whose period is the
+ * one with the largest fixed-phase score; for long units that is often a multiple or a neighbour of the true one, and the piece is
+ * cut into copies of the wrong unit.  Here every piece gets the record trew_hip_resolve would give it.)
+ * Integer-exact (tests/resolved_ref.py is the reference).  The arguments are those of the plain entry point, with
+ * the same checks and error texts, then candidates = C as for trew_hip_resolve, with its check and text.
+ * resolved(piece, C), for a piece [lo, hi) of a read, is what steps 1 to 3 of trew_hip_resolve give the bases lo .. hi - 1 taken as
+ * a read of their own: the number of candidates m; the winner's sixteen words W in trew_hip_refined's layout, start and end
+ * shifted by lo, scored_period the winner's k_c; and the trew_hip_periods tract T0 of candidate 0, shifted likewise, which is the
+ * tract trew_hip_tandems splits a weak piece around.  m = 0 exactly when the piece has no trew_hip_refine record.
+ * trew_hip_tandems_resolved.  tandems(piece): m = 0, nothing; W.score >= min_score, the record W, then tandems([lo, W.start)) and
+ *   tandems([W.end, hi)); otherwise (a weak piece) no record, then tandems([lo, T0.start)) and tandems([T0.end, hi)).  Depths, the
+ *   sort order, counts, the log and the overflow protocol are trew_hip_tandems'.  W.score >= R_0.score, so a piece that gives
+ *   trew_hip_tandems a record gives one here.  The candidates of a piece are periods of the piece, each with its own segment, so
+ *   the winner can be another tract than candidate 0's; what is left of the piece is found in the children.
+ * trew_hip_decompose_resolved.  trew_hip_decompose with resolved([0, n), C)'s W in the place of trew_hip_refine's record.
+ * trew_hip_dissect_resolved.  trew_hip_dissect over the pieces and records of trew_hip_tandems_resolved.
+ * In the last two the anchor, the table restarted at W.start, the end phase, the items, the workspace and the three counters are
+ * the plain entry point's: (score, start, end, consumed, matches) of W is the alignment of the piece against W.unit.
+ * Records keep their types (trew_hip_tandem, trew_hip_refined with reserved = the anchor, trew_hip_trace_item).  Consequences:
+ * with C = 1 every result equals the plain entry point's word for word; a read has a depth-0 record exactly when
+ * trew_hip_resolve's score reaches min_score, and it is that record.  Limits: candidates, rank, first_period and first_score of
+ * trew_hip_resolved are NOT carried by these records (run trew_hip_resolve for them); a tract found at depth 0 here can be one
+ * that trew_hip_tandems finds deeper, so depths differ between the two; up to C times the alignment passes per piece; the limits
+ * of trew_hip_resolve and of the plain entry points apply.  Also additive: TREW_HIP_ABI_VERSION stays 4.
+ * Each call queues on the state of its plain sibling: the results are fetched with trew_hip_tandems_results,
+ * trew_hip_decompose_results and trew_hip_dissect_results, the "repeat once with the exact numbers" protocol included, and a
+ * plain and a resolved call on one slot replace each other's results. */
+int trew_hip_tandems_resolved(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                              uint32_t min_score, int candidates, uint64_t max_records);
+int trew_hip_decompose_resolved(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                                uint32_t min_score, int candidates, uint64_t max_items, uint64_t max_rows);
+int trew_hip_dissect_resolved(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                              uint32_t min_score, int candidates, uint64_t max_records, uint64_t max_items, uint64_t max_rows);
+/* The same on the host, from the definition, over packed planes; arguments as the plain host functions', candidates after min_score. */
+int trew_tandems_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                               int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_tandem *out, uint64_t cap, uint64_t *n,
+                               uint32_t *counts);
+int trew_decompose_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                 int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_trace_item *items, uint64_t cap,
+                                 uint64_t *n_items, uint32_t *counts, trew_hip_refined *records);
+int trew_dissect_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                               int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_tandem *records, uint64_t rec_cap,
+                               trew_hip_trace_item *items, uint64_t item_cap, uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows,
+                               uint32_t *counts);
 
 /* ---- host-side packing: the codes[] lookup of kmer.cpp:14-31 applied once per base ---- */
 /* words needed for a read of n bases */

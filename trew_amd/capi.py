@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "trew_hip_decompose", "trew_hip_decompose_results", "trew_decompose_host",
     "trew_hip_dissect", "trew_hip_dissect_results", "trew_dissect_host",
     "trew_hip_resolve", "trew_hip_resolve_results", "trew_resolve_host",
+    "trew_hip_tandems_resolved", "trew_tandems_resolved_host", "trew_hip_decompose_resolved", "trew_decompose_resolved_host",
+    "trew_hip_dissect_resolved", "trew_dissect_resolved_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain", "dead_entries")
@@ -323,6 +325,15 @@ def load():
     lib.trew_hip_tandems.argtypes = lib.trew_hip_repeats.argtypes
     lib.trew_hip_tandems_results.argtypes = lib.trew_hip_repeats_results.argtypes
     lib.trew_tandems_host.argtypes = lib.trew_repeats_host.argtypes
+    # the resolved forms: `candidates` behind min_score, the rest as the plain entry point's
+
+    def with_candidates(argtypes):
+        at = argtypes.index(C.c_uint32) + 1
+        return argtypes[:at] + [i32] + argtypes[at:]
+
+    for name in ("tandems", "decompose", "dissect"):
+        getattr(lib, "trew_hip_%s_resolved" % name).argtypes = with_candidates(getattr(lib, "trew_hip_%s" % name).argtypes)
+        getattr(lib, "trew_%s_resolved_host" % name).argtypes = with_candidates(getattr(lib, "trew_%s_host" % name).argtypes)
     lib.trew_pack_words.argtypes = [u64]
     lib.trew_pack_words.restype = u64
     lib.trew_pack_reads.argtypes = [C.c_char_p, vp, vp, u64, vp, u64, vp, vp]
@@ -569,42 +580,53 @@ def trace_host(reads_or_packed, motifs, penalty=3, min_score=24, cap=None):
     return out, counts[:, :nm], records[:, :nm], found
 
 
-def decompose_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
+def _resolved_call(lib, name, candidates):
+    """(entry point, the arguments that follow min_score): `name` itself with candidates = 1, its _resolved form otherwise"""
+    if int(candidates) == 1:
+        return getattr(lib, name), ()
+    stem, host = (name[:-5], "_host") if name.endswith("_host") else (name, "")
+    return getattr(lib, stem + "_resolved" + host), (int(candidates),)
+
+
+def decompose_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None, candidates=1):
     """trew_decompose_host: refine_host's record of every read, its unit turned to its smallest rotation (the record's
     `reserved` word is the anchor, the offset of that rotation in the unit) and the traceback of the read's forward strand
     against it, computed on the host with the full table.  reads_or_packed as for annotate_host.  Returns (TRACE_DTYPE items
     sorted by (read, start), motif = strand = 0, counts of shape (n_reads,), REFINE_DTYPE records of shape (n_reads,), n_items);
-    with `cap` at most that many items."""
+    with `cap` at most that many items.  candidates > 1: trew_decompose_resolved_host, resolve_host's record in refine_host's place."""
     lib = load()
     words, offsets, lengths = _packed(reads_or_packed)
     counts = np.zeros(len(offsets), dtype=np.uint32)
     records = np.zeros(len(offsets), dtype=REFINE_DTYPE)
+    f, cand = _resolved_call(lib, "trew_decompose_host", candidates)
 
     def call(ptr, room, n):
-        if lib.trew_decompose_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
-                                   int(penalty), int(min_score), ptr, room, C.byref(n), counts.ctypes.data, records.ctypes.data) != 0:
-            _host_fail("trew_decompose_host")
+        if f(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+             int(penalty), int(min_score), *cand, ptr, room, C.byref(n), counts.ctypes.data, records.ctypes.data) != 0:
+            _host_fail(f.__name__)
 
     out, found = _sized_call(call, TRACE_DTYPE, cap)
     return out, counts, records, found
 
 
-def dissect_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, rec_cap=None, item_cap=None):
+def dissect_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, rec_cap=None, item_cap=None, candidates=1):
     """trew_dissect_host: tandems_host's records of every read, each with its unit's anchor in `reserved`, and for every record
     decompose_host's items of its piece taken as a read of its own, in read coordinates, computed on the host.  reads_or_packed
     as for annotate_host.  Returns (TANDEM_DTYPE records sorted by (read, start), TRACE_DTYPE items sorted by (read, start) with
     motif = the index of the item's tract among its read's records and strand = 0, counts of shape (n_reads, 2) = (tracts,
-    items), n_records, n_items, n_rows); with rec_cap / item_cap at most that many records / items."""
+    items), n_records, n_items, n_rows); with rec_cap / item_cap at most that many records / items.  candidates > 1:
+    trew_dissect_resolved_host, resolve_host's record of every piece in refine_host's place."""
     lib = load()
     words, offsets, lengths = _packed(reads_or_packed)
     counts = np.zeros((len(offsets), 2), dtype=np.uint32)
     nr, ni, nw = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    f, cand = _resolved_call(lib, "trew_dissect_host", candidates)
 
     def call(recs, items):
-        if lib.trew_dissect_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
-                                 int(penalty), int(min_score), recs.ctypes.data if len(recs) else None, len(recs),
-                                 items.ctypes.data if len(items) else None, len(items), C.byref(nr), C.byref(ni), C.byref(nw), counts.ctypes.data) != 0:
-            _host_fail("trew_dissect_host")
+        if f(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+             int(penalty), int(min_score), *cand, recs.ctypes.data if len(recs) else None, len(recs),
+             items.ctypes.data if len(items) else None, len(items), C.byref(nr), C.byref(ni), C.byref(nw), counts.ctypes.data) != 0:
+            _host_fail(f.__name__)
 
     recs = np.zeros(0 if rec_cap is None else int(rec_cap), dtype=TANDEM_DTYPE)
     items = np.zeros(0 if item_cap is None else int(item_cap), dtype=TRACE_DTYPE)
@@ -653,16 +675,16 @@ def trace_signature(items, read, k):
     return units, edited, " ".join(tokens)
 
 
-def _tracts_host(name, dtype, reads_or_packed, min_period, max_period, penalty, min_score, cap):
-    """trew_repeats_host, trew_satellites_host and trew_tandems_host, which differ in the record only"""
-    f = getattr(load(), name)
+def _tracts_host(name, dtype, reads_or_packed, min_period, max_period, penalty, min_score, cap, candidates=1):
+    """trew_repeats_host, trew_satellites_host and trew_tandems_host, which differ in the record only (candidates: tandems alone)"""
+    f, cand = _resolved_call(load(), name, candidates)
     words, offsets, lengths = _packed(reads_or_packed)
     counts = np.zeros(len(offsets), dtype=np.uint32)
 
     def call(ptr, room, n):
         if f(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period), int(penalty), int(min_score),
-             ptr, room, C.byref(n), counts.ctypes.data) != 0:
-            _host_fail(name)
+             *cand, ptr, room, C.byref(n), counts.ctypes.data) != 0:
+            _host_fail(f.__name__)
 
     out, found = _sized_call(call, dtype, cap)
     return out, counts, found
@@ -702,12 +724,12 @@ def resolve_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sc
     return out
 
 
-def tandems_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None):
+def tandems_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, cap=None, candidates=1):
     """trew_tandems_host: every de novo repeat tract of every read under indels computed on the host, piece by piece from the
     definition (the refined record of a piece, then what lies in front of its tract and behind it).  reads_or_packed as for
     annotate_host.  Returns (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,), found); with `cap` at most
-    that many records."""
-    return _tracts_host("trew_tandems_host", TANDEM_DTYPE, reads_or_packed, min_period, max_period, penalty, min_score, cap)
+    that many records.  candidates > 1: trew_tandems_resolved_host, resolve_host's record of every piece in refine_host's place."""
+    return _tracts_host("trew_tandems_host", TANDEM_DTYPE, reads_or_packed, min_period, max_period, penalty, min_score, cap, candidates)
 
 
 def refine_columns(record, penalty):
@@ -953,13 +975,13 @@ class TrewHip:
             self._chk(results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n), None, None), what)
         return (out, counts, found, ms.value) if want_ms else (out, counts, found)
 
-    def _queue_tracts(self, measure, batch, min_period, max_period, penalty, min_score, max_records, slot):
+    def _queue_tracts(self, measure, batch, min_period, max_period, penalty, min_score, max_records, slot, candidates=1):
         """the queue call of repeats, tandems and satellites; max_records: default the batch's read count, at least 1"""
         if max_records is None:
             max_records = max(int(batch.n_reads), 1)
         self._queue(measure, slot, batch, None, 1, shape=(int(max_records),))
-        what = "trew_hip_%s" % measure
-        self._chk(getattr(self.lib, what)(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score), int(max_records)), what)
+        f, cand = _resolved_call(self.lib, "trew_hip_%s" % measure, candidates)
+        self._chk(f(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score), *cand, int(max_records)), f.__name__)
 
     def annotate(self, batch, motifs, slot=0):
         """Queue the annotation of every read of `batch` against `motifs` (texts or Motif, at most 8) on the slot's stream."""
@@ -1117,13 +1139,15 @@ class TrewHip:
                       "trew_hip_trace_results")
         return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
 
-    def decompose(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_items=None, max_rows=None, slot=0):
+    def decompose(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_items=None, max_rows=None, slot=0, candidates=1):
         """Queue refine's unit of every read of `batch`, anchored at its smallest rotation, and the traceback of the read against
-        it on the slot's stream (no motifs).  max_items, max_rows: as for trace with one motif; a row has 32 bytes here."""
+        it on the slot's stream (no motifs).  max_items, max_rows: as for trace with one motif; a row has 32 bytes here.
+        candidates > 1: trew_hip_decompose_resolved, resolve's record in refine's place; the results call is the same."""
         max_items, max_rows = _trace_room(batch, 1, max_items, max_rows)
         self._queue("decompose", slot, batch, None, 1, shape=(int(max_items), int(max_rows)))
-        self._chk(self.lib.trew_hip_decompose(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
-                                              int(max_items), int(max_rows)), "trew_hip_decompose")
+        f, cand = _resolved_call(self.lib, "trew_hip_decompose", candidates)
+        self._chk(f(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score), *cand, int(max_items), int(max_rows)),
+                  f.__name__)
 
     def decompose_results(self, slot=0, want_ms=False):
         """Results of the slot's last decompose: (TRACE_DTYPE items sorted by (read, start), counts of shape (n_reads,),
@@ -1143,16 +1167,19 @@ class TrewHip:
                       "trew_hip_decompose_results")
         return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
 
-    def dissect(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, max_items=None, max_rows=None, slot=0):
+    def dissect(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, max_items=None, max_rows=None, slot=0,
+                candidates=1):
         """Queue every de novo repeat tract under indels of every read of `batch`, each with its unit anchored and the traceback
         of its piece against it, on the slot's stream (no motifs).  max_records: as for tandems; max_items, max_rows: as for
-        decompose."""
+        decompose.  candidates > 1: trew_hip_dissect_resolved, resolve's record of every piece in refine's place; the results
+        call is the same."""
         if max_records is None:
             max_records = max(int(batch.n_reads), 1)
         max_items, max_rows = _trace_room(batch, 1, max_items, max_rows)
         self._queue("dissect", slot, batch, None, 1, shape=(int(max_records), int(max_items), int(max_rows)))
-        self._chk(self.lib.trew_hip_dissect(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score),
-                                            int(max_records), int(max_items), int(max_rows)), "trew_hip_dissect")
+        f, cand = _resolved_call(self.lib, "trew_hip_dissect", candidates)
+        self._chk(f(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score), *cand, int(max_records),
+                    int(max_items), int(max_rows)), f.__name__)
 
     def dissect_results(self, slot=0, want_ms=False):
         """Results of the slot's last dissect: (TANDEM_DTYPE records sorted by (read, start) with reserved = anchor, TRACE_DTYPE
@@ -1185,10 +1212,11 @@ class TrewHip:
         found."""
         return self._fetch_log("repeats", slot, REPEAT_DTYPE, want_ms)
 
-    def tandems(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0):
+    def tandems(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_records=None, slot=0, candidates=1):
         """Queue every de novo repeat tract under indels of every read of `batch` on the slot's stream (no motifs).
-        max_records: the capacity of the log for this call (default: the batch's read count, at least 1)."""
-        self._queue_tracts("tandems", batch, min_period, max_period, penalty, min_score, max_records, slot)
+        max_records: the capacity of the log for this call (default: the batch's read count, at least 1).  candidates > 1:
+        trew_hip_tandems_resolved, resolve's record of every piece in refine's place; the results call is the same."""
+        self._queue_tracts("tandems", batch, min_period, max_period, penalty, min_score, max_records, slot, candidates)
 
     def tandems_results(self, slot=0, want_ms=False):
         """Results of the slot's last tandems: (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,), found
@@ -1516,33 +1544,34 @@ def trace(reads, motifs, penalty=3, min_score=24, device=0, max_items=None, max_
         return _fetch_with_retry(lambda items, rows: t.trace(b, motifs, penalty, min_score, items, rows), t.trace_results, room, (3, 4))[:3]
 
 
-def decompose(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_items=None, max_rows=None):
+def decompose(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_items=None, max_rows=None, candidates=1):
     """Units in place with no motif given on the GPU: for every read (bytes / str) `refine`'s record, its unit turned to its
     smallest rotation (the record's `reserved` word is the anchor; decompose_anchor gives the rotation) and, when the score
     reaches min_score, the traceback of the read against it cut into copies -- `trace`'s items for that unit, in read
     orientation.  Returns (TRACE_DTYPE items sorted by (read, start), counts of shape (n_reads,), REFINE_DTYPE records of shape
     (n_reads,)); trace_signature turns a read's items into text with k = period.  The first call's log and workspace hold
     max_items items and max_rows rows (defaults: TrewHip.trace's for one motif); when more are found the call is repeated once
-    with the exact numbers."""
+    with the exact numbers.  candidates > 1 (at most 4): `resolve`'s record with that many candidates in `refine`'s place."""
     t, b = _one_batch(reads, device)
     with t:
         room = _trace_room(b, 1, max_items, max_rows)
-        return _fetch_with_retry(lambda items, rows: t.decompose(b, min_period, max_period, penalty, min_score, items, rows), t.decompose_results, room,
+        return _fetch_with_retry(lambda items, rows: t.decompose(b, min_period, max_period, penalty, min_score, items, rows, candidates=candidates), t.decompose_results, room,
                                  (3, 4))[:3]
 
 
-def dissect(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None, max_items=None, max_rows=None):
+def dissect(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None, max_items=None, max_rows=None, candidates=1):
     """Units in place for every tract of a read with no motif given on the GPU: `tandems`' records of every read (bytes / str),
     each with its unit turned to its smallest rotation (`reserved` is the anchor; decompose_anchor gives the rotation), and for
     every record `decompose`'s items of its piece, in read coordinates.  Returns (TANDEM_DTYPE records sorted by (read, start),
     TRACE_DTYPE items sorted by (read, start) with motif = the index of the item's tract in its read, counts of shape (n_reads,
     2) = (tracts, items)); trace_signature turns a tract's items into text with k = period, tandem_columns gives a record's
     columns.  The first call's logs and workspace hold max_records records, max_items items and max_rows rows (defaults:
-    TrewHip.dissect's); when more are found the call is repeated once with the exact numbers."""
+    TrewHip.dissect's); when more are found the call is repeated once with the exact numbers.  candidates > 1 (at most 4): every
+    piece gets `resolve`'s record with that many candidates in `refine`'s place."""
     t, b = _one_batch(reads, device)
     with t:
         room = (max(int(b.n_reads), 1) if max_records is None else int(max_records),) + _trace_room(b, 1, max_items, max_rows)
-        return _fetch_with_retry(lambda recs, items, rows: t.dissect(b, min_period, max_period, penalty, min_score, recs, items, rows), t.dissect_results,
+        return _fetch_with_retry(lambda recs, items, rows: t.dissect(b, min_period, max_period, penalty, min_score, recs, items, rows, candidates=candidates), t.dissect_results,
                                  room, (3, 4, 5))[:3]
 
 
@@ -1558,17 +1587,18 @@ def repeats(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=
         return _fetch_with_retry(lambda cap: t.repeats(b, min_period, max_period, penalty, min_score, cap), t.repeats_results, room, (2,))[:2]
 
 
-def tandems(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None):
+def tandems(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_records=None, candidates=1):
     """Every de novo repeat tract under indels on the GPU: for every read (bytes / str) what `refine` gives it (depth 0) and, in
     the same way, what it gives the bases in front of that tract and behind it, each piece a read of its own, until nothing
     repeats; a piece whose refined score stays below min_score gives no record and is searched around its `periods` tract.
     Returns (TANDEM_DTYPE records sorted by (read, start), counts of shape (n_reads,)); tandem_columns gives the copies,
     mismatches, insertions and deletions.  The first call's log holds max_records records (default: one per read); when more
-    are found the call is repeated once with the exact number."""
+    are found the call is repeated once with the exact number.  candidates > 1 (at most 4): every piece gets `resolve`'s record
+    with that many candidates in `refine`'s place (`rank` and `first_period` are not reported here)."""
     t, b = _one_batch(reads, device)
     with t:
         room = (max(int(b.n_reads), 1) if max_records is None else int(max_records),)
-        return _fetch_with_retry(lambda cap: t.tandems(b, min_period, max_period, penalty, min_score, cap), t.tandems_results, room, (2,))[:2]
+        return _fetch_with_retry(lambda cap: t.tandems(b, min_period, max_period, penalty, min_score, cap, candidates=candidates), t.tandems_results, room, (2,))[:2]
 
 
 def satellites(reads, min_period=1, max_period=SATELLITE_MAX_PERIOD, penalty=3, min_score=24, device=0, max_records=None):

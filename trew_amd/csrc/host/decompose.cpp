@@ -2,7 +2,7 @@
 // the unit of `trew refine`, anchored at its smallest rotation, and the traceback of `trew trace` against it on the strand the
 // unit was found on: the runs of complete exact copies, the copies with a substituted, an inserted or a deleted base, and the
 // end pieces, in place (`=41 TCAGGG =3 TGAGGG =212`).  The definition is in include/trew_hip.h (trew_hip_decompose) and DESIGN
-// 4.7i; the options are `trew refine`'s and `--items`, the file path is `trew annotate`'s (process.cpp) and so are the
+// 4.7i; the options are `trew refine`'s, `--candidates` (above 1: trew_hip_decompose_resolved) and `--items`, the file path is `trew annotate`'s (process.cpp) and so are the
 // conventions: CSV on stdout, messages on stderr, exit status 1 and an empty stdout on an argument error.
 //
 //   >/abs/path/file.fastq
@@ -26,12 +26,14 @@ namespace trew_host {
 
 static void decompose_usage() {
     fprintf(stderr,
-            "Usage: decompose [--help] [--thread THREAD] [--min_period K] [--max_period K] [--penalty P] [--min_score S] [--items] [--devices LIST] [--stats] FASTQ...\n\n"
+            "Usage: decompose [--help] [--thread THREAD] [--min_period K] [--max_period K] [--penalty P] [--min_score S] [--candidates C] [--items] [--devices LIST] [--stats] FASTQ...\n\n"
             "Report, for every read, in which order the units of its own repeat come when bases are missing or extra, without a motif\n"
             "given: the unit of `refine` (periods MIN_PERIOD to MAX_PERIOD, 1 to 32, default all; a matching base scores 1, a wrong, an\n"
             "extra and a missing base cost P, 1 to 64, default 3, each; tracts that score less than S, default 24, are not reported),\n"
             "turned to its smallest rotation, and the tract cut into copies of it as `trace` does -- runs of exact copies, copies with\n"
-            "their errors and the end pieces, in place, in read orientation.  --items lists one item per row.\n");
+            "their errors and the end pieces, in place, in read orientation.  --items lists one item per row.  With C above 1 (1 to 4, default 1) the\n"
+            "unit is what `resolve` reports with C candidates, the period chosen by alignment; `resolve`'s candidates and rank are not\n"
+            "reported here.\n");
 }
 
 // the anchored unit M: rotation `anchor` of the record's unit, M[j] = U[(j + anchor) mod k]
@@ -53,9 +55,11 @@ static std::string decompose_unit_text(const TraceRow &row, uint32_t k) {
 int decompose_main(int argc, char **argv) {
     PeriodOptions o;
     bool items = false;
+    int candidates = 1;  // the plain entry point
     MotifCli cli;
     cli.usage = decompose_usage;
     period_options(cli, o, 32);
+    candidates_option(cli, candidates);
     cli.flags = {{"--items", [&]() { items = true; }}};
     cli.print_rows = [&](const AnnotFileResult &r, const std::vector<std::string> &) {
         if (items)

@@ -2,7 +2,7 @@
 // `trew tandems`, each with its unit anchored at its smallest rotation and cut into copies of it as `trew decompose` cuts a read's
 // best tract: the runs of complete exact copies, the copies with a substituted, an inserted or a deleted base, and the end
 // pieces, in place.  The definition is in include/trew_hip.h (trew_hip_dissect) and DESIGN 4.7j; the options are `trew
-// decompose`'s, the file path is `trew annotate`'s (process.cpp) and so are the conventions: CSV on stdout, messages on stderr,
+// decompose`'s (`--candidates` above 1: trew_hip_dissect_resolved), the file path is `trew annotate`'s (process.cpp) and so are the conventions: CSV on stdout, messages on stderr,
 // exit status 1 and an empty stdout on an argument error.
 //
 //   >/abs/path/file.fastq
@@ -25,13 +25,14 @@ namespace trew_host {
 
 static void dissect_usage() {
     fprintf(stderr,
-            "Usage: dissect [--help] [--thread THREAD] [--min_period K] [--max_period K] [--penalty P] [--min_score S] [--items] [--devices LIST] [--stats] FASTQ...\n\n"
+            "Usage: dissect [--help] [--thread THREAD] [--min_period K] [--max_period K] [--penalty P] [--min_score S] [--candidates C] [--items] [--devices LIST] [--stats] FASTQ...\n\n"
             "Report, for every repeat tract of every read, in which order the units of its repeat come when bases are missing or extra,\n"
             "without a motif given: the tracts of `tandems` (periods MIN_PERIOD to MAX_PERIOD, 1 to 32, default all; a matching base\n"
             "scores 1, a wrong, an extra and a missing base cost P, 1 to 64, default 3, each; tracts that score less than S, default 24,\n"
             "are not reported), each with its unit turned to its smallest rotation and cut into copies of it as `decompose` does --\n"
             "runs of exact copies, copies with their errors and the end pieces, in place, in read orientation.  --items lists one item\n"
-            "per row.\n");
+            "per row.  With C above 1 (1 to 4, default 1) every piece gets what `resolve` reports for it with C candidates, the period\n"
+            "chosen by alignment, in the place of `refine`'s; `resolve`'s candidates and rank are not reported here.\n");
 }
 
 // the anchored unit M: rotation `anchor` of the record's unit, M[j] = U[(j + anchor) mod k]
@@ -53,9 +54,11 @@ static std::string dissect_unit_text(const TraceRow &row, uint32_t k) {
 int dissect_main(int argc, char **argv) {
     PeriodOptions o;
     bool items = false;
+    int candidates = 1;  // the plain entry point
     MotifCli cli;
     cli.usage = dissect_usage;
     period_options(cli, o, 32);
+    candidates_option(cli, candidates);
     cli.flags = {{"--items", [&]() { items = true; }}};
     cli.print_rows = [&](const AnnotFileResult &r, const std::vector<std::string> &) {
         if (items)

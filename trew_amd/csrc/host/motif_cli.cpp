@@ -79,6 +79,21 @@ void period_options(MotifCli &cli, PeriodOptions &o, int bound) {
     };
 }
 
+void candidates_option(MotifCli &cli, int &candidates) {
+    static_assert(TREW_RESOLVE_MAX_CANDIDATES == 4, "the text below");
+    cli.options.push_back({"--candidates", [&candidates](const char *s) { return parse_int(s, &candidates); }, "CANDIDATES must be a number."});
+    const auto period_check = cli.check;
+    cli.check = [&candidates, period_check]() -> const char * {
+        if (const char *e = period_check()) return e;
+        return candidates < 1 || candidates > TREW_RESOLVE_MAX_CANDIDATES ? "CANDIDATES must be in range 1 to 4." : nullptr;
+    };
+    const auto period_fill = cli.fill;
+    cli.fill = [&candidates, period_fill](AnnotRequest &rq) {
+        period_fill(rq);
+        rq.candidates = candidates;
+    };
+}
+
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
     Config cfg;
     std::vector<std::string> positional;

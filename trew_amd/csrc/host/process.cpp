@@ -1532,9 +1532,9 @@ static void tally_units(const Rec *recs, uint64_t found, Map &units, KeyOf key_o
 
 // What repeats, satellites and tandems share: their queue and results calls differ in the record type only.  The log starts at
 // one record per read; a batch whose log overflows is resubmitted once, with the exact number.  Then tally_units.
-template <class Rec, class Map, class KeyOf, class Each>
+template <class Rec, class Queue, class Map, class KeyOf, class Each>
 static void fold_tract_log(const AnnotBatch &x, AnnotFileResult &p, const char *queue_name, const char *results_name, const char *twice,
-                           int (*queue)(trew_hip_ctx *, const trew_hip_batch *, int, int, int, int, uint32_t, uint64_t),
+                           Queue queue,  // the queue call: (ctx, batch, slot, min_period, max_period, penalty, min_score, max_records)
                            int (*results)(trew_hip_ctx *, int, Rec *, uint64_t, uint64_t *, uint32_t *, float *), Map &units, KeyOf key_of, Each each) {
     Annotator::Worker *w = x.w;
     const AnnotRequest &rq = *x.rq;
@@ -1570,9 +1570,17 @@ static void fold_satellites(const AnnotBatch &x, AnnotFileResult &p) {
 
 // trew tandems: fold_repeats with the refined record; every record is a row (the kernel stores only those that reach MIN_SCORE).
 // tandem_units counts per (period, strand-canonical unit) the reads that have such a tract, the tracts, their bases and copies.
+// --candidates above 1: trew_hip_tandems_resolved queues, the results call is the same.
 static void fold_tandems(const AnnotBatch &x, AnnotFileResult &p) {
+    const int candidates = x.rq->candidates;
+    auto queue = [candidates](trew_hip_ctx *c, const trew_hip_batch *b, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                              uint64_t max_records) {
+        return candidates == 1 ? trew_hip_tandems(c, b, slot, min_period, max_period, penalty, min_score, max_records)
+                               : trew_hip_tandems_resolved(c, b, slot, min_period, max_period, penalty, min_score, candidates, max_records);
+    };
     fold_tract_log<trew_hip_tandem>(
-        x, p, "trew_hip_tandems", "trew_hip_tandems_results", "internal error: the tandem log overflowed twice", trew_hip_tandems, trew_hip_tandems_results, p.tandem_units,
+        x, p, candidates == 1 ? "trew_hip_tandems" : "trew_hip_tandems_resolved", "trew_hip_tandems_results", "internal error: the tandem log overflowed twice",
+        queue, trew_hip_tandems_results, p.tandem_units,
         [](const trew_hip_tandem &rec) { return std::pair<uint32_t, uint64_t>{rec.period, canonical_unit(rec.unit, (int) rec.period)}; },
         [&](const trew_hip_tandem &rec, TandemUnit &u) {
             u.copies += rec.consumed / rec.period;
@@ -1707,8 +1715,13 @@ static void fold_decompose(const AnnotBatch &x, AnnotFileResult &p) {
     const uint64_t items = fetch_with_retry(
         p, LogRoom{16 * x.n, std::max<uint64_t>(bases, 1)}, "internal error: the decompose log overflowed twice",
         [&](LogRoom room) {
-            if (trew_hip_decompose(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.log, room.rows))
-                hip_die(x.c, "trew_hip_decompose");
+            if (rq.candidates == 1) {
+                if (trew_hip_decompose(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.log, room.rows))
+                    hip_die(x.c, "trew_hip_decompose");
+            } else if (trew_hip_decompose_resolved(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, rq.candidates, room.log,
+                                                   room.rows)) {
+                hip_die(x.c, "trew_hip_decompose_resolved");
+            }
         },
         [&](LogRoom room) {
             LogRoom need{0, 0};
@@ -1754,8 +1767,13 @@ static void fold_dissect(const AnnotBatch &x, AnnotFileResult &p) {
     const LogRoom found = fetch_with_retry(
         p, LogRoom{16 * x.n, std::max<uint64_t>(bases, 1), 4 * x.n + 16}, "internal error: the dissect logs overflowed twice",
         [&](LogRoom room) {
-            if (trew_hip_dissect(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.tracts, room.log, room.rows))
-                hip_die(x.c, "trew_hip_dissect");
+            if (rq.candidates == 1) {
+                if (trew_hip_dissect(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, room.tracts, room.log, room.rows))
+                    hip_die(x.c, "trew_hip_dissect");
+            } else if (trew_hip_dissect_resolved(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score, rq.candidates, room.tracts,
+                                                 room.log, room.rows)) {
+                hip_die(x.c, "trew_hip_dissect_resolved");
+            }
         },
         [&](LogRoom room) {
             LogRoom need{0, 0, 0};

@@ -34,17 +34,7 @@ int resolve_main(int argc, char **argv) {
     MotifCli cli;
     cli.usage = resolve_usage;
     period_options(cli, o, 32);
-    cli.options.push_back({"--candidates", [&candidates](const char *s) { return parse_int(s, &candidates); }, "CANDIDATES must be a number."});
-    const auto period_check = cli.check;
-    cli.check = [&candidates, period_check]() -> const char * {
-        if (const char *e = period_check()) return e;
-        return candidates < 1 || candidates > TREW_RESOLVE_MAX_CANDIDATES ? "CANDIDATES must be in range 1 to 4." : nullptr;
-    };
-    const auto period_fill = cli.fill;
-    cli.fill = [&candidates, period_fill](AnnotRequest &rq) {
-        period_fill(rq);
-        rq.candidates = candidates;
-    };
+    candidates_option(cli, candidates);
     cli.print_rows = [&](const AnnotFileResult &r, const std::vector<std::string> &) {
         printf("read,length,period,unit,canonical,start,end,score,copies,consumed,matches,mismatches,insertions,deletions,seed_period,seed_unit,seed_score,"
                "changed,scored_period,candidates,rank,first_period,first_score\n");

@@ -1,7 +1,7 @@
 // tandems.cpp -- `trew tandems FASTQ...`: every repeat tract of every read when bases are missing or extra, without a motif
 // given -- the recursion of `trew repeats` over what lies in front of a tract and behind it, with the seed, the wraparound
 // alignment and the re-voted unit of `trew refine` for each piece.  The definition is in include/trew_hip.h (trew_hip_tandem) and
-// DESIGN 4.7g; the options are `trew periods`'s, the file path is `trew annotate`'s (process.cpp) and so are the conventions: CSV
+// DESIGN 4.7g, with `--candidates` above 1 in 4.7l (trew_hip_tandems_resolved); the options are `trew periods`'s and `--candidates`, the file path is `trew annotate`'s (process.cpp) and so are the conventions: CSV
 // on stdout, messages on stderr, exit status 1 and an empty stdout on an argument error.
 //
 //   >/abs/path/file.fastq
@@ -20,19 +20,23 @@ namespace trew_host {
 
 static void tandems_usage() {
     fprintf(stderr,
-            "Usage: tandems [--help] [--thread THREAD] [--min_period K] [--max_period K] [--penalty P] [--min_score S] [--devices LIST] [--stats] FASTQ...\n\n"
+            "Usage: tandems [--help] [--thread THREAD] [--min_period K] [--max_period K] [--penalty P] [--min_score S] [--candidates C] [--devices LIST] [--stats] FASTQ...\n\n"
             "Report, for every read, every repeat tract when bases are missing or extra: what `refine` reports for the read (period\n"
             "MIN_PERIOD to MAX_PERIOD, 1 to 32, default all; a unit taken from the read, the read aligned against it, the unit voted\n"
             "again), then the same for what lies in front of that tract and for what lies behind it, each on its own, until nothing\n"
             "repeats.  A matching base scores 1, a wrong, an extra and a missing base cost P (1 to 64, default 3) each; a tract that\n"
-            "scores less than S (default 24) is not reported, and the search goes on around it.\n");
+            "scores less than S (default 24) is not reported, and the search goes on around it.  With C above 1 (1 to 4, default 1)\n"
+            "every piece gets what `resolve` reports for it with C candidates, the period chosen by alignment, in the place of\n"
+            "`refine`'s; `resolve`'s candidates, rank, first_period and first_score are not reported here.\n");
 }
 
 int tandems_main(int argc, char **argv) {
     PeriodOptions o;
+    int candidates = 1;  // the plain entry point
     MotifCli cli;
     cli.usage = tandems_usage;
     period_options(cli, o, 32);
+    candidates_option(cli, candidates);
     cli.print_rows = [&](const AnnotFileResult &r, const std::vector<std::string> &) {
         printf("read,length,depth,period,unit,canonical,start,end,score,copies,consumed,matches,mismatches,insertions,deletions,seed_period,seed_unit,"
                "seed_score,changed,scored_period\n");

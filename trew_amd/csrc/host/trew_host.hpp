@@ -113,7 +113,7 @@ struct AnnotRequest {
     int min_period = 1, max_period = 32;                  // periods, repeats, satellites, refine, tandems (which take no motifs: n_motifs = 0)
     uint32_t min_score = 24;                              // periods, repeats, satellites, align, refine, tandems, trace
     trew_hip_interval_rule rules[TREW_ANNOT_MAX_MOTIFS];  // intervals
-    int candidates = 3;                                   // resolve
+    int candidates = 3;                                   // resolve; tandems, decompose, dissect: their commands fill in 1 (the plain entry point)
 };
 struct AnnotRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
@@ -282,6 +282,9 @@ struct PeriodOptions {
     int min_period = 1, max_period = 32, penalty = 3, min_score = 24;
 };
 void period_options(MotifCli &cli, PeriodOptions &o, int bound);
+// --candidates C on top of period_options (resolve: default 3; tandems, decompose, dissect: default 1): the option, its range
+// check behind the periods' and the request's `candidates`.  `candidates` holds the default and must outlive `cli`.
+void candidates_option(MotifCli &cli, int &candidates);
 int annotate_main(int argc, char **argv);
 int tracts_main(int argc, char **argv);
 int intervals_main(int argc, char **argv);

@@ -26,8 +26,15 @@
 // are not stored; the walk then fills its block by computing the rows from `start` again, as in trace.inc.  No scalar
 // stores, no inline assembly.
 
-__global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, TraceLog lg,
-                                                             u32 *__restrict__ out, u32 *__restrict__ counts) {
+// kResolved (trew_hip_decompose_resolved, DESIGN 4.7l): resolve_piece (kernels/resolve_piece.inc) over the whole read in the place
+// of refine_piece, with `candidates` its C; the record stays word i in lane i, the words the anchor and the rows need are read out
+// of it and the store takes it as it is.  <false> is trew_hip_decompose's kernel as it was; it ignores `candidates`.
+// Registers.  Left to itself <true> takes 132 VGPRs and three waves a SIMD; asked for four it finds 128 without a spill and without
+// scratch, so it asks.  <false> gets (1, 8), which is what a 256-thread block has without the attribute: 126 VGPRs as before.
+template <bool kResolved>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kResolved ? 4 : 1, kResolved ? 4 : 8)))
+decompose_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, TraceLog lg,
+                                                             u32 *__restrict__ out, u32 *__restrict__ counts, u32 candidates) {
     __shared__ u32 bins[4][kPeriodBins];
     __shared__ uint4 dec_lds[4][kTraceBlock * 2u];
     const u32 lane = lane_id();
@@ -47,7 +54,15 @@ __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min
     for (u64 r = wave; r < B.n_reads; r += n_waves) {
         const ReadRef rd = uni(get_read(B, r));
         u32 rec[16], r_start, r_end;  // the periods tract is for kernels/tandems.inc: not used here
-        refine_piece(rd, Piece{0u, rd.len}, kmin, kmax, P, smin, h, rec, r_start, r_end);  // the whole read; all zero without a record
+        u32 won = 0;  // kResolved: the record, word i in lane i
+        if constexpr (kResolved) {
+            u32 m;
+            resolve_piece(rd, Piece{0u, rd.len}, kmin, kmax, P, smin, rfl(candidates), h, won, r_start, r_end, m, [](u32, u32, u32, bool) {});
+            rec[0] = record_word(won, 0), rec[4] = record_word(won, 4), rec[5] = record_word(won, 5), rec[6] = record_word(won, 6);
+            rec[7] = record_word(won, 7), rec[8] = record_word(won, 8), rec[12] = record_word(won, 12), rec[13] = record_word(won, 13);
+        } else {
+            refine_piece(rd, Piece{0u, rd.len}, kmin, kmax, P, smin, h, rec, r_start, r_end);  // the whole read; all zero without a record
+        }
         const u32 k = rfl(rec[0]), score = rfl(rec[4]), start = rfl(rec[5]), en = rfl(rec[6]), consumed_r = rfl(rec[7]), matches_r = rfl(rec[8]);
         u32 rho = 0, found = 0;
         if (k != 0u && score >= smin && en > start && en <= rd.len) {  // wave-uniform; a record's tract lies inside its read
@@ -95,9 +110,14 @@ __global__ void __launch_bounds__(256) decompose_wave_kernel(DevBatch B, int min
             });
         }
         // sixteen lanes write the record's sixteen words (trew_hip_refined), its reserved word the anchor: one vector store
-        u32 x = rec[15];
+        u32 x;
+        if constexpr (kResolved) {
+            x = lane == 11u ? rho : won;
+        } else {
+            x = rec[15];
 #pragma unroll
-        for (int w = 14; w >= 0; w--) x = lane == (u32) w ? (w == 11 ? rho : rec[w]) : x;
+            for (int w = 14; w >= 0; w--) x = lane == (u32) w ? (w == 11 ? rho : rec[w]) : x;
+        }
         if (lane < 16) out[r * 16ull + lane] = x;
         if (lane == 0) counts[r] = found;
     }

@@ -30,8 +30,16 @@
 // the kernels beside it; asked for four waves it finds 127 without a spill and without scratch, so the kernel asks.  Keeping lo
 // and hi of an entry in the two halves of one register instead saves one VGPR (130): not enough, and not kept.
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
-dissect_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, RepeatLog rl, TraceLog lg, u32 *__restrict__ counts) {
+// kResolved (trew_hip_dissect_resolved, DESIGN 4.7l): resolve_piece (kernels/resolve_piece.inc) in the place of refine_piece, with
+// `candidates` its C; the record stays word i in lane i, the words the walk, the anchor and the rows need are read out of it and the
+// store moves it two lanes up.  <false> is trew_hip_dissect's kernel as it was; it ignores `candidates`.
+// Registers.  <true> under the four-wave request spills (128 VGPRs, 4 spilled, 20 bytes of scratch; 2 and 12 with the stack, and
+// with the candidate list as well, in LDS: the pressure is in SGPRs), so it does not ask ((1, 8) is a 256-thread block's default):
+// 137 VGPRs, three waves a SIMD, no scratch (DESIGN 4.7l).
+template <bool kResolved>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kResolved ? 1 : 4, kResolved ? 8 : 4)))
+dissect_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, RepeatLog rl, TraceLog lg, u32 *__restrict__ counts,
+                    u32 candidates) {
     __shared__ u32 bins[4][kPeriodBins];
     __shared__ uint4 dis_lds[4][kTraceBlock * 2u];
     const u32 lane = lane_id();
@@ -57,7 +65,16 @@ dissect_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32
         bool have = repeat_worth(lo, hi, kmin, smin);
         while (have) {  // wave-uniform
             u32 rec[16], r_start = 0, r_end = 0;
-            const bool split = refine_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, r_start, r_end);
+            u32 won = 0;  // kResolved: the record, word i in lane i
+            bool split;
+            if constexpr (kResolved) {
+                u32 m;
+                split = resolve_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, rfl(candidates), h, won, r_start, r_end, m, [](u32, u32, u32, bool) {});
+                rec[0] = record_word(won, 0), rec[4] = record_word(won, 4), rec[5] = record_word(won, 5), rec[6] = record_word(won, 6);
+                rec[7] = record_word(won, 7), rec[8] = record_word(won, 8), rec[12] = record_word(won, 12), rec[13] = record_word(won, 13);
+            } else {
+                split = refine_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, r_start, r_end);
+            }
             u32 a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // the children; a the shorter
             if (split) {
                 const u32 score = rfl(rec[4]);
@@ -83,9 +100,15 @@ dissect_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32
                     rho = rho < k ? rho : 0u;
                     // ---- the record: read, depth, refine's sixteen words with the anchor in the reserved one
                     {
-                        u32 x = rec[15];
+                        u32 x;
+                        if constexpr (kResolved) {
+                            x = lane_read(won, ((lane - 2u) & 63u) << 2);  // word i into lane i + 2
+                            x = lane == 13u ? rho : x;
+                        } else {
+                            x = rec[15];
 #pragma unroll
-                        for (int i = 14; i >= 0; i--) x = lane == (u32) (i + 2) ? (i == 11 ? rho : rec[i]) : x;
+                            for (int i = 14; i >= 0; i--) x = lane == (u32) (i + 2) ? (i == 11 ? rho : rec[i]) : x;
+                        }
                         x = lane == 1u ? depth : x;
                         x = lane == 0u ? (u32) r : x;
                         log_append<kTandemWords>(rl.counter, rl.recs, rl.cap, x);

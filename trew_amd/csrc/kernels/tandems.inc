@@ -26,8 +26,12 @@
 constexpr u32 kTandemWords = 18;  // trew_hip_tandem: read, depth, the sixteen words of trew_hip_refined
 
 // counts: one u32 per read; the counter of lg is zero when the kernel starts (the caller's memset on the same stream)
+// kResolved (trew_hip_tandems_resolved, DESIGN 4.7l): resolve_piece (kernels/resolve_piece.inc) in the place of refine_piece, with
+// `candidates` its C; the record stays word i in lane i, three words are read out of it and the store moves it two lanes up.
+// <false> is trew_hip_tandems' kernel, instruction for instruction what it was without the parameter; it ignores `candidates`.
+template <bool kResolved>
 __global__ void __launch_bounds__(256) tandems_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32 min_score, RepeatLog lg,
-                                                           u32 *__restrict__ counts) {
+                                                           u32 *__restrict__ counts, u32 candidates) {
     __shared__ u32 bins[4][kPeriodBins];
     const u32 lane = lane_id();
     u32 *h = bins[threadIdx.x >> 6];
@@ -49,7 +53,15 @@ __global__ void __launch_bounds__(256) tandems_wave_kernel(DevBatch B, int min_p
         bool have = repeat_worth(lo, hi, kmin, smin);
         while (have) {  // wave-uniform
             u32 rec[16], r_start = 0, r_end = 0;
-            const bool split = refine_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, r_start, r_end);
+            u32 won = 0;  // kResolved: the record, word i in lane i
+            bool split;
+            if constexpr (kResolved) {
+                u32 m;
+                split = resolve_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, rfl(candidates), h, won, r_start, r_end, m, [](u32, u32, u32, bool) {});
+                rec[4] = record_word(won, 4), rec[5] = record_word(won, 5), rec[6] = record_word(won, 6);
+            } else {
+                split = refine_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, r_start, r_end);
+            }
             u32 a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // the children; a the shorter
             if (split) {
                 const bool strong = rfl(rec[4]) >= smin;
@@ -62,9 +74,14 @@ __global__ void __launch_bounds__(256) tandems_wave_kernel(DevBatch B, int min_p
                     u64 idx = 0;
                     if (lane == 0) idx = atomicAdd(lg.counter, 1ull);
                     idx = rfl64(idx);
-                    u32 x = rec[15];
+                    u32 x;
+                    if constexpr (kResolved) {
+                        x = lane_read(won, ((lane - 2u) & 63u) << 2);  // word i into lane i + 2
+                    } else {
+                        x = rec[15];
 #pragma unroll
-                    for (int i = 14; i >= 0; i--) x = lane == (u32) (i + 2) ? rec[i] : x;
+                        for (int i = 14; i >= 0; i--) x = lane == (u32) (i + 2) ? rec[i] : x;
+                    }
                     x = lane == 1u ? depth : x;
                     x = lane == 0u ? (u32) r : x;
                     if (idx < lg.cap && lane < kTandemWords) lg.recs[idx * (u64) kTandemWords + lane] = x;

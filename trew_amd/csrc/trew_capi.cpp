@@ -1379,6 +1379,27 @@ extern "C" int trew_dissect_host(const uint32_t *words, const uint32_t *offsets,
                                     n_records, n_items, n_rows, counts));
 }
 
+extern "C" int trew_tandems_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                          int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_tandem *out, uint64_t cap,
+                                          uint64_t *n, uint32_t *counts) {
+    return host_status(tandems_resolved_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, candidates, out, cap, n, counts));
+}
+
+extern "C" int trew_decompose_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                            int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_trace_item *items, uint64_t cap,
+                                            uint64_t *n_items, uint32_t *counts, trew_hip_refined *records) {
+    return host_status(decompose_resolved_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, candidates, items, cap,
+                                               n_items, counts, records));
+}
+
+extern "C" int trew_dissect_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                          int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_tandem *records, uint64_t rec_cap,
+                                          trew_hip_trace_item *items, uint64_t item_cap, uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows,
+                                          uint32_t *counts) {
+    return host_status(dissect_resolved_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, candidates, records, rec_cap,
+                                             items, item_cap, n_records, n_items, n_rows, counts));
+}
+
 extern "C" int trew_resolve_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
                                  int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_resolved *out) {
     return host_status(resolve_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, candidates, out));
@@ -1696,19 +1717,35 @@ extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trac
 // ---------------------------------------------------------------- units in place with no motif given: refine's unit, anchored, traced
 // As trace: `records` is the item log, `counter` two values (items, rows); `counts` one u32 per read, `aligned` the
 // trew_hip_refined of every read (its reserved word the anchor), `rows` 32 bytes a row.
-extern "C" int trew_hip_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
-                                  uint32_t min_score, uint64_t max_items, uint64_t max_rows) {
+// candidates 0: trew_hip_decompose and its kernel; otherwise trew_hip_decompose_resolved (the sibling's checks, then resolve_error's)
+static int queue_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                           bool resolved, int candidates, uint64_t max_items, uint64_t max_rows) {
     auto own = [&]() -> const char * {
         if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-        return max_items < 1 ? "max_items must be at least 1" : max_rows < 1 ? "max_rows must be at least 1" : nullptr;
+        if (const char *e = max_items < 1 ? "max_items must be at least 1" : max_rows < 1 ? "max_rows must be at least 1" : nullptr) return e;
+        return resolved ? resolve_error(min_period, max_period, penalty, min_score, candidates) : nullptr;
     };
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 1, false, max_rows, 1, 32, sizeof(trew_hip_refined)};
     return queue_log(ctx, batch, slot, nullptr, 0, kDecompose, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
-        HIPCHK(ctx, launch_decompose(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, (trew_hip_refined *) st.aligned.p,
-                                     (u32 *) st.counts.p));
+        if (resolved)
+            HIPCHK(ctx, launch_decompose_resolved(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, candidates, lg,
+                                                  (trew_hip_refined *) st.aligned.p, (u32 *) st.counts.p));
+        else
+            HIPCHK(ctx, launch_decompose(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, (trew_hip_refined *) st.aligned.p,
+                                         (u32 *) st.counts.p));
         return 0;
     });
+}
+
+extern "C" int trew_hip_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                                  uint32_t min_score, uint64_t max_items, uint64_t max_rows) {
+    return queue_decompose(ctx, batch, slot, min_period, max_period, penalty, min_score, false, 0, max_items, max_rows);
+}
+
+extern "C" int trew_hip_decompose_resolved(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                                           uint32_t min_score, int candidates, uint64_t max_items, uint64_t max_rows) {
+    return queue_decompose(ctx, batch, slot, min_period, max_period, penalty, min_score, true, candidates, max_items, max_rows);
 }
 
 extern "C" int trew_hip_decompose_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
@@ -1732,22 +1769,38 @@ extern "C" int trew_hip_decompose_results(trew_hip_ctx *ctx, int slot, trew_hip_
 // ---------------------------------------------------------------- units in place for every tract of a read, no motif given
 // As decompose: `records` is the item log, `rows` 32 bytes a row; `aligned` is the log of trew_hip_tandem records (reserved: the
 // anchor), `counter` three values (items, rows, records), `counts` two u32 per read (tracts, items).
-extern "C" int trew_hip_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
-                                uint64_t max_records, uint64_t max_items, uint64_t max_rows) {
+static int queue_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                         bool resolved, int candidates, uint64_t max_records, uint64_t max_items, uint64_t max_rows) {
     auto own = [&]() -> const char * {
         if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-        return max_records < 1 ? "max_records must be at least 1"
-               : max_items < 1 ? "max_items must be at least 1"
-               : max_rows < 1  ? "max_rows must be at least 1"
-                               : nullptr;
+        if (const char *e = max_records < 1 ? "max_records must be at least 1"
+                            : max_items < 1 ? "max_items must be at least 1"
+                            : max_rows < 1  ? "max_rows must be at least 1"
+                                            : nullptr)
+            return e;
+        return resolved ? resolve_error(min_period, max_period, penalty, min_score, candidates) : nullptr;
     };
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 2, false, max_rows, 0, 32, sizeof(trew_hip_tandem), max_records};
     return queue_log(ctx, batch, slot, nullptr, 0, kDissect, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         const RepeatLog rl = {st.counter + 2, (u32 *) st.aligned.p, st.n};
-        HIPCHK(ctx, launch_dissect(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, rl, lg, (u32 *) st.counts.p));
+        if (resolved)
+            HIPCHK(ctx, launch_dissect_resolved(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, candidates, rl, lg,
+                                                (u32 *) st.counts.p));
+        else
+            HIPCHK(ctx, launch_dissect(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, rl, lg, (u32 *) st.counts.p));
         return 0;
     });
+}
+
+extern "C" int trew_hip_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score,
+                                uint64_t max_records, uint64_t max_items, uint64_t max_rows) {
+    return queue_dissect(ctx, batch, slot, min_period, max_period, penalty, min_score, false, 0, max_records, max_items, max_rows);
+}
+
+extern "C" int trew_hip_dissect_resolved(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                                         uint32_t min_score, int candidates, uint64_t max_records, uint64_t max_items, uint64_t max_rows) {
+    return queue_dissect(ctx, batch, slot, min_period, max_period, penalty, min_score, true, candidates, max_records, max_items, max_rows);
 }
 
 extern "C" int trew_hip_dissect_results(trew_hip_ctx *ctx, int slot, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items,
@@ -2024,6 +2077,20 @@ extern "C" int trew_hip_tandems(trew_hip_ctx *ctx, const trew_hip_batch *batch, 
     auto error = [&]() { return periods_error(min_period, max_period, penalty, min_score); };
     return queue_tracts(ctx, batch, slot, kTandems, sizeof(trew_hip_tandem), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
         HIPCHK(ctx, launch_tandems(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, lg, counts));
+        return 0;
+    });
+}
+
+// the sibling's checks (queue_tracts adds max_records) come first, then resolve_error's check of the candidates
+extern "C" int trew_hip_tandems_resolved(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty,
+                                         uint32_t min_score, int candidates, uint64_t max_records) {
+    auto error = [&]() -> const char * {
+        if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+        if (max_records < 1) return "max_records must be at least 1";
+        return resolve_error(min_period, max_period, penalty, min_score, candidates);
+    };
+    return queue_tracts(ctx, batch, slot, kTandems, sizeof(trew_hip_tandem), max_records, error, [&](Slot &s, const DevBatch &db, const RepeatLog &lg, u32 *counts) -> int {
+        HIPCHK(ctx, launch_tandems_resolved(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, candidates, lg, counts));
         return 0;
     });
 }

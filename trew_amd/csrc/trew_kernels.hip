@@ -48,11 +48,12 @@
 //   satellites.inc     satellites_wave_kernel (de novo repeats with periods up to 256: the wide eq word, 1024 consensus bins and a 16-word unit; shares periods.inc's and pieces.inc's functions)
 //   align.inc          align_wave_kernel (indel-aware motif tract per read: wraparound alignment, the row of the table in registers, a phase per lane)
 //   refine.inc         refine_wave_kernel (de novo repeats under indels: periods.inc's period and tract, a seed unit from the longest run of eq_k, align.inc's row step for the alignment, the vote and the re-voted unit)
-//   tandems.inc        tandems_wave_kernel (de novo repeats under indels, every tract of a read: the recursion of pieces.inc over pieces, written out in the kernel, with refine.inc's refine_piece per piece)
+//   resolve_piece.inc  resolve_piece (resolve's period choice for one piece: the four best periods.inc scores, refine.inc's refine_at per candidate in a runtime loop, the record with the largest final score held word i in lane i; no kernel)
+//   tandems.inc        tandems_wave_kernel<kResolved> (<true>: resolve_piece in the place of refine_piece, trew_hip_tandems_resolved; so for decompose.inc and dissect.inc) (de novo repeats under indels, every tract of a read: the recursion of pieces.inc over pieces, written out in the kernel, with refine.inc's refine_piece per piece)
 //   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
 //   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
 //   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: tandems.inc's piece loop, written out once more, with decompose.inc's anchor, rows and walk for every piece that gives a record)
-//   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, refine.inc's refine_at per candidate in a runtime loop, the record with the largest final score)
+//   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, resolve_piece.inc's resolve_piece over the whole read, and the record's own four words)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -96,6 +97,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/wraparound.inc"
 #include "kernels/align.inc"
 #include "kernels/refine.inc"
+#include "kernels/resolve_piece.inc"
 #include "kernels/tandems.inc"
 #include "kernels/trace.inc"
 #include "kernels/decompose.inc"
@@ -454,7 +456,12 @@ hipError_t launch_refine(hipStream_t st, u32 n_cu, const DevBatch &B, int min_pe
 
 hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &lg,
                           u32 *d_counts) {
-    return launch_wave_per_read(st, n_cu, B, tandems_wave_kernel, min_period, max_period, penalty, min_score, lg, d_counts);
+    return launch_wave_per_read(st, n_cu, B, tandems_wave_kernel<false>, min_period, max_period, penalty, min_score, lg, d_counts, 0u);
+}
+
+hipError_t launch_tandems_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                   const RepeatLog &lg, u32 *d_counts) {
+    return launch_wave_per_read(st, n_cu, B, tandems_wave_kernel<true>, min_period, max_period, penalty, min_score, lg, d_counts, (u32) candidates);
 }
 
 hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, u32 min_score,
@@ -464,12 +471,23 @@ hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const Annot
 
 hipError_t launch_decompose(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const TraceLog &lg,
                             trew_hip_refined *d_out, u32 *d_counts) {
-    return launch_wave_per_read(st, n_cu, B, decompose_wave_kernel, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts);
+    return launch_wave_per_read(st, n_cu, B, decompose_wave_kernel<false>, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts, 0u);
+}
+
+hipError_t launch_decompose_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                     const TraceLog &lg, trew_hip_refined *d_out, u32 *d_counts) {
+    return launch_wave_per_read(st, n_cu, B, decompose_wave_kernel<true>, min_period, max_period, penalty, min_score, lg, (u32 *) d_out, d_counts,
+                                (u32) candidates);
 }
 
 hipError_t launch_dissect(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &rl,
                           const TraceLog &lg, u32 *d_counts) {
-    return launch_wave_per_read(st, n_cu, B, dissect_wave_kernel, min_period, max_period, penalty, min_score, rl, lg, d_counts);
+    return launch_wave_per_read(st, n_cu, B, dissect_wave_kernel<false>, min_period, max_period, penalty, min_score, rl, lg, d_counts, 0u);
+}
+
+hipError_t launch_dissect_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                   const RepeatLog &rl, const TraceLog &lg, u32 *d_counts) {
+    return launch_wave_per_read(st, n_cu, B, dissect_wave_kernel<true>, min_period, max_period, penalty, min_score, rl, lg, d_counts, (u32) candidates);
 }
 
 hipError_t launch_resolve(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,

@@ -83,6 +83,14 @@ hipError_t launch_tandems(hipStream_t st, u32 n_cu, const DevBatch &B, int min_p
 // of 18 u32, `lg` items and rows of 32 bytes; all three counters are zero when it starts; d_counts: (tracts, items) per read
 hipError_t launch_dissect(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, const RepeatLog &rl,
                           const TraceLog &lg, u32 *d_counts);
+// trew_hip_tandems_resolved, _decompose_resolved, _dissect_resolved: the <true> instantiations of the three kernels above, with
+// resolve's period choice per piece (kernels/resolve_piece.inc); 1 <= candidates <= 4; logs, counters and counts as their siblings'
+hipError_t launch_tandems_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                   const RepeatLog &lg, u32 *d_counts);
+hipError_t launch_decompose_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                     const TraceLog &lg, trew_hip_refined *d_out, u32 *d_counts);
+hipError_t launch_dissect_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                   const RepeatLog &rl, const TraceLog &lg, u32 *d_counts);
 // trew_hip_resolve: the wave-per-read kernel of kernels/resolve.inc on the grid of launch_tracts; no motifs; 1 <= candidates <= 4
 hipError_t launch_resolve(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
                           trew_hip_resolved *d_out);

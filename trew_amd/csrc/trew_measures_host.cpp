@@ -866,9 +866,10 @@ const char *resolve_error(int min_period, int max_period, int penalty, u32 min_s
     return candidates < 1 || candidates > TREW_RESOLVE_MAX_CANDIDATES ? "resolve: 1 <= candidates <= 4 is required" : nullptr;
 }
 
-// the record of one read, step by step from the definition (trew_hip_resolved, include/trew_hip.h)
+// the record of one read, step by step from the definition (trew_hip_resolved, include/trew_hip.h); t0, where given: the periods
+// tract [t0[0], t0[1]) of candidate 0, which is refine_read_host's R (untouched without a candidate), for the weak pieces of 4.7l
 static void resolve_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, int candidates,
-                              trew_hip_resolved &o) {
+                              trew_hip_resolved &o, u32 *t0 = nullptr) {
     memset(&o, 0, sizeof(o));
     // 1. scores: the first C of the order (score descending, k ascending) that reach min_score
     struct Candidate {
@@ -904,6 +905,7 @@ static void resolve_read_host(const unsigned char *base, u32 n, int min_period, 
     if (m == 0) return;
     memcpy(&o, &win, sizeof(win));  // the first sixteen words are trew_hip_refined's
     o.candidates = m;
+    if (t0) t0[0] = cand[0].b, t0[1] = cand[0].e + cand[0].k;
 }
 
 const char *resolve_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
@@ -918,27 +920,68 @@ const char *resolve_host(const u32 *words, const u32 *offsets, const u32 *length
     return nullptr;
 }
 
+// ---------------------------------------------------------------- what the every-tract and in-place measures ask of a piece
+// The bases of a piece as a read of their own: false without a periods record; otherwise x the record the measure works with and
+// [t_start, t_end) the periods tract that a weak piece is split around, all in the piece's coordinates.
+// refine's one period (4.7g, 4.7i, 4.7j)
+static bool refined_piece_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, trew_hip_refined &x,
+                               u32 &t_start, u32 &t_end) {
+    trew_hip_period R;
+    refine_read_host(base, n, min_period, max_period, penalty, min_score, x, R);
+    t_start = R.start, t_end = R.end;
+    return R.scored_period != 0;
+}
+
+// resolve's winner among the first `candidates` periods, and the periods tract of candidate 0 (4.7l)
+static bool resolved_piece_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, int candidates,
+                                trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+    trew_hip_resolved o;
+    u32 t0[2] = {0, 0};
+    resolve_read_host(base, n, min_period, max_period, penalty, min_score, candidates, o, t0);
+    memcpy(&x, &o, sizeof(x));  // the first sixteen words are trew_hip_refined's
+    t_start = t0[0], t_end = t0[1];
+    return o.candidates != 0;
+}
+
 // ---------------------------------------------------------------- de novo repeats under indels: every tract of a read
 void sort_tandems(trew_hip_tandem *v, u64 n) {
     std::sort(v, v + n, [](const trew_hip_tandem &a, const trew_hip_tandem &b) { return a.read != b.read ? a.read < b.read : a.start < b.start; });
 }
 
-const char *tandems_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
-                         u32 min_score, trew_hip_tandem *out, u64 cap, u64 *n, u32 *counts) {
-    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-    return every_tract_host("trew_tandems_host", words, offsets, lengths, n_reads, out, cap, n, counts,
+// tandems_host and tandems_resolved_host: every_tract_host over `piece`, one of the two entries above
+template <class PieceFn>
+static const char *tandems_walk_host(const char *name, const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, u32 min_score,
+                                     trew_hip_tandem *out, u64 cap, u64 *n, u32 *counts, PieceFn piece) {
+    return every_tract_host(name, words, offsets, lengths, n_reads, out, cap, n, counts,
                             [&](const unsigned char *base, u32 r, u32 lo, u32 hi, u32 depth, trew_hip_tandem &rec, u32 &start, u32 &end) {
                                 trew_hip_refined x;
-                                trew_hip_period R;
-                                refine_read_host(base + lo, hi - lo, min_period, max_period, penalty, min_score, x, R);  // the piece as a read of its own
-                                if (R.scored_period == 0) return PieceResult::none;
-                                start = lo + R.start, end = lo + R.end;  // a weak piece: around the periods tract
+                                u32 t_start = 0, t_end = 0;
+                                if (!piece(base + lo, hi - lo, x, t_start, t_end)) return PieceResult::none;  // the piece as a read of its own
+                                start = lo + t_start, end = lo + t_end;  // a weak piece: around the periods tract
                                 if (x.score < min_score) return PieceResult::split_only;
                                 start = lo + x.start, end = lo + x.end;
                                 rec = trew_hip_tandem{r, depth, x.period, x.seed_period, x.scored_period, x.changed, x.score, start, end, x.consumed,
                                                       x.matches, x.seed_score, x.support, 0, x.unit, x.seed_unit};
                                 return PieceResult::record;
                             });
+}
+
+const char *tandems_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, trew_hip_tandem *out, u64 cap, u64 *n, u32 *counts) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    return tandems_walk_host("trew_tandems_host", words, offsets, lengths, n_reads, min_score, out, cap, n, counts,
+                             [&](const unsigned char *base, u32 len, trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+                                 return refined_piece_host(base, len, min_period, max_period, penalty, min_score, x, t_start, t_end);
+                             });
+}
+
+const char *tandems_resolved_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                                  u32 min_score, int candidates, trew_hip_tandem *out, u64 cap, u64 *n, u32 *counts) {
+    if (const char *e = resolve_error(min_period, max_period, penalty, min_score, candidates)) return e;
+    return tandems_walk_host("trew_tandems_resolved_host", words, offsets, lengths, n_reads, min_score, out, cap, n, counts,
+                             [&](const unsigned char *base, u32 len, trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+                                 return resolved_piece_host(base, len, min_period, max_period, penalty, min_score, candidates, x, t_start, t_end);
+                             });
 }
 
 // ---------------------------------------------------------------- units in place under indels: the traceback of the alignment
@@ -1076,20 +1119,21 @@ static void anchor_and_trace_host(const unsigned char *base, u32 n, trew_hip_ref
     R.reserved = rho;
 }
 
-const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
-                           u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_refined *records) {
-    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-    if (!n_items || (cap && !items)) return "trew_decompose_host: null argument";
-    if (n_reads && (!words || !offsets || !lengths)) return "trew_decompose_host: null argument";
-    if (n_reads > 0xffffffffull) return "trew_decompose_host: more than 2^32 - 1 reads";
+// decompose_host and decompose_resolved_host: the walk over the reads with `piece` for the whole read
+template <class PieceFn>
+static const char *decompose_walk_host(const char *name, const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int penalty, u32 min_score,
+                                       trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_refined *records, PieceFn piece) {
+    if (!n_items || (cap && !items)) return named_error(name, "null argument");
+    if (n_reads && (!words || !offsets || !lengths)) return named_error(name, "null argument");
+    if (n_reads > 0xffffffffull) return named_error(name, "more than 2^32 - 1 reads");
     std::vector<unsigned char> base, dirs;
     std::vector<trew_hip_trace_item> mine;
     u64 found = 0;
     for (u64 r = 0; r < n_reads; r++) {
         unpack_bases(words + offsets[r], lengths[r], base);
         trew_hip_refined R;
-        trew_hip_period periods;
-        refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, R, periods);
+        u32 t_start, t_end;
+        piece(base.data(), lengths[r], R, t_start, t_end);
         mine.clear();
         anchor_and_trace_host(base.data(), lengths[r], R, penalty, min_score, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mine);
         append_reversed(mine, items, cap, found);
@@ -1100,16 +1144,36 @@ const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *leng
     return nullptr;
 }
 
+const char *decompose_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                           u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts, trew_hip_refined *records) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    return decompose_walk_host("trew_decompose_host", words, offsets, lengths, n_reads, penalty, min_score, items, cap, n_items, counts, records,
+                               [&](const unsigned char *base, u32 len, trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+                                   return refined_piece_host(base, len, min_period, max_period, penalty, min_score, x, t_start, t_end);
+                               });
+}
+
+const char *decompose_resolved_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                                    u32 min_score, int candidates, trew_hip_trace_item *items, u64 cap, u64 *n_items, u32 *counts,
+                                    trew_hip_refined *records) {
+    if (const char *e = resolve_error(min_period, max_period, penalty, min_score, candidates)) return e;
+    return decompose_walk_host("trew_decompose_resolved_host", words, offsets, lengths, n_reads, penalty, min_score, items, cap, n_items, counts, records,
+                               [&](const unsigned char *base, u32 len, trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+                                   return resolved_piece_host(base, len, min_period, max_period, penalty, min_score, candidates, x, t_start, t_end);
+                               });
+}
+
 // ---------------------------------------------------------------- units in place for every tract of a read, no motif given
 //  tandems_host's piece walk, and for every piece that gives a record decompose_host's anchor and traceback of the
 // piece's bases as a read of their own, its items shifted into read coordinates and numbered by the tract's place in the read.
-const char *dissect_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
-                         u32 min_score, trew_hip_tandem *records, u64 rec_cap, trew_hip_trace_item *items, u64 item_cap, u64 *n_records, u64 *n_items,
-                         u64 *n_rows, u32 *counts) {
-    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
-    if (!n_records || !n_items || (rec_cap && !records) || (item_cap && !items)) return "trew_dissect_host: null argument";
-    if (n_reads && (!words || !offsets || !lengths)) return "trew_dissect_host: null argument";
-    if (n_reads > 0xffffffffull) return "trew_dissect_host: more than 2^32 - 1 reads";
+// dissect_host and dissect_resolved_host: the walk over the pieces of every read with `piece` for each
+template <class PieceFn>
+static const char *dissect_walk_host(const char *name, const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int penalty, u32 min_score,
+                                     trew_hip_tandem *records, u64 rec_cap, trew_hip_trace_item *items, u64 item_cap, u64 *n_records, u64 *n_items,
+                                     u64 *n_rows, u32 *counts, PieceFn piece) {
+    if (!n_records || !n_items || (rec_cap && !records) || (item_cap && !items)) return named_error(name, "null argument");
+    if (n_reads && (!words || !offsets || !lengths)) return named_error(name, "null argument");
+    if (n_reads > 0xffffffffull) return named_error(name, "more than 2^32 - 1 reads");
     struct Tract {
         trew_hip_tandem rec;
         std::vector<trew_hip_trace_item> items;  // last to first
@@ -1129,10 +1193,9 @@ const char *dissect_host(const u32 *words, const u32 *offsets, const u32 *length
             const Todo t = todo.back();
             todo.pop_back();
             trew_hip_refined x;
-            trew_hip_period R;
-            refine_read_host(base.data() + t.lo, t.hi - t.lo, min_period, max_period, penalty, min_score, x, R);  // the piece as a read of its own
-            if (R.scored_period == 0) continue;
-            u32 start = t.lo + R.start, end = t.lo + R.end;  // a weak piece: around the periods tract
+            u32 t_start = 0, t_end = 0;
+            if (!piece(base.data() + t.lo, t.hi - t.lo, x, t_start, t_end)) continue;  // the piece as a read of its own
+            u32 start = t.lo + t_start, end = t.lo + t_end;  // a weak piece: around the periods tract
             if (x.score >= min_score) {
                 Tract tr;
                 anchor_and_trace_host(base.data() + t.lo, t.hi - t.lo, x, penalty, min_score, dirs, trew_hip_trace_item{(u32) r, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
@@ -1162,6 +1225,26 @@ const char *dissect_host(const u32 *words, const u32 *offsets, const u32 *length
     *n_items = found_items;
     if (n_rows) *n_rows = rows;
     return nullptr;
+}
+
+const char *dissect_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                         u32 min_score, trew_hip_tandem *records, u64 rec_cap, trew_hip_trace_item *items, u64 item_cap, u64 *n_records, u64 *n_items,
+                         u64 *n_rows, u32 *counts) {
+    if (const char *e = periods_error(min_period, max_period, penalty, min_score)) return e;
+    return dissect_walk_host("trew_dissect_host", words, offsets, lengths, n_reads, penalty, min_score, records, rec_cap, items, item_cap, n_records,
+                             n_items, n_rows, counts, [&](const unsigned char *base, u32 len, trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+                                 return refined_piece_host(base, len, min_period, max_period, penalty, min_score, x, t_start, t_end);
+                             });
+}
+
+const char *dissect_resolved_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                                  u32 min_score, int candidates, trew_hip_tandem *records, u64 rec_cap, trew_hip_trace_item *items, u64 item_cap,
+                                  u64 *n_records, u64 *n_items, u64 *n_rows, u32 *counts) {
+    if (const char *e = resolve_error(min_period, max_period, penalty, min_score, candidates)) return e;
+    return dissect_walk_host("trew_dissect_resolved_host", words, offsets, lengths, n_reads, penalty, min_score, records, rec_cap, items, item_cap,
+                             n_records, n_items, n_rows, counts, [&](const unsigned char *base, u32 len, trew_hip_refined &x, u32 &t_start, u32 &t_end) {
+                                 return resolved_piece_host(base, len, min_period, max_period, penalty, min_score, candidates, x, t_start, t_end);
+                             });
 }
 
 // `items` sorted by (read, start) with `motif` still the start of each item's tract, `records` sorted by (read, start): motif

@@ -77,6 +77,17 @@ const char *dissect_host(const uint32_t *words, const uint32_t *offsets, const u
                          int penalty, uint32_t min_score, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items, uint64_t item_cap,
                          uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts);
 void sort_dissect_items(trew_hip_trace_item *v, uint64_t n);  // by (read, start)
+// tandems, decompose and dissect with resolve's period choice per piece: the three walks above with resolve_host's
+// winner among the first `candidates` periods of a piece in the place of refine_host's record, and the periods tract of candidate 0
+// for a weak piece; resolve_error is their argument check
+const char *tandems_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                                  int penalty, uint32_t min_score, int candidates, trew_hip_tandem *out, uint64_t cap, uint64_t *n, uint32_t *counts);
+const char *decompose_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                    int max_period, int penalty, uint32_t min_score, int candidates, trew_hip_trace_item *items, uint64_t cap,
+                                    uint64_t *n_items, uint32_t *counts, trew_hip_refined *records);
+const char *dissect_resolved_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                                  int penalty, uint32_t min_score, int candidates, trew_hip_tandem *records, uint64_t rec_cap, trew_hip_trace_item *items,
+                                  uint64_t item_cap, uint64_t *n_records, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts);
 // items sorted by (read, start) whose motif word is the start of their tract, records sorted by (read, start): motif becomes the tract's index in its read
 void number_dissect_items(const trew_hip_tandem *records, uint64_t n_records, trew_hip_trace_item *items, uint64_t n_items);
 
