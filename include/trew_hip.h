@@ -38,8 +38,9 @@ extern "C" {
  * entry points (trew_hip_tandems, trew_hip_tandems_results, trew_tandems_host), the traceback entry points (trew_hip_trace,
  * trew_hip_trace_results, trew_trace_host), the decomposition entry points (trew_hip_decompose, trew_hip_decompose_results,
  * trew_decompose_host), the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host), the
- * resolution entry points (trew_hip_resolve, trew_hip_resolve_results, trew_resolve_host) and the resolved forms of three
- * of them (trew_hip_tandems_resolved, trew_hip_decompose_resolved, trew_hip_dissect_resolved and their _host functions): they
+ * resolution entry points (trew_hip_resolve, trew_hip_resolve_results, trew_resolve_host), the resolved forms of three
+ * of them (trew_hip_tandems_resolved, trew_hip_decompose_resolved, trew_hip_dissect_resolved and their _host functions) and
+ * the monomer entry points (trew_monomer_parse, trew_hip_monomers, trew_hip_monomers_results, trew_monomers_host): they
  * are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
@@ -635,6 +636,45 @@ int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out,
 /* The same records on the host, base by base from the definition, over packed planes. */
 int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                     const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_alignment *out);
+
+/* ---- wraparound alignment for units of up to 256 bases: satellite monomers, given, in noisy reads ----
+ * (where in this read is the array of this monomer, how many copies, and how do its errors split, when the copies have
+ * diverged from each other by a fifth or more and bases are missing or extra?)  Integer-exact.  The definition is that of
+ * trew_hip_alignment, above, word for word: the codes, M_s, an N matches nothing, 1 <= penalty <= 64, the tuple (score, start,
+ * consumed, matches), V, H, the maximum over d = 0 .. k-1 deleted unit bases, the record order (score, -end, start, consumed,
+ * matches), zeros at score 0, and the derived columns.  The only change is 3 <= k <= TREW_MONOMER_MAX.  The record is
+ * trew_hip_alignment, unchanged, laid out out[r * n_monomers + m].
+ *   unit   base j of the unit (j < k) lies in bits [2 (j & 15), 2 (j & 15) + 2) of unit[j >> 4], as in trew_hip_satellite;
+ *          codes T 0, G 1, C 2, A 3; every bit at or above base k is zero
+ * Consequences: for k <= 32 the records equal trew_hip_align's field for field; every rotation of a unit gives the same
+ * record; score_rev(x) = score_fwd(reverse complement of x); the derived columns are never negative.
+ * Limits: one tract per read, monomer and strand, the best one; linear gap cost; k <= 256; no traceback yet (trew_hip_trace
+ * and the measures built on it stay at k <= 32); with penalty 1 and long units a random read scores over its whole length
+ * (match +1 and every error -1 is the linear phase of local alignment), so use penalty >= 2; higher-order repeat units of
+ * kilobases are out of reach.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
+#define TREW_MONOMER_MAX 256
+#define TREW_MONOMERS_MAX 8 /* monomers a call */
+typedef struct {
+    int32_t k; /* 3 .. TREW_MONOMER_MAX */
+    int32_t reserved;
+    uint32_t unit[16];
+} trew_hip_monomer; /* 72 bytes */
+/* 'ACGT...' (upper or lower case, 3 .. 256 bases) -> monomer.  0 or -1; the text of the error through
+ * trew_hip_last_error(NULL).  Touches no device. */
+int trew_monomer_parse(const char *text, trew_hip_monomer *out);
+/* Like trew_hip_align in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode, the penalty check and its error text), with 1 <= n_monomers <= 8, a result buffer and
+ * a staged monomer table of its own that the slot's first call allocates, and independent of the scan and of the other
+ * fifteen kernels.  Argument errors: "n_monomers must be in [1, 8]", "monomers is NULL", "monomer: k must be in [3, 256]",
+ * "monomer: unit has bits at or above base k".  One kernel, a wave per read, for every read length; the largest k of the
+ * call picks how many phases a lane holds. */
+int trew_hip_monomers(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_monomer *monomers, int n_monomers, int penalty);
+/* Waits for the slot and copies the records of its last trew_hip_monomers; arguments as trew_hip_annotate_results. */
+int trew_hip_monomers_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The same records on the host from the definition, over packed planes; the maximum over d in the linear-plus-wrap form
+ * (DESIGN 4.7m), O(n k) a strand. */
+int trew_monomers_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                       const trew_hip_monomer *monomers, int n_monomers, int penalty, trew_hip_alignment *out);
 
 /* ---- de novo repeats under indels: seed a unit, align against it with wraparound, re-vote the unit from the alignment ----
  * (what repeats in this noisy long read, with which unit, from where to where, and how many copies?)  Integer-exact.  The

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_resolve", "trew_hip_resolve_results", "trew_resolve_host",
     "trew_hip_tandems_resolved", "trew_tandems_resolved_host", "trew_hip_decompose_resolved", "trew_decompose_resolved_host",
     "trew_hip_dissect_resolved", "trew_dissect_resolved_host",
+    "trew_monomer_parse", "trew_hip_monomers", "trew_hip_monomers_results", "trew_monomers_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain", "dead_entries")
@@ -185,6 +186,16 @@ class Alignment(C.Structure):
 ALIGN_DTYPE = np.dtype([(name, "<u4") for name, _ in Alignment._fields_])
 assert ALIGN_DTYPE.itemsize == C.sizeof(Alignment) == 40
 
+MONOMER_MAX = 256  # TREW_MONOMER_MAX
+MONOMERS_MAX = 8   # TREW_MONOMERS_MAX
+
+
+class Monomer(C.Structure):
+    _fields_ = [("k", C.c_int32), ("reserved", C.c_int32), ("unit", C.c_uint32 * 16)]
+
+
+assert C.sizeof(Monomer) == 72
+
 
 class TraceItem(C.Structure):
     _fields_ = [(name, C.c_uint32) for name in ("read", "motif", "strand", "start", "bases", "count", "phase", "consumed", "mismatches",
@@ -307,6 +318,10 @@ def load():
     lib.trew_hip_align.argtypes = lib.trew_hip_tracts.argtypes
     lib.trew_hip_align_results.argtypes = lib.trew_hip_tracts_results.argtypes
     lib.trew_align_host.argtypes = lib.trew_tracts_host.argtypes
+    lib.trew_monomer_parse.argtypes = [C.c_char_p, C.POINTER(Monomer)]
+    lib.trew_hip_monomers.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Monomer), i32, i32]
+    lib.trew_hip_monomers_results.argtypes = lib.trew_hip_tracts_results.argtypes
+    lib.trew_monomers_host.argtypes = [vp, vp, vp, u64, C.POINTER(Monomer), i32, i32, vp]
     lib.trew_hip_trace.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Motif), i32, i32, C.c_uint32, u64, u64]
     lib.trew_hip_trace_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(C.c_float)]
     lib.trew_trace_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
@@ -440,6 +455,36 @@ def align_host(reads_or_packed, motifs, penalty=3):
     out = np.zeros((len(offsets), max(nm, 1)), dtype=ALIGN_DTYPE)
     if lib.trew_align_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
         raise TrewHipError("trew_align_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out[:, :nm]
+
+
+def monomer(text):
+    """'ACGT...' (str or bytes, either case, 3 to 256 bases) -> Monomer; raises TrewHipError for other characters or lengths."""
+    lib = load()
+    if isinstance(text, Monomer):
+        return text
+    m = Monomer()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    if lib.trew_monomer_parse(raw, C.byref(m)) != 0:
+        raise TrewHipError("trew_monomer_parse failed: %s" % lib.trew_hip_last_error(None).decode())
+    return m
+
+
+def _monomer_array(monomers):
+    ms = [monomer(m) for m in monomers]
+    return (Monomer * max(len(ms), 1))(*ms), len(ms)
+
+
+def monomers_host(reads_or_packed, monomers, penalty=3):
+    """trew_monomers_host: align_host for units of 3 to 256 bases (texts or Monomer, at most 8), computed on the host from the
+    definition.  reads_or_packed as for annotate_host.  Returns ALIGN_DTYPE records of shape (n_reads, n_monomers); align_columns
+    serves them with k = the monomer's length."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    arr, nm = _monomer_array(monomers)
+    out = np.zeros((len(offsets), max(nm, 1)), dtype=ALIGN_DTYPE)
+    if lib.trew_monomers_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), out.ctypes.data) != 0:
+        raise TrewHipError("trew_monomers_host failed: %s" % lib.trew_hip_last_error(None).decode())
     return out[:, :nm]
 
 
@@ -1018,6 +1063,18 @@ class TrewHip:
         res = self._fetch_records("align", slot, ALIGN_DTYPE, want_ms)
         return res if want_ms else res[0]
 
+    def monomers(self, batch, monomers, penalty=3, slot=0):
+        """Queue `align` for units of 3 to 256 bases: the wraparound alignment of every read of `batch` against `monomers`
+        (texts or Monomer, at most 8) on the slot's stream."""
+        arr, nm = _monomer_array(monomers)
+        self._queue("monomers", slot, batch, arr, nm)
+        self._chk(self.lib.trew_hip_monomers(self.ctx, C.byref(batch), slot, arr, nm, int(penalty)), "trew_hip_monomers")
+
+    def monomers_results(self, slot=0, want_ms=False):
+        """Records of the slot's last monomers: ALIGN_DTYPE array of shape (n_reads, n_monomers) [, kernel ms]."""
+        res = self._fetch_records("monomers", slot, ALIGN_DTYPE, want_ms)
+        return res if want_ms else res[0]
+
     def periods(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, slot=0):
         """Queue the de novo repeat period and unit of every read of `batch` on the slot's stream (no motifs)."""
         self._queue("periods", slot, batch, None, 1)
@@ -1463,6 +1520,17 @@ def align(reads, motifs, penalty=3, device=0):
     with t:
         t.align(b, motifs, penalty)
         return t.align_results()
+
+
+def monomers(reads, monomers, penalty=3, device=0):
+    """`align` for units of 3 to 256 bases on the GPU (satellite monomers in noisy reads): for every read (bytes / str) and
+    monomer (text) the best local alignment against the monomer repeated without end on each strand, as ALIGN_DTYPE records of
+    shape (n_reads, n_monomers); align_columns with k = the monomer's length gives the copies and the error split.  Use a
+    penalty of 2 or more: at 1 a random read scores over its whole length against a long unit."""
+    t, b = _one_batch(reads, device)
+    with t:
+        t.monomers(b, monomers, penalty)
+        return t.monomers_results()
 
 
 def periods(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0):

@@ -1,12 +1,14 @@
 // motif_cli.cpp -- what the command lines share: the argument helpers of every subcommand, and the front end of the six
 // per-read motif subcommands `trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ...` and of the motif-less
-// `trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...` (motif_cli_main).  A
+// `trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...` (motif_cli_main), and of
+// `trew monomers [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ...`, whose units have up to 256 bases and may come from a FASTA file.  A
 // subcommand's own file (annotate.cpp, ...) holds its usage text, its options and their defaults, its rows and its summary.
 // The conventions are those of `short` and `long`: CSV on stdout, messages on stderr, exit status 1 and an empty stdout on an
 // argument error.
 #include <climits>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <sys/stat.h>
 
 #include "trew_host.hpp"
@@ -94,6 +96,27 @@ void candidates_option(MotifCli &cli, int &candidates) {
     };
 }
 
+// The records of a FASTA file: the name is the header's first word, the sequence may span lines.  "" or the complaint.
+static std::string read_fasta(const std::string &path, std::vector<std::string> *names, std::vector<std::string> *units) {
+    std::ifstream in(path);
+    if (!is_regular_file(path) || !in) return path + " : file not found";
+    std::string line;
+    while (std::getline(in, line)) {
+        while (!line.empty() && strchr(" \t\r", line.back())) line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            const size_t end = line.find_first_of(" \t", 1);
+            names->push_back(line.substr(1, end == std::string::npos ? std::string::npos : end - 1));
+            if (names->back().empty()) names->back() = "monomer" + std::to_string(names->size());
+            units->push_back("");
+        } else {
+            if (units->empty()) return path + " : sequence in front of the first header";
+            units->back() += line;
+        }
+    }
+    return names->empty() ? path + " : no FASTA records" : "";
+}
+
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
     Config cfg;
     std::vector<std::string> positional;
@@ -137,13 +160,24 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
             positional.push_back(a);
         }
     }
-    if (positional.empty()) return bad(cli.motif_less ? "FASTQ is required." : "MOTIF is required.");
+    const char *fasta = cli.long_units && cli.fasta ? cli.fasta() : nullptr;
+    if (positional.empty()) return bad(cli.motif_less || fasta ? "FASTQ is required." : cli.long_units ? "MONOMER or --fasta FILE is required." : "MOTIF is required.");
     if (cfg.NUM_THREAD <= 0) return bad("number of threads must be positive.");
     if (const char *e = cli.check()) return bad(e);
 
     // MOTIF[,MOTIF...], printed as given
-    std::vector<std::string> names;
-    if (!cli.motif_less) {
+    std::vector<std::string> names, units;  // units: the bases of a monomer (long_units), typed or from the FASTA file
+    size_t first_file = cli.motif_less ? 0 : 1;
+    if (cli.long_units && fasta) {  // every positional argument is a file
+        const std::string &p0 = positional[0];
+        if (!is_regular_file(p0) && p0.find_first_not_of("ACGTacgt,") == std::string::npos)
+            return bad("MONOMER and --fasta cannot both be given.");
+        const std::string e = read_fasta(fasta, &names, &units);
+        if (!e.empty()) return bad(e);
+        first_file = 0;
+    } else if (cli.long_units && is_regular_file(positional[0])) {
+        return bad("MONOMER or --fasta FILE is required.");
+    } else if (!cli.motif_less) {
         const std::string &list = positional[0];
         size_t pos = 0;
         while (pos <= list.size()) {
@@ -153,10 +187,21 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
             pos = comma + 1;
         }
     }
-    if (names.size() > TREW_ANNOT_MAX_MOTIFS) return bad("At most 8 motifs can be given.");
+    static_assert(TREW_MONOMERS_MAX == TREW_ANNOT_MAX_MOTIFS && TREW_MONOMER_MAX == 256, "the texts below, and the request's n_motifs");
+    if (names.size() > TREW_ANNOT_MAX_MOTIFS) return bad(cli.long_units ? "At most 8 monomers can be given." : "At most 8 motifs can be given.");
     AnnotRequest rq;
     rq.kind = kind;
-    for (const auto &name : names) {
+    if (cli.long_units && units.empty()) units = names;
+    for (size_t m = 0; m < units.size(); m++) {
+        const std::string &unit = units[m], shown = fasta ? names[m] : unit.size() <= 40 ? unit : unit.substr(0, 37) + "...";
+        for (char ch : unit)
+            if (!strchr("ACGTacgt", ch) || !ch) return bad("MONOMER '" + shown + "' must consist of A, C, G and T.");
+        if (unit.size() < 3 || unit.size() > TREW_MONOMER_MAX) return bad("MONOMER '" + shown + "': the length must be in range 3 to 256.");
+        if (trew_monomer_parse(unit.c_str(), &rq.monomers[rq.n_motifs])) return bad(trew_hip_last_error(nullptr));
+        cli.per_motif(rq, rq.n_motifs, (uint32_t) unit.size());
+        rq.n_motifs++;
+    }
+    for (const auto &name : cli.long_units ? std::vector<std::string>() : names) {
         for (char ch : name)
             if (!strchr("ACGTacgt", ch) || !ch) return bad("MOTIF '" + name + "' must consist of A, C, G and T.");
         if (name.size() < 3 || name.size() > 32) return bad("MOTIF '" + name + "': the length must be in range 3 to 32.");
@@ -165,8 +210,8 @@ int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli) {
         rq.n_motifs++;
     }
     if (cli.motif_less) cli.fill(rq);
-    if (positional.size() < (cli.motif_less ? 1u : 2u)) return bad("FASTQ is required.");
-    std::vector<std::string> files(positional.begin() + (cli.motif_less ? 0 : 1), positional.end());
+    if (positional.size() < first_file + 1) return bad("FASTQ is required.");
+    std::vector<std::string> files(positional.begin() + (long) first_file, positional.end());
     for (const auto &f : files)
         if (!is_regular_file(f)) return bad(f + " : file not found");
     if (cfg.NUM_THREAD - 1 > 16 * (int) cfg.devices.size()) cfg.NUM_THREAD = 16 * (int) cfg.devices.size() + 1;

@@ -1178,11 +1178,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve, fold_monomers).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1589,7 +1589,7 @@ static void fold_tandems(const AnnotBatch &x, AnnotFileResult &p) {
 }
 
 // A row per (read, motif, strand) of `recs` whose score reaches MIN_SCORE; align_sums: the sums over those rows.  What trew
-// align prints, and trew trace from the records that come with its items.
+// align and trew monomers print, and trew trace from the records that come with its items.
 static void align_rows(const AnnotBatch &x, const trew_hip_alignment *recs, AnnotFileResult &p) {
     const int nm = x.rq->n_motifs;
     for (uint64_t r = 0; r < x.n; r++)
@@ -1605,7 +1605,8 @@ static void align_rows(const AnnotBatch &x, const trew_hip_alignment *recs, Anno
                 row.strand = s;
                 for (int i = 0; i < 5; i++) row.rec[i] = f[i];
                 p.arows.push_back(row);
-                const AlignColumns c = align_columns(row.rec, (uint32_t) x.rq->motifs[m].k, x.rq->penalty);
+                const uint32_t k = (uint32_t) (x.rq->kind == Measure::Monomers ? x.rq->monomers[m].k : x.rq->motifs[m].k);
+                const AlignColumns c = align_columns(row.rec, k, x.rq->penalty);
                 const uint64_t add[kAlignSums] = {1, (uint64_t) f[2] - f[1], f[0], c.copies, f[3], f[4], c.mismatches, c.insertions, c.deletions};
                 for (int i = 0; i < kAlignSums; i++) p.align_sums[m][s][i] += add[i];
             }
@@ -1620,6 +1621,17 @@ static void fold_align(const AnnotBatch &x, AnnotFileResult &p) {
     trew_hip_alignment *recs = records<trew_hip_alignment>(w, x.n * (uint64_t) nm);
     uint64_t got = 0;
     if (trew_hip_align_results(x.c, w->slot, recs, x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_align_results");
+    align_rows(x, recs, p);
+}
+
+// trew monomers: align_rows of one record per (read, monomer).
+static void fold_monomers(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    if (trew_hip_monomers(x.c, &x.b, w->slot, x.rq->monomers, nm, x.rq->penalty)) hip_die(x.c, "trew_hip_monomers");
+    trew_hip_alignment *recs = records<trew_hip_alignment>(w, x.n * (uint64_t) nm);
+    uint64_t got = 0;
+    if (trew_hip_monomers_results(x.c, w->slot, recs, x.n * (uint64_t) nm, &got, nullptr)) hip_die(x.c, "trew_hip_monomers_results");
     align_rows(x, recs, p);
 }
 
@@ -1854,6 +1866,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Decompose: fold_decompose(x, p); break;
             case Measure::Dissect: fold_dissect(x, p); break;
             case Measure::Resolve: fold_resolve(x, p); break;
+            case Measure::Monomers: fold_monomers(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1945,7 +1958,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     });
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and

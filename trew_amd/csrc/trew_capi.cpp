@@ -25,11 +25,11 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve, _monomers) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMonomers, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers"};
 // whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
-const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false};
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false, false};  // monomers: its own table (stage_monomers), no pattern table
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -42,7 +42,7 @@ struct MeasureState {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, timed = false;  // a call was queued / its kernel was launched between the events
     // the numbers of the last call, set in one place each: queue_records (the fixed-size records), queue_log (the append logs)
-    u64 n = 0;         // annotate, tracts, variants, align: its records, n_reads * n_motifs; periods, refine, resolve: n_reads
+    u64 n = 0;         // annotate, tracts, variants, align, monomers: its records, n_reads * n_motifs; periods, refine, resolve: n_reads
     u64 max_log = 0;   // intervals: its max_intervals; chain: its max_events; repeats, satellites, tandems: their max_records
     u64 n_counts = 0;  // intervals: n_reads * n_motifs * 2; chain: twice that; repeats, satellites, tandems: n_reads
     int n_motifs = 0;  // variants
@@ -89,6 +89,8 @@ struct Slot {
     // the slot's first call of a measure (a context that only scans allocates nothing of it)
     AnnotMotifDev *d_motifs = nullptr, *h_motifs = nullptr;  // kAnnotMaxMotifs pattern tables: device copy and pinned staging
     int motifs_staged = 0;                                   // motifs of h_motifs that d_motifs holds (or will, in stream order)
+    trew_hip_monomer *d_monomers = nullptr, *h_monomers = nullptr;  // monomers: TREW_MONOMERS_MAX (k, unit) entries, staged as the pattern tables are
+    int monomers_staged = 0;
     MeasureState measure[kMeasures];
 };
 
@@ -424,6 +426,8 @@ extern "C" void trew_hip_destroy(trew_hip_ctx *ctx) {
                 if (s.ev[i][j]) (void) hipEventDestroy(s.ev[i][j]);
         if (s.d_motifs) (void) hipFree(s.d_motifs);
         if (s.h_motifs) (void) hipHostFree(s.h_motifs);
+        if (s.d_monomers) (void) hipFree(s.d_monomers);
+        if (s.h_monomers) (void) hipHostFree(s.h_monomers);
         for (auto &st : s.measure) {
             for (void *p : {st.records.p, st.counts.p, st.rows.p, st.aligned.p, (void *) st.counter, (void *) st.hist})
                 if (p) (void) hipFree(p);
@@ -1283,8 +1287,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve
-// The fifteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers
+// The sixteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
 // fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
@@ -1347,6 +1351,17 @@ extern "C" int trew_satellites_host(const uint32_t *words, const uint32_t *offse
 extern "C" int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                                const trew_hip_motif *motifs, int n_motifs, int penalty, trew_hip_alignment *out) {
     return host_status(align_host(words, offsets, lengths, n_reads, motifs, n_motifs, penalty, out));
+}
+
+extern "C" int trew_monomer_parse(const char *text, trew_hip_monomer *out) {
+    const std::string e = monomer_parse(text, out);
+    if (!e.empty()) g_thread_error = g_init_error = e;
+    return e.empty() ? 0 : -1;
+}
+
+extern "C" int trew_monomers_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                  const trew_hip_monomer *monomers, int n_monomers, int penalty, trew_hip_alignment *out) {
+    return host_status(monomers_host(words, offsets, lengths, n_reads, monomers, n_monomers, penalty, out));
 }
 
 extern "C" int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
@@ -1673,6 +1688,47 @@ extern "C" int trew_hip_align(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
 
 extern "C" int trew_hip_align_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
     return results_records(ctx, slot, kAlign, out, cap, sizeof(trew_hip_alignment), n, ms_kernel);
+}
+
+// ---------------------------------------------------------------- wraparound alignment for units of up to 256 bases
+// The (k, unit[16]) entries of a slot, beside the pattern tables and staged as they are (stage_motifs): created by the first
+// call, on the slot's stream in front of the kernel, and only when they changed.
+static int stage_monomers(trew_hip_ctx *ctx, Slot &s, const trew_hip_monomer *monomers, int n_monomers) {
+    const size_t bytes = sizeof(trew_hip_monomer) * (size_t) n_monomers;
+    if (!s.d_monomers) HIPCHK(ctx, hipMalloc((void **) &s.d_monomers, sizeof(trew_hip_monomer) * TREW_MONOMERS_MAX));
+    if (!s.h_monomers) HIPCHK(ctx, hipHostMalloc((void **) &s.h_monomers, sizeof(trew_hip_monomer) * TREW_MONOMERS_MAX, hipHostMallocDefault));
+    trew_hip_monomer tab[TREW_MONOMERS_MAX];
+    for (int m = 0; m < n_monomers; m++) {
+        tab[m] = monomers[m];
+        tab[m].reserved = 0;
+    }
+    if (s.monomers_staged < n_monomers || memcmp(tab, s.h_monomers, bytes) != 0) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));  // an earlier copy may still be reading the staging buffer
+        memcpy(s.h_monomers, tab, bytes);
+        HIPCHK(ctx, hipMemcpyAsync(s.d_monomers, s.h_monomers, bytes, hipMemcpyHostToDevice, s.stream));
+        s.monomers_staged = n_monomers;
+    }
+    return 0;
+}
+
+// Enters through the motif-less path of measure_begin: the monomers' check is one of the measure's own.
+extern "C" int trew_hip_monomers(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_monomer *monomers, int n_monomers, int penalty) {
+    auto own = [&]() -> const char * {
+        if (const char *e = monomers_error(monomers, n_monomers)) return e;
+        return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]" : nullptr;
+    };
+    auto setup = [&](Slot &s, MeasureState &) -> int { return stage_monomers(ctx, s, monomers, n_monomers); };
+    return queue_records(ctx, batch, slot, nullptr, 0, kMonomers, n_monomers > 0 ? n_monomers : 0, sizeof(trew_hip_alignment), own, setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             u32 max_k = 0;
+                             for (int m = 0; m < n_monomers; m++) max_k = std::max(max_k, (u32) monomers[m].k);
+                             HIPCHK(ctx, launch_monomers(s.stream, measure_cu(ctx), db, s.d_monomers, n_monomers, max_k, penalty, (trew_hip_alignment *) st.records.p));
+                             return 0;
+                         });
+}
+
+extern "C" int trew_hip_monomers_results(trew_hip_ctx *ctx, int slot, trew_hip_alignment *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    return results_records(ctx, slot, kMonomers, out, cap, sizeof(trew_hip_alignment), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- units in place under indels: the traceback of the alignment

@@ -54,6 +54,7 @@
 //   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
 //   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: tandems.inc's piece loop, written out once more, with decompose.inc's anchor, rows and walk for every piece that gives a record)
 //   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, resolve_piece.inc's resolve_piece over the whole read, and the record's own four words)
+//   monomers.inc       monomers_wave_kernel<Q> (wraparound alignment for units of up to 256 bases: wraparound.inc's cell, the row over all 64 lanes with Q phases a lane, the maximum over deleted bases as a linear prefix closure plus one wrap)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -103,6 +104,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/decompose.inc"
 #include "kernels/dissect.inc"
 #include "kernels/resolve.inc"
+#include "kernels/monomers.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -493,6 +495,14 @@ hipError_t launch_dissect_resolved(hipStream_t st, u32 n_cu, const DevBatch &B, 
 hipError_t launch_resolve(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, int candidates,
                           trew_hip_resolved *d_out) {
     return launch_wave_per_read(st, n_cu, B, resolve_wave_kernel, min_period, max_period, penalty, min_score, (u32) candidates, (u32 *) d_out);
+}
+
+// the smallest Q with 64 Q >= max_k
+hipError_t launch_monomers(hipStream_t st, u32 n_cu, const DevBatch &B, const trew_hip_monomer *d_monomers, int n_monomers, u32 max_k, int penalty,
+                           trew_hip_alignment *d_out) {
+    if (max_k <= 64u) return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<1>, d_monomers, n_monomers, penalty, (u32 *) d_out);
+    if (max_k <= 128u) return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<2>, d_monomers, n_monomers, penalty, (u32 *) d_out);
+    return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<4>, d_monomers, n_monomers, penalty, (u32 *) d_out);
 }
 
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words) {

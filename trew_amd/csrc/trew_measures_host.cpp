@@ -759,6 +759,112 @@ const char *align_host(const u32 *words, const u32 *offsets, const u32 *lengths,
     return nullptr;
 }
 
+// ---------------------------------------------------------------- wraparound alignment for units of up to 256 bases
+const char *monomer_error(const trew_hip_monomer &m) {
+    if (m.k < 3 || m.k > TREW_MONOMER_MAX) return "monomer: k must be in [3, 256]";
+    for (int j = m.k; j < TREW_MONOMER_MAX; j++)
+        if ((m.unit[j >> 4] >> (2 * (j & 15))) & 3u) return "monomer: unit has bits at or above base k";
+    return nullptr;
+}
+
+const char *monomers_error(const trew_hip_monomer *monomers, int n_monomers) {
+    if (n_monomers < 1 || n_monomers > TREW_MONOMERS_MAX) return "n_monomers must be in [1, 8]";
+    if (!monomers) return "monomers is NULL";
+    for (int m = 0; m < n_monomers; m++)
+        if (const char *e = monomer_error(monomers[m])) return e;
+    return nullptr;
+}
+
+std::string monomer_parse(const char *text, trew_hip_monomer *out) {
+    if (!text || !out) return "trew_monomer_parse: null argument";
+    const size_t k = strlen(text);
+    const std::string shown = k <= 40 ? std::string(text) : std::string(text, 37) + "...";
+    trew_hip_monomer m;
+    memset(&m, 0, sizeof(m));
+    for (size_t i = 0; i < k; i++) {
+        u32 c;
+        switch (text[i]) {
+        case 'T': case 't': c = 0; break;
+        case 'G': case 'g': c = 1; break;
+        case 'C': case 'c': c = 2; break;
+        case 'A': case 'a': c = 3; break;
+        default: return "monomer '" + shown + "': only A, C, G and T are allowed";
+        }
+        if (i < TREW_MONOMER_MAX) m.unit[i >> 4] |= c << (2 * (i & 15));
+    }
+    if (k < 3 || k > TREW_MONOMER_MAX) return "monomer '" + shown + "': the length must be in [3, 256]";
+    m.k = (int32_t) k;
+    *out = m;
+    return "";
+}
+
+// c shifted by d deleted unit bases; a candidate that does not score can never win (it loses to the fresh start every V holds)
+static AlignCell shifted(const AlignCell &c, int penalty, u32 d) { return AlignCell{c.score - (long long) penalty * d, c.start, c.consumed + d, c.matches}; }
+static void take_scoring(AlignCell &into, const AlignCell &cand) {
+    if (cand.score > 0 && into < cand) into = cand;
+}
+
+// wrap_table_host's cells and record for 1 <= k <= 256, the maximum over d in the linear-plus-wrap form: L[j] = max(V[j],
+// L[j-1] shifted by 1) is the maximum over the sources j' <= j; W = L[k-1]; H[j] = max(L[j], W shifted by j + 1), which
+// adds the sources j' > j with exactly d = j + k - j' and, a whole turn and so P k lower, the sources j' <= j once more.
+static void monomer_table_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5]) {
+    std::vector<AlignCell> H((size_t) k, AlignCell{0, 0, 0, 0}), V((size_t) k);
+    AlignCell best{0, 0, 0, 0};
+    u32 best_end = 0;
+    for (u32 i = 1; i <= n; i++) {
+        const u32 c = base[i - 1];
+        for (int j = 0; j < k; j++) {
+            const AlignCell &d = H[(size_t) ((j + k - 1) % k)];
+            const AlignCell D = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
+                                          : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
+            const AlignCell ins{H[(size_t) j].score - penalty, H[(size_t) j].start, H[(size_t) j].consumed, H[(size_t) j].matches};
+            V[(size_t) j] = AlignCell{0, i, 0, 0};
+            if (V[(size_t) j] < D) V[(size_t) j] = D;
+            if (V[(size_t) j] < ins) V[(size_t) j] = ins;
+        }
+        for (int j = 1; j < k; j++) take_scoring(V[(size_t) j], shifted(V[(size_t) j - 1], penalty, 1));
+        const AlignCell W = V[(size_t) k - 1];
+        for (int j = 0; j < k; j++) {
+            take_scoring(V[(size_t) j], shifted(W, penalty, (u32) j + 1u));
+            H[(size_t) j] = V[(size_t) j];
+            if (H[(size_t) j].score > best.score || (H[(size_t) j].score == best.score && best_end == i && best < H[(size_t) j])) {
+                best = H[(size_t) j];
+                best_end = i;
+            }
+        }
+    }
+    if (best.score <= 0) {
+        for (u32 &x : o) x = 0;
+        return;
+    }
+    o[0] = (u32) best.score, o[1] = best.start, o[2] = best_end, o[3] = best.consumed, o[4] = best.matches;
+}
+
+const char *monomers_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_monomer *monomers, int n_monomers,
+                          int penalty, trew_hip_alignment *out) {
+    if (const char *e = monomers_error(monomers, n_monomers)) return e;
+    if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_monomers_host: null argument";
+    std::vector<unsigned char> base;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        for (int m = 0; m < n_monomers; m++) {
+            const int k = monomers[m].k;
+            u32 rec[2][5], t[TREW_MONOMER_MAX];
+            for (int s = 0; s < 2; s++) {
+                for (int j = 0; j < k; j++) {
+                    const int src = s ? k - 1 - j : j;
+                    const u32 code = (monomers[m].unit[src >> 4] >> (2 * (src & 15))) & 3u;
+                    t[j] = s ? 3u - code : code;
+                }
+                monomer_table_host(base.data(), lengths[r], t, k, penalty, rec[s]);
+            }
+            spread_alignment(rec[0], rec[1], out[r * (u64) n_monomers + (u64) m]);
+        }
+    }
+    return nullptr;
+}
+
 // ---------------------------------------------------------------- de novo repeats under indels: seed, align, re-vote
 // the length of the primitive root of u[0 .. k - 1]
 static u32 primitive_root(const u32 *u, u32 k) {

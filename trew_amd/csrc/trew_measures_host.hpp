@@ -51,6 +51,12 @@ const char *chain_host(const uint32_t *words, const uint32_t *offsets, const uin
 // indel-aware motif tract per read: the wraparound alignment of include/trew_hip.h, cell by cell; the checks of tracts_host
 const char *align_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                        int n_motifs, int penalty, trew_hip_alignment *out);
+// wraparound alignment for units of up to 256 bases: align_host's definition and record, the maximum over deleted
+// bases in the linear-plus-wrap form, O(n k) a strand; the monomers' check, and 'ACGT...' -> monomer as motif_parse
+const char *monomers_error(const trew_hip_monomer *monomers, int n_monomers);
+std::string monomer_parse(const char *text, trew_hip_monomer *out);
+const char *monomers_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_monomer *monomers,
+                          int n_monomers, int penalty, trew_hip_alignment *out);
 // de novo repeats under indels: seed, wraparound alignment, re-vote (include/trew_hip.h); the checks of periods_host
 const char *refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                         int penalty, uint32_t min_score, trew_hip_refined *out);
