@@ -15,6 +15,7 @@ import dissect_ref as X
 import oracle as O
 from period_cases import junk, noisy
 from refine_cases import TEL
+from repeat_cases import stack_reads
 from trew_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -46,18 +47,20 @@ def ctx(mode=capi.MODE_SHORT, n_slots=1, words=1 << 22, reads=1 << 18):
     return capi.TrewHip(mode=mode, n_slots=n_slots, max_batch_words=words, max_batch_reads=reads, table_log2_slots=16)
 
 
-def gpu(reads, penalty=3, min_score=24, min_period=1, max_period=32, mode=capi.MODE_SHORT, max_records=1 << 16, max_items=1 << 20, max_rows=BIG):
+def gpu(reads, penalty=3, min_score=24, min_period=1, max_period=32, mode=capi.MODE_SHORT, max_records=1 << 16, max_items=1 << 20, max_rows=BIG,
+        candidates=1):
     words, offsets, lengths = capi.pack_reads(reads)
     with ctx(mode, words=max(len(words) + 64, 1 << 12), reads=max(len(reads), 16)) as t:
-        t.dissect(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score, max_records, max_items, max_rows)
+        t.dissect(t.host_batch(words, offsets, lengths), min_period, max_period, penalty, min_score, max_records, max_items, max_rows,
+                  candidates=candidates)
         out = t.dissect_results()
     assert out[3] <= max_records and out[4] <= max_items and out[5] <= max_rows
     assert out[3] == len(out[0]) == out[2][:, 0].sum() and out[4] == len(out[1]) == out[2][:, 1].sum()
     return out
 
 
-def host(reads, penalty=3, min_score=24, min_period=1, max_period=32):
-    return capi.dissect_host(reads, min_period, max_period, penalty, min_score)
+def host(reads, penalty=3, min_score=24, min_period=1, max_period=32, candidates=1):
+    return capi.dissect_host(reads, min_period, max_period, penalty, min_score, candidates=candidates)
 
 
 @pytest.fixture(scope="module")
@@ -185,6 +188,23 @@ def test_one_long_read_with_three_long_tracts():
     want = host([read])
     assert want[3] == 3 and ((want[0]["end"] - want[0]["start"]) > 2048).all() and want[4] > 1000
     same(gpu([read], mode=capi.MODE_LONG), want)
+
+
+def test_a_deep_stack_with_a_trace_at_every_level():
+    """repeat_cases.stack_reads(): six tracts as a right-deep chain, a left-deep chain and a balanced tree, and a read of 64
+    tracts: entries stay on the stack while tract after tract is traced, up to 64 traces in one read; refine's record of a
+    piece and resolve's"""
+    reads = stack_reads()
+    assert [len(r) for r in reads] == [1767, 1767, 1767, 5672]
+    for candidates in (1, 2):
+        want = host(reads, candidates=candidates)
+        recs, counts = want[0], want[2]
+        assert counts[:, 0].tolist() == [6, 6, 6, 64]
+        assert (counts[:3, 1] >= 18).all() and counts[3, 1] >= 64
+        depth = [int(recs[recs["read"] == r]["depth"].max()) for r in range(4)]
+        assert depth[:3] == [5, 5, 2] and depth[3] >= 4
+        same(gpu(reads, candidates=candidates), want)
+        same(gpu(reads * 3, 64, 8, candidates=candidates), host(reads * 3, 64, 8, candidates=candidates))
 
 
 def test_overflow_of_each_capacity(two_tract):

@@ -1675,11 +1675,22 @@ static void fold_resolve(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
-// trew trace: align_rows from the records that come with the items, and the items of those keys with the read
-// bases of every item that is no run (the signature prints them).  trace_sums: units (the copies of the items with consumed =
-// k count), edited (the items with an error), items.  The workspace holds a row for every base and motif, which no batch
-// exceeds; the log starts at sixteen items per read and motif, and a batch whose log overflows is resubmitted once, with the
-// exact numbers.
+// One item of trace, decompose or dissect against its unit of k bases: its row, with the read bases of an item that is no run
+// (the signature prints them), and the three sums of its unit: units (the copies of the items with consumed = k count), edited
+// (the items with an error), items.
+static void fold_item(const AnnotBatch &x, AnnotFileResult &p, const trew_hip_trace_item &it, uint32_t k, uint64_t &units, uint64_t &edited, uint64_t &items) {
+    const bool errors = it.mismatches || it.insertions || it.deletions;
+    if (it.consumed == k * it.count) units += it.count;
+    edited += errors;
+    items++;
+    const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
+    p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
+                               run ? std::string() : std::string(x.text + x.w->st[it.read] + it.start, (size_t) it.bases)});
+}
+
+// trew trace: align_rows from the records that come with the items, and fold_item for the items of those keys, into
+// trace_sums.  The workspace holds a row for every base and motif, which no batch exceeds; the log starts at sixteen items
+// per read and motif, and a batch whose log overflows is resubmitted once, with the exact numbers.
 static void fold_trace(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
     const int nm = x.rq->n_motifs;
@@ -1701,15 +1712,8 @@ static void fold_trace(const AnnotBatch &x, AnnotFileResult &p) {
     const trew_hip_trace_item *recs = static_cast<const trew_hip_trace_item *>(w->recs);
     for (uint64_t i = 0; i < items; i++) {
         const trew_hip_trace_item &it = recs[i];
-        const uint32_t k = (uint32_t) x.rq->motifs[it.motif].k;
-        const bool errors = it.mismatches || it.insertions || it.deletions;
         uint64_t *sums = p.trace_sums[it.motif][it.strand];
-        if (it.consumed == k * it.count) sums[0] += it.count;
-        sums[1] += errors;
-        sums[2]++;
-        const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
-        p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
-                                   run ? std::string() : std::string(x.text + w->st[it.read] + it.start, (size_t) it.bases)});
+        fold_item(x, p, it, (uint32_t) x.rq->motifs[it.motif].k, sums[0], sums[1], sums[2]);
     }
 }
 
@@ -1754,15 +1758,8 @@ static void fold_decompose(const AnnotBatch &x, AnnotFileResult &p) {
     for (uint64_t i = 0; i < items; i++) {
         const trew_hip_trace_item &it = recs[i];
         const trew_hip_refined &rec = w->drecs[it.read];
-        const uint32_t k = rec.period;
-        const bool errors = it.mismatches || it.insertions || it.deletions;
-        DecomposeUnit &u = p.decompose_units[{k, canonical_unit(rec.unit, (int) k)}];
-        if (it.consumed == k * it.count) u.units += it.count;
-        u.edited += errors;
-        u.items++;
-        const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
-        p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
-                                   run ? std::string() : std::string(x.text + w->st[it.read] + it.start, (size_t) it.bases)});
+        DecomposeUnit &u = p.decompose_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
+        fold_item(x, p, it, rec.period, u.units, u.edited, u.items);
     }
 }
 
@@ -1810,15 +1807,8 @@ static void fold_dissect(const AnnotBatch &x, AnnotFileResult &p) {
         while (q < found.tracts && (trecs[q].read < it.read || (trecs[q].read == it.read && trecs[q].end <= it.start))) q++;
         if (q >= found.tracts) die("internal error: a dissect item without its record");
         const trew_hip_tandem &rec = trecs[q];
-        const uint32_t k = rec.period;
-        const bool errors = it.mismatches || it.insertions || it.deletions;
-        DissectUnit &u = p.dissect_units[{k, canonical_unit(rec.unit, (int) k)}];
-        if (it.consumed == k * it.count) u.units += it.count;
-        u.edited += errors;
-        u.items++;
-        const bool run = it.phase == 0 && it.consumed == k * it.count && !errors;
-        p.xrows.push_back(TraceRow{x.first_read + it.read, x.lengths[it.read], it,
-                                   run ? std::string() : std::string(x.text + w->st[it.read] + it.start, (size_t) it.bases)});
+        DissectUnit &u = p.dissect_units[{rec.period, canonical_unit(rec.unit, (int) rec.period)}];
+        fold_item(x, p, it, rec.period, u.units, u.edited, u.items);
     }
 }
 

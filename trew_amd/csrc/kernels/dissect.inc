@@ -3,7 +3,7 @@
 // piece that gives a record decompose.inc's anchor and traceback of that piece against its own unit.  A kernel beside the scan
 // and beside the other thirteen measures: it reads the same bit planes, takes no pattern table and writes only buffers of its
 // own (a log of records, a log of items, a direction workspace, their three counters, two counts per read).  refine_piece is
-// refine.inc's; the rows and the walk are wrap_fill<32>, wrap_fetch<32> and wrap_walk<32> of kernels/wraparound.inc.
+// refine.inc's, the recursion over the pieces kernels/pieces.inc's, the anchor and the trace of a tract decompose.inc's.
 //
 // Definition (DESIGN 4.7j, include/trew_hip.h).  The pieces of a read, their depths and which of them give a record are those
 // of trew_hip_tandems (4.7g), the weak-piece rule and repeat_worth included.  A piece [lo, hi) with a record X (score >=
@@ -11,16 +11,25 @@
 // complement) and the items of 4.7i for the bases [lo, hi) taken as a read of their own, in read coordinates.  A weak piece
 // yields nothing and claims no rows.
 //
-// The piece loop is tandems.inc's, written out once more: the wave-uniform stack of (lo, hi, depth) across the lanes of three
-// VGPRs, the LONGER child pushed, the SHORTER continued, both children of a weak piece as well; a fix to the walk there or in
-// pieces.inc has to be made here too.  The stack stays live across a trace; the piece at hand, the stack pointer and the
-// record are wave-uniform.  For a strong piece, in the order of decompose.inc: the anchor (lane j < k forms rotation j of the
-// packed unit, two wave maxima and a ballot name the smallest), the claim of end - start rows of 32 bytes with one returning
-// atomic, the rows by wrap_fill<32> from `start` -- refine_piece saw nothing outside the piece and X lies inside it, so the
-// table restarted at X.start holds the path (fact (b) of trace.inc) whatever lies in front of the piece -- the end phase from
-// row `end`, and wrap_walk<32>.  Every cell's start is a read coordinate, as X.start is: the items come out in read
-// coordinates.  `fits` is decided per tract; a tract whose rows do not fit is traced by recomputing its blocks.  The word
-// `motif` of an item holds the tract's start here; the host turns it into the tract's index where it sorts (trew_capi.cpp).
+// The piece loop is walk_pieces of kernels/pieces.inc: the wave-uniform stack of (lo, hi, depth) across the lanes of three
+// VGPRs, the LONGER child pushed, the SHORTER continued, both children of a weak piece as well.  This file is the eval of a
+// piece: refine_piece (or resolve_piece), and for a strong piece whose tract lies inside it unit_anchor and trace_tract of
+// kernels/decompose.inc, where the account of the anchor, the rows, the end phase and the walk stands.  refine_piece saw
+// nothing outside the piece and X lies inside it, so the table restarted at X.start holds the path (fact (b) of trace.inc)
+// whatever lies in front of the piece.  Every cell's start is a read coordinate, as X.start is: the items come out in read
+// coordinates.  The stack stays live across a trace.  The eval hands back the tract and this lane's word of the record from
+// lane 2 on; walk_pieces checks the tract, adds read and depth and appends the record, so a record goes out after its tract's
+// items and not before them: the two logs have counters of their own and the host sorts both, so no result, count or overflow
+// number depends on that order.  walk_pieces checks a tract only after the eval returns, so the eval checks it too: a tract
+// that does not lie inside its piece claims no rows, is handed back without a record, and walk_pieces ends the read.  A weak
+// piece, and a strong one with k = 0, split without a record.  The word `motif` of an item holds the tract's start here; the
+// host turns it into the tract's index where it sorts (trew_capi.cpp).
+//
+// The eval returns at once for a piece without a tract, in front of the words it reads out of a record.  That is for the
+// registers, not for the work: without that return <false> took 55.0 .. 55.1 ms for the long reads of tools/dissect_bench.py
+// on the MI355X against 53.4 on its own walk (76 SGPR spills against 68); with one return behind the if constexpr <true> took
+// 56.0 .. 56.2 against 54.4 .. 54.5 (112 spills against 95); as it stands 53.1 .. 53.2 and 53.9 .. 54.1, 77 and 92 spills
+// (profiles/unit_walk/README.md).
 //
 // Append.  One returning 64-bit vector-memory atomic per record and per item on its log's counter, wave-uniform; eighteen
 // lanes store a record, twelve an item, nothing at or beyond a capacity while the counters keep counting.  counts[read] =
@@ -31,8 +40,8 @@
 // and hi of an entry in the two halves of one register instead saves one VGPR (130): not enough, and not kept.
 
 // kResolved (trew_hip_dissect_resolved, DESIGN 4.7l): resolve_piece (kernels/resolve_piece.inc) in the place of refine_piece, with
-// `candidates` its C; the record stays word i in lane i, the words the walk, the anchor and the rows need are read out of it and the
-// store moves it two lanes up.  <false> is trew_hip_dissect's kernel as it was; it ignores `candidates`.
+// `candidates` its C; the record stays word i in lane i, the words the eval, the anchor and the rows need are read out of it and the
+// record's word is taken two lanes up.  <false> is trew_hip_dissect's kernel as it was; it ignores `candidates`.
 // Registers.  <true> under the four-wave request spills (128 VGPRs, 4 spilled, 20 bytes of scratch; 2 and 12 with the stack, and
 // with the candidate list as well, in LDS: the pressure is in SGPRs), so it does not ask ((1, 8) is a 256-thread block's default):
 // 137 VGPRs, three waves a SIMD, no scratch (DESIGN 4.7l).
@@ -53,126 +62,48 @@ dissect_wave_kernel(DevBatch B, int min_period, int max_period, int penalty, u32
     const int P = rfl_i(penalty);
     const u32 kmin = (u32) rfl_i(min_period), kmax = (u32) rfl_i(max_period);
     const u32 smin = rfl(min_score);
-    const u32 j = lane & 31u;
     uint4 *const blk4 = dis_lds[(threadIdx.x >> 6) & 3u];
-    unsigned char *const blk = (unsigned char *) blk4;
     for (u64 r = wave; r < B.n_reads; r += n_waves) {
         const ReadRef rd = uni(get_read(B, r));
-        u32 st_lo = 0, st_hi = 0, st_d = 0;  // the stack: entry i in lane i
-        u32 sp = 0;                          // entries pending (wave-uniform, at most 32: kernels/pieces.inc)
-        u32 lo = 0, hi = rd.len, depth = 0;  // the piece at hand
-        u32 found = 0, n_items = 0;
-        bool have = repeat_worth(lo, hi, kmin, smin);
-        while (have) {  // wave-uniform
+        u32 n_items = 0;
+        const u32 found = walk_pieces<kTandemWords>(r, rd.len, kmin, smin, rl, [&](u32 lo, u32 hi) __attribute__((always_inline)) {
             u32 rec[16], r_start = 0, r_end = 0;
             u32 won = 0;  // kResolved: the record, word i in lane i
             bool split;
             if constexpr (kResolved) {
                 u32 m;
                 split = resolve_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, rfl(candidates), h, won, r_start, r_end, m, [](u32, u32, u32, bool) {});
+                if (!split) return PieceEval{false, false, 0u, 0u, 0u};
                 rec[0] = record_word(won, 0), rec[4] = record_word(won, 4), rec[5] = record_word(won, 5), rec[6] = record_word(won, 6);
                 rec[7] = record_word(won, 7), rec[8] = record_word(won, 8), rec[12] = record_word(won, 12), rec[13] = record_word(won, 13);
             } else {
                 split = refine_piece(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, r_start, r_end);
+                if (!split) return PieceEval{false, false, 0u, 0u, 0u};
             }
-            u32 a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;  // the children; a the shorter
-            if (split) {
-                const u32 score = rfl(rec[4]);
-                const bool strong = score >= smin;
-                // the children lie around the refined tract, or around the periods tract of a weak piece
-                const u32 start = strong ? rfl(rec[5]) : rfl(r_start), en = strong ? rfl(rec[6]) : rfl(r_end);
-                // a tract lies inside its piece; the pieces below are formed from it, the rows are claimed by it
-                if (!(start >= lo && en <= hi && start < en)) break;
-                const u32 k = rfl(rec[0]);
-                if (strong && k != 0u) {
-                    found++;
-                    const u32 consumed_r = rfl(rec[7]), matches_r = rfl(rec[8]);
-                    // ---- anchor: the smallest rotation of the packed unit, first base most significant
-                    const u64 unit = ((u64) rfl(rec[13]) << 32) | rfl(rec[12]);
-                    const u64 mask = k >= 32u ? ~0ull : (1ull << (2u * k)) - 1ull;
-                    const bool live = lane < k;  // one half forms the rotations
-                    const u32 sh = live ? 2u * lane : 0u;
-                    const u64 rot = sh ? ((unit << sh) | (unit >> ((2u * k - sh) & 63u))) & mask : unit;  // rotation `lane`
-                    const u32 nhi = ~(u32) (rot >> 32), nlo = ~(u32) rot;
-                    bool tie = live & (nhi == wave_max_u32(live ? nhi : 0u));
-                    tie &= nlo == wave_max_u32(tie ? nlo : 0u);
-                    u32 rho = (u32) __builtin_ctzll(__ballot(tie) | (1ull << 63));  // the unit is primitive: one lane is left
-                    rho = rho < k ? rho : 0u;
-                    // ---- the record: read, depth, refine's sixteen words with the anchor in the reserved one
-                    {
-                        u32 x;
-                        if constexpr (kResolved) {
-                            x = lane_read(won, ((lane - 2u) & 63u) << 2);  // word i into lane i + 2
-                            x = lane == 13u ? rho : x;
-                        } else {
-                            x = rec[15];
+            const u32 score = rfl(rec[4]), k = rfl(rec[0]);
+            const bool strong = score >= smin;
+            // the children lie around the refined tract, or around the periods tract of a weak piece
+            const u32 start = strong ? rfl(rec[5]) : rfl(r_start), en = strong ? rfl(rec[6]) : rfl(r_end);
+            // a tract lies inside its piece: one that does not claims no rows, has no record, and walk_pieces ends the read
+            const bool record = split && strong && k != 0u && start >= lo && en <= hi && start < en;
+            u32 x = 0;
+            if (record) {  // wave-uniform
+                const u64 unit = ((u64) rfl(rec[13]) << 32) | rfl(rec[12]);
+                const u32 rho = unit_anchor(unit, k);
+                // the record's words from lane 2 on: refine's sixteen with the anchor in the reserved one
+                if constexpr (kResolved) {
+                    x = lane_read(won, ((lane - 2u) & 63u) << 2);  // word i into lane i + 2
+                    x = lane == 13u ? rho : x;
+                } else {
+                    x = rec[15];
 #pragma unroll
-                            for (int i = 14; i >= 0; i--) x = lane == (u32) (i + 2) ? (i == 11 ? rho : rec[i]) : x;
-                        }
-                        x = lane == 1u ? depth : x;
-                        x = lane == 0u ? (u32) r : x;
-                        log_append<kTandemWords>(rl.counter, rl.recs, rl.cap, x);
-                    }
-                    const u32 at = j >= k ? 0u : j + rho >= k ? j + rho - k : j + rho;  // (j + rho) mod k for the lanes j < k
-                    const u32 tb = j < k ? (u32) (unit >> (2u * (k - 1u - at))) & 3u : 8u;  // M[j]; both halves alike
-                    u32 src[5];
-                    wrap_sources(k, src);
-                    // ---- rows
-                    const u32 rows = en - start;  // >= 1
-                    u64 first = 0;
-                    if (lane == 0) first = atomicAdd(lg.row_counter, (unsigned long long) rows);
-                    first = rfl64(first);
-                    const bool fits = first + (u64) rows <= lg.max_rows;
-                    unsigned char *const ws = lg.rows + first * 32ull;  // formed, not touched, when the rows do not fit
-                    // the end cell: the lowest phase whose cell of row `end` is the record's tuple
-                    auto end_phase = [&](const AlignCell &H) {
-                        const bool is_end = (lane < k) & (H.score == score) & (H.start == start) & (H.consumed == consumed_r) & (H.matches == matches_r);
-                        const u32 p = (u32) __builtin_ctzll(__ballot(is_end) | (1ull << 63));
-                        return p < k ? p : 0u;  // never: the cell exists (fact (b) of trace.inc)
-                    };
-                    u32 jj = 0;
-                    if (fits) {
-                        jj = end_phase(wrap_fill<32>(rd, start, en, start, tb, P, k, src, ws, start));
-                        __threadfence();  // other lanes of this wave read the rows back
-                    }
-                    // ---- the walk and the items, one strand; the item's motif word: the tract's start
-                    n_items += wrap_walk<32>(lg, (u32) r, start, 0u, k, start, en, jj, blk, [&](u32 blk_lo, u32 i) {
-                        if (fits) {
-                            wrap_fetch<32>(ws, start, blk4, blk_lo, i);
-                        } else {
-                            const AlignCell H = wrap_fill<32>(rd, start, i, start, tb, P, k, src, blk, blk_lo);
-                            if (i == en) jj = end_phase(H);  // the first block ends at row `end`
-                        }
-                    });
+                    for (int i = 14; i >= 0; i--) x = lane == (u32) (i + 2) ? (i == 11 ? rho : rec[i]) : x;
                 }
-                const bool left_short = start - lo <= hi - en;
-                a_lo = left_short ? lo : en;
-                a_hi = left_short ? start : hi;
-                b_lo = left_short ? en : lo;
-                b_hi = left_short ? hi : start;
-                depth++;
-                if (repeat_worth(b_lo, b_hi, kmin, smin)) {  // push the longer child
-                    if (lane == sp) {
-                        st_lo = b_lo;
-                        st_hi = b_hi;
-                        st_d = depth;
-                    }
-                    sp++;
-                }
+                // the items, the word `motif` of each the tract's start
+                n_items += trace_tract(rd, lg, (u32) r, start, unit, k, rho, score, start, en, rfl(rec[7]), rfl(rec[8]), P, blk4);
             }
-            if (split && repeat_worth(a_lo, a_hi, kmin, smin)) {  // go on with the shorter child
-                lo = a_lo;
-                hi = a_hi;
-            } else if (sp != 0u) {  // pop
-                sp--;
-                sp = rfl(sp);
-                lo = (u32) __builtin_amdgcn_readlane((int) st_lo, sp);
-                hi = (u32) __builtin_amdgcn_readlane((int) st_hi, sp);
-                depth = (u32) __builtin_amdgcn_readlane((int) st_d, sp);
-            } else {
-                have = false;
-            }
-        }
+            return PieceEval{split, record, start, en, x};
+        });
         if (lane < 2) counts[r * 2ull + lane] = lane ? n_items : found;
     }
 }

@@ -1,8 +1,9 @@
 // kernels/pieces.inc -- part of trew_kernels.hip (included there, inside namespace trew; not a translation unit of its own).
-// What the every-tract measures share below their own work on a piece (repeats.inc, satellites.inc), and the two smaller
-// things that the other wave-per-read kernels share with them: a record's words spread over lanes (periods.inc, refine.inc,
-// tandems.inc) and the append of one record to a log (tandems.inc, trace.inc, decompose.inc).  No kernel here; plain C++ and
-// builtins.  tandems.inc keeps a walk of its own, for the reason given at its head.
+// What the every-tract measures share below their own work on a piece (repeats.inc, satellites.inc, dissect.inc), and the two
+// smaller things that the other wave-per-read kernels share with them: a record's words spread over lanes (periods.inc,
+// refine.inc) and the append of one record to a log (wraparound.inc's wrap_walk for trace.inc, decompose.inc and dissect.inc).
+// No kernel here; plain C++ and builtins.  tandems.inc keeps a walk and an append of its own, the one other copy of the walk,
+// for the reason given at its head.
 //
 //   lane_words    rec[N] -> one word per lane, for one vector store of the record
 //   log_append    one record into an append log: one returning atomic on the counter, kWords lanes store
@@ -40,13 +41,16 @@ __device__ __forceinline__ bool repeat_worth(u32 lo, u32 hi, u32 kmin, u32 min_s
 
 // what a measure's eval(lo, hi) says of the piece [lo, hi); all but `word` wave-uniform
 struct PieceEval {
-    bool split;      // the piece has a record, whose tract is [start, end): its children [lo, start) and [end, hi) are formed
+    bool split;      // the piece has a tract [start, end): its children [lo, start) and [end, hi) are formed
+    bool record;     // and a record of that tract (dissect.inc's weak piece has none: it splits around a tract that is used up)
     u32 start, end;  // the tract, in read coordinates
     u32 word;        // this lane's word of the record from lane 2 on; lanes 0 and 1 get the read and the depth here
 };
 
-// The pieces of read r of `len` bases, depth first: eval(lo, hi) judges a piece, its record goes to lg as
+// The pieces of read r of `len` bases, depth first: eval(lo, hi) judges a piece, its record if it has one goes to lg as
 // {read, depth, eval's words}, and the walk goes on below it.  Returns the records of the read (counted past lg.cap as well).
+// The tract of a split piece is checked here, after eval returns: an eval that does more with a tract than hand it back checks
+// it as well, and hands a tract that fails back without a record, which ends the read.
 //
 // The recursion runs inside the wave, over a wave-uniform stack of (lo, hi, depth) kept across the lanes of three VGPRs
 // (entry i in lane i; a push is a store by one lane, a pop a v_readlane with a uniform index).  After a split the LONGER child
@@ -69,11 +73,13 @@ __device__ __forceinline__ u32 walk_pieces(u64 r, u32 len, u32 kmin, u32 smin, c
             const u32 start = rfl(e.start), end = rfl(e.end);
             // a tract lies inside its piece; the pieces below are formed from it, so nothing else may ever reach them
             if (!(start >= lo && end <= hi && start < end)) break;
-            found++;
-            u32 x = e.word;
-            x = lane == 1u ? depth : x;
-            x = lane == 0u ? (u32) r : x;
-            log_append<kWords>(lg.counter, lg.recs, lg.cap, x);
+            if (e.record) {
+                found++;
+                u32 x = e.word;
+                x = lane == 1u ? depth : x;
+                x = lane == 0u ? (u32) r : x;
+                log_append<kWords>(lg.counter, lg.recs, lg.cap, x);
+            }
             const bool left_short = start - lo <= hi - end;
             a_lo = left_short ? lo : end;
             a_hi = left_short ? start : hi;

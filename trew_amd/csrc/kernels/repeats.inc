@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) repeats_wave_kernel(DevBatch B, int min_p
         const u32 found = walk_pieces<kRepeatWords>(r, rd.len, kmin, smin, lg, [&](u32 lo, u32 hi) __attribute__((always_inline)) {
             u32 rec[10];
             const bool split = period_record(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec);
-            return PieceEval{split, rec[3], rec[4], lane_words<10, 2>(rec, rec[9])};
+            return PieceEval{split, split, rec[3], rec[4], lane_words<10, 2>(rec, rec[9])};
         });
         if (lane == 0) counts[r] = found;
     }

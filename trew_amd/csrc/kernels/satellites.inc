@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(256, 5) satellites_wave_kernel(DevBatch B, int
         const u32 found = walk_pieces<kSatelliteWords>(r, rd.len, kmin, smin, lg, [&](u32 lo, u32 hi) __attribute__((always_inline)) {
             u32 rec[8], unit_word;  // unit_word: lanes 10 .. 25
             const bool split = satellite_record(rd, Piece{lo, hi}, kmin, kmax, P, smin, h, rec, unit_word);
-            return PieceEval{split, rec[3], rec[4], lane_words<8, 2>(rec, unit_word)};
+            return PieceEval{split, split, rec[3], rec[4], lane_words<8, 2>(rec, unit_word)};
         });
         if (lane == 0) counts[r] = found;
     }

@@ -16,8 +16,9 @@
 // shrink), hence at most 32 entries pending; a piece that repeat_worth rules out can have no periods record and is neither
 // pushed nor walked.  It is written out here and does not call walk_pieces, lane_words or log_append: with any of them this
 // kernel's registers come out differently (113 VGPRs instead of 119 with the walk, the hot loops of refine_piece the same
-// instructions on other registers) and long reads take 2.1 to 2.9 % longer on the MI355X (profiles/piece_walk/README.md).  A fix
-// to the walk there has to be made here as well.
+// instructions on other registers) and long reads take 2.1 to 2.9 % longer on the MI355X (profiles/piece_walk/README.md).  So
+// the walk stands twice, there and here (dissect.inc calls walk_pieces: profiles/unit_walk/README.md): a fix to it there has to
+// be made here as well.
 //
 // Append.  One returning 64-bit vector-memory atomic per record on the log's counter, wave-uniform (lane 0 adds, the others
 // get the index through readfirstlane); the record's eighteen words go out from eighteen lanes, those of a record at or beyond

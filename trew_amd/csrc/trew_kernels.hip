@@ -49,10 +49,10 @@
 //   align.inc          align_wave_kernel (indel-aware motif tract per read: wraparound alignment, the row of the table in registers, a phase per lane)
 //   refine.inc         refine_wave_kernel (de novo repeats under indels: periods.inc's period and tract, a seed unit from the longest run of eq_k, align.inc's row step for the alignment, the vote and the re-voted unit)
 //   resolve_piece.inc  resolve_piece (resolve's period choice for one piece: the four best periods.inc scores, refine.inc's refine_at per candidate in a runtime loop, the record with the largest final score held word i in lane i; no kernel)
-//   tandems.inc        tandems_wave_kernel<kResolved> (<true>: resolve_piece in the place of refine_piece, trew_hip_tandems_resolved; so for decompose.inc and dissect.inc) (de novo repeats under indels, every tract of a read: the recursion of pieces.inc over pieces, written out in the kernel, with refine.inc's refine_piece per piece)
+//   tandems.inc        tandems_wave_kernel<kResolved> (<true>: resolve_piece in the place of refine_piece, trew_hip_tandems_resolved; so for decompose.inc and dissect.inc) (de novo repeats under indels, every tract of a read: the recursion of pieces.inc over pieces, written out in the kernel -- the one copy of it beside walk_pieces --, with refine.inc's refine_piece per piece)
 //   trace.inc          trace_wave_kernel (units in place under indels: align.inc's cells with the directions beside them, the tract's rows into a workspace, the walk through LDS blocks into an item log)
-//   decompose.inc      decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log)
-//   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: tandems.inc's piece loop, written out once more, with decompose.inc's anchor, rows and walk for every piece that gives a record)
+//   decompose.inc      unit_anchor, trace_tract, decompose_wave_kernel (units in place with no motif given: refine.inc's refine_piece, the unit's smallest rotation, trace.inc's row step into rows of one strand, the walk into an item log; the anchor and the trace of a tract are dissect.inc's as well)
+//   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: pieces.inc's walk_pieces with an eval that does tandems.inc's work on a piece and calls decompose.inc's unit_anchor and trace_tract for every piece that gives a record)
 //   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, resolve_piece.inc's resolve_piece over the whole read, and the record's own four words)
 //   monomers.inc       monomers_wave_kernel<Q> (wraparound alignment for units of up to 256 bases: wraparound.inc's cell, the row over all 64 lanes with Q phases a lane, the maximum over deleted bases as a linear prefix closure plus one wrap)
 // The launchers (host code) follow the includes.
