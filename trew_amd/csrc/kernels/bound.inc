@@ -58,6 +58,31 @@ __device__ __forceinline__ void prefix_parity<3>(const u32 (&f)[3], u32 (&P)[3])
     P[2] = (y << 1) | top;
 }
 
+// and for 5 words (a whole read of up to 160 bases; P at bits 0 .. 159 -- the parity of all 160 bases has no bit here) as two
+// 64-bit pairs and one word, the carry chained from each into the next.
+// A function of its own, not the specialisation prefix_parity<5>: that one would also be picked up by the 5-word kernels
+// (segment_setup<5>, filter_segment<5>), which are to stay as they are.
+__device__ __forceinline__ void prefix_parity_read5(const u32 (&f)[5], u32 (&P)[5]) {
+    u64 x = ((u64) f[1] << 32) | f[0], y = ((u64) f[3] << 32) | f[2];
+    x ^= x << 1, y ^= y << 1;
+    x ^= x << 2, y ^= y << 2;
+    x ^= x << 4, y ^= y << 4;
+    x ^= x << 8, y ^= y << 8;
+    x ^= x << 16, y ^= y << 16;
+    x ^= x << 32, y ^= y << 32;  // bit i = parity of the pair's own bits 0..i
+    u32 z = word_parity(f[4]);
+    const u32 topx = (u32) (x >> 63);
+    y ^= 0ull - (u64) topx;  // the parity of words 0..1 carries into every bit of words 2..3
+    const u32 topy = (u32) (y >> 63);
+    z ^= 0u - topy;  // and that of words 0..3 into word 4
+    const u64 ex = x << 1, ey = (y << 1) | topx;
+    P[0] = (u32) ex;
+    P[1] = (u32) (ex >> 32);
+    P[2] = (u32) ey;
+    P[3] = (u32) (ey >> 32);
+    P[4] = (z << 1) | topy;
+}
+
 // the segment [0, L) of the planes holds an N (or another non-ACGT byte): non-zero if so
 template <int NW>
 __device__ __forceinline__ u32 segment_has_n(const u32 (&nm)[NW], int L) {

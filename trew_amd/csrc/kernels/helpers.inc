@@ -182,6 +182,31 @@ __device__ __forceinline__ void load_planes_lds(const ReadRef &rd, u32 s, u32 (&
     load_planes_from<NW>((lds_u32) rd.w, rd.nw, s, lo, hi, nm);
 }
 
+// A whole read of at most five triples (160 bases; the prefilter's caller stops at 159, see halves_prefix_read5), loaded once: word j of a plane holds bases 32 j .. 32 j + 31 as they lie in
+// memory, no funnel shift.  For callers that cut several segments out of the same read (the prefilter's joint loop: both halves).
+// The caller knows the read has four or five triples; a lane with fewer (an inactive one: nw = 0) loads nothing and gets zeros,
+// so no address past the read's own triples is ever formed.  The loads of a branch are adjacent: the compiler may merge them.
+struct ReadPlanes5 {
+    u32 lo[5], hi[5], nm[5];
+};
+__device__ __forceinline__ void load_read5(const ReadRef &rd, ReadPlanes5 &r) {
+#pragma unroll
+    for (int j = 0; j < 5; j++) r.lo[j] = r.hi[j] = r.nm[j] = 0u;
+    if (rd.nw >= 4u) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            r.lo[j] = rd.w[3 * j + 0];
+            r.hi[j] = rd.w[3 * j + 1];
+            r.nm[j] = rd.w[3 * j + 2];
+        }
+    }
+    if (rd.nw >= 5u) {
+        r.lo[4] = rd.w[12];
+        r.hi[4] = rd.w[13];
+        r.nm[4] = rd.w[14];
+    }
+}
+
 // Wave-aggregated append to a list in LDS: one atomic on its counter per wave (the first flagged lane's); every flagged lane then
 // calls put(index of its entry).  (A callback, not a return value: the store stays inside the two conditions, as the generated
 // code has it; a capture by value where the callback reads variables the caller goes on using.)

@@ -4,6 +4,13 @@
 
 // ------------------------------------------------------------------ prefilter
 
+// '; MARK name' comments in the ISA around the joint branch's set-up (tools/isa_regions.py), with -DTREW_MARK_READ_SETUP only
+#ifdef TREW_MARK_READ_SETUP
+#define TREW_SETUP_MARK(n) asm volatile("; MARK " #n)
+#else
+#define TREW_SETUP_MARK(n)
+#endif
+
 // (x ^ y) & m as ONE instruction (v_bitop3_b32, truth table 0x28 = (0xF0 ^ 0xCC) & 0xAA)
 __device__ __forceinline__ u32 xor_and(u32 x, u32 y, u32 m) { return __builtin_amdgcn_bitop3_b32(x, y, m, 0x28); }
 
@@ -414,6 +421,49 @@ __device__ __forceinline__ void halves_prefix(const u32 (&lo)[3], const u32 (&hi
     u32 none[3];
     segment_setup<3, false, false>(lo, hi, /* N plane: not read */ lo, L, /* v1, P3: not written */ none, o.P1, o.P2, none);
 }
+// ---- both halves of a read from ONE load and ONE prefix parity per plane (load_read5, helpers.inc) ----
+// The left half starts at base 0 and the right half at base h, 64 <= h < 96 (wave-uniform), of a read of at most 159 bases.
+// three words of a 5-word plane (or prefix parity) from base h on; bs = h & 31
+__device__ __forceinline__ void read5_from64(const u32 (&x)[5], u32 bs, u32 (&o)[3]) {
+    o[0] = alignbit(x[3], x[2], bs);
+    o[1] = alignbit(x[4], x[3], bs);
+    o[2] = alignbit(0u, x[4], bs);
+}
+// an N among bases [0, len) (left: words 0..2, len <= 95) / among bases [h, h + len) (right: words 2..4, h >= 64, h + len <= 159)
+// of the raw N plane: the masks are wave-uniform, the plane is not shifted for them
+__device__ __forceinline__ u32 read5_left_has_n(const u32 (&nm)[5], int len) {
+    return (nm[0] & low_mask(len)) | (nm[1] & low_mask(len - 32)) | (nm[2] & low_mask(len - 64));
+}
+__device__ __forceinline__ u32 read5_right_has_n(const u32 (&nm)[5], int h, int len) {
+    u32 anyn = 0;
+#pragma unroll
+    for (int j = 2; j < 5; j++) anyn |= nm[j] & low_mask(h + len - 32 * j) & ~low_mask(h - 32 * j);
+    return anyn;
+}
+// The prefix parities of both halves from one prefix parity of the whole read per plane.  P of the read at bit i is the parity of
+// bases 0 .. i-1, whatever lies behind them: the left half's words are words 0..2 as they stand, with no mask at all.  From base
+// h on the words hold the right half's own prefix parity XOR the constant P[h], which drops out of every window parity
+// P[i] ^ P[i + k].  filter_halves_uni reads a half's P at bits 0 .. L, bit L included (the last window of a k): range (b) takes
+// bits 0 .. 63 + k with k <= L - 64, range (c) the container's bits s .. s + 63 = L (s = L - 63; a shorter half: s = 0 and the second word masked to COUNT - 32 windows,
+// all below L), and what the 64-bit shift fills with zeros lies at windows >= COUNT, which wm masks -- so neither the bases
+// behind a half (the right half's, for the left one; the extra base of an odd-length read) nor the bits behind the read in its
+// last word are ever looked at, and nothing is masked to a length here.
+// Bit L of the right half is bit h + L of the read, and five words hold the read's P at bits 0 .. 159 only: P[160], the parity
+// of all 160 bases, has no place in them (read5_from64 would hand the loop a zero for it).  So the read has at most 159 bases
+// -- h + L <= 159, the caller's condition; a batch of 160-base reads keeps a prefix parity per half, whose third word has room.
+__device__ __forceinline__ void halves_prefix_read5(const ReadPlanes5 &r, u32 bs, HalvesP &left, HalvesP &right) {
+    u32 P1[5], P2[5];
+    prefix_parity_read5(r.lo, P1);
+    prefix_parity_read5(r.hi, P2);
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        left.P1[j] = P1[j];
+        left.P2[j] = P2[j];
+    }
+    read5_from64(P1, bs, right.P1);
+    read5_from64(P2, bs, right.P2);
+}
+
 // 4-bucket statistics of one half at one k from its two window-parity words (second word already masked to the windows that
 // exist), as SIGNS: with the popcount chains started at -2 ithr (c1x, cx1) and -ithr (c11),
 // p = c10 - ithr, q = c01 - ithr, c = c11 - ithr and t = (COUNT - c00) - jthr - 1 come out of the same two subtractions and one
@@ -911,6 +961,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             u32 hsel = 0;
             if constexpr (NW <= 5) {
                 if (uni) {
+                    TREW_SETUP_MARK(read_setup);
                     ReadRef rd[2];
                     unit_reads(P, B, unit, active, rd);
                     dfr = false;
@@ -931,24 +982,56 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                             if (!(sA.valid && sB.valid && (sA.len == sB.len || uneq) && sA.len <= 95u && sA.kmin == sB.kmin && sA.kmax == sB.kmax &&
                                   klo >= L + 1 - kUniSubsetMax && khi <= L - 32 && klo <= 31))
                                 break;
-                            u32 loA[3], hiA[3], nmA[3], loB[3], hiB[3], nmB[3];
-                            load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, loA, hiA, nmA);
-                            load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, loB, hiB, nmB);
-                            const u32 nA = segment_has_n<3>(nmA, L), nB = segment_has_n<3>(nmB, (int) sB.len);  // an N in the right half's extra base counts
-                            dfr_n = dfr_n || (active && (nA | nB) != 0);
-                            HalvesP hA, hB;
-                            halves_prefix(loA, hiA, L, hA);
-                            halves_prefix(loB, hiB, L, hB);
+                            // The two halves as the loop sees them: p and q, of slots slot_p and slot_q (scalars).  The loop treats both
+                            // alike (one length L, one row of thresholds), so which is which matters only for the slot handed to the drain.
+                            HalvesP hp, hq;
+                            u32 np, nq;
+                            u32 slot_p = (u32) slot0, slot_q = (u32) slot0 + 1u;
+                            // Both halves lie in one read of at most five triples, one from base 0 and the other from a base in
+                            // [64, 96), whatever the k range (reads of 128 .. 159 bases; at 5 .. 32 the joint loop takes 128 .. 153): the
+                            // read is loaded once, and p is its left half.  Pair mode's second mate has its right half in the first
+                            // slot.  Not 160: bit L of the right half's prefix parity would be bit 160 of the read's (halves_prefix_read5).
+                            const bool a_left = sA.start == 0u;
+                            const u32 h = rfl(a_left ? sB.start : sA.start), len_l = rfl(a_left ? sA.len : sB.len), len_r = rfl(a_left ? sB.len : sA.len);
+                            const bool one_load = UL <= 159u && sA.mate == sB.mate && (a_left ? sA.start : sB.start) == 0u && (h >> 5) == 2u && h + len_r <= UL;
+                            if (one_load) {
+                                TREW_SETUP_MARK(one_load);
+                                ReadPlanes5 r;
+                                load_read5(sA.mate ? rd[1] : rd[0], r);
+                                np = read5_left_has_n(r.nm, (int) len_l);
+                                nq = read5_right_has_n(r.nm, (int) h, (int) len_r);  // an N in the right half's extra base counts
+                                if (!a_left) slot_p = (u32) slot0 + 1u, slot_q = (u32) slot0;
+#ifndef TREW_AB_NO_READ_PREFIX
+                                halves_prefix_read5(r, h & 31u, hp, hq);
+#else  // A/B builds (profiles/read_setup): the one load alone, a prefix parity per half as before
+                                u32 loq[3], hiq[3];
+                                read5_from64(r.lo, h & 31u, loq);
+                                read5_from64(r.hi, h & 31u, hiq);
+                                const u32 lop[3] = {r.lo[0], r.lo[1], r.lo[2]}, hip[3] = {r.hi[0], r.hi[1], r.hi[2]};
+                                halves_prefix(lop, hip, L, hp);
+                                halves_prefix(loq, hiq, L, hq);
+#endif
+                            } else {
+                                TREW_SETUP_MARK(two_loads);
+                                u32 loA[3], hiA[3], nmA[3], loB[3], hiB[3], nmB[3];
+                                load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, loA, hiA, nmA);
+                                load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, loB, hiB, nmB);
+                                np = segment_has_n<3>(nmA, L), nq = segment_has_n<3>(nmB, (int) sB.len);  // an N in the right half's extra base counts
+                                halves_prefix(loA, hiA, L, hp);
+                                halves_prefix(loB, hiB, L, hq);
+                            }
+                            dfr_n = dfr_n || (active && (np | nq) != 0);
                             // thresholds: halves of the same length share the row of the first; unequal ones have a joint row
-                            bool passA, passB;
-                            filter_halves_uni(hA, hB, L, klo, khi, joint_thresholds(thr_tab) + (uneq ? 2 + slot0 / 2 : slot0 / 2) * kThrRow, wm_tab, passA, passB);
+                            bool passp, passq;
+                            TREW_SETUP_MARK(joint_loop);
+                            filter_halves_uni(hp, hq, L, klo, khi, joint_thresholds(thr_tab) + (uneq ? 2 + slot0 / 2 : slot0 / 2) * kThrRow, wm_tab, passp, passq);
                             // A half with an N does not fit the model, and a half some k of which passes the 4-bucket test needs its
                             // 8-bucket verdicts: the drain takes them, a lane per read or half (the verdict of a read never depends on
                             // its neighbours, so the flagged reads are the same).  A half that is neither cannot flag the read.
-                            const bool needA = active && (nA != 0 || passA), needB = active && (nB != 0 || passB);
-                            nneed += (u32) needA + (u32) needB;
-                            hsel = needB ? (u32) slot0 + 1u : (needA ? (u32) slot0 : hsel);
-                            dfr = dfr || needA || needB;
+                            const bool needp = active && (np != 0 || passp), needq = active && (nq != 0 || passq);
+                            nneed += (u32) needp + (u32) needq;
+                            hsel = needq ? slot_q : (needp ? slot_p : hsel);  // read only when exactly one half of the unit is needed
+                            dfr = dfr || needp || needq;
                         }
                         // one half to judge, every half went through the joint loop and the drain knows this geometry: the half list
                         dfr_half = uni_drain && slot0 == n_halves && nneed == 1u;
@@ -1028,15 +1111,25 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                 *list_n = at;
                 if (halves || uni_drain) atomicAdd(&g_fallback[halves ? kFallbackHalfDrain : kFallbackUnitDrain], take);
             }
-#ifndef TREW_AB_SKIP_DRAIN
+#if !defined(TREW_AB_SKIP_DRAIN) && !defined(TREW_AB_SKIP_UNIT_DRAIN)
             const u64 any2 = halves      ? (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, gmax_run, cnt_thr)
                              : uni_drain ? (u64) filter_deferred_uni(P, B, unit2, active2, gmax_run, cnt_thr)
                                          : general(unit2, active2);
-#else  // A/B builds (instruction attribution, profiles/r05): the drain computes nothing; its inputs are kept alive
+#else  // A/B builds (instruction attribution): the drain computes nothing and its inputs are kept alive -- both drains with
+       // TREW_AB_SKIP_DRAIN (profiles/r05), the whole-unit drain alone with TREW_AB_SKIP_UNIT_DRAIN (profiles/read_setup)
+#ifdef TREW_AB_SKIP_DRAIN
+            constexpr bool kSkipHalves = true;
+#else
+            constexpr bool kSkipHalves = false;
+#endif
             u64 any2 = 0;
-            u32 keep = unit2 + kind2;
-            asm volatile("" : "+v"(keep), "+v"(any2));
-            (void) keep;
+            if (halves && !kSkipHalves) {
+                any2 = (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, gmax_run, cnt_thr);
+            } else {
+                u32 keep = unit2 + kind2;
+                asm volatile("" : "+v"(keep), "+v"(any2));
+                (void) keep;
+            }
 #endif
             // The reads with an N go to the worklist behind the others of this block-full, next to each other: the exact kernel
             // decides two consecutive reads of the worklist in one pass and runs the N variant of its bounds when either holds

@@ -26,9 +26,9 @@
 // No CUDA shims, no dual paths: HIP for gfx950 only.
 //
 // One translation unit; the device code lives in kernels/*.inc, included below in dependency order:
-//   helpers.inc        funnel shifts, DPP wave reductions, read descriptors (unit_reads), plane loads, wave_append
+//   helpers.inc        funnel shifts, DPP wave reductions, read descriptors (unit_reads), plane loads (load_planes; load_read5: a whole read once), wave_append
 //   bound.inc          the parity-bucket bound's building blocks, shared by the prefilter and the exact kernel: low_mask,
-//                      prefix_parity, segment_setup, segment_has_n, windows_without_n, max_bucket8, class_links
+//                      prefix_parity (prefix_parity_read5: a whole read of five words), segment_setup, segment_has_n, windows_without_n, max_bucket8, class_links
 //   prefilter.inc      filter_kernel<NW> (general path + uniform-geometry fast path + joint halves loop + uniform drains of units and of halves)
 //   count_table.inc    table_add / table_add_wide / spill log
 //   exact_core.inc     LDS working set, eval_k / eval_runs (Lemma A), lane_bounds, decide, emit_k, run_short, run_segment
