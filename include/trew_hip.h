@@ -648,8 +648,8 @@ int trew_align_host(const uint32_t *words, const uint32_t *offsets, const uint32
  *          codes T 0, G 1, C 2, A 3; every bit at or above base k is zero
  * Consequences: for k <= 32 the records equal trew_hip_align's field for field; every rotation of a unit gives the same
  * record; score_rev(x) = score_fwd(reverse complement of x); the derived columns are never negative.
- * Limits: one tract per read, monomer and strand, the best one; linear gap cost; k <= 256; no traceback yet (trew_hip_trace
- * and the measures built on it stay at k <= 32); with penalty 1 and long units a random read scores over its whole length
+ * Limits: one tract per read, monomer and strand, the best one; linear gap cost; k <= 256; counts only (the traceback is
+ * trew_hip_copies, below; the de novo measures built on trew_hip_trace stay at k <= 32); with penalty 1 and long units a random read scores over its whole length
  * (match +1 and every error -1 is the linear phase of local alignment), so use penalty >= 2; higher-order repeat units of
  * kilobases are out of reach.  Also additive: TREW_HIP_ABI_VERSION stays 4. */
 #define TREW_MONOMER_MAX 256
@@ -829,6 +829,39 @@ int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *ite
 int trew_trace_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_motif *motifs,
                     int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
                     trew_hip_alignment *records);
+
+/* ---- copies in place for units of up to 256 bases: the traceback of trew_hip_monomers' alignment, cut into copies ----
+ * (where does each copy of this satellite monomer begin and end, which copies are intact, and which carry which
+ * substitutions, insertions and deletions?)  Integer-exact.  The definition is trew_hip_trace's, above, word for word, with
+ * 3 <= k <= TREW_MONOMER_MAX: the tuples, V and H are those of trew_hip_alignment / trew_hip_monomers; the three tie rules
+ * hold (op in the order F, D, I; the smallest d; the end cell with the smallest phase on equal (score, -end, start,
+ * consumed, matches)); the walk, the segments and the merging of complete exact copies are trew_hip_trace's; the item is
+ * trew_hip_trace_item as it is, its word `motif` holding the monomer's index; the alignment records beside the items are
+ * trew_hip_monomers', field for field.  A key (read, monomer, strand) has items if and only if its score is >= min_score;
+ * items are sorted by (read, monomer, strand, start).  n_rows is defined per key: the sum of end - start over the keys that
+ * have items (the strands are walked one after the other, there is no union range as in trew_hip_trace).
+ * Consequences: those of trew_hip_trace; for k <= 32 the items equal trew_hip_trace's field for field.
+ * Limits: one tract per key, linear gaps, k <= 256; the de novo measures (trew_hip_decompose, trew_hip_dissect,
+ * trew_hip_refine) stay at k <= 32.  Also additive: TREW_HIP_ABI_VERSION stays 4.
+ *
+ * The arguments, checks, error texts, the grow-only log and workspace, the zeroed counters and the retry contract are those of
+ * trew_hip_trace; the units are trew_hip_monomers, checked and staged as trew_hip_monomers does (its four argument errors come
+ * first).  A row of the workspace is 64 Q bytes, Q = 1, 2, 4 the smallest with 64 Q >= the largest k of the call.  One
+ * kernel, a wave per read, for every read length. */
+int trew_hip_copies(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_monomer *monomers, int n_monomers, int penalty,
+                    uint32_t min_score, uint64_t max_items, uint64_t max_rows);
+/* The contract of trew_hip_trace_results, with counts at [read][monomer][strand] and records (n_reads * n_monomers) equal to
+ * trew_hip_monomers'.  Argument errors: "trew_hip_copies_results: n_items and n_rows must not be null",
+ * "trew_hip_copies_results: items must not be null". */
+int trew_hip_copies_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                            uint32_t *counts, trew_hip_alignment *records, float *ms_kernel);
+/* The definition on the host over packed planes: trew_monomers_host's linear-plus-wrap closure with one direction byte a cell
+ * of the traced tract only (op, and one bit for "the smallest d is not 0": DESIGN 4.7n), O(n k) a strand.  *n_items = items
+ * found, *n_rows (may be NULL) the rows as defined above, min(cap, *n_items) items (the first ones of the sorted order),
+ * counts and records as above (each may be NULL). */
+int trew_copies_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_monomer *monomers,
+                     int n_monomers, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                     uint32_t *counts, trew_hip_alignment *records);
 
 /* ---- units in place with no motif given: trew_hip_refine's unit, anchored at a fixed rotation, and trew_hip_trace against it ----
  * (what is this telomere made of, and in which order, when nobody knows its motif?)  Integer-exact (DESIGN 4.7i;

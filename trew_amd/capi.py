@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_tandems_resolved", "trew_tandems_resolved_host", "trew_hip_decompose_resolved", "trew_decompose_resolved_host",
     "trew_hip_dissect_resolved", "trew_dissect_resolved_host",
     "trew_monomer_parse", "trew_hip_monomers", "trew_hip_monomers_results", "trew_monomers_host",
+    "trew_hip_copies", "trew_hip_copies_results", "trew_copies_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain", "dead_entries")
@@ -326,6 +327,9 @@ def load():
     lib.trew_hip_trace_results.argtypes = [vp, i32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(C.c_float)]
     lib.trew_trace_host.argtypes = [vp, vp, vp, u64, C.POINTER(Motif), i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
     lib.trew_hip_decompose.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64, u64]
+    lib.trew_hip_copies.argtypes = [vp, C.POINTER(Batch), i32, C.POINTER(Monomer), i32, i32, C.c_uint32, u64, u64]
+    lib.trew_hip_copies_results.argtypes = lib.trew_hip_trace_results.argtypes
+    lib.trew_copies_host.argtypes = [vp, vp, vp, u64, C.POINTER(Monomer), i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp]
     lib.trew_hip_decompose_results.argtypes = lib.trew_hip_trace_results.argtypes
     lib.trew_decompose_host.argtypes = [vp, vp, vp, u64, i32, i32, i32, C.c_uint32, vp, u64, C.POINTER(u64), vp, vp]
     lib.trew_hip_dissect.argtypes = [vp, C.POINTER(Batch), i32, i32, i32, i32, C.c_uint32, u64, u64, u64]
@@ -625,6 +629,27 @@ def trace_host(reads_or_packed, motifs, penalty=3, min_score=24, cap=None):
     return out, counts[:, :nm], records[:, :nm], found
 
 
+def copies_host(reads_or_packed, monomers, penalty=3, min_score=24, cap=None):
+    """trew_copies_host: trace_host for units of 3 to 256 bases (texts or Monomer, at most 8), computed on the host with one
+    direction byte a cell of the traced tract.  reads_or_packed as for annotate_host.  Returns (TRACE_DTYPE items sorted by
+    (read, monomer, strand, start), counts of shape (n_reads, n_monomers, 2), ALIGN_DTYPE records of shape (n_reads,
+    n_monomers), n_items, n_rows); with `cap` at most that many items."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    arr, nm = _monomer_array(monomers)
+    counts = np.zeros((len(offsets), max(nm, 1), 2), dtype=np.uint32)
+    records = np.zeros((len(offsets), max(nm, 1)), dtype=ALIGN_DTYPE)
+    n_rows = C.c_uint64(0)
+
+    def call(ptr, room, n):
+        if lib.trew_copies_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), arr, nm, int(penalty), int(min_score),
+                                ptr, room, C.byref(n), C.byref(n_rows), counts.ctypes.data, records.ctypes.data) != 0:
+            _host_fail("trew_copies_host")
+
+    out, found = _sized_call(call, TRACE_DTYPE, cap)
+    return out, counts[:, :nm], records[:, :nm], found, int(n_rows.value)
+
+
 def _resolved_call(lib, name, candidates):
     """(entry point, the arguments that follow min_score): `name` itself with candidates = 1, its _resolved form otherwise"""
     if int(candidates) == 1:
@@ -717,6 +742,28 @@ def trace_signature(items, read, k):
         if int(it["strand"]):
             text = "".join(_TRACE_COMP.get(c, "N") for c in reversed(text))
         tokens.append(text if consumed == k else text.lower())
+    return units, edited, " ".join(tokens)
+
+
+def copies_signature(items, read, k, bases=False):
+    """(units, edited, signature) as `trew copies` prints them for the TRACE_DTYPE items of one (read, monomer, strand), given
+    in start order.  For k <= 32, or with bases, trace_signature's text.  Above 32 an item that is no run of complete exact
+    copies prints as `bases:mismatches.insertions.deletions`, an end piece (consumed < k) in parentheses: `=3 172:28.2.1 =1
+    (40:0.0.0)`."""
+    if k <= 32 or bases:
+        return trace_signature(items, read, k)
+    units = edited = 0
+    tokens = []
+    for it in items:
+        count, consumed = int(it["count"]), int(it["consumed"])
+        errors = int(it["mismatches"]) + int(it["insertions"]) + int(it["deletions"])
+        units += count if consumed == k * count else 0
+        edited += errors > 0
+        if consumed == k * count and int(it["phase"]) == 0 and not errors:
+            tokens.append("=%d" % count)
+            continue
+        text = "%d:%d.%d.%d" % (int(it["bases"]), int(it["mismatches"]), int(it["insertions"]), int(it["deletions"]))
+        tokens.append(text if consumed == k else "(" + text + ")")
     return units, edited, " ".join(tokens)
 
 
@@ -866,6 +913,13 @@ def synth_long_ascii(seed, first_read, n_reads):
     st_u64 = np.ascontiguousarray(st, dtype=np.uint64)  # keep the array alive across the call
     lib.trew_synth_long_ascii(seed, first_read, n_reads, st_u64.ctypes.data, out.ctypes.data)
     return out.tobytes(), st, st + lens - 1
+
+
+def _copies_room(batch, nm, max_items, max_rows):
+    """(max_items, max_rows) of a copies call with the defaults of TrewHip.copies filled in: trace's items, and its rows for
+    each strand (a key claims end - start rows of its own)"""
+    items, _ = _trace_room(batch, nm, max_items, 1)
+    return items, (_trace_room(batch, 2 * nm, 1, None)[1] if max_rows is None else int(max_rows))
 
 
 def _trace_room(batch, nm, max_items, max_rows):
@@ -1194,6 +1248,35 @@ class TrewHip:
         if len(out):
             self._chk(self.lib.trew_hip_trace_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n_items), C.byref(n_rows), None, None, None),
                       "trew_hip_trace_results")
+        return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
+
+    def copies(self, batch, monomers, penalty=3, min_score=24, max_items=None, max_rows=None, slot=0):
+        """Queue `trace` for units of 3 to 256 bases: the traceback of the `monomers` alignment of every read of `batch` for
+        `monomers` (texts or Monomer, at most 8) on the slot's stream.  max_items: as for trace; max_rows: the rows of the
+        direction workspace, 64, 128 or 256 bytes each by the largest k of the call.  A key claims end - start rows, so two rows
+        per base and monomer always suffice and are the default where the lengths are known on the host."""
+        arr, nm = _monomer_array(monomers)
+        max_items, max_rows = _copies_room(batch, nm, max_items, max_rows)
+        self._queue("copies", slot, batch, arr, nm, shape=(int(max_items), int(max_rows)))
+        self._chk(self.lib.trew_hip_copies(self.ctx, C.byref(batch), slot, arr, nm, int(penalty), int(min_score), int(max_items), int(max_rows)),
+                  "trew_hip_copies")
+
+    def copies_results(self, slot=0, want_ms=False):
+        """Results of the slot's last copies: (TRACE_DTYPE items sorted by (read, monomer, strand, start), counts of shape
+        (n_reads, n_monomers, 2), ALIGN_DTYPE records of shape (n_reads, n_monomers), n_items, n_rows [, kernel ms]).  n_items >
+        max_items or n_rows > max_rows: no items, everything else is exact; repeat the call with both at least what was reported."""
+        n_items, n_rows = C.c_uint64(0), C.c_uint64(0)
+        ms = C.c_float(0)
+        n_reads, nm, max_items, max_rows = self._queued.get(("copies", slot), (0, 1, 0, 0))
+        counts = np.zeros((n_reads, nm, 2), dtype=np.uint32)
+        records = np.zeros((n_reads, nm), dtype=ALIGN_DTYPE)
+        self._chk(self.lib.trew_hip_copies_results(self.ctx, slot, None, 0, C.byref(n_items), C.byref(n_rows), counts.ctypes.data, records.ctypes.data,
+                                                   C.byref(ms) if want_ms else None), "trew_hip_copies_results")
+        items, rows = int(n_items.value), int(n_rows.value)
+        out = np.zeros(items if items <= max_items and rows <= max_rows else 0, dtype=TRACE_DTYPE)
+        if len(out):
+            self._chk(self.lib.trew_hip_copies_results(self.ctx, slot, out.ctypes.data, len(out), C.byref(n_items), C.byref(n_rows), None, None, None),
+                      "trew_hip_copies_results")
         return (out, counts, records, items, rows, ms.value) if want_ms else (out, counts, records, items, rows)
 
     def decompose(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, max_items=None, max_rows=None, slot=0, candidates=1):
@@ -1610,6 +1693,19 @@ def trace(reads, motifs, penalty=3, min_score=24, device=0, max_items=None, max_
     with t:
         room = _trace_room(b, _motif_array(motifs)[1], max_items, max_rows)
         return _fetch_with_retry(lambda items, rows: t.trace(b, motifs, penalty, min_score, items, rows), t.trace_results, room, (3, 4))[:3]
+
+
+def copies(reads, monomers, penalty=3, min_score=24, device=0, max_items=None, max_rows=None):
+    """`trace` for units of 3 to 256 bases on the GPU (the monomer decomposition of a satellite array): for every read (bytes /
+    str) and monomer (text) the traceback of `monomers`' alignment on each strand whose score reaches min_score, cut into copies
+    of the monomer.  Returns (TRACE_DTYPE items sorted by (read, monomer, strand, start), counts of shape (n_reads, n_monomers,
+    2), ALIGN_DTYPE records of shape (n_reads, n_monomers)); copies_signature turns a key's items into text.  The first
+    call's log and workspace hold max_items items and max_rows rows (defaults: TrewHip.copies'); when more are found the call
+    is repeated once with the exact numbers."""
+    t, b = _one_batch(reads, device)
+    with t:
+        room = _copies_room(b, _monomer_array(monomers)[1], max_items, max_rows)
+        return _fetch_with_retry(lambda items, rows: t.copies(b, monomers, penalty, min_score, items, rows), t.copies_results, room, (3, 4))[:3]
 
 
 def decompose(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0, max_items=None, max_rows=None, candidates=1):

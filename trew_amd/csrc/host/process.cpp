@@ -1182,7 +1182,7 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve, fold_monomers).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve, fold_monomers, fold_copies).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1605,7 +1605,7 @@ static void align_rows(const AnnotBatch &x, const trew_hip_alignment *recs, Anno
                 row.strand = s;
                 for (int i = 0; i < 5; i++) row.rec[i] = f[i];
                 p.arows.push_back(row);
-                const uint32_t k = (uint32_t) (x.rq->kind == Measure::Monomers ? x.rq->monomers[m].k : x.rq->motifs[m].k);
+                const uint32_t k = (uint32_t) (x.rq->kind == Measure::Monomers || x.rq->kind == Measure::Copies ? x.rq->monomers[m].k : x.rq->motifs[m].k);
                 const AlignColumns c = align_columns(row.rec, k, x.rq->penalty);
                 const uint64_t add[kAlignSums] = {1, (uint64_t) f[2] - f[1], f[0], c.copies, f[3], f[4], c.mismatches, c.insertions, c.deletions};
                 for (int i = 0; i < kAlignSums; i++) p.align_sums[m][s][i] += add[i];
@@ -1714,6 +1714,35 @@ static void fold_trace(const AnnotBatch &x, AnnotFileResult &p) {
         const trew_hip_trace_item &it = recs[i];
         uint64_t *sums = p.trace_sums[it.motif][it.strand];
         fold_item(x, p, it, (uint32_t) x.rq->motifs[it.motif].k, sums[0], sums[1], sums[2]);
+    }
+}
+
+// trew copies: fold_trace for monomers.  The workspace and the log are sized as fold_trace's are (a row for every base and
+// monomer: a key claims end - start rows, so a batch in which both strands of long tracts reach MIN_SCORE can exceed it);
+// a batch whose log or workspace overflows is resubmitted once, with the exact numbers.
+static void fold_copies(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const int nm = x.rq->n_motifs;
+    uint64_t bases = 0;
+    for (uint64_t r = 0; r < x.n; r++) bases += x.lengths[r];
+    if (w->arecs.size() < x.n * (size_t) nm) w->arecs.resize(x.n * (size_t) nm);
+    const uint64_t items = fetch_with_retry(
+        p, LogRoom{16 * x.n * (uint64_t) nm + 1024, std::max<uint64_t>(bases * (uint64_t) nm, 1)}, "internal error: the copies log overflowed twice",
+        [&](LogRoom room) {
+            if (trew_hip_copies(x.c, &x.b, w->slot, x.rq->monomers, nm, x.rq->penalty, x.rq->min_score, room.log, room.rows)) hip_die(x.c, "trew_hip_copies");
+        },
+        [&](LogRoom room) {
+            LogRoom need{0, 0};
+            if (trew_hip_copies_results(x.c, w->slot, records<trew_hip_trace_item>(w, room.log), room.log, &need.log, &need.rows, nullptr, w->arecs.data(), nullptr))
+                hip_die(x.c, "trew_hip_copies_results");
+            return need;
+        }).log;
+    align_rows(x, w->arecs.data(), p);
+    const trew_hip_trace_item *recs = static_cast<const trew_hip_trace_item *>(w->recs);
+    for (uint64_t i = 0; i < items; i++) {
+        const trew_hip_trace_item &it = recs[i];
+        uint64_t *sums = p.trace_sums[it.motif][it.strand];
+        fold_item(x, p, it, (uint32_t) x.rq->monomers[it.motif].k, sums[0], sums[1], sums[2]);
     }
 }
 
@@ -1857,6 +1886,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Dissect: fold_dissect(x, p); break;
             case Measure::Resolve: fold_resolve(x, p); break;
             case Measure::Monomers: fold_monomers(x, p); break;
+            case Measure::Copies: fold_copies(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1948,7 +1978,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     });
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers", "copies"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -2027,7 +2057,8 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
         } logs[] = {{Measure::Intervals, "intervals", out.irows.size()}, {Measure::Chain, "items", out.crows.size()},
                     {Measure::Repeats, "tracts", out.rrows.size()},      {Measure::Satellites, "tracts", out.srows.size()},
                     {Measure::Tandems, "tracts", out.trows.size()},      {Measure::Trace, "items", out.xrows.size()},
-                    {Measure::Decompose, "items", out.xrows.size()},     {Measure::Dissect, "items", out.xrows.size()}};
+                    {Measure::Decompose, "items", out.xrows.size()},     {Measure::Dissect, "items", out.xrows.size()},
+                    {Measure::Copies, "items", out.xrows.size()}};
         for (const auto &l : logs)
             if (rq.kind == l.kind)
                 fprintf(stderr, "[trew] %s: %llu %s, %llu batch(es) resubmitted with a larger log\n", file_name, (unsigned long long) l.rows, l.noun,

@@ -33,7 +33,7 @@ static void trace_usage() {
 }
 
 // an item's read bases as the signature prints them: motif orientation, upper case for a complete copy, lower for an end piece
-static std::string trace_unit_text(const TraceRow &row, uint32_t k) {
+std::string trace_unit_text(const TraceRow &row, uint32_t k) {
     std::string t = row.text;
     if (row.it.strand) {
         std::string rc(t.rbegin(), t.rend());

@@ -99,16 +99,16 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ..., trew monomers [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...: the per-read measures.
+// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ..., trew monomers|copies [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...: the per-read measures.
 // One file path for all sixteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp, dissect.cpp, resolve.cpp and monomers.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect, Resolve, Monomers };
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp, dissect.cpp, resolve.cpp, monomers.cpp and copies.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect, Resolve, Monomers, Copies };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
     // a (read, motif) is reported when its longer tract has at least this many bases (variants, chain: MIN_UNITS; intervals: not read)
     uint32_t min_tract[TREW_ANNOT_MAX_MOTIFS];
-    trew_hip_monomer monomers[TREW_MONOMERS_MAX];  // monomers: n_motifs of them, in the place of motifs
+    trew_hip_monomer monomers[TREW_MONOMERS_MAX];  // monomers, copies: n_motifs of them, in the place of motifs
     int n_motifs = 0;
     int penalty = 0;                                      // tracts, periods, repeats, satellites, align, refine, tandems, trace, monomers
     int min_period = 1, max_period = 32;                  // periods, repeats, satellites, refine, tandems (which take no motifs: n_motifs = 0)
@@ -274,7 +274,7 @@ struct MotifCli {
     std::function<void(const AnnotFileResult &total, const std::vector<std::string> &names)> print_summary;
     bool motif_less = false;                      // periods, repeats, satellites, refine, tandems, decompose, dissect, resolve: every positional argument is a file, `names` stays empty
     std::function<void(AnnotRequest &rq)> fill;   // motif_less: the request's parameters
-    bool long_units = false;                      // monomers: the units have 3 to 256 bases and fill the request's `monomers`; `names` holds the typed texts or the FASTA names
+    bool long_units = false;                      // monomers, copies: the units have 3 to 256 bases and fill the request's `monomers`; `names` holds the typed texts or the FASTA names
     std::function<const char *()> fasta;          // long_units: the FILE of --fasta, nullptr when the option was not given; with it every positional argument is a file
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
@@ -304,6 +304,9 @@ int decompose_main(int argc, char **argv);
 int dissect_main(int argc, char **argv);
 int resolve_main(int argc, char **argv);
 int monomers_main(int argc, char **argv);
+int copies_main(int argc, char **argv);
+// an item's read bases as a signature prints them (trace.cpp): motif orientation, upper case for a complete copy, lower for an end piece
+std::string trace_unit_text(const TraceRow &row, uint32_t k);
 uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest rotations of a unit and of its reverse complement: the form of the scan's rows
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement

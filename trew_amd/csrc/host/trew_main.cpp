@@ -2,7 +2,7 @@
 // (and `trew annotate` / `trew tracts` / `trew intervals` / `trew variants` / `trew chain` / `trew align` / `trew trace MOTIF[,MOTIF...] FASTQ...` and
 // `trew monomers [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ...` and
 // `trew periods` / `trew repeats` / `trew satellites` / `trew refine` / `trew tandems` / `trew decompose` / `trew dissect` / `trew resolve FASTQ...`, which have no counterpart in the reference: host/annotate.cpp, host/tracts.cpp,
-// host/intervals.cpp, host/variants.cpp, host/periods.cpp, host/chain.cpp, host/repeats.cpp, host/satellites.cpp, host/align.cpp, host/refine.cpp, host/tandems.cpp, host/trace.cpp, host/decompose.cpp, host/dissect.cpp, host/resolve.cpp, host/monomers.cpp).
+// host/intervals.cpp, host/variants.cpp, host/periods.cpp, host/chain.cpp, host/repeats.cpp, host/satellites.cpp, host/align.cpp, host/refine.cpp, host/tandems.cpp, host/trace.cpp, host/decompose.cpp, host/dissect.cpp, host/resolve.cpp, host/monomers.cpp, host/copies.cpp).
 //
 // Same sub-commands, positional arguments, options, limits and messages as the reference CLI
 // (trew.cpp:22-478): stdout carries the CSV sections, stderr errors/usage, exit code 1 on error.
@@ -33,7 +33,7 @@ static void usage(const char *mode) {
                 "             [--batch_mib N] [--host_pack] [--compat_g1] MIN_MER MAX_MER [SHORT_FASTQ]...\n\n"
                 "Estimate TRM from short-read sequencing data.\n");
     } else {
-        fprintf(stderr, "Usage: trew [--help] [--version] {long,short,annotate,tracts,intervals,variants,periods,chain,repeats,satellites,align,refine,tandems,trace,decompose,dissect,resolve,monomers}\n\nSubcommands:\n  long          Estimate TRM from long-read sequencing data.\n"
+        fprintf(stderr, "Usage: trew [--help] [--version] {long,short,annotate,tracts,intervals,variants,periods,chain,repeats,satellites,align,refine,tandems,trace,decompose,dissect,resolve,monomers,copies}\n\nSubcommands:\n  long          Estimate TRM from long-read sequencing data.\n"
                         "  short         Estimate TRM from short-read sequencing data.\n"
                         "  annotate      Report the reads that carry given repeat motifs and their longest tracts.\n"
                         "  tracts        Report the error-tolerant tracts of given repeat motifs at both ends of every read.\n"
@@ -50,7 +50,8 @@ static void usage(const char *mode) {
                         "  decompose     Report the order of the units of every read's own repeat without a motif given: `refine`'s unit, anchored, and the traceback against it.\n"
                         "  dissect       The same for every repeat tract of every read: `tandems`' tracts, each cut into copies of its own unit.\n"
                         "  resolve       `refine` with the period chosen by alignment: the few best-scoring periods each refined, the best record kept.\n"
-                        "  monomers      `align` for given units of up to 256 bases: arrays of diverged satellite monomers in noisy reads.\n");
+                        "  monomers      `align` for given units of up to 256 bases: arrays of diverged satellite monomers in noisy reads.\n"
+                        "  copies        `trace` for given units of up to 256 bases: where each copy of a satellite monomer lies and which errors it carries.\n");
     }
 }
 
@@ -92,6 +93,7 @@ int main(int argc, char **argv) {
     if (mode == "dissect") return dissect_main(argc, argv);
     if (mode == "resolve") return resolve_main(argc, argv);
     if (mode == "monomers") return monomers_main(argc, argv);
+    if (mode == "copies") return copies_main(argc, argv);
     if (mode != "short" && mode != "long") {
         usage(nullptr);
         return 1;

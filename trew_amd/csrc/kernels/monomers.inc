@@ -44,6 +44,9 @@ __device__ __forceinline__ void mono_take(AlignCell &V, const AlignCell &v, int 
     V = align_pick(take, cand, V);
 }
 
+// bit positions of a cell's direction byte (copies.inc): op in bits 0 .. 1 and hit in bit 7 as in wrap_row's byte, del in bit 2
+constexpr u32 kMonoDel = 4u, kMonoHit = 128u;
+
 // slot `slot` (wave-uniform) of a lane's cells: selects over the unrolled slots
 template <int Q>
 __device__ __forceinline__ AlignCell mono_slot(const AlignCell (&X)[Q], u32 slot) {
@@ -55,12 +58,16 @@ __device__ __forceinline__ AlignCell mono_slot(const AlignCell (&X)[Q], u32 slot
 
 // One row: H of row i - 1 -> H of row i for the read base c against the lane's unit bases tb.  last_lane, last_slot: where
 // phase k - 1 sits; diag_src: the lane slot 0 takes its diagonal from, as a byte index (lane 0: last_lane).
-template <int Q>
-__device__ __forceinline__ void mono_row(AlignCell (&H)[Q], u32 c, const u32 (&tb)[Q], u32 i, int P, u32 lane, u32 diag_src, u32 last_lane,
+// kDirs: the directions are kept and the byte of slot q is returned in bits [8 q, 8 q + 8) (0 without): op | del << 2 |
+// hit << 7, op by the order of the selects as in wrap_row, del: H is strictly larger than V was in front of step (a) -- the
+// smallest d of the cell is not 0 (the proof that one bit carries d stands at the head of copies.inc).
+template <int Q, bool kDirs>
+__device__ __forceinline__ u32 mono_row(AlignCell (&H)[Q], u32 c, const u32 (&tb)[Q], u32 i, int P, u32 lane, u32 diag_src, u32 last_lane,
                                          u32 last_slot) {
     const AlignCell mine = align_pick(lane == last_lane, mono_slot<Q>(H, last_slot), H[Q - 1]);
     const AlignCell prev = align_from(mine, diag_src);
-    AlignCell V[Q];
+    AlignCell V[Q], V0[kDirs ? Q : 1];
+    u32 dirs = 0;
 #pragma unroll
     for (int q = 0; q < Q; q++) {
         const AlignCell d = q ? H[q ? q - 1 : 0] : prev;
@@ -69,7 +76,12 @@ __device__ __forceinline__ void mono_row(AlignCell (&H)[Q], u32 c, const u32 (&t
         V[q] = align_pick(ds > 0, AlignCell{(u32) ds, d.start, d.consumed + 1u, d.matches + (hit ? 1u : 0u)}, AlignCell{0, i, 0, 0});
         const int is = (int) H[q].score - P;
         const AlignCell ins{(u32) is, H[q].start, H[q].consumed, H[q].matches};
-        V[q] = align_pick((is > 0) & align_gt(ins, V[q]), ins, V[q]);
+        const bool by_ins = (is > 0) & align_gt(ins, V[q]);
+        V[q] = align_pick(by_ins, ins, V[q]);
+        if constexpr (kDirs) {
+            V0[q] = V[q];
+            dirs |= ((by_ins ? 2u : ds > 0 ? 1u : 0u) | (hit ? kMonoHit : 0u)) << (8 * q);
+        }
     }
     // (a) inside the lane, then across the lanes: C is the closed cell of phase Q lane - 1 (lane 0: none)
 #pragma unroll
@@ -93,18 +105,27 @@ __device__ __forceinline__ void mono_row(AlignCell (&H)[Q], u32 c, const u32 (&t
     for (int q = 0; q < Q; q++) {
         mono_take(V[q], W, P, (u32) Q * lane + (u32) q + 1u, true);
         H[q] = V[q];
+        if constexpr (kDirs) dirs |= (align_gt(V[q], V0[q]) ? kMonoDel : 0u) << (8 * q);
     }
+    return dirs;
 }
 
-// the largest (score, -end, start, consumed, matches) of the wave, in every lane: one butterfly
-__device__ __forceinline__ void mono_reduce_wave(AlignCell &best, u32 &best_end) {
+// the largest (score, -end, start, consumed, matches[, -phase]) of the wave, in every lane: one butterfly
+template <bool kPhase>
+__device__ __forceinline__ void mono_reduce_wave(AlignCell &best, u32 &best_end, u32 &best_j) {
     const u32 lane = lane_id();
 #pragma unroll
     for (u32 off = 32; off >= 1; off >>= 1) {
         const u32 from = (lane ^ off) << 2;
         const AlignCell o = align_from(best, from);
         const u32 o_end = lane_read(best_end, from);
-        const bool take = o.score != best.score ? o.score > best.score : o_end != best_end ? o_end < best_end : align_gt(o, best);
+        bool take = o.score != best.score ? o.score > best.score : o_end != best_end ? o_end < best_end : align_gt(o, best);
+        if constexpr (kPhase) {
+            const u32 o_j = lane_read(best_j, from);
+            const bool same = (o.score == best.score) & (o_end == best_end) & !align_gt(o, best) & !align_gt(best, o);
+            take = same ? o_j < best_j : take;
+            best_j = take ? o_j : best_j;
+        }
         best = align_pick(take, o, best);
         best_end = take ? o_end : best_end;
     }
@@ -139,21 +160,21 @@ __global__ void __launch_bounds__(256) monomers_wave_kernel(DevBatch B, const tr
                 AlignCell H[Q], best{0, 0, 0, 0};
 #pragma unroll
                 for (int q = 0; q < Q; q++) H[q] = AlignCell{0, 0, 0, 0};
-                u32 best_end = 0;
+                u32 best_end = 0, no_phase = 0;
                 for (u32 w = 0; w < rd.nw; w++) {
                     const u32 lo = rfl(rd.w[3ull * w + 0]), hi = rfl(rd.w[3ull * w + 1]), nm = rfl(rd.w[3ull * w + 2]);
                     const u32 left = rd.len - (w << 5);  // >= 1
                     const u32 nb = left < 32u ? left : 32u;
                     for (u32 b = 0; b < nb; b++) {
                         const u32 i = (w << 5) + b + 1u;
-                        mono_row<Q>(H, base_code(lo, hi, nm, b), tb, i, P, lane, diag_src, last_lane, last_slot);
+                        mono_row<Q, false>(H, base_code(lo, hi, nm, b), tb, i, P, lane, diag_src, last_lane, last_slot);
                         AlignCell top = H[0];
 #pragma unroll
                         for (int q = 1; q < Q; q++) top = align_pick(live[q] & align_gt(H[q], top), H[q], top);
                         wrap_keep_best(top, i, live[0], best, best_end);
                     }
                 }
-                mono_reduce_wave(best, best_end);
+                mono_reduce_wave<false>(best, best_end, no_phase);
                 const u32 x = lane == 0u ? best.score : lane == 1u ? best.start : lane == 2u ? best_end : lane == 3u ? best.consumed : best.matches;
                 if (lane < 5u) out[(r * (u64) n_monomers + (u64) m) * 10ull + 5ull * strand + lane] = x;
             }

@@ -8,7 +8,8 @@
 //   wrap_row                   H of row i - 1 -> H of row i, with the direction byte when asked for
 //   wrap_keep_best, wrap_reduce_half, wrap_store_alignment   the best cell: per lane, per half, as a trew_hip_alignment
 //   wrap_fill, wrap_fetch      the direction bytes of a range of rows: computed, or brought from the workspace into LDS
-//   wrap_walk                  from the end cell down to the fresh start: the items of trew_hip_trace_item
+//   wrap_walk                  from the end cell down to the fresh start: the items of trew_hip_trace_item (copies.inc walks
+//                              its own rows with it: the row size, the rows of a block and the decoder are template parameters)
 //
 // Layout.  The row lives in registers: lanes 0 .. 31 hold the phases j of one strand, lanes 32 .. 63 those of the other (or
 // mirror them), lanes with (lane & 31) >= k are idle: no lane ever reads from them and they keep no best cell.  No lane read
@@ -178,7 +179,9 @@ __device__ __forceinline__ void wrap_fetch(const unsigned char *ws, u32 ws_lo, u
 // column, a run of complete exact copies is emitted when a segment that is none closes behind it.  One returning atomic an
 // item on the log's counter, twelve lanes store its words, nothing at or beyond the capacity while the counter keeps
 // counting.  Returns the number of items.
-template <u32 kRowBytes, class Refill>
+// kBlock: the rows of a block.  kDelBit (copies.inc): bits 2 .. 6 of a byte hold not d but whether d > 0, and the walk emits one
+// `del` column and looks again until the bit is clear.
+template <u32 kRowBytes, u32 kBlock = kTraceBlock, bool kDelBit = false, class Refill>
 __device__ __forceinline__ u32 wrap_walk(const TraceLog &lg, u32 w_read, u32 w_motif, u32 w_strand, u32 k, u32 start, u32 en, u32 &jj,
                                          const unsigned char *blk, Refill refill) {
     const u32 lane = lane_id();
@@ -209,7 +212,7 @@ __device__ __forceinline__ u32 wrap_walk(const TraceLog &lg, u32 w_read, u32 w_m
     };
     while (i > start) {
         if (i <= blk_lo) {  // the next block: the rows blk_lo + 1 .. i
-            blk_lo = i - start > kTraceBlock ? i - kTraceBlock : start;
+            blk_lo = i - start > kBlock ? i - kBlock : start;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             refill(blk_lo, i);
@@ -217,12 +220,17 @@ __device__ __forceinline__ u32 wrap_walk(const TraceLog &lg, u32 w_read, u32 w_m
             __builtin_amdgcn_wave_barrier();
         }
         const unsigned char *row = blk + (i - blk_lo - 1u) * kRowBytes;
-        const u32 d = rfl((u32) row[jj]) >> 2 & 31u;
-        for (u32 q = 0; q < d; q++) {
+        auto del_column = [&]() {
             phase = jj;
             consumed++, del++, cols++;
             if (jj == 0) close();
             jj = jj ? jj - 1u : k - 1u;
+        };
+        if constexpr (kDelBit) {
+            while (rfl((u32) row[jj]) >> 2 & 31u) del_column();
+        } else {
+            const u32 d = rfl((u32) row[jj]) >> 2 & 31u;
+            for (u32 q = 0; q < d; q++) del_column();
         }
         const u32 cell = rfl((u32) row[jj]);
         const u32 op = cell & 3u;

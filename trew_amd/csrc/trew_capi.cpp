@@ -25,11 +25,11 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve, _monomers) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMonomers, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve, _monomers, _copies) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMonomers, kCopies, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers", "copies"};
 // whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
-const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false, false};  // monomers: its own table (stage_monomers), no pattern table
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false, false, false};  // monomers, copies: their own table (stage_monomers), no pattern table
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -1287,8 +1287,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers
-// The sixteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers, copies
+// The seventeen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
 // fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
@@ -1362,6 +1362,12 @@ extern "C" int trew_monomer_parse(const char *text, trew_hip_monomer *out) {
 extern "C" int trew_monomers_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
                                   const trew_hip_monomer *monomers, int n_monomers, int penalty, trew_hip_alignment *out) {
     return host_status(monomers_host(words, offsets, lengths, n_reads, monomers, n_monomers, penalty, out));
+}
+
+extern "C" int trew_copies_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads,
+                                const trew_hip_monomer *monomers, int n_monomers, int penalty, uint32_t min_score, trew_hip_trace_item *items,
+                                uint64_t cap, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts, trew_hip_alignment *records) {
+    return host_status(copies_host(words, offsets, lengths, n_reads, monomers, n_monomers, penalty, min_score, items, cap, n_items, n_rows, counts, records));
 }
 
 extern "C" int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
@@ -1479,6 +1485,7 @@ static int measure_begin(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slo
     return 0;
 }
 static const char *no_own_checks() { return nullptr; }
+static int no_setup(Slot &, MeasureState &) { return 0; }
 
 // A device buffer that only grows.  The fields are zeroed between free and malloc, so that a call that fails here can
 // simply be repeated.
@@ -1524,7 +1531,6 @@ static int queue_records(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slo
     if (need == 0) return 0;
     return timed_launch(ctx, s, st, [&]() -> int { return launch(s, st, db); });
 }
-static int no_setup(Slot &, MeasureState &) { return 0; }
 
 // What a measure with an append log asks of queue_log besides its kernel.
 struct LogShape {
@@ -1534,18 +1540,19 @@ struct LogShape {
     bool zero_counts;        // the kernel adds to its counts (repeats, satellites, tandems); the others store every one of them
     u64 max_rows;            // trace, decompose: the rows of the direction workspace for this call, and a second counter for them; else 0
     u64 aligned_per_read;    // trace: n_motifs alignment records; decompose: one refined record; else 0
-    size_t row_bytes;        // trace: 64, decompose: 32; else 0
+    size_t row_bytes;        // trace: 64, decompose: 32, copies: 64 Q (the call's phases a lane); else 0
     size_t aligned_bytes;    // of one of the records beside the log; else 0
     u64 max_tracts;          // dissect: the capacity of its second log, the records kept in `aligned`, and a third counter for them; else 0
 };
 
-// The queue call of the measures with an append log (intervals, chain, repeats, satellites, tandems, trace, decompose): measure_begin, the
+// The queue call of the measures with an append log (intervals, chain, repeats, satellites, tandems, trace, decompose, dissect, copies): measure_begin, the
 // counter (one word, trace and decompose two, dissect three: a fixed size, allocated on first use), room for the counts, the log and trace's two buffers,
 // then the numbers of the call, all in one place, the counter back to zero -- every call starts from zero, also one without
-// reads, whose results then report nothing found -- and `launch` between the events unless the batch is empty.
-template <class Own, class Launch>
+// reads, whose results then report nothing found -- and `launch` between the events unless the batch is empty.  `setup`: what
+// else the measure keeps on the device (the monomers of copies), as in queue_records.
+template <class Own, class Setup, class Launch>
 static int queue_log(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, Measure which,
-                     const LogShape &shape, Own own, Launch launch) {
+                     const LogShape &shape, Own own, Setup setup, Launch launch) {
     Slot *sp = nullptr;
     DevBatch db;
     if (int rc = measure_begin(ctx, batch, slot, motifs, n_motifs, which, own, &sp, &db)) return rc;
@@ -1558,6 +1565,7 @@ static int queue_log(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, c
     if (int rc = grow(ctx, s, st.counts, n_counts * sizeof(u32))) return rc;
     if (int rc = grow(ctx, s, st.records, shape.max_log * shape.rec_bytes)) return rc;
     if (int rc = grow(ctx, s, st.rows, shape.max_rows * shape.row_bytes)) return rc;
+    if (int rc = setup(s, st)) return rc;
     st.valid = true;
     st.timed = false;
     st.n = n_aligned;
@@ -1744,7 +1752,7 @@ extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
                                            : nullptr;
     };
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, (u64) n_motifs * 2ull, false, max_rows, (u64) n_motifs, 64, sizeof(trew_hip_alignment)};
-    return queue_log(ctx, batch, slot, motifs, n_motifs, kTrace, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+    return queue_log(ctx, batch, slot, motifs, n_motifs, kTrace, shape, own, no_setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         HIPCHK(ctx, launch_trace(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
                                  (u32 *) st.counts.p));
@@ -1752,14 +1760,13 @@ extern "C" int trew_hip_trace(trew_hip_ctx *ctx, const trew_hip_batch *batch, in
     });
 }
 
-extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
-                                      uint32_t *counts, trew_hip_alignment *records, float *ms_kernel) {
-    const char *arg_error = !n_items || !n_rows ? "trew_hip_trace_results: n_items and n_rows must not be null"
-                            : cap && !items     ? "trew_hip_trace_results: items must not be null"
-                                                : nullptr;
+// the results call of trace and copies, whole; null_error, items_error: the texts of the two argument checks
+static int results_traced(trew_hip_ctx *ctx, int slot, Measure which, const char *null_error, const char *items_error, trew_hip_trace_item *items,
+                          uint64_t cap, uint64_t *n_items, uint64_t *n_rows, uint32_t *counts, trew_hip_alignment *records, float *ms_kernel) {
+    const char *arg_error = !n_items || !n_rows ? null_error : cap && !items ? items_error : nullptr;
     Slot *sp = nullptr;
-    if (int rc = fetch_begin(ctx, slot, kTrace, arg_error, &sp)) return rc;
-    const MeasureState &st = sp->measure[kTrace];
+    if (int rc = fetch_begin(ctx, slot, which, arg_error, &sp)) return rc;
+    const MeasureState &st = sp->measure[which];
     unsigned long long found[2] = {0, 0};
     if (int rc = fetch_counted(ctx, st, found, 2, counts)) return rc;
     *n_items = found[0];
@@ -1768,6 +1775,46 @@ extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trac
     // a workspace that overflowed did not stop the walk, but the contract is one: both fit, or no items
     if (int rc = fetch_log(ctx, st, items, cap, found[1] <= st.max_rows ? whole_log(st, found[0]) : 0, sort_trace_items)) return rc;
     return fetch_end(ctx, st, ms_kernel);
+}
+
+extern "C" int trew_hip_trace_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                                      uint32_t *counts, trew_hip_alignment *records, float *ms_kernel) {
+    return results_traced(ctx, slot, kTrace, "trew_hip_trace_results: n_items and n_rows must not be null", "trew_hip_trace_results: items must not be null",
+                          items, cap, n_items, n_rows, counts, records, ms_kernel);
+}
+
+// ---------------------------------------------------------------- copies in place for units of up to 256 bases: the traceback of monomers' alignment
+// As trace: `records` is the item log, `counter` two values (items, rows), `aligned` the trew_hip_alignment of every (read,
+// monomer), `counts` one u32 per (read, monomer, strand); `rows` 64 Q bytes a row, Q the phases a lane holds in this call (the
+// largest k picks it, as in launch_monomers).  Enters through the motif-less path as monomers does; the staged table is the slot's.
+extern "C" int trew_hip_copies(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_monomer *monomers, int n_monomers, int penalty,
+                               uint32_t min_score, uint64_t max_items, uint64_t max_rows) {
+    auto own = [&]() -> const char * {
+        if (const char *e = monomers_error(monomers, n_monomers)) return e;
+        return penalty < 1 || penalty > 64 ? "penalty must be in [1, 64]"
+               : min_score < 1             ? "min_score must be at least 1"
+               : max_items < 1             ? "max_items must be at least 1"
+               : max_rows < 1              ? "max_rows must be at least 1"
+                                           : nullptr;
+    };
+    u32 max_k = 0;
+    for (int m = 0; monomers && m < n_monomers && m < TREW_MONOMERS_MAX; m++) max_k = std::max(max_k, (u32) monomers[m].k);
+    const size_t row_bytes = max_k <= 64u ? 64 : max_k <= 128u ? 128 : 256;
+    const u64 per_read = n_monomers > 0 ? (u64) n_monomers : 0;
+    const LogShape shape = {sizeof(trew_hip_trace_item), max_items, per_read * 2ull, false, max_rows, per_read, row_bytes, sizeof(trew_hip_alignment)};
+    auto setup = [&](Slot &s, MeasureState &) -> int { return stage_monomers(ctx, s, monomers, n_monomers); };
+    return queue_log(ctx, batch, slot, nullptr, 0, kCopies, shape, own, setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+        const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
+        HIPCHK(ctx, launch_copies(s.stream, measure_cu(ctx), db, s.d_monomers, n_monomers, max_k, penalty, min_score, lg, (trew_hip_alignment *) st.aligned.p,
+                                  (u32 *) st.counts.p));
+        return 0;
+    });
+}
+
+extern "C" int trew_hip_copies_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                                       uint32_t *counts, trew_hip_alignment *records, float *ms_kernel) {
+    return results_traced(ctx, slot, kCopies, "trew_hip_copies_results: n_items and n_rows must not be null",
+                          "trew_hip_copies_results: items must not be null", items, cap, n_items, n_rows, counts, records, ms_kernel);
 }
 
 // ---------------------------------------------------------------- units in place with no motif given: refine's unit, anchored, traced
@@ -1782,7 +1829,7 @@ static int queue_decompose(trew_hip_ctx *ctx, const trew_hip_batch *batch, int s
         return resolved ? resolve_error(min_period, max_period, penalty, min_score, candidates) : nullptr;
     };
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 1, false, max_rows, 1, 32, sizeof(trew_hip_refined)};
-    return queue_log(ctx, batch, slot, nullptr, 0, kDecompose, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+    return queue_log(ctx, batch, slot, nullptr, 0, kDecompose, shape, own, no_setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         if (resolved)
             HIPCHK(ctx, launch_decompose_resolved(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, candidates, lg,
@@ -1837,7 +1884,7 @@ static int queue_dissect(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slo
         return resolved ? resolve_error(min_period, max_period, penalty, min_score, candidates) : nullptr;
     };
     const LogShape shape = {sizeof(trew_hip_trace_item), max_items, 2, false, max_rows, 0, 32, sizeof(trew_hip_tandem), max_records};
-    return queue_log(ctx, batch, slot, nullptr, 0, kDissect, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+    return queue_log(ctx, batch, slot, nullptr, 0, kDissect, shape, own, no_setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         const TraceLog lg = {st.counter, (u32 *) st.records.p, st.max_log, st.counter + 1, (unsigned char *) st.rows.p, st.max_rows};
         const RepeatLog rl = {st.counter + 2, (u32 *) st.aligned.p, st.n};
         if (resolved)
@@ -1898,7 +1945,7 @@ extern "C" int trew_hip_intervals(trew_hip_ctx *ctx, const trew_hip_batch *batch
         return max_intervals < 1 ? "max_intervals must be at least 1" : nullptr;
     };
     const LogShape shape = {sizeof(trew_hip_interval), max_intervals, (u64) n_motifs * 2ull, false, 0, 0, 0, 0};
-    return queue_log(ctx, batch, slot, motifs, n_motifs, kIntervals, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+    return queue_log(ctx, batch, slot, motifs, n_motifs, kIntervals, shape, own, no_setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         IntervalRulesDev rd;
         memset(&rd, 0, sizeof(rd));
         for (int m = 0; m < n_motifs; m++) {
@@ -2007,7 +2054,7 @@ extern "C" int trew_hip_resolve_results(trew_hip_ctx *ctx, int slot, trew_hip_re
 extern "C" int trew_hip_chain(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, const trew_hip_motif *motifs, int n_motifs, uint64_t max_events) {
     auto own = [&]() -> const char * { return max_events < 1 ? "max_events must be at least 1" : nullptr; };
     const LogShape shape = {sizeof(uint4), max_events, (u64) n_motifs * 4ull, false, 0, 0, 0, 0};
-    return queue_log(ctx, batch, slot, motifs, n_motifs, kChain, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+    return queue_log(ctx, batch, slot, motifs, n_motifs, kChain, shape, own, no_setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         for (int m = 0; m < n_motifs; m++) st.k[m] = (u32) motifs[m].k;  // a batch without reads has no events to pair
         const ChainLog lg = {st.counter, (uint4 *) st.records.p, st.max_log};
         HIPCHK(ctx, launch_chain(s.stream, measure_cu(ctx), db, s.d_motifs, n_motifs, lg, (u32 *) st.counts.p));
@@ -2077,7 +2124,7 @@ static int queue_tracts(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot
         return max_records < 1 ? "max_records must be at least 1" : nullptr;
     };
     const LogShape shape = {rec_bytes, max_records, 1, true, 0, 0, 0, 0};
-    return queue_log(ctx, batch, slot, nullptr, 0, which, shape, own, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+    return queue_log(ctx, batch, slot, nullptr, 0, which, shape, own, no_setup, [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
         return launch(s, db, RepeatLog{st.counter, (u32 *) st.records.p, st.max_log}, (u32 *) st.counts.p);
     });
 }

@@ -55,6 +55,7 @@
 //   dissect.inc        dissect_wave_kernel (units in place for every tract of a read, no motif given: pieces.inc's walk_pieces with an eval that does tandems.inc's work on a piece and calls decompose.inc's unit_anchor and trace_tract for every piece that gives a record)
 //   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, resolve_piece.inc's resolve_piece over the whole read, and the record's own four words)
 //   monomers.inc       monomers_wave_kernel<Q> (wraparound alignment for units of up to 256 bases: wraparound.inc's cell, the row over all 64 lanes with Q phases a lane, the maximum over deleted bases as a linear prefix closure plus one wrap)
+//   copies.inc         copies_wave_kernel<Q> (copies in place for units of up to 256 bases: monomers.inc's row step with a direction byte a cell, op, hit and one bit for the deleted bases, the strand's rows into a workspace, wraparound.inc's walk through LDS blocks into an item log)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -105,6 +106,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/dissect.inc"
 #include "kernels/resolve.inc"
 #include "kernels/monomers.inc"
+#include "kernels/copies.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -503,6 +505,13 @@ hipError_t launch_monomers(hipStream_t st, u32 n_cu, const DevBatch &B, const tr
     if (max_k <= 64u) return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<1>, d_monomers, n_monomers, penalty, (u32 *) d_out);
     if (max_k <= 128u) return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<2>, d_monomers, n_monomers, penalty, (u32 *) d_out);
     return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<4>, d_monomers, n_monomers, penalty, (u32 *) d_out);
+}
+
+hipError_t launch_copies(hipStream_t st, u32 n_cu, const DevBatch &B, const trew_hip_monomer *d_monomers, int n_monomers, u32 max_k, int penalty,
+                         u32 min_score, const TraceLog &lg, trew_hip_alignment *d_out, u32 *d_counts) {
+    if (max_k <= 64u) return launch_wave_per_read(st, n_cu, B, copies_wave_kernel<1>, d_monomers, n_monomers, penalty, min_score, lg, (u32 *) d_out, d_counts);
+    if (max_k <= 128u) return launch_wave_per_read(st, n_cu, B, copies_wave_kernel<2>, d_monomers, n_monomers, penalty, min_score, lg, (u32 *) d_out, d_counts);
+    return launch_wave_per_read(st, n_cu, B, copies_wave_kernel<4>, d_monomers, n_monomers, penalty, min_score, lg, (u32 *) d_out, d_counts);
 }
 
 hipError_t launch_synth_short(hipStream_t st, u64 seed, u64 first, u64 n, u32 len, u32 *d_words) {

@@ -69,6 +69,11 @@ hipError_t launch_align(hipStream_t st, u32 n_cu, const DevBatch &B, const Annot
 // largest k of d_monomers, which picks the phases a lane holds (1, 2 or 4)
 hipError_t launch_monomers(hipStream_t st, u32 n_cu, const DevBatch &B, const trew_hip_monomer *d_monomers, int n_monomers, u32 max_k, int penalty,
                            trew_hip_alignment *d_out);
+// trew_hip_copies: the wave-per-read kernel of kernels/copies.inc on the grid of launch_tracts; max_k picks Q as in
+// launch_monomers, and with it the row of the workspace (64 Q bytes); both counters of `lg` are zero when the kernel starts;
+// d_out: the alignment records, d_counts: the items of every (read, monomer, strand)
+hipError_t launch_copies(hipStream_t st, u32 n_cu, const DevBatch &B, const trew_hip_monomer *d_monomers, int n_monomers, u32 max_k, int penalty,
+                         u32 min_score, const TraceLog &lg, trew_hip_alignment *d_out, u32 *d_counts);
 // trew_hip_trace: the wave-per-read kernel of kernels/trace.inc on the grid of launch_tracts; both counters of `lg` are zero
 // when the kernel starts; d_out: the alignment records, d_counts: the items of every (read, motif, strand)
 hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, u32 min_score,

@@ -807,37 +807,60 @@ static void take_scoring(AlignCell &into, const AlignCell &cand) {
 // wrap_table_host's cells and record for 1 <= k <= 256, the maximum over d in the linear-plus-wrap form: L[j] = max(V[j],
 // L[j-1] shifted by 1) is the maximum over the sources j' <= j; W = L[k-1]; H[j] = max(L[j], W shifted by j + 1), which
 // adds the sources j' > j with exactly d = j + k - j' and, a whole turn and so P k lower, the sources j' <= j once more.
-static void monomer_table_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5]) {
-    std::vector<AlignCell> H((size_t) k, AlignCell{0, 0, 0, 0}), V((size_t) k);
+// With end_phase also the end cell's phase, the smallest on equal tuples (rule 3 of 4.7h).  With dirs the table is the one
+// that starts from (0, row0, 0, 0) in row row0 and ends with row n, and dirs gets a byte a cell of the rows row0 .. n (row
+// row0: zeros): op of V in bits 0 .. 1 under rule 1, and in bit 2 whether H is strictly larger than V was before the closure
+// -- whether the smallest d of rule 2 is not 0 (4.7n).
+static void monomer_table_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5], int *end_phase = nullptr,
+                               std::vector<unsigned char> *dirs = nullptr, u32 row0 = 0) {
+    std::vector<AlignCell> H((size_t) k, AlignCell{0, row0, 0, 0}), V((size_t) k), V0((size_t) k);
     AlignCell best{0, 0, 0, 0};
     u32 best_end = 0;
-    for (u32 i = 1; i <= n; i++) {
+    int best_j = 0;
+    if (dirs) dirs->assign(((size_t) (n - row0) + 1) * (size_t) k, 0);
+    for (u32 i = row0 + 1; i <= n; i++) {
         const u32 c = base[i - 1];
+        unsigned char *row = dirs ? dirs->data() + (size_t) (i - row0) * (size_t) k : nullptr;
         for (int j = 0; j < k; j++) {
             const AlignCell &d = H[(size_t) ((j + k - 1) % k)];
             const AlignCell D = c == t[j] ? AlignCell{d.score + 1, d.start, d.consumed + 1, d.matches + 1}
                                           : AlignCell{d.score - penalty, d.start, d.consumed + 1, d.matches};
             const AlignCell ins{H[(size_t) j].score - penalty, H[(size_t) j].start, H[(size_t) j].consumed, H[(size_t) j].matches};
             V[(size_t) j] = AlignCell{0, i, 0, 0};
-            if (V[(size_t) j] < D) V[(size_t) j] = D;
-            if (V[(size_t) j] < ins) V[(size_t) j] = ins;
+            unsigned char op = 0;
+            if (V[(size_t) j] < D) V[(size_t) j] = D, op = 1;
+            if (V[(size_t) j] < ins) V[(size_t) j] = ins, op = 2;
+            if (row) row[j] = op, V0[(size_t) j] = V[(size_t) j];
         }
         for (int j = 1; j < k; j++) take_scoring(V[(size_t) j], shifted(V[(size_t) j - 1], penalty, 1));
         const AlignCell W = V[(size_t) k - 1];
         for (int j = 0; j < k; j++) {
             take_scoring(V[(size_t) j], shifted(W, penalty, (u32) j + 1u));
             H[(size_t) j] = V[(size_t) j];
+            if (row && V0[(size_t) j] < H[(size_t) j]) row[j] |= 4;
             if (H[(size_t) j].score > best.score || (H[(size_t) j].score == best.score && best_end == i && best < H[(size_t) j])) {
                 best = H[(size_t) j];
                 best_end = i;
+                best_j = j;
             }
         }
     }
+    if (end_phase) *end_phase = best_j;
     if (best.score <= 0) {
         for (u32 &x : o) x = 0;
         return;
     }
     o[0] = (u32) best.score, o[1] = best.start, o[2] = best_end, o[3] = best.consumed, o[4] = best.matches;
+}
+
+// the codes of strand s of a monomer: the unit's base j, or the complement of its base k - 1 - j
+static void monomer_codes(const trew_hip_monomer &mono, int s, u32 (&t)[TREW_MONOMER_MAX]) {
+    const int k = mono.k;
+    for (int j = 0; j < k; j++) {
+        const int src = s ? k - 1 - j : j;
+        const u32 code = (mono.unit[src >> 4] >> (2 * (src & 15))) & 3u;
+        t[j] = s ? 3u - code : code;
+    }
 }
 
 const char *monomers_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_monomer *monomers, int n_monomers,
@@ -852,11 +875,7 @@ const char *monomers_host(const u32 *words, const u32 *offsets, const u32 *lengt
             const int k = monomers[m].k;
             u32 rec[2][5], t[TREW_MONOMER_MAX];
             for (int s = 0; s < 2; s++) {
-                for (int j = 0; j < k; j++) {
-                    const int src = s ? k - 1 - j : j;
-                    const u32 code = (monomers[m].unit[src >> 4] >> (2 * (src & 15))) & 3u;
-                    t[j] = s ? 3u - code : code;
-                }
+                monomer_codes(monomers[m], s, t);
                 monomer_table_host(base.data(), lengths[r], t, k, penalty, rec[s]);
             }
             spread_alignment(rec[0], rec[1], out[r * (u64) n_monomers + (u64) m]);
@@ -1103,9 +1122,11 @@ void sort_trace_items(trew_hip_trace_item *v, u64 n) {
 // The walk over the direction bytes of wrap_table_host from the end cell (row end, phase j) to the fresh start, against the
 // unit t[0 .. k - 1].  It meets the columns last to first, so a segment closes at its first column, an item is known when
 // its segment closes, and a run of complete exact copies when a segment that is none closes behind it; the items, proto with
-// their own fields filled in, are appended to `items` last to first.
+// their own fields filled in, are appended to `items` last to first.  dirs holds the rows from row0 on.  Bits 2 and above of a
+// byte are d, or (copies_host) whether d > 0: the walk looks again after the d columns, and with the whole d in the byte it then
+// finds 0 (the cell d phases down attains its tuple at d = 0).
 static void wrap_walk_host(const unsigned char *base, const u32 *t, int k, const std::vector<unsigned char> &dirs, u32 end, int j,
-                           trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &items) {
+                           trew_hip_trace_item proto, std::vector<trew_hip_trace_item> &items, u32 row0 = 0) {
     u32 i = end, seg_end = end, consumed = 0, sub = 0, ins = 0, del = 0, phase = 0, cols = 0, run = 0, run_start = 0;
     auto flush_run = [&]() {
         if (!run) return;
@@ -1129,14 +1150,14 @@ static void wrap_walk_host(const unsigned char *base, const u32 *t, int k, const
         consumed = sub = ins = del = phase = cols = 0;
     };
     for (;;) {
-        const u32 d = dirs[(size_t) i * (size_t) k + (size_t) j] >> 2;
-        for (u32 q = 0; q < d; q++) {
-            phase = (u32) j;
-            consumed++, del++, cols++;
-            if (j == 0) close();
-            j = j ? j - 1 : k - 1;
-        }
-        const u32 op = dirs[(size_t) i * (size_t) k + (size_t) j] & 3u;
+        while (const u32 d = dirs[(size_t) (i - row0) * (size_t) k + (size_t) j] >> 2)
+            for (u32 q = 0; q < d; q++) {
+                phase = (u32) j;
+                consumed++, del++, cols++;
+                if (j == 0) close();
+                j = j ? j - 1 : k - 1;
+            }
+        const u32 op = dirs[(size_t) (i - row0) * (size_t) k + (size_t) j] & 3u;
         if (op == 0) break;
         i--;
         cols++;
@@ -1198,6 +1219,49 @@ const char *trace_host(const u32 *words, const u32 *offsets, const u32 *lengths,
         }
     }
     *n_items = found;
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- copies in place for units of up to 256 bases: the traceback of monomers' alignment
+//  monomer_table_host's record and end phase over the whole read; then, from min_score on, the table of the tract
+// alone, started again in row start (fact (b) of 4.7h), with a direction byte a cell, and wrap_walk_host over it: O(n k) time a
+// strand and (end - start + 1) k bytes.
+const char *copies_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, const trew_hip_monomer *monomers, int n_monomers,
+                        int penalty, u32 min_score, trew_hip_trace_item *items, u64 cap, u64 *n_items, u64 *n_rows, u32 *counts,
+                        trew_hip_alignment *records) {
+    if (const char *e = monomers_error(monomers, n_monomers)) return e;
+    if (penalty < 1 || penalty > 64) return "penalty must be in [1, 64]";
+    if (min_score < 1) return "min_score must be at least 1";
+    if (!n_items || (cap && !items)) return "trew_copies_host: null argument";
+    if (n_reads && (!words || !offsets || !lengths)) return "trew_copies_host: null argument";
+    if (n_reads > 0xffffffffull) return "trew_copies_host: more than 2^32 - 1 reads";
+    std::vector<unsigned char> base, dirs;
+    std::vector<trew_hip_trace_item> mine;
+    u64 found = 0, rows = 0;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        for (int m = 0; m < n_monomers; m++) {
+            const int k = monomers[m].k;
+            u32 rec[2][5], again[5], t[TREW_MONOMER_MAX];
+            for (int s = 0; s < 2; s++) {
+                int j = 0;
+                monomer_codes(monomers[m], s, t);
+                monomer_table_host(base.data(), lengths[r], t, k, penalty, rec[s], &j);
+                mine.clear();
+                if (rec[s][0] >= min_score) {
+                    monomer_table_host(base.data(), rec[s][2], t, k, penalty, again, nullptr, &dirs, rec[s][1]);
+                    wrap_walk_host(base.data(), t, k, dirs, rec[s][2], j, trew_hip_trace_item{(u32) r, (u32) m, (u32) s, 0, 0, 0, 0, 0, 0, 0, 0, 0}, mine,
+                                   rec[s][1]);
+                    rows += rec[s][2] - rec[s][1];
+                }
+                append_reversed(mine, items, cap, found);
+                if (counts) counts[(r * (u64) n_monomers + (u64) m) * 2ull + (u64) s] = (u32) mine.size();
+            }
+            if (records) spread_alignment(rec[0], rec[1], records[r * (u64) n_monomers + (u64) m]);
+        }
+    }
+    *n_items = found;
+    if (n_rows) *n_rows = rows;
     return nullptr;
 }
 

@@ -74,6 +74,12 @@ const char *trace_host(const uint32_t *words, const uint32_t *offsets, const uin
                        int n_motifs, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
                        trew_hip_alignment *records);
 void sort_trace_items(trew_hip_trace_item *v, uint64_t n);  // by (read, motif, strand, start)
+// copies in place for units of up to 256 bases: monomers_host's table with trace_host's tie rules, a direction
+// byte a cell of the traced tract only (one bit for the deleted bases), O(n k) a strand; *n_rows (may be NULL): the sum of
+// end - start over the keys with items
+const char *copies_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_monomer *monomers,
+                        int n_monomers, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
+                        uint32_t *counts, trew_hip_alignment *records);
 // units in place with no motif given: refine_host's record, its unit's smallest rotation and trace_host's table for one strand
 const char *decompose_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                            int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint32_t *counts,
