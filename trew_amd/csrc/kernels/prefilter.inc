@@ -1,6 +1,7 @@
 // kernels/prefilter.inc -- part of trew_kernels.hip (included there, inside namespace trew; not a translation unit of its own).
 // filter_kernel<NW>: one lane per read, bit-parallel parity-bucket bound for every (segment, k); general path, uniform-geometry fast path
-// and the two drains of what the fast path sets aside (whole units, single halves).
+// and the two drains of what the fast path sets aside (whole units, single halves).  The fast path and its drains derive no
+// geometry: they read the block the host filled for the batch's read length (FilterGeom, trew_common.hpp).
 
 // ------------------------------------------------------------------ prefilter
 
@@ -511,6 +512,57 @@ __device__ __forceinline__ int4 load_thr4(const int4 *p) {
 
 __device__ __forceinline__ const int4 *joint_thresholds(const int2 *thr_tab) { return (const int4 *) (thr_tab + kThrRows * kThrRow); }
 
+// The batch geometry behind the thresholds (FilterGeom, filled by the host with them).  One 32- or 64-byte struct of it from a
+// wave-uniform address in the constant address space: one s_load_dwordx8 / x16 that the scalar cache serves, its fields SGPRs.
+// (two of them: [1] is the block of a launch that writes the per-slot candidate masks, with nothing for the joint loop)
+__device__ __forceinline__ const FilterGeom *filter_geom(const int2 *thr_tab, bool masks) {
+    return (const FilterGeom *) ((const char *) thr_tab + kThrGeomOffset) + (masks ? 1 : 0);
+}
+template <typename T>
+__device__ __forceinline__ T load_geom(const T *p) {
+    constexpr int N = (int) (sizeof(T) / 4);
+    static_assert(N == 8 || N == 16, "one scalar load");
+    typedef u32 vNu __attribute__((ext_vector_type(N)));
+    typedef const __attribute__((address_space(4))) vNu *cptr;
+    // a cast between address spaces, not through an integer: that would let the table's pointer escape, and with it the promise
+    // (__restrict__) that no store of the kernel reaches the table -- the k loops' threshold loads then stop being scalar loads
+    const vNu v = *(cptr) p;
+    T o;
+    __builtin_memcpy(&o, &v, sizeof(T));
+    return o;
+}
+// The block's address as a value the compiler cannot follow, taken where a round (or a drain) starts: the loads behind it stay at
+// their point of use.  Left alone the compiler hoists them out of the persistent loop, runs out of SGPRs and parks the fields in
+// VGPR lanes, a v_readlane for every use -- what became of the geometry when the kernel derived it (profiles/round_geometry).
+// tick: the round's number, an input of the statement, so that it belongs to its round without being volatile.
+__device__ __forceinline__ const FilterGeom *geom_here(const FilterGeom *g, u32 tick) {
+    asm("" : "+s"(g) : "s"(tick));
+    return g;
+}
+// the read `mate` of a unit of a batch of equal-length reads (no offsets, no lengths: stage_thresholds); an inactive lane gets an
+// empty descriptor
+__device__ __forceinline__ ReadRef uniform_read(const DevBatch &B, u32 reads_per_unit, u64 unit, u32 mate, bool active, u32 read_words) {
+    ReadRef r;
+    r.w = B.words + (active ? (unit * reads_per_unit + mate) * (u64) B.uniform_stride : 0ull);
+    r.len = active ? B.uniform_length : 0u;
+    r.nw = active ? read_words : 0u;
+    return r;
+}
+__device__ __forceinline__ ReadRef uniform_read(const DevBatch &B, u32 reads_per_unit, u64 unit, u32 mate, bool active) {
+    return uniform_read(B, reads_per_unit, unit, mate, active, (B.uniform_length + 31u) >> 5);
+}
+// prefix parities of one half from its planes and the (wave-uniform) masks of its L bases: halves_prefix with the masks given
+__device__ __forceinline__ void halves_prefix_masked(const u32 (&lo)[3], const u32 (&hi)[3], const u32 (&lm)[3], HalvesP &o) {
+    u32 f1[3], f2[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        f1[j] = lo[j] & lm[j];
+        f2[j] = hi[j] & lm[j];
+    }
+    prefix_parity<3>(f1, o.P1);
+    prefix_parity<3>(f2, o.P2);
+}
+
 // Both halves of a read in ONE k loop.  passA / passB: this lane's half passes the 4-bucket test at some k of [klo, khi].
 // That is all the loop decides: such a half (3 % of the reads have one: the telomeric ones and a few near misses) is set aside and
 // judged by the drain with the other set-aside halves, a lane each -- the 8-bucket verdict used to be taken here, by the whole
@@ -644,25 +696,6 @@ __device__ __forceinline__ bool drain_pass8(const u32 (&F1)[N], const u32 (&F2)[
     return (int) m8 >= ithr;
 }
 
-// Geometry the drains need (block-uniform, from the batch's uniform length): the valid segments are exactly the 2 (short) or 4
-// (pair) halves, pairing up as (0, 1) and (2, 3), all with the same [kmin, kmax], at most 95 bases and one base apart, k <= length.
-__device__ __forceinline__ bool drain_uni_applies(const DevParams &P, u32 UL, int gmax_run) {
-    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : (P.mode == TREW_MODE_SHORT ? 2 : 0);
-    if (n_halves == 0) return false;
-    for (int slot = n_halves; slot < mode_slots(P.mode); slot++)
-        if (get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len).valid) return false;
-    const Segment first = get_segment(P.mode, 0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-    for (int p = 0; p < n_halves; p += 2) {
-        const Segment a = get_segment(P.mode, p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-        const Segment b = get_segment(P.mode, p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-        const int la = (int) a.len, lb = (int) b.len, lmin = la < lb ? la : lb, lmax = la < lb ? lb : la;
-        const int khi = a.kmax < gmax_run ? a.kmax : gmax_run;
-        if (!(a.valid && b.valid && a.kmin == b.kmin && a.kmax == b.kmax && lmax <= 95 && lmax - lmin <= 1 && a.kmin >= 1 && khi <= lmin)) return false;
-        if (a.kmin != first.kmin || a.kmax != first.kmax) return false;  // filter_deferred_half: one k loop for halves of either pair
-    }
-    return true;
-}
-
 // One half at one k of the drain: the lanes whose 8-bucket maximum over the windows of V_k reaches ithr(COUNT).  The 8-bucket
 // stage runs only when some lane not in `flag` (the lanes decided already) passes the 4-bucket test.  cnt_thr: LDS, kCntThr entries.
 // k with more than 64 windows in some lane (k <= 31): three words, funnel shifts
@@ -706,25 +739,25 @@ __device__ __forceinline__ u64 drain_probe2(const DrainHalf &h, u64 Q1, u64 Q2, 
 }
 
 // Verdict of one unit (short: a read, pair: two mates) set aside by the uniform path with two or more halves to judge.
-__device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const DevBatch &B, u64 unit, bool active, int gmax_run,
+__device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const DevBatch &B, u64 unit, bool active, const FilterGeom *geom, u32 tick,
                                                     const int4 *cnt_thr) {
-    const u32 UL = B.uniform_length;
-    ReadRef rd[2];
-    unit_reads(P, B, unit, active, rd);
+    // the geometry of the halves from the batch's block (drain_ok: slot[i] is half i, and every half has the drain's k range)
+    const FilterGeom *g = geom_here(geom, tick);
+    const GeomHead hd = load_geom(&g->head);
+    const u32 rpu = P.mode == TREW_MODE_PAIR ? 2u : 1u;
     const u64 actm = __ballot(active);
     u64 flag = 0;
-    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : 2;
+    const int n_halves = (int) hd.n_halves;
     for (int p = 0; p < n_halves && flag != actm; p += 2) {
-        const Segment sA = get_segment(P.mode, p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-        const Segment sB = get_segment(P.mode, p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-        const int LA = rfl_i((int) sA.len), LB = rfl_i((int) sB.len), Lmax = LA < LB ? LB : LA;
-        const int klo = rfl_i(sA.kmin > P.min_mer ? sA.kmin : P.min_mer), khi = rfl_i(sA.kmax < gmax_run ? sA.kmax : gmax_run);
+        const SlotGeom sA = load_geom(&g->slot[p]), sB = load_geom(&g->slot[p + 1]);
+        const int LA = (int) sA.len, LB = (int) sB.len, Lmax = LA < LB ? LB : LA;
+        const int klo = hd.drain_klo, khi = hd.drain_khi;
         DrainHalf A, Bh;
         {
             u32 lo[3], hi[3], nm[3];
-            load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, lo, hi, nm);
+            load_planes<3>(uniform_read(B, rpu, unit, sA.mate, active), sA.start, lo, hi, nm);
             drain_half_init(lo, hi, nm, LA, active, A);
-            load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, lo, hi, nm);
+            load_planes<3>(uniform_read(B, rpu, unit, sB.mate, active), sB.start, lo, hi, nm);
             drain_half_init(lo, hi, nm, LB, active, Bh);
         }
         for (int t = 1; t < klo; t++) {  // V_klo
@@ -760,30 +793,20 @@ __device__ __forceinline__ bool filter_deferred_uni(const DevParams &P, const De
 // thresholds it uses (fill_thresholds), so they cannot flag the unit.  The k loop is filter_deferred_uni's, once per k instead
 // of twice; every half has the same [kmin, kmax] (drain_uni_applies).  Length, start and container offset are per lane: the
 // halves of an odd-length read differ by one base, and the probes take their window masks from V_k, not from the length.
-__device__ __forceinline__ bool filter_deferred_half(const DevParams &P, const DevBatch &B, u64 unit, u32 half, bool active, int gmax_run,
+__device__ __forceinline__ bool filter_deferred_half(const DevParams &P, const DevBatch &B, u64 unit, u32 half, bool active, const FilterGeom *geom, u32 tick,
                                                      const int4 *cnt_thr) {
-    const u32 UL = B.uniform_length;
-    ReadRef rd[2];
-    unit_reads(P, B, unit, active, rd);
-    Segment sg = get_segment(P.mode, 0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-    int Lmax = (int) sg.len;
-    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : 2;
-    for (int slot = 1; slot < n_halves; slot++) {  // the lane's own half out of the (wave-uniform) geometry of all of them
-        const Segment o = get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-        Lmax = (int) o.len > Lmax ? (int) o.len : Lmax;
-        if (half == (u32) slot) {
-            sg.mate = o.mate;
-            sg.start = o.start;
-            sg.len = o.len;
-        }
-    }
-    Lmax = rfl_i(Lmax);
-    const int L = (int) sg.len;
-    const int klo = rfl_i(sg.kmin > P.min_mer ? sg.kmin : P.min_mer), khi = rfl_i(sg.kmax < gmax_run ? sg.kmax : gmax_run);
+    const FilterGeom *g = geom_here(geom, tick);
+    const GeomHead hd = load_geom(&g->head);
+    const u32 rpu = P.mode == TREW_MODE_PAIR ? 2u : 1u;
+    // the lane's own half out of the block (drain_ok: slot[i] is half i; half < n_halves, 0 for an idle lane): a load per lane
+    const SlotGeom *mine = &g->slot[half < hd.n_halves ? half : 0u];
+    const u32 mate = mine->mate, start = mine->start;
+    const int L = (int) mine->len;
+    const int Lmax = hd.drain_lmax, klo = hd.drain_klo, khi = hd.drain_khi;
     DrainHalf h;
     {
         u32 lo[3], hi[3], nm[3];
-        load_planes<3>(sg.mate ? rd[1] : rd[0], sg.start, lo, hi, nm);
+        load_planes<3>(uniform_read(B, rpu, unit, mate, active), start, lo, hi, nm);
         drain_half_init(lo, hi, nm, L, active, h);
     }
     for (int t = 1; t < klo; t++) drain_v_step3(h.V);  // V_klo
@@ -873,7 +896,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
         if (full) flush();
     };
     const int nslots = mode_slots(P.mode);
-    const int gmax_run = (P.flags & TREW_FLAG_DEBUG_NO_KLOOP) ? P.min_mer - 1 : P.max_mer;
+    const int gmax_run = filter_gmax_run(P);
     // general path: any read length, N anywhere
     auto general = [&](u64 unit, bool active) __attribute__((always_inline)) -> u64 {
         ReadRef rd[2];
@@ -929,9 +952,30 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
     // thr_tab[slot * kThrRow + k - 1] = pass thresholds of (slot, k) for this batch's uniform geometry (fill_thresholds, below): read-only
     // global memory at a wave-uniform address, i.e. scalar loads into SGPRs -- the k loops spend no vector instruction on them
     const u32 UL = B.uniform_length;
-    const bool uni = NW <= 5 && UL != 0 && thr_tab != nullptr && P.mode != TREW_MODE_LONG && !(P.flags & TREW_FLAG_NO_FILTER);
+    // The batch geometry (FilterGeom: which slots are valid and where they lie, what the joint loop and the drains need) stands
+    // behind the thresholds, filled by the host for this read length, this instantiation and P.flags.  The rounds read it at the
+    // point of use (geom_here / load_geom); what is read here, once, is only what decides the path of the whole launch.
+    const FilterGeom *geom = thr_tab ? filter_geom(thr_tab, dbg_masks != nullptr) : nullptr;
+    // head.nw == NW always holds: launch_filter picks NW from the longest valid segment of the uniform length (batch_geometry,
+    // trew_capi.cpp) and fill_thresholds fills the block for pick_nw of the same maximum over the same get_segment calls.  Were they
+    // ever to differ, the thresholds (uni_windows) would be another instantiation's as well, so the launch takes the general path.
+    const bool uni = NW <= 5 && UL != 0 && thr_tab != nullptr && P.mode != TREW_MODE_LONG && !(P.flags & TREW_FLAG_NO_FILTER) &&
+                     load_geom(&geom->head).nw == (u32) NW;
     // the reads set aside by the uniform path are judged by filter_deferred_uni, or by the general path (any NW, dbg_masks, A/B)
-    const bool uni_drain = NW == 3 && uni && !dbg_masks && !(P.flags & TREW_FLAG_DEBUG_NO_UNI_DRAIN) && drain_uni_applies(P, UL, gmax_run);
+    const bool uni_drain = NW == 3 && uni && !dbg_masks && !(P.flags & TREW_FLAG_DEBUG_NO_UNI_DRAIN) && load_geom(&geom->head).drain_ok != 0u;
+#ifdef TREW_AB_PIN_GEOM  // A/B builds (profiles/round_geometry, step 0): the round's geometry read ONCE, here, and pinned in scalar
+                         // registers across the persistent loop (single-end batches: the first pair of halves serves every round)
+    GeomHead hd_pin = {};
+    HalvesRound hr_pin = {};
+    if (uni) {
+        hd_pin = load_geom(&geom->head);
+        hr_pin = load_geom(&geom->round[0]);
+    }
+    asm volatile("" : "+s"(hd_pin.n_halves), "+s"(hd_pin.n_joint), "+s"(hd_pin.n_slots));
+    asm volatile("" : "+s"(hr_pin.L), "+s"(hr_pin.klo), "+s"(hr_pin.khi), "+s"(hr_pin.row), "+s"(hr_pin.one_load), "+s"(hr_pin.mate), "+s"(hr_pin.bs),
+                 "+s"(hr_pin.slot_p), "+s"(hr_pin.slot_q), "+s"(hr_pin.read_words));
+    asm volatile("" : "+s"(hr_pin.nl[0]), "+s"(hr_pin.nl[1]), "+s"(hr_pin.nl[2]), "+s"(hr_pin.nr[0]), "+s"(hr_pin.nr[1]), "+s"(hr_pin.nr[2]));
+#endif
     if (threadIdx.x == 0) defer_n = 0;
     if constexpr (NW == 3) {  // the half list is unused, and so not allocated, in the other instantiations
         if (threadIdx.x == 0) half_n = 0;
@@ -962,90 +1006,88 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
             if constexpr (NW <= 5) {
                 if (uni) {
                     TREW_SETUP_MARK(read_setup);
-                    ReadRef rd[2];
-                    unit_reads(P, B, unit, active, rd);
+                    // nothing below derives geometry: no get_segment, no branch on the mode or the slot, no mask of a length
+                    const FilterGeom *g = geom_here(geom, round);
+#ifndef TREW_AB_PIN_GEOM
+                    const GeomHead hd = load_geom(&g->head);
+#else
+                    const GeomHead hd = hd_pin;
+#endif
+                    const u32 rpu = P.mode == TREW_MODE_PAIR ? 2u : 1u;  // reads of a unit
                     dfr = false;
-                    int slot0 = 0;
+                    u32 first = 0;  // valid slots the joint loop has taken: slot[first ..] go through the per-segment loops
                     if constexpr (NW == 3) {
-                        // halves of equal length whose whole k range has 32..72 windows (150-bp reads at 5..32: 44..71): both
-                        // halves of a read in one k loop (filter_halves_uni); anything else takes the per-segment loops below
-                        const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : (P.mode == TREW_MODE_SHORT ? 2 : 0);
+                        // halves of equal length (or a right half one base longer) whose whole k range has 32..72 windows (150-bp
+                        // reads at 5..32: 44..71): both halves of a read in one k loop (filter_halves_uni); anything else takes the
+                        // per-segment loops below.  Which pairs of halves: the host decided (joint_loop_admits, build_filter_geom).
+                        const u32 n_joint = hd.n_joint;  // none where the candidate masks are wanted: that launch has a block of its own
                         u32 nneed = 0;  // halves of this unit the drain has to judge
-                        for (; slot0 + 1 < n_halves && !dbg_masks && !(P.flags & TREW_FLAG_DEBUG_NO_JOINT); slot0 += 2) {
-                            const Segment sA = get_segment(P.mode, slot0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-                            const Segment sB = get_segment(P.mode, slot0 + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-                            const int L = rfl_i((int) sA.len);  // wave-uniform: keep everything derived from it on the scalar unit
-                            const int klo = rfl_i(sA.kmin > P.min_mer ? sA.kmin : P.min_mer), khi = rfl_i(sA.kmax < gmax_run ? sA.kmax : gmax_run);
-                            // halves of equal length, or a right half one base longer (reads of odd length): then it is judged by
-                            // its first L bases against the joint thresholds of row kMaxSlots + pair (fill_thresholds)
-                            const bool uneq = sB.len == sA.len + 1u;
-                            if (!(sA.valid && sB.valid && (sA.len == sB.len || uneq) && sA.len <= 95u && sA.kmin == sB.kmin && sA.kmax == sB.kmax &&
-                                  klo >= L + 1 - kUniSubsetMax && khi <= L - 32 && klo <= 31))
-                                break;
+                        for (u32 pr = 0; pr < n_joint; pr++) {
+#ifndef TREW_AB_PIN_GEOM
+                            const HalvesRound hr = load_geom(&g->round[pr]);
+#else
+                            const HalvesRound hr = hr_pin;
+#endif
                             // The two halves as the loop sees them: p and q, of slots slot_p and slot_q (scalars).  The loop treats both
                             // alike (one length L, one row of thresholds), so which is which matters only for the slot handed to the drain.
                             HalvesP hp, hq;
                             u32 np, nq;
-                            u32 slot_p = (u32) slot0, slot_q = (u32) slot0 + 1u;
-                            // Both halves lie in one read of at most five triples, one from base 0 and the other from a base in
+                            // one_load: both halves lie in one read of at most five triples, one from base 0 and the other from a base in
                             // [64, 96), whatever the k range (reads of 128 .. 159 bases; at 5 .. 32 the joint loop takes 128 .. 153): the
                             // read is loaded once, and p is its left half.  Pair mode's second mate has its right half in the first
                             // slot.  Not 160: bit L of the right half's prefix parity would be bit 160 of the read's (halves_prefix_read5).
-                            const bool a_left = sA.start == 0u;
-                            const u32 h = rfl(a_left ? sB.start : sA.start), len_l = rfl(a_left ? sA.len : sB.len), len_r = rfl(a_left ? sB.len : sA.len);
-                            const bool one_load = UL <= 159u && sA.mate == sB.mate && (a_left ? sA.start : sB.start) == 0u && (h >> 5) == 2u && h + len_r <= UL;
-                            if (one_load) {
+                            if (hr.one_load) {
                                 TREW_SETUP_MARK(one_load);
                                 ReadPlanes5 r;
-                                load_read5(sA.mate ? rd[1] : rd[0], r);
-                                np = read5_left_has_n(r.nm, (int) len_l);
-                                nq = read5_right_has_n(r.nm, (int) h, (int) len_r);  // an N in the right half's extra base counts
-                                if (!a_left) slot_p = (u32) slot0 + 1u, slot_q = (u32) slot0;
+                                load_read5(uniform_read(B, rpu, unit, hr.mate, active, hr.read_words), r);
+                                np = (r.nm[0] & hr.nl[0]) | (r.nm[1] & hr.nl[1]) | (r.nm[2] & hr.nl[2]);
+                                nq = (r.nm[2] & hr.nr[0]) | (r.nm[3] & hr.nr[1]) | (r.nm[4] & hr.nr[2]);  // an N in the right half's extra base counts
 #ifndef TREW_AB_NO_READ_PREFIX
-                                halves_prefix_read5(r, h & 31u, hp, hq);
+                                halves_prefix_read5(r, hr.bs, hp, hq);
 #else  // A/B builds (profiles/read_setup): the one load alone, a prefix parity per half as before
                                 u32 loq[3], hiq[3];
-                                read5_from64(r.lo, h & 31u, loq);
-                                read5_from64(r.hi, h & 31u, hiq);
+                                read5_from64(r.lo, hr.bs, loq);
+                                read5_from64(r.hi, hr.bs, hiq);
                                 const u32 lop[3] = {r.lo[0], r.lo[1], r.lo[2]}, hip[3] = {r.hi[0], r.hi[1], r.hi[2]};
-                                halves_prefix(lop, hip, L, hp);
-                                halves_prefix(loq, hiq, L, hq);
+                                halves_prefix(lop, hip, hr.L, hp);
+                                halves_prefix(loq, hiq, hr.L, hq);
 #endif
                             } else {
                                 TREW_SETUP_MARK(two_loads);
+                                const HalvesLoads hl = load_geom(&g->loads[pr]);
                                 u32 loA[3], hiA[3], nmA[3], loB[3], hiB[3], nmB[3];
-                                load_planes<3>(sA.mate ? rd[1] : rd[0], sA.start, loA, hiA, nmA);
-                                load_planes<3>(sB.mate ? rd[1] : rd[0], sB.start, loB, hiB, nmB);
-                                np = segment_has_n<3>(nmA, L), nq = segment_has_n<3>(nmB, (int) sB.len);  // an N in the right half's extra base counts
-                                halves_prefix(loA, hiA, L, hp);
-                                halves_prefix(loB, hiB, L, hq);
+                                load_planes<3>(uniform_read(B, rpu, unit, hl.mate_a, active, hr.read_words), hl.start_a, loA, hiA, nmA);
+                                load_planes<3>(uniform_read(B, rpu, unit, hl.mate_b, active, hr.read_words), hl.start_b, loB, hiB, nmB);
+                                np = (nmA[0] & hr.nl[0]) | (nmA[1] & hr.nl[1]) | (nmA[2] & hr.nl[2]);
+                                nq = (nmB[0] & hr.nr[0]) | (nmB[1] & hr.nr[1]) | (nmB[2] & hr.nr[2]);  // an N in the right half's extra base counts
+                                halves_prefix_masked(loA, hiA, hr.nl, hp);
+                                halves_prefix_masked(loB, hiB, hr.nl, hq);
                             }
                             dfr_n = dfr_n || (active && (np | nq) != 0);
                             // thresholds: halves of the same length share the row of the first; unequal ones have a joint row
                             bool passp, passq;
                             TREW_SETUP_MARK(joint_loop);
-                            filter_halves_uni(hp, hq, L, klo, khi, joint_thresholds(thr_tab) + (uneq ? 2 + slot0 / 2 : slot0 / 2) * kThrRow, wm_tab, passp, passq);
+                            filter_halves_uni(hp, hq, hr.L, hr.klo, hr.khi, joint_thresholds(thr_tab) + hr.row * (u32) kThrRow, wm_tab, passp, passq);
                             // A half with an N does not fit the model, and a half some k of which passes the 4-bucket test needs its
                             // 8-bucket verdicts: the drain takes them, a lane per read or half (the verdict of a read never depends on
                             // its neighbours, so the flagged reads are the same).  A half that is neither cannot flag the read.
                             const bool needp = active && (np != 0 || passp), needq = active && (nq != 0 || passq);
                             nneed += (u32) needp + (u32) needq;
-                            hsel = needq ? slot_q : (needp ? slot_p : hsel);  // read only when exactly one half of the unit is needed
+                            hsel = needq ? hr.slot_q : (needp ? hr.slot_p : hsel);  // read only when exactly one half of the unit is needed
                             dfr = dfr || needp || needq;
                         }
+                        first = 2u * n_joint;  // admitted halves are valid: their place in slot[] is their slot
                         // one half to judge, every half went through the joint loop and the drain knows this geometry: the half list
-                        dfr_half = uni_drain && slot0 == n_halves && nneed == 1u;
+                        dfr_half = uni_drain && first == hd.n_halves && nneed == 1u;
                     }
-                    for (int slot = slot0; slot < nslots; slot++) {  // wave-uniform geometry: no need to unroll
-                        const Segment sg = get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len);
-                        if (!sg.valid) continue;
-                        if (sg.len > (u32) (32 * NW - 1)) {  // too long for this instantiation: the general path keeps every k
+                    for (u32 i = first; i < hd.n_slots; i++) {  // the valid slots left, wave-uniform geometry: no need to unroll
+                        const SlotGeom sg = load_geom(&g->slot[i < (u32) kMaxSlots ? i : 0u]);
+                        if (sg.too_long) {  // too long for this instantiation: the general path keeps every k
                             dfr = dfr || active;
                             continue;
                         }
                         u32 lo[NW], hi[NW], nm[NW];
-                        const ReadRef r = sg.mate ? rd[1] : rd[0];
-                        load_planes<NW>(r, sg.start, lo, hi, nm);
+                        load_planes<NW>(uniform_read(B, rpu, unit, sg.mate, active), sg.start, lo, hi, nm);
                         u32 anyn = 0;  // segment_has_n<NW> written out: the call costs filter_kernel<5> two instructions (profiles/bound_refactor/README.md)
 #pragma unroll
                         for (int j = 0; j < NW; j++) {
@@ -1054,12 +1096,12 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                             anyn |= nm[j] & lm;
                         }
                         UniVerdict vd;
-                        filter_segment_uni<NW>(lo, hi, (int) sg.len, sg.kmin, sg.kmax, P.min_mer, gmax_run, thr_tab + slot * kThrRow, dbg_masks != nullptr, vd);
+                        filter_segment_uni<NW>(lo, hi, (int) sg.len, sg.kmin, sg.kmax, P.min_mer, gmax_run, thr_tab + sg.slot * (u32) kThrRow, dbg_masks != nullptr, vd);
                         dfr = dfr || (active && anyn != 0);
                         dfr_n = dfr_n || (active && anyn != 0);
                         any |= (vd.flagm >> lane_id()) & 1ull;
-                        if (dbg_masks && active && anyn == 0 && slot < dbg_slots)
-                            dbg_masks[unit * (u64) dbg_slots + slot] = ((((u64) vd.chi) << 32) | vd.clo) & all_k_mask(sg.kmin, sg.kmax);
+                        if (dbg_masks && active && anyn == 0 && (int) sg.slot < dbg_slots)
+                            dbg_masks[unit * (u64) dbg_slots + sg.slot] = ((((u64) vd.chi) << 32) | vd.clo) & all_k_mask(sg.kmin, sg.kmax);
                     }
                 }
             }
@@ -1112,8 +1154,8 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
                 if (halves || uni_drain) atomicAdd(&g_fallback[halves ? kFallbackHalfDrain : kFallbackUnitDrain], take);
             }
 #if !defined(TREW_AB_SKIP_DRAIN) && !defined(TREW_AB_SKIP_UNIT_DRAIN)
-            const u64 any2 = halves      ? (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, gmax_run, cnt_thr)
-                             : uni_drain ? (u64) filter_deferred_uni(P, B, unit2, active2, gmax_run, cnt_thr)
+            const u64 any2 = halves      ? (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, geom, round, cnt_thr)
+                             : uni_drain ? (u64) filter_deferred_uni(P, B, unit2, active2, geom, round, cnt_thr)
                                          : general(unit2, active2);
 #else  // A/B builds (instruction attribution): the drain computes nothing and its inputs are kept alive -- both drains with
        // TREW_AB_SKIP_DRAIN (profiles/r05), the whole-unit drain alone with TREW_AB_SKIP_UNIT_DRAIN (profiles/read_setup)
@@ -1124,7 +1166,7 @@ __global__ __launch_bounds__(kFilterThreads, (NW <= 3 ? TREW_FILTER3_WAVES : (NW
 #endif
             u64 any2 = 0;
             if (halves && !kSkipHalves) {
-                any2 = (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, gmax_run, cnt_thr);
+                any2 = (u64) filter_deferred_half(P, B, unit2, kind2 >> 1, active2, geom, round, cnt_thr);
             } else {
                 u32 keep = unit2 + kind2;
                 asm volatile("" : "+v"(keep), "+v"(any2));

@@ -76,6 +76,7 @@ struct Slot {
     hipEvent_t ev_tail = nullptr, ev_copied = nullptr;  // order the context's copy stream behind / in front of this slot's stream (BatchCopy)
     u32 *h_seen = nullptr;   // TREW_FLAG_TRACK_PRESSURE: the counter line as of the end of this slot's last batch (pinned, behind h_thr)
     u32 thr_length = 0;      // uniform read length d_thr was computed for (0: none yet)
+    u32 thr_flags = 0;       // and the context's flags: the batch geometry behind the thresholds (FilterGeom) folds the debug flags in
     SegResults res = {nullptr, nullptr, nullptr, nullptr};
     // ring of (before filter, between, after exact) events: submits may be queued back to back
     // on the slot's stream without a wait in between, each keeps its own timestamps
@@ -631,16 +632,18 @@ static int stage_batch(trew_hip_ctx *ctx, const trew_hip_batch *b, Slot &s, DevB
 }
 
 // Thresholds of the prefilter's uniform-geometry path for this batch (nullptr: the batch is ragged).  They depend only
-// on the read length, so a slot recomputes and re-sends its 3 KB table when the length changes; the copy is queued on
+// on the read length (and the batch geometry behind them on the context's flags as well), so a slot recomputes and re-sends its
+// 9 KB table when the length changes; the copy is queued on
 // the slot's stream, in front of the kernel that reads it.
 static int stage_thresholds(trew_hip_ctx *ctx, Slot &s, const DevBatch &db, const int2 **out) {
     *out = nullptr;
     if (db.offsets || db.lengths || db.uniform_length == 0) return 0;
-    if (s.thr_length != db.uniform_length) {
+    if (s.thr_length != db.uniform_length || s.thr_flags != ctx->dp.flags) {
         HIPCHK(ctx, hipStreamSynchronize(s.stream));  // an earlier copy may still be reading the staging buffer
         fill_thresholds(ctx->dp, db.uniform_length, s.h_thr);
         HIPCHK(ctx, hipMemcpyAsync(s.d_thr, s.h_thr, kThrTableBytes, hipMemcpyHostToDevice, s.stream));
         s.thr_length = db.uniform_length;
+        s.thr_flags = ctx->dp.flags;
     }
     *out = s.d_thr;
     return 0;

@@ -21,7 +21,7 @@ constexpr int kTablePartBits = 9;   // low word bits that select the table parti
 constexpr int kThrRows = kMaxSlots + 2;  // rows of the threshold table: one per slot + one per pair of halves of unequal length (joint rows, fill_thresholds)
 constexpr int kThrJointRows = 4;    // behind those, four rows of int4 for the loop that judges both halves of a read at once: halves 0/1 and 2/3 of equal length, then of unequal length
 constexpr int kThrRow = 66;         // threshold-table entries per slot: k = 1..64, one of read-ahead padding, one to keep rows 16-byte aligned
-constexpr size_t kThrTableBytes = (size_t) kThrRows * kThrRow * 8 + (size_t) kThrJointRows * kThrRow * 16;
+// (kThrTableBytes, below: those rows and the batch geometry behind them, FilterGeom)
 constexpr int kThrNever = 1 << 20;  // a threshold nothing reaches (small enough to be doubled and tripled in the joint rows)
 
 struct DevParams {
@@ -308,6 +308,175 @@ TREW_HD inline int uni_windows(int nw, int L, int k) {
 
 TREW_HD inline int mode_slots(int mode) {
     return mode == TREW_MODE_SHORT ? 3 : mode == TREW_MODE_PAIR ? 6 : mode == TREW_MODE_LONG ? 2 : 1;
+}
+
+// ---- the prefilter's batch geometry, worked out on the host once per read length (build_filter_geom below) ----
+// A batch of equal-length reads has one segment geometry.  filter_kernel used to derive it in every round of its persistent
+// loop (get_segment per slot, the joint loop's admission test, the has-N masks); it now reads the block below, which lies
+// behind the joint rows of the threshold table, through wave-uniform scalar loads at the point of use.
+// Every struct is a whole number of 32- or 64-byte lines: one s_load_dwordx8 / x16 each.
+
+// the k loop the prefilter runs: MAX_MER, or nothing with TREW_FLAG_DEBUG_NO_KLOOP
+TREW_HD inline int filter_gmax_run(const DevParams &P) { return (P.flags & TREW_FLAG_DEBUG_NO_KLOOP) ? P.min_mer - 1 : P.max_mer; }
+TREW_HD inline u32 geom_low_mask(int bits) { return bits >= 32 ? 0xffffffffu : (bits <= 0 ? 0u : ((1u << bits) - 1u)); }
+
+// The joint loop (filter_halves_uni, 3-word kernel) takes the halves a, b of slots 2p, 2p + 1: equal length, or a right half
+// one base longer (reads of odd length: it is judged by its first L bases against the joint thresholds of row 2 + p), at most 95
+// bases, one k range, and every k of the loop with 32..kUniSubsetMax windows.
+TREW_HD inline bool joint_loop_admits(const Segment &a, const Segment &b, int klo, int khi) {
+    const int L = (int) a.len;
+    const bool uneq = b.len == a.len + 1u;
+    return a.valid && b.valid && (a.len == b.len || uneq) && a.len <= 95u && a.kmin == b.kmin && a.kmax == b.kmax &&
+           klo >= L + 1 - kUniSubsetMax && khi <= L - 32 && klo <= 31;
+}
+
+// Geometry the drains of the 3-word kernel need (filter_deferred_uni, filter_deferred_half): the valid segments are exactly the
+// 2 (short) or 4 (pair) halves, pairing up as (0, 1) and (2, 3), all with the same [kmin, kmax], at most 95 bases and one base
+// apart, k <= length.
+TREW_HD inline bool drain_uni_applies(const DevParams &P, u32 UL, int gmax_run) {
+    const int n_halves = P.mode == TREW_MODE_PAIR ? 4 : (P.mode == TREW_MODE_SHORT ? 2 : 0);
+    if (n_halves == 0) return false;
+    for (int slot = n_halves; slot < mode_slots(P.mode); slot++)
+        if (get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len).valid) return false;
+    const Segment first = get_segment(P.mode, 0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+    for (int p = 0; p < n_halves; p += 2) {
+        const Segment a = get_segment(P.mode, p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const Segment b = get_segment(P.mode, p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const int la = (int) a.len, lb = (int) b.len, lmin = la < lb ? la : lb, lmax = la < lb ? lb : la;
+        const int khi = a.kmax < gmax_run ? a.kmax : gmax_run;
+        if (!(a.valid && b.valid && a.kmin == b.kmin && a.kmax == b.kmax && lmax <= 95 && lmax - lmin <= 1 && a.kmin >= 1 && khi <= lmin)) return false;
+        if (a.kmin != first.kmin || a.kmax != first.kmax) return false;  // filter_deferred_half: one k loop for halves of either pair
+    }
+    return true;
+}
+
+// What a round of the joint loop reads for one pair of halves.  The loop treats both halves alike (one length L, one row of
+// thresholds): p and q are the halves as it sees them, of slots slot_p and slot_q (which matters only for the slot handed to
+// the half drain).
+struct HalvesRound {
+    int L, klo, khi;   // length the loop judges both halves by; its k range
+    u32 row;           // joint threshold row: p for equal halves, 2 + p for a right half one base longer
+    u32 one_load;      // both halves from one load and one prefix parity of the whole read (load_read5), p its left half
+    u32 mate;          // one_load: the read that holds both halves
+    u32 bs;            // one_load: (first base of the right half) & 31; that base lies in word 2
+    u32 slot_p, slot_q;
+    // has-N masks.  one_load: of words 0..2 (left half) and words 2..4 (right half) of the read's raw N plane.
+    // Otherwise of the three words of half a = p (L bases: its feature mask as well) and of half b = q (its own length: an N in
+    // the right half's extra base counts).
+    u32 nl[3], nr[3];
+    u32 read_words;    // triples of a read of the batch: (uniform_length + 31) / 32
+};
+// What the two-load path reads on top (halves starting in word 1, reads of 160 bases)
+struct HalvesLoads {
+    u32 mate_a, start_a, mate_b, start_b;
+    u32 pad[4];
+};
+// one valid slot: get_segment's answer, and whether the segment is too long for the batch's kernel instantiation
+struct SlotGeom {
+    u32 slot, mate, start, len;
+    int kmin, kmax;
+    u32 too_long, pad;
+};
+struct GeomHead {
+    u32 nw;         // the kernel instantiation the block was filled for (pick_nw of the longest valid segment)
+    u32 n_halves;   // 2 short, 4 pair, else 0
+    u32 n_joint;    // leading pairs of halves the joint loop takes (their slots are slot[0 .. 2 n_joint - 1])
+    u32 n_slots;    // valid slots, in slot order, in slot[]
+    u32 drain_ok;   // drain_uni_applies
+    int drain_klo, drain_khi;  // the drains' k loop
+    int drain_lmax;            // the longest half
+};
+struct FilterGeom {  // every member aligned to its own size
+    HalvesRound round[2];  // per pair of halves
+    HalvesLoads loads[2];
+    SlotGeom slot[kMaxSlots];
+    GeomHead head;
+    u32 pad[8];
+};
+static_assert(sizeof(HalvesRound) == 64 && sizeof(HalvesLoads) == 32 && sizeof(SlotGeom) == 32 && sizeof(GeomHead) == 32, "one scalar load each");
+constexpr size_t kThrGeomOffset = (size_t) kThrRows * kThrRow * 8 + (size_t) kThrJointRows * kThrRow * 16;  // behind the joint rows
+static_assert(kThrGeomOffset % 64 == 0 && sizeof(FilterGeom) % 64 == 0, "the block's lines are aligned");
+// two blocks: the batch's, and the same with no pair of halves handed to the joint loop -- what a launch that wants the per-slot
+// candidate masks (trew_hip_filter_masks) reads, so that no round has to ask
+constexpr size_t kThrTableBytes = kThrGeomOffset + 2 * sizeof(FilterGeom);
+
+// The block for reads of uniform_length in an nw-word kernel.  P.flags count: TREW_FLAG_DEBUG_NO_JOINT (no pair goes to the joint
+// loop) and TREW_FLAG_DEBUG_NO_KLOOP (the k ranges are empty).
+TREW_HD inline void build_filter_geom(const DevParams &P, u32 UL, int nw, FilterGeom *g) {
+    const int gmax_run = filter_gmax_run(P);
+    const int nslots = mode_slots(P.mode);
+    GeomHead &hd = g->head;
+    hd.nw = (u32) nw;
+    hd.n_halves = P.mode == TREW_MODE_PAIR ? 4u : (P.mode == TREW_MODE_SHORT ? 2u : 0u);
+    hd.n_joint = 0;
+    hd.n_slots = 0;
+    for (int j = 0; j < 8; j++) g->pad[j] = 0;
+    for (int i = 0; i < kMaxSlots; i++) {
+        SlotGeom &o = g->slot[i];
+        o.slot = o.mate = o.start = o.len = 0;
+        o.kmin = 1, o.kmax = 0;
+        o.too_long = o.pad = 0;
+    }
+    for (int slot = 0; slot < nslots; slot++) {
+        const Segment sg = get_segment(P.mode, slot, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        if (!sg.valid) continue;
+        SlotGeom &o = g->slot[hd.n_slots++];
+        o.slot = (u32) slot, o.mate = sg.mate, o.start = sg.start, o.len = sg.len;
+        o.kmin = sg.kmin, o.kmax = sg.kmax;
+        o.too_long = sg.len > (u32) (32 * nw - 1) ? 1u : 0u;
+    }
+    bool joint = nw == 3 && !(P.flags & TREW_FLAG_DEBUG_NO_JOINT);
+    for (int p = 0; p < 2; p++) {
+        HalvesRound &r = g->round[p];
+        HalvesLoads &l = g->loads[p];
+        r.L = r.klo = 0, r.khi = -1;
+        r.row = r.one_load = r.mate = r.bs = r.slot_p = r.slot_q = 0;
+        r.read_words = (UL + 31u) >> 5;
+        for (int j = 0; j < 3; j++) r.nl[j] = r.nr[j] = 0;
+        l.mate_a = l.start_a = l.mate_b = l.start_b = 0;
+        for (int j = 0; j < 4; j++) l.pad[j] = 0;
+        if (2 * p + 1 >= (int) hd.n_halves) joint = false;
+        if (!joint) continue;
+        const Segment a = get_segment(P.mode, 2 * p, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const Segment b = get_segment(P.mode, 2 * p + 1, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+        const int klo = a.kmin > P.min_mer ? a.kmin : P.min_mer, khi = a.kmax < gmax_run ? a.kmax : gmax_run;
+        if (!joint_loop_admits(a, b, klo, khi)) {  // as the kernel's loop over the pairs did: the first pair it does not take ends it
+            joint = false;
+            continue;
+        }
+        hd.n_joint = (u32) p + 1u;
+        r.L = (int) a.len, r.klo = klo, r.khi = khi;
+        const bool uneq = b.len == a.len + 1u;
+        r.row = (u32) (uneq ? 2 + p : p);
+        l.mate_a = a.mate, l.start_a = a.start, l.mate_b = b.mate, l.start_b = b.start;
+        // the halves by position: a is the left one; the first base of the right one; their lengths
+        const bool a_left = a.start == 0u;
+        const u32 h = a_left ? b.start : a.start, len_l = a_left ? a.len : b.len, len_r = a_left ? b.len : a.len;
+        // Both halves lie in one read of at most five triples, one from base 0 and the other from a base in [64, 96).  Not 160
+        // bases: bit L of the right half's prefix parity would be bit 160 of the read's (halves_prefix_read5).
+        r.one_load = (UL <= 159u && a.mate == b.mate && (a_left ? a.start : b.start) == 0u && (h >> 5) == 2u && h + len_r <= UL) ? 1u : 0u;
+        r.mate = a.mate;
+        r.bs = h & 31u;
+        r.slot_p = (u32) (2 * p), r.slot_q = (u32) (2 * p + 1);
+        if (r.one_load) {
+            if (!a_left) r.slot_p = (u32) (2 * p + 1), r.slot_q = (u32) (2 * p);
+            for (int j = 0; j < 3; j++) {
+                r.nl[j] = geom_low_mask((int) len_l - 32 * j);
+                r.nr[j] = geom_low_mask((int) (h + len_r) - 32 * (j + 2)) & ~geom_low_mask((int) h - 32 * (j + 2));
+            }
+        } else {
+            for (int j = 0; j < 3; j++) {
+                r.nl[j] = geom_low_mask(r.L - 32 * j);
+                r.nr[j] = geom_low_mask((int) b.len - 32 * j);
+            }
+        }
+    }
+    hd.drain_ok = drain_uni_applies(P, UL, gmax_run) ? 1u : 0u;
+    const Segment first = get_segment(P.mode, 0, UL, UL, P.min_mer, P.max_mer, P.slice_len);
+    hd.drain_klo = first.kmin > P.min_mer ? first.kmin : P.min_mer;
+    hd.drain_khi = first.kmax < gmax_run ? first.kmax : gmax_run;
+    hd.drain_lmax = 0;
+    for (u32 i = 0; i < hd.n_halves && i < hd.n_slots; i++) hd.drain_lmax = (int) g->slot[i].len > hd.drain_lmax ? (int) g->slot[i].len : hd.drain_lmax;
 }
 
 }  // namespace trew

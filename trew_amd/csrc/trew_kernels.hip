@@ -117,7 +117,7 @@ int pick_nw(u32 max_seg_len) {
 }
 
 // Pass thresholds of the uniform-geometry fast path for one batch geometry: table[slot * kThrRow + k - 1] = {ithr, jthr}
-// (kThrTableBytes in all: the int2 rows, then the joint loop's int4 rows).
+// (kThrTableBytes in all: the int2 rows, then the joint loop's int4 rows, then the batch geometry).
 // Host side (single-precision multiply, the same IEEE operation the general path performs on the device).
 void fill_thresholds(const DevParams &P, u32 uniform_length, int2 *table) {
     const int nslots = mode_slots(P.mode);
@@ -178,6 +178,13 @@ void fill_thresholds(const DevParams &P, u32 uniform_length, int2 *table) {
             joint[r * kThrRow + k - 1] = make_int4(-2 * th.x, -th.x, 3 * th.x - th.y - 1, th.x);
         }
     }
+    FilterGeom *geom = (FilterGeom *) ((char *) table + kThrGeomOffset);
+    // The batch geometry behind them (FilterGeom, trew_common.hpp): everything a round of filter_kernel used to derive from the
+    // read length.  build_filter_geom calls get_segment and the kernel's predicates themselves, so both sides agree by construction.
+    build_filter_geom(P, uniform_length, nw, &geom[0]);
+    DevParams no_joint = P;  // the block of a launch that wants the per-slot candidate masks: every slot through the per-segment loops
+    no_joint.flags |= TREW_FLAG_DEBUG_NO_JOINT;
+    build_filter_geom(no_joint, uniform_length, nw, &geom[1]);
 }
 
 hipError_t launch_filter(hipStream_t st, u32 n_cu, u32 max_seg_len, const DevParams &P, const DevBatch &B, u32 *wl, u32 *wl_count,
