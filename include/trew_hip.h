@@ -40,7 +40,8 @@ extern "C" {
  * trew_decompose_host), the dissection entry points (trew_hip_dissect, trew_hip_dissect_results, trew_dissect_host), the
  * resolution entry points (trew_hip_resolve, trew_hip_resolve_results, trew_resolve_host), the resolved forms of three
  * of them (trew_hip_tandems_resolved, trew_hip_decompose_resolved, trew_hip_dissect_resolved and their _host functions) and
- * the monomer entry points (trew_monomer_parse, trew_hip_monomers, trew_hip_monomers_results, trew_monomers_host): they
+ * the monomer entry points (trew_monomer_parse, trew_hip_monomers, trew_hip_monomers_results, trew_monomers_host), the
+ * copies entry points and the polish entry points (trew_hip_polish, trew_hip_polish_results, trew_polish_host): they
  * are purely additive -- no existing
  * structure, enumerator or function changed. */
 #define TREW_HIP_ABI_VERSION 4
@@ -862,6 +863,49 @@ int trew_hip_copies_results(trew_hip_ctx *ctx, int slot, trew_hip_trace_item *it
 int trew_copies_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, const trew_hip_monomer *monomers,
                      int n_monomers, int penalty, uint32_t min_score, trew_hip_trace_item *items, uint64_t cap, uint64_t *n_items, uint64_t *n_rows,
                      uint32_t *counts, trew_hip_alignment *records);
+
+/* ---- de novo repeats under indels for periods up to 256: trew_hip_refine's seed, align and re-vote with a long unit ----
+ * (where does this minisatellite or satellite array begin and end in a noisy long read, how many copies does it hold, how do
+ * its errors split, and what is its monomer -- when nobody has typed that monomer?)  Integer-exact (DESIGN 4.7o;
+ * tests/polish_ref.py is the reference).  The definition is trew_hip_refine's (steps 1 to 7 above), word for word, with three
+ * changes:
+ * 1. Periods.  R is the depth-0 record of trew_hip_satellites for the read: the periods record with k over [min_period,
+ *    min(max_period, n - 1)], 1 <= min_period <= max_period <= TREW_POLISH_MAX_PERIOD (256); its unreduced consensus serves
+ *    the N of a seed window.  The checks and error texts are trew_hip_satellites': "1 <= min_period <= max_period <= 256",
+ *    and penalty and min_score as there.
+ * 2. The recurrence of steps 3, 4 and 6 is trew_hip_monomers', for every unit length 1 .. 256 (the lower limit of 3 is a
+ *    check on typed units, not a property of the recurrence).  The tuples, the tie rules, the vote's V (not H), "the smallest
+ *    phase on a tie" and "the diagonal candidate equals V[i][j*]" are unchanged.
+ * 3. The record is trew_hip_polished, 176 bytes, one per read: refine's twelve words in refine's order, then unit[16] and
+ *    seed_unit[16], packed as trew_hip_satellite.unit: base j in bits [2 (j & 15), 2 (j & 15) + 2) of word j >> 4, zero at
+ *    and above period / seed_period.
+ * Consequences: with max_period <= 32 the twelve words equal trew_hip_refine's on the same input and arguments and the two
+ * units decode to the same strings; score >= seed_score; a zero step-1 record gives a zero record; unit and seed_unit are
+ * primitive; the derived columns (trew_hip_alignment's, with k = period) are never negative; whenever seed_period >= 3,
+ * seed_score equals the forward score of trew_hip_monomers with the unit S, with changed = 0 all five fields of A2 do, and
+ * with changed > 0 the fields of A2 equal those with the unit U; on a perfect repeat period, unit, changed = 0, start, end
+ * and score are trew_hip_satellites' depth-0 period and unit and trew_hip_monomers' forward record; (unit) x m with one base
+ * removed is one deletion with consumed = m k, with one base added one insertion, the unit unchanged in both.
+ * Limits: one tract per read; periods of at most 256; linear gap costs; a wrong scored_period is not repaired, and with the
+ * wide range it is wrong more often than in trew_hip_refine (DESIGN 4.7o has the measured figures); the vote is a forward
+ * decode, not a traceback; one round; a penalty of 1 is in the linear phase for long units, so use 2 or more, as for
+ * trew_hip_monomers; trew_hip_resolve, _tandems, _decompose and _dissect stay at periods <= 32.  Also additive:
+ * TREW_HIP_ABI_VERSION stays 4. */
+#define TREW_POLISH_MAX_PERIOD 256
+typedef struct {
+    uint32_t period, seed_period, scored_period, changed; /* of U, of S, of step 1; phases the vote changed */
+    uint32_t score, start, end, consumed, matches;        /* A2 */
+    uint32_t seed_score, support, reserved;               /* A1.score; the sum of the winning counts; 0 */
+    uint32_t unit[16], seed_unit[16];                     /* U and S, packed as trew_hip_satellite.unit */
+} trew_hip_polished;
+/* Like trew_hip_refine in every respect (batch shapes including device-resident and pair mode, staging, asynchronous on the
+ * slot's stream, a context of any mode).  One kernel, a wave per read, for every read length. */
+int trew_hip_polish(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score);
+/* Waits for the slot and copies the records of its last trew_hip_polish; arguments as trew_hip_refine_results. */
+int trew_hip_polish_results(trew_hip_ctx *ctx, int slot, trew_hip_polished *out, uint64_t cap, uint64_t *n, float *ms_kernel);
+/* The definition on the host, step by step, over packed planes; out has n_reads records. */
+int trew_polish_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                     int penalty, uint32_t min_score, trew_hip_polished *out);
 
 /* ---- units in place with no motif given: trew_hip_refine's unit, anchored at a fixed rotation, and trew_hip_trace against it ----
  * (what is this telomere made of, and in which order, when nobody knows its motif?)  Integer-exact (DESIGN 4.7i;

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "trew_hip_dissect_resolved", "trew_dissect_resolved_host",
     "trew_monomer_parse", "trew_hip_monomers", "trew_hip_monomers_results", "trew_monomers_host",
     "trew_hip_copies", "trew_hip_copies_results", "trew_copies_host",
+    "trew_hip_polish", "trew_hip_polish_results", "trew_polish_host",
 )
 DEBUG_COUNTERS = ("strict_rerun", "windows_fallback", "wide_spin_timeout", "inserted", "inserted_wide", "group_punt", "group_routed", "group_target",
                   "half_drain", "unit_drain", "dead_entries")
@@ -216,6 +217,17 @@ REFINE_DTYPE = np.dtype([(name, "<u8" if name in ("unit", "seed_unit") else "<u4
 assert REFINE_DTYPE.itemsize == C.sizeof(Refined) == 64
 
 
+POLISH_MAX_PERIOD = 256  # TREW_POLISH_MAX_PERIOD
+
+
+class Polished(C.Structure):
+    _fields_ = list(Refined._fields_[:12]) + [("unit", C.c_uint32 * 16), ("seed_unit", C.c_uint32 * 16)]
+
+
+POLISH_DTYPE = np.dtype([(name, "<u4") for name, _ in Refined._fields_[:12]] + [("unit", "<u4", (16,)), ("seed_unit", "<u4", (16,))])
+assert POLISH_DTYPE.itemsize == C.sizeof(Polished) == 176
+
+
 class Resolved(C.Structure):
     _fields_ = list(Refined._fields_) + [(name, C.c_uint32) for name in ("candidates", "rank", "first_period", "first_score")]
 
@@ -338,6 +350,9 @@ def load():
     lib.trew_hip_refine.argtypes = lib.trew_hip_periods.argtypes
     lib.trew_hip_refine_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_refine_host.argtypes = lib.trew_periods_host.argtypes
+    lib.trew_hip_polish.argtypes = lib.trew_hip_periods.argtypes
+    lib.trew_hip_polish_results.argtypes = lib.trew_hip_periods_results.argtypes
+    lib.trew_polish_host.argtypes = lib.trew_periods_host.argtypes
     lib.trew_hip_resolve.argtypes = lib.trew_hip_periods.argtypes + [i32]
     lib.trew_hip_resolve_results.argtypes = lib.trew_hip_periods_results.argtypes
     lib.trew_resolve_host.argtypes = lib.trew_periods_host.argtypes[:-1] + [i32, vp]
@@ -802,6 +817,20 @@ def refine_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_sco
     return out
 
 
+def polish_host(reads_or_packed, min_period=1, max_period=POLISH_MAX_PERIOD, penalty=3, min_score=24):
+    """trew_polish_host: refine_host for periods up to 256 (step 1 is the depth-0 record of `satellites`, the recurrence is
+    that of `monomers`) computed on the host, step by step from the definition.  reads_or_packed as for annotate_host.
+    Returns POLISH_DTYPE records of shape (n_reads,): refine's twelve words, then unit and seed_unit as sixteen words each
+    (satellite_unit_text turns either into text; refine_columns takes the records as they are)."""
+    lib = load()
+    words, offsets, lengths = _packed(reads_or_packed)
+    out = np.zeros(len(offsets), dtype=POLISH_DTYPE)
+    if lib.trew_polish_host(words.ctypes.data, offsets.ctypes.data, lengths.ctypes.data, len(offsets), int(min_period), int(max_period),
+                            int(penalty), int(min_score), out.ctypes.data) != 0:
+        raise TrewHipError("trew_polish_host failed: %s" % lib.trew_hip_last_error(None).decode())
+    return out
+
+
 def resolve_host(reads_or_packed, min_period=1, max_period=32, penalty=3, min_score=24, candidates=3):
     """trew_resolve_host: refine's unit with the period chosen by alignment, computed on the host step by step from the
     definition: the `candidates` (1 .. 4) best-scoring periods of `periods`' score each refined as refine_host refines its one,
@@ -1149,6 +1178,17 @@ class TrewHip:
     def refine_results(self, slot=0, want_ms=False):
         """Records of the slot's last refine: REFINE_DTYPE array of shape (n_reads,) [, kernel ms]."""
         res = self._fetch_records("refine", slot, REFINE_DTYPE, want_ms)
+        return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
+
+    def polish(self, batch, min_period=1, max_period=POLISH_MAX_PERIOD, penalty=3, min_score=24, slot=0):
+        """Queue the refined de novo repeat of every read of `batch` for periods up to 256 on the slot's stream (no motifs)."""
+        self._queue("polish", slot, batch, None, 1)
+        self._chk(self.lib.trew_hip_polish(self.ctx, C.byref(batch), slot, int(min_period), int(max_period), int(penalty), int(min_score)),
+                  "trew_hip_polish")
+
+    def polish_results(self, slot=0, want_ms=False):
+        """Records of the slot's last polish: POLISH_DTYPE array of shape (n_reads,) [, kernel ms]."""
+        res = self._fetch_records("polish", slot, POLISH_DTYPE, want_ms)
         return (res[0][:, 0], res[1]) if want_ms else res[0][:, 0]
 
     def resolve(self, batch, min_period=1, max_period=32, penalty=3, min_score=24, candidates=3, slot=0):
@@ -1634,6 +1674,17 @@ def refine(reads, min_period=1, max_period=32, penalty=3, min_score=24, device=0
     with t:
         t.refine(b, min_period, max_period, penalty, min_score)
         return t.refine_results()
+
+
+def polish(reads, min_period=1, max_period=POLISH_MAX_PERIOD, penalty=3, min_score=24, device=0):
+    """`refine` for periods up to 256 on the GPU: for every read (bytes / str) the period and tract of `satellites`' depth-0
+    record, a seed unit taken from the read, the wraparound alignment of `monomers` against it and the unit re-voted from that
+    alignment, as POLISH_DTYPE records of shape (n_reads,); refine_columns gives the copies, mismatches, insertions and
+    deletions, capi.satellite_unit_text the two units.  No motif is given."""
+    t, b = _one_batch(reads, device)
+    with t:
+        t.polish(b, min_period, max_period, penalty, min_score)
+        return t.polish_results()
 
 
 def resolve(reads, min_period=1, max_period=32, penalty=3, min_score=24, candidates=3, device=0):

@@ -1,6 +1,6 @@
 // motif_cli.cpp -- what the command lines share: the argument helpers of every subcommand, and the front end of the six
 // per-read motif subcommands `trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ...` and of the motif-less
-// `trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...` (motif_cli_main), and of
+// `trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve|polish FASTQ...` (motif_cli_main), and of
 // `trew monomers [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ...`, whose units have up to 256 bases and may come from a FASTA file.  A
 // subcommand's own file (annotate.cpp, ...) holds its usage text, its options and their defaults, its rows and its summary.
 // The conventions are those of `short` and `long`: CSV on stdout, messages on stderr, exit status 1 and an empty stdout on an

@@ -1178,11 +1178,11 @@ FinalFastqOutput process_kmer_long(Scanner *s, const Config &cfg, const char *fi
     return run_file(s, cfg, file_name, nullptr, is_gz, false);
 }
 
-// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers
+// ---------------------------------------------------------------- trew annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers, copies, polish
 // A per-read measure of one FASTQ file (plain or .gz) through the serial reader shape: read_fastq_thread hands out
 // 4 MiB chunks, every worker finds the sequence lines of its chunk, packs them, queues the measure that AnnotRequest::kind
 // names on a slot of its own, fetches the records and folds them into its part of the file's result (fold_annotate,
-// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve, fold_monomers, fold_copies).  The ordinal of a read is the index of its sequence line among the file's
+// fold_tracts, fold_intervals, fold_variants, fold_periods, fold_chain, fold_repeats, fold_satellites, fold_align, fold_refine, fold_tandems, fold_trace, fold_decompose, fold_dissect, fold_resolve, fold_monomers, fold_copies, fold_polish).  The ordinal of a read is the index of its sequence line among the file's
 // sequence lines: Chunk::num_before (newlines in front of the chunk) gives the ordinal of the chunk's first read, so the rows
 // come out the same for any number of workers once they are sorted.
 struct Annotator {
@@ -1655,6 +1655,25 @@ static void fold_refine(const AnnotBatch &x, AnnotFileResult &p) {
     }
 }
 
+// trew polish: fold_refine with the wide record; the key's unit is a string of codes, as in fold_satellites.
+static void fold_polish(const AnnotBatch &x, AnnotFileResult &p) {
+    Annotator::Worker *w = x.w;
+    const AnnotRequest &rq = *x.rq;
+    if (trew_hip_polish(x.c, &x.b, w->slot, rq.min_period, rq.max_period, rq.penalty, rq.min_score)) hip_die(x.c, "trew_hip_polish");
+    trew_hip_polished *recs = records<trew_hip_polished>(w, x.n);
+    uint64_t got = 0;
+    if (trew_hip_polish_results(x.c, w->slot, recs, x.n, &got, nullptr)) hip_die(x.c, "trew_hip_polish_results");
+    for (uint64_t r = 0; r < x.n; r++) {
+        const trew_hip_polished &rec = recs[r];
+        if (rec.period == 0 || rec.score < rq.min_score) continue;
+        RefineUnit &u = p.polish_units[{rec.period, satellite_canonical(unit_codes(rec.unit, rec.period))}];
+        u.reads++;
+        u.bases += rec.end - rec.start;
+        u.copies += rec.consumed / rec.period;
+        p.prows.push_back(PolishRow{x.first_read + r, x.lengths[r], rec});
+    }
+}
+
 // trew resolve: fold_refine with the resolved record; resolve_units also counts the rows with rank > 0.
 static void fold_resolve(const AnnotBatch &x, AnnotFileResult &p) {
     Annotator::Worker *w = x.w;
@@ -1887,6 +1906,7 @@ static void annotate_worker_loop(Annotator *a, Annotator::Worker *w, ChunkQueue 
             case Measure::Resolve: fold_resolve(x, p); break;
             case Measure::Monomers: fold_monomers(x, p); break;
             case Measure::Copies: fold_copies(x, p); break;
+            case Measure::Polish: fold_polish(x, p); break;
             }
         }
         free(ch->buffer1);
@@ -1947,6 +1967,11 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
         u.bases += v.bases;
         u.copies += v.copies;
     });
+    merge_units(into.polish_units, from.polish_units, [](RefineUnit &u, const RefineUnit &v) {
+        u.reads += v.reads;
+        u.bases += v.bases;
+        u.copies += v.copies;
+    });
     merge_units(into.resolve_units, from.resolve_units, [](ResolveUnit &u, const ResolveUnit &v) {
         u.reads += v.reads;
         u.bases += v.bases;
@@ -1978,7 +2003,7 @@ void add_totals(AnnotFileResult &into, const AnnotFileResult &from) {
     });
 }
 
-static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers", "copies"};  // in the order of Measure
+static const char *const kMeasureNames[] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers", "copies", "polish"};  // in the order of Measure
 
 // The chunk length of the measure path: LENGTH, or TREW_MEASURE_CHUNK_BYTES where it names a value in [64, LENGTH] (a test and
 // experiment knob, like TREW_SCAN_BLOCK_KIB: it moves the chunk borders, and with them the batches, to chosen places; buffers and
@@ -2039,6 +2064,7 @@ AnnotFileResult process_annotate(Annotator *a, const Config &cfg, const char *fi
     merge_rows(a, &AnnotFileResult::srows, out, by_read_start(&SatelliteRow::st));
     merge_rows(a, &AnnotFileResult::trows, out, by_read_start(&TandemRow::td));
     merge_rows(a, &AnnotFileResult::frows, out, [](const RefineRow &x, const RefineRow &y) { return x.read < y.read; });
+    merge_rows(a, &AnnotFileResult::prows, out, [](const PolishRow &x, const PolishRow &y) { return x.read < y.read; });
     merge_rows(a, &AnnotFileResult::vrows, out, [](const ResolveRow &x, const ResolveRow &y) { return x.read < y.read; });
     merge_rows(a, &AnnotFileResult::arows, out, [](const AlignRow &x, const AlignRow &y) {
         if (x.read != y.read) return x.read < y.read;

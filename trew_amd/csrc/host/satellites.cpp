@@ -16,11 +16,13 @@
 
 namespace trew_host {
 
-std::string satellite_codes(const trew_hip_satellite &rec) {
-    std::string c((size_t) rec.period, '\0');
-    for (uint32_t j = 0; j < rec.period; j++) c[j] = (char) ((rec.unit[j >> 4] >> (2 * (j & 15u))) & 3u);
+std::string unit_codes(const uint32_t (&unit)[16], uint32_t period) {
+    std::string c((size_t) period, '\0');
+    for (uint32_t j = 0; j < period; j++) c[j] = (char) ((unit[j >> 4] >> (2 * (j & 15u))) & 3u);
     return c;
 }
+
+std::string satellite_codes(const trew_hip_satellite &rec) { return unit_codes(rec.unit, rec.period); }
 
 // the smallest rotation of a string of codes
 static std::string smallest_rotation(const std::string &c) {

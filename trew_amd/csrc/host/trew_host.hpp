@@ -99,10 +99,10 @@ bool is_regular_file(const std::string &p);
 bool has_gz_ext(const std::string &p);
 std::string canonical(const std::string &p);
 
-// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ..., trew monomers|copies [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve FASTQ...: the per-read measures.
-// One file path for all sixteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
-// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp, dissect.cpp, resolve.cpp, monomers.cpp and copies.cpp hold what is a measure's own. ----
-enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect, Resolve, Monomers, Copies };
+// ---- trew annotate|tracts|intervals|variants|chain|align|trace MOTIF[,MOTIF...] FASTQ..., trew monomers|copies [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ... and trew periods|repeats|satellites|refine|tandems|decompose|dissect|resolve|polish FASTQ...: the per-read measures.
+// One file path for all eighteen (process.cpp), one command-line front end (host/motif_cli.cpp); host/annotate.cpp, tracts.cpp,
+// intervals.cpp, variants.cpp, periods.cpp, chain.cpp, repeats.cpp, satellites.cpp, align.cpp, refine.cpp, tandems.cpp, trace.cpp, decompose.cpp, dissect.cpp, resolve.cpp, monomers.cpp, copies.cpp and polish.cpp hold what is a measure's own. ----
+enum class Measure { Annotate, Tracts, Intervals, Variants, Periods, Chain, Repeats, Satellites, Align, Refine, Tandems, Trace, Decompose, Dissect, Resolve, Monomers, Copies, Polish };
 struct AnnotRequest {
     Measure kind = Measure::Annotate;  // picks the device call and the record type
     trew_hip_motif motifs[TREW_ANNOT_MAX_MOTIFS];
@@ -177,6 +177,11 @@ struct RefineRow {
 struct RefineUnit {
     uint64_t reads = 0, bases = 0, copies = 0;  // rows with such a unit, the sums of their end - start and of their copies
 };
+struct PolishRow {
+    uint64_t read;    // ordinal of the read in its file, 0-based
+    uint32_t length;  // bases
+    trew_hip_polished pl;
+};
 struct ResolveRow {
     uint64_t read;    // ordinal of the read in its file, 0-based
     uint32_t length;  // bases
@@ -221,6 +226,7 @@ struct AnnotFileResult {
     uint64_t trace_sums[TREW_ANNOT_MAX_MOTIFS][2][kTraceSums] = {};  // trace: [motif][strand], over the rows
     std::vector<RefineRow> frows;    // refine, decompose (rf.reserved: the anchor): sorted by read
     std::vector<ResolveRow> vrows;   // resolve: sorted by read
+    std::vector<PolishRow> prows;    // polish: sorted by read
     std::vector<TandemRow> trows;    // tandems, dissect (td.reserved: the anchor): sorted by read, start
     uint64_t reads = 0, bases = 0;
     uint64_t windows_fwd[TREW_ANNOT_MAX_MOTIFS] = {}, windows_rev[TREW_ANNOT_MAX_MOTIFS] = {}, reported[TREW_ANNOT_MAX_MOTIFS] = {};
@@ -235,6 +241,8 @@ struct AnnotFileResult {
     std::map<std::pair<uint32_t, uint64_t>, std::pair<uint64_t, uint64_t>> period_units;
     // refine: (period, strand-canonical unit) -> its rows, bases and copies
     std::map<std::pair<uint32_t, uint64_t>, RefineUnit> refine_units;
+    // polish: the same, the canonical unit as its codes (as satellite_units)
+    std::map<std::pair<uint32_t, std::string>, RefineUnit> polish_units;
     // resolve: the same, and the rows whose period the alignment chose against step 1
     std::map<std::pair<uint32_t, uint64_t>, ResolveUnit> resolve_units;
     // decompose: (period, strand-canonical unit) -> its rows, bases and copies, and the units, edited items and items of their signatures
@@ -278,7 +286,7 @@ struct MotifCli {
     std::function<const char *()> fasta;          // long_units: the FILE of --fasta, nullptr when the option was not given; with it every positional argument is a file
 };
 int motif_cli_main(int argc, char **argv, Measure kind, const MotifCli &cli);
-// The command line the measures without motifs share (periods, repeats, refine, tandems: bound 32; satellites: 256):
+// The command line the measures without motifs share (periods, repeats, refine, tandems: bound 32; satellites, polish: 256):
 // --min_period, --max_period (default: bound), --penalty and --min_score with their check, and the request filled from them.
 // `o` must outlive `cli`.
 struct PeriodOptions {
@@ -298,6 +306,7 @@ int repeats_main(int argc, char **argv);
 int satellites_main(int argc, char **argv);
 int align_main(int argc, char **argv);
 int refine_main(int argc, char **argv);
+int polish_main(int argc, char **argv);
 int tandems_main(int argc, char **argv);
 int trace_main(int argc, char **argv);
 int decompose_main(int argc, char **argv);
@@ -311,6 +320,7 @@ uint64_t canonical_unit(uint64_t unit, int k);  // the smaller of the smallest r
 // the same for a unit of up to 256 bases: the codes of unit[16] / period (one char a base, first base first) and the smaller,
 // base by base in code order, of the smallest rotation of the codes and the smallest rotation of their reverse complement
 std::string satellite_codes(const trew_hip_satellite &rec);
+std::string unit_codes(const uint32_t (&unit)[16], uint32_t period);  // the codes of a unit packed as trew_hip_satellite.unit
 std::string satellite_canonical(const std::string &codes);
 
 struct RunStats {

@@ -1,8 +1,8 @@
 // trew_main.cpp -- the `trew short|long MIN_MER MAX_MER` command line of the MI355X-native build
 // (and `trew annotate` / `trew tracts` / `trew intervals` / `trew variants` / `trew chain` / `trew align` / `trew trace MOTIF[,MOTIF...] FASTQ...` and
 // `trew monomers [--fasta FILE] [MONOMER[,MONOMER...]] FASTQ...` and
-// `trew periods` / `trew repeats` / `trew satellites` / `trew refine` / `trew tandems` / `trew decompose` / `trew dissect` / `trew resolve FASTQ...`, which have no counterpart in the reference: host/annotate.cpp, host/tracts.cpp,
-// host/intervals.cpp, host/variants.cpp, host/periods.cpp, host/chain.cpp, host/repeats.cpp, host/satellites.cpp, host/align.cpp, host/refine.cpp, host/tandems.cpp, host/trace.cpp, host/decompose.cpp, host/dissect.cpp, host/resolve.cpp, host/monomers.cpp, host/copies.cpp).
+// `trew periods` / `trew repeats` / `trew satellites` / `trew refine` / `trew tandems` / `trew decompose` / `trew dissect` / `trew resolve` / `trew polish FASTQ...`, which have no counterpart in the reference: host/annotate.cpp, host/tracts.cpp,
+// host/intervals.cpp, host/variants.cpp, host/periods.cpp, host/chain.cpp, host/repeats.cpp, host/satellites.cpp, host/align.cpp, host/refine.cpp, host/tandems.cpp, host/trace.cpp, host/decompose.cpp, host/dissect.cpp, host/resolve.cpp, host/monomers.cpp, host/copies.cpp, host/polish.cpp).
 //
 // Same sub-commands, positional arguments, options, limits and messages as the reference CLI
 // (trew.cpp:22-478): stdout carries the CSV sections, stderr errors/usage, exit code 1 on error.
@@ -33,7 +33,7 @@ static void usage(const char *mode) {
                 "             [--batch_mib N] [--host_pack] [--compat_g1] MIN_MER MAX_MER [SHORT_FASTQ]...\n\n"
                 "Estimate TRM from short-read sequencing data.\n");
     } else {
-        fprintf(stderr, "Usage: trew [--help] [--version] {long,short,annotate,tracts,intervals,variants,periods,chain,repeats,satellites,align,refine,tandems,trace,decompose,dissect,resolve,monomers,copies}\n\nSubcommands:\n  long          Estimate TRM from long-read sequencing data.\n"
+        fprintf(stderr, "Usage: trew [--help] [--version] {long,short,annotate,tracts,intervals,variants,periods,chain,repeats,satellites,align,refine,tandems,trace,decompose,dissect,resolve,monomers,copies,polish}\n\nSubcommands:\n  long          Estimate TRM from long-read sequencing data.\n"
                         "  short         Estimate TRM from short-read sequencing data.\n"
                         "  annotate      Report the reads that carry given repeat motifs and their longest tracts.\n"
                         "  tracts        Report the error-tolerant tracts of given repeat motifs at both ends of every read.\n"
@@ -51,7 +51,8 @@ static void usage(const char *mode) {
                         "  dissect       The same for every repeat tract of every read: `tandems`' tracts, each cut into copies of its own unit.\n"
                         "  resolve       `refine` with the period chosen by alignment: the few best-scoring periods each refined, the best record kept.\n"
                         "  monomers      `align` for given units of up to 256 bases: arrays of diverged satellite monomers in noisy reads.\n"
-                        "  copies        `trace` for given units of up to 256 bases: where each copy of a satellite monomer lies and which errors it carries.\n");
+                        "  copies        `trace` for given units of up to 256 bases: where each copy of a satellite monomer lies and which errors it carries.\n"
+                        "  polish        `refine` for periods up to 256: minisatellite and satellite arrays under indels without a monomer given.\n");
     }
 }
 
@@ -88,6 +89,7 @@ int main(int argc, char **argv) {
     if (mode == "align") return align_main(argc, argv);
     if (mode == "trace") return trace_main(argc, argv);
     if (mode == "refine") return refine_main(argc, argv);
+    if (mode == "polish") return polish_main(argc, argv);
     if (mode == "tandems") return tandems_main(argc, argv);
     if (mode == "decompose") return decompose_main(argc, argv);
     if (mode == "dissect") return dissect_main(argc, argv);

@@ -61,9 +61,14 @@ __device__ __forceinline__ AlignCell mono_slot(const AlignCell (&X)[Q], u32 slot
 // kDirs: the directions are kept and the byte of slot q is returned in bits [8 q, 8 q + 8) (0 without): op | del << 2 |
 // hit << 7, op by the order of the selects as in wrap_row, del: H is strictly larger than V was in front of step (a) -- the
 // smallest d of the cell is not 0 (the proof that one bit carries d stands at the head of copies.inc).
-template <int Q, bool kDirs>
+// mid(q, V[q], the diagonal was taken with a positive score and the inserted base did not beat it) runs per slot between the
+// inserted-base select and step (a), where wrap_row has its own (polish.inc's vote); the default does nothing.
+struct MonoNoMid {
+    __device__ __forceinline__ void operator()(int, const AlignCell &, bool) const {}
+};
+template <int Q, bool kDirs, class Mid = MonoNoMid>
 __device__ __forceinline__ u32 mono_row(AlignCell (&H)[Q], u32 c, const u32 (&tb)[Q], u32 i, int P, u32 lane, u32 diag_src, u32 last_lane,
-                                         u32 last_slot) {
+                                         u32 last_slot, Mid mid = Mid{}) {
     const AlignCell mine = align_pick(lane == last_lane, mono_slot<Q>(H, last_slot), H[Q - 1]);
     const AlignCell prev = align_from(mine, diag_src);
     AlignCell V[Q], V0[kDirs ? Q : 1];
@@ -78,6 +83,7 @@ __device__ __forceinline__ u32 mono_row(AlignCell (&H)[Q], u32 c, const u32 (&tb
         const AlignCell ins{(u32) is, H[q].start, H[q].consumed, H[q].matches};
         const bool by_ins = (is > 0) & align_gt(ins, V[q]);
         V[q] = align_pick(by_ins, ins, V[q]);
+        mid(q, V[q], (ds > 0) & !by_ins);
         if constexpr (kDirs) {
             V0[q] = V[q];
             dirs |= ((by_ins ? 2u : ds > 0 ? 1u : 0u) | (hit ? kMonoHit : 0u)) << (8 * q);

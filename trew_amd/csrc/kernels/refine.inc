@@ -46,7 +46,9 @@ __device__ __forceinline__ void refine_pack(u32 u, u32 d, u32 &lo, u32 &hi) {
     hi = wave_sum_u32((u32) (term >> 32));
 }
 
-// the start of the longest run of set bits of the piece's eq_k among the positions [b, e), the first of the longest; b without one
+// the start of the longest run of set bits of the piece's eq_k among the positions [b, e), the first of the longest; b without one.
+// kWide (kernels/polish.inc): k may exceed 32, handed on to period_eq_word; the instantiation without it is the code as it was.
+template <bool kWide = false>
 __device__ __forceinline__ u32 refine_longest_run(const ReadRef &rd, Piece pc, u32 k, u32 b, u32 e) {
     const u32 lane = lane_id();
     u32 best_len = 0, best_start = b, carry = 0;  // carry: the run that ends at the end of the iteration in front
@@ -54,7 +56,7 @@ __device__ __forceinline__ u32 refine_longest_run(const ReadRef &rd, Piece pc, u
         const u32 w = t0 + lane;
         const u64 p0 = (u64) w << 5;
         u32 vm;
-        u32 eq = period_eq_word(rd, pc, k, w, vm);
+        u32 eq = period_eq_word<kWide>(rd, pc, k, w, vm);
         const u32 first = p0 >= (u64) b ? 0u : (u64) b - p0 >= 32u ? 32u : b - (u32) p0;   // bits in front of b
         const u32 last = p0 >= (u64) e ? 0u : (u64) e - p0 >= 32u ? 32u : e - (u32) p0;    // one past the last bit in front of e
         eq &= (last >= 32u ? 0xffffffffu : (1u << last) - 1u) & (first >= 32u ? 0u : 0xffffffffu << first);

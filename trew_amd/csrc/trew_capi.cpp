@@ -25,11 +25,11 @@ using namespace trew;
 
 namespace {
 
-// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve, _monomers, _copies) and what a slot keeps of each.
-enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMonomers, kCopies, kMeasures };
-const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers", "copies"};
+// The per-read measures (trew_hip_annotate, _tracts, _intervals, _variants, _periods, _chain, _repeats, _satellites, _align, _refine, _tandems, _trace, _decompose, _dissect, _resolve, _monomers, _copies, _polish) and what a slot keeps of each.
+enum Measure { kAnnotate, kTracts, kIntervals, kVariants, kPeriods, kChain, kRepeats, kSatellites, kAlign, kRefine, kTandems, kTrace, kDecompose, kDissect, kResolve, kMonomers, kCopies, kPolish, kMeasures };
+const char *const kMeasureName[kMeasures] = {"annotate", "tracts", "intervals", "variants", "periods", "chain", "repeats", "satellites", "align", "refine", "tandems", "trace", "decompose", "dissect", "resolve", "monomers", "copies", "polish"};
 // whether the measure takes motifs: one that takes none has no motif check and no pattern table (measure_begin)
-const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false, false, false};  // monomers, copies: their own table (stage_monomers), no pattern table
+const bool kMeasureHasMotifs[kMeasures] = {true, true, true, true, false, true, false, false, true, false, false, true, false, false, false, false, false, false};  // monomers, copies: their own table (stage_monomers), no pattern table
 struct DevBuf {
     void *p = nullptr;
     u64 bytes = 0;  // capacity
@@ -1290,8 +1290,8 @@ extern "C" int trew_hip_last_timing(trew_hip_ctx *ctx, int slot, float *ms_filte
     return 0;
 }
 
-// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers, copies
-// The seventeen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
+// ---------------------------------------------------------------- per-read measures: annotate, tracts, intervals, variants, periods, chain, repeats, satellites, align, refine, tandems, trace, decompose, dissect, resolve, monomers, copies, polish
+// The eighteen measures share everything on the host side but their kernel and the shape of their results: a queue call stages the
 // batch and the motifs and launches one kernel between two events (MeasureState, Slot), a results call waits and copies.
 // That shared part exists once: queue_records and results_records for the measures with fixed-size records, queue_log,
 // fetch_counted and fetch_log for those with an append log.  An entry point holds what is its measure's own: its argument
@@ -1376,6 +1376,11 @@ extern "C" int trew_copies_host(const uint32_t *words, const uint32_t *offsets, 
 extern "C" int trew_refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
                                 int max_period, int penalty, uint32_t min_score, trew_hip_refined *out) {
     return host_status(refine_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out));
+}
+
+extern "C" int trew_polish_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
+                                int max_period, int penalty, uint32_t min_score, trew_hip_polished *out) {
+    return host_status(polish_host(words, offsets, lengths, n_reads, min_period, max_period, penalty, min_score, out));
 }
 
 extern "C" int trew_tandems_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period,
@@ -2034,6 +2039,20 @@ extern "C" int trew_hip_refine(trew_hip_ctx *ctx, const trew_hip_batch *batch, i
 
 extern "C" int trew_hip_refine_results(trew_hip_ctx *ctx, int slot, trew_hip_refined *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
     return results_records(ctx, slot, kRefine, out, cap, sizeof(trew_hip_refined), n, ms_kernel);
+}
+
+// ---------------------------------------------------------------- de novo repeats under indels for periods up to 256
+extern "C" int trew_hip_polish(trew_hip_ctx *ctx, const trew_hip_batch *batch, int slot, int min_period, int max_period, int penalty, uint32_t min_score) {
+    auto own = [&]() -> const char * { return satellites_error(min_period, max_period, penalty, min_score); };
+    return queue_records(ctx, batch, slot, nullptr, 0, kPolish, 1, sizeof(trew_hip_polished), own, no_setup,
+                         [&](Slot &s, MeasureState &st, const DevBatch &db) -> int {
+                             HIPCHK(ctx, launch_polish(s.stream, measure_cu(ctx), db, min_period, max_period, penalty, min_score, (trew_hip_polished *) st.records.p));
+                             return 0;
+                         });
+}
+
+extern "C" int trew_hip_polish_results(trew_hip_ctx *ctx, int slot, trew_hip_polished *out, uint64_t cap, uint64_t *n, float *ms_kernel) {
+    return results_records(ctx, slot, kPolish, out, cap, sizeof(trew_hip_polished), n, ms_kernel);
 }
 
 // ---------------------------------------------------------------- refine's unit with the period chosen by alignment

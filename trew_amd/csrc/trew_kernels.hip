@@ -56,6 +56,7 @@
 //   resolve.inc        resolve_wave_kernel (refine's unit with the period chosen by alignment: periods.inc's score for every k, the four best kept, resolve_piece.inc's resolve_piece over the whole read, and the record's own four words)
 //   monomers.inc       monomers_wave_kernel<Q> (wraparound alignment for units of up to 256 bases: wraparound.inc's cell, the row over all 64 lanes with Q phases a lane, the maximum over deleted bases as a linear prefix closure plus one wrap)
 //   copies.inc         copies_wave_kernel<Q> (copies in place for units of up to 256 bases: monomers.inc's row step with a direction byte a cell, op, hit and one bit for the deleted bases, the strand's rows into a workspace, wraparound.inc's walk through LDS blocks into an item log)
+//   polish.inc         polish_wave_kernel<Q> (de novo repeats under indels for periods up to 256: satellites.inc's step 1, refine.inc's longest run with the wide eq word, monomers.inc's row step in one pass function that a loop of three wave-uniform passes drives, the vote in the row step's `mid`, re-vote, root and pack through the bins)
 // The launchers (host code) follow the includes.
 #include <hip/hip_runtime.h>
 
@@ -107,6 +108,7 @@ typedef unsigned __int128 u128;  // 2k-bit words for k in (32, 64] (k_mer_check_
 #include "kernels/resolve.inc"
 #include "kernels/monomers.inc"
 #include "kernels/copies.inc"
+#include "kernels/polish.inc"
 
 // ------------------------------------------------------------------ launchers
 int pick_nw(u32 max_seg_len) {
@@ -512,6 +514,12 @@ hipError_t launch_monomers(hipStream_t st, u32 n_cu, const DevBatch &B, const tr
     if (max_k <= 64u) return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<1>, d_monomers, n_monomers, penalty, (u32 *) d_out);
     if (max_k <= 128u) return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<2>, d_monomers, n_monomers, penalty, (u32 *) d_out);
     return launch_wave_per_read(st, n_cu, B, monomers_wave_kernel<4>, d_monomers, n_monomers, penalty, (u32 *) d_out);
+}
+
+hipError_t launch_polish(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_polished *d_out) {
+    if (max_period <= 64) return launch_wave_per_read(st, n_cu, B, polish_wave_kernel<1>, min_period, max_period, penalty, min_score, (u32 *) d_out);
+    if (max_period <= 128) return launch_wave_per_read(st, n_cu, B, polish_wave_kernel<2>, min_period, max_period, penalty, min_score, (u32 *) d_out);
+    return launch_wave_per_read(st, n_cu, B, polish_wave_kernel<4>, min_period, max_period, penalty, min_score, (u32 *) d_out);
 }
 
 hipError_t launch_copies(hipStream_t st, u32 n_cu, const DevBatch &B, const trew_hip_monomer *d_monomers, int n_monomers, u32 max_k, int penalty,

@@ -74,6 +74,9 @@ hipError_t launch_monomers(hipStream_t st, u32 n_cu, const DevBatch &B, const tr
 // d_out: the alignment records, d_counts: the items of every (read, monomer, strand)
 hipError_t launch_copies(hipStream_t st, u32 n_cu, const DevBatch &B, const trew_hip_monomer *d_monomers, int n_monomers, u32 max_k, int penalty,
                          u32 min_score, const TraceLog &lg, trew_hip_alignment *d_out, u32 *d_counts);
+// trew_hip_polish: the wave-per-read kernel of kernels/polish.inc on the grid of launch_tracts; no motifs; max_period picks Q as
+// launch_monomers' max_k does
+hipError_t launch_polish(hipStream_t st, u32 n_cu, const DevBatch &B, int min_period, int max_period, int penalty, u32 min_score, trew_hip_polished *d_out);
 // trew_hip_trace: the wave-per-read kernel of kernels/trace.inc on the grid of launch_tracts; both counters of `lg` are zero
 // when the kernel starts; d_out: the alignment records, d_counts: the items of every (read, motif, strand)
 hipError_t launch_trace(hipStream_t st, u32 n_cu, const DevBatch &B, const AnnotMotifDev *d_motifs, int n_motifs, int penalty, u32 min_score,

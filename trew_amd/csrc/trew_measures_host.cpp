@@ -810,10 +810,12 @@ static void take_scoring(AlignCell &into, const AlignCell &cand) {
 // With end_phase also the end cell's phase, the smallest on equal tuples (rule 3 of 4.7h).  With dirs the table is the one
 // that starts from (0, row0, 0, 0) in row row0 and ends with row n, and dirs gets a byte a cell of the rows row0 .. n (row
 // row0: zeros): op of V in bits 0 .. 1 under rule 1, and in bit 2 whether H is strictly larger than V was before the closure
-// -- whether the smallest d of rule 2 is not 0 (4.7n).
+// -- whether the smallest d of rule 2 is not 0 (4.7n).  With cnt (trew_hip_polished's vote) also wrap_table_host's forward
+// decode: the phase j* with the largest V in front of the closure, the smallest on a tie, and cnt[j*][base] += 1 when the
+// base is valid and the diagonal candidate is that cell.
 static void monomer_table_host(const unsigned char *base, u32 n, const u32 *t, int k, int penalty, u32 (&o)[5], int *end_phase = nullptr,
-                               std::vector<unsigned char> *dirs = nullptr, u32 row0 = 0) {
-    std::vector<AlignCell> H((size_t) k, AlignCell{0, row0, 0, 0}), V((size_t) k), V0((size_t) k);
+                               std::vector<unsigned char> *dirs = nullptr, u32 row0 = 0, u32 (*cnt)[4] = nullptr) {
+    std::vector<AlignCell> H((size_t) k, AlignCell{0, row0, 0, 0}), V((size_t) k), V0((size_t) k), Dg(cnt ? (size_t) k : 0);
     AlignCell best{0, 0, 0, 0};
     u32 best_end = 0;
     int best_j = 0;
@@ -831,6 +833,13 @@ static void monomer_table_host(const unsigned char *base, u32 n, const u32 *t, i
             if (V[(size_t) j] < D) V[(size_t) j] = D, op = 1;
             if (V[(size_t) j] < ins) V[(size_t) j] = ins, op = 2;
             if (row) row[j] = op, V0[(size_t) j] = V[(size_t) j];
+            if (cnt) Dg[(size_t) j] = D;
+        }
+        if (cnt) {
+            size_t js = 0;
+            for (size_t j = 1; j < (size_t) k; j++)
+                if (V[js] < V[j]) js = j;  // strictly: the smallest j keeps a tie
+            if (c < 4 && !(Dg[js] < V[js])) cnt[js][c]++;  // V >= D always: equal
         }
         for (int j = 1; j < k; j++) take_scoring(V[(size_t) j], shifted(V[(size_t) j - 1], penalty, 1));
         const AlignCell W = V[(size_t) k - 1];
@@ -980,6 +989,85 @@ const char *refine_host(const u32 *words, const u32 *offsets, const u32 *lengths
         unpack_bases(words + offsets[r], lengths[r], base);
         trew_hip_period R;
         refine_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, out[r], R);
+    }
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- de novo repeats under indels for periods up to 256
+static_assert(TREW_POLISH_MAX_PERIOD == TREW_SATELLITE_MAX_PERIOD, "step 1 is satellites' depth-0 record");
+static void pack_unit_words(const u32 *u, u32 k, u32 (&w)[16]) {
+    for (u32 j = 0; j < k; j++) w[j >> 4] |= u[j] << (2 * (j & 15u));
+}
+
+// the record of one read, step by step from the definition (trew_hip_polished, include/trew_hip.h): refine_read_host and
+// refine_at_period with arrays of 256 and monomer_table_host in the place of wrap_table_host
+static void polish_read_host(const unsigned char *base, u32 n, int min_period, int max_period, int penalty, u32 min_score, trew_hip_polished &o) {
+    memset(&o, 0, sizeof(o));
+    // 1. periods: satellites' depth-0 record and the unreduced consensus
+    trew_hip_satellite R;
+    memset(&R, 0, sizeof(R));
+    u32 cons[TREW_POLISH_MAX_PERIOD];
+    if (!piece_record<TREW_SATELLITE_MAX_PERIOD>(base, 0, n, min_period, max_period, penalty, min_score, R, cons)) return;
+    const u32 k = R.scored_period, b = R.start, e = R.end - k;
+    // 2. seed: the longest run of eq_k in [b, e), the first of the longest
+    u32 rs = b, longest = 0, run = 0;
+    for (u32 i = b; i < e; i++) {
+        run = base[i] < 4 && base[i] == base[i + k] ? run + 1 : 0;
+        if (run > longest) {
+            longest = run;
+            rs = i + 1 - run;
+        }
+    }
+    u32 S[TREW_POLISH_MAX_PERIOD], U[TREW_POLISH_MAX_PERIOD];
+    for (u32 j = 0; j < k; j++) S[j] = base[rs + j] < 4 ? base[rs + j] : cons[(rs + j - b) % k];
+    const u32 ks = primitive_root(S, k);
+    // 3. align against the seed
+    u32 a1[5], a2[5];
+    monomer_table_host(base, n, S, (int) ks, penalty, a1);
+    // 4. vote over the tract alone
+    u32 cnt[TREW_POLISH_MAX_PERIOD][4] = {};
+    monomer_table_host(base + a1[1], a1[2] - a1[1], S, (int) ks, penalty, a2, nullptr, nullptr, 0, cnt);
+    // 5. re-vote
+    u32 changed = 0, support = 0;
+    for (u32 j = 0; j < ks; j++) {
+        u32 top = 0;
+        for (u32 c = 1; c < 4; c++)
+            if (cnt[j][c] > cnt[j][top]) top = c;  // strictly: the smallest code among the largest
+        U[j] = cnt[j][S[j]] == cnt[j][top] ? S[j] : top;
+        support += cnt[j][U[j]];
+        changed += U[j] != S[j];
+    }
+    u32 ku = primitive_root(U, ks);
+    // 6. final
+    for (int i = 0; i < 5; i++) a2[i] = a1[i];
+    if (changed) {
+        monomer_table_host(base, n, U, (int) ku, penalty, a2);
+        if (a2[0] < a1[0]) {  // the seed is kept
+            for (int i = 0; i < 5; i++) a2[i] = a1[i];
+            for (u32 j = 0; j < ks; j++) U[j] = S[j];
+            ku = ks;
+            changed = 0;
+        }
+    }
+    o.period = ku;
+    o.seed_period = ks;
+    o.scored_period = k;
+    o.changed = changed;
+    o.score = a2[0], o.start = a2[1], o.end = a2[2], o.consumed = a2[3], o.matches = a2[4];
+    o.seed_score = a1[0];
+    o.support = support;
+    pack_unit_words(U, ku, o.unit);
+    pack_unit_words(S, ks, o.seed_unit);
+}
+
+const char *polish_host(const u32 *words, const u32 *offsets, const u32 *lengths, u64 n_reads, int min_period, int max_period, int penalty,
+                        u32 min_score, trew_hip_polished *out) {
+    if (const char *e = satellites_error(min_period, max_period, penalty, min_score)) return e;
+    if (n_reads && (!words || !offsets || !lengths || !out)) return "trew_polish_host: null argument";
+    std::vector<unsigned char> base;
+    for (u64 r = 0; r < n_reads; r++) {
+        unpack_bases(words + offsets[r], lengths[r], base);
+        polish_read_host(base.data(), lengths[r], min_period, max_period, penalty, min_score, out[r]);
     }
     return nullptr;
 }

@@ -60,6 +60,9 @@ const char *monomers_host(const uint32_t *words, const uint32_t *offsets, const 
 // de novo repeats under indels: seed, wraparound alignment, re-vote (include/trew_hip.h); the checks of periods_host
 const char *refine_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
                         int penalty, uint32_t min_score, trew_hip_refined *out);
+// the same for periods up to 256: satellites_host's depth-0 record, monomers_host's table; the checks of satellites_host
+const char *polish_host(const uint32_t *words, const uint32_t *offsets, const uint32_t *lengths, uint64_t n_reads, int min_period, int max_period,
+                        int penalty, uint32_t min_score, trew_hip_polished *out);
 // refine's unit with the period chosen by alignment: refine_host's steps 2 to 6 for the best-scoring periods, the best record kept;
 // resolve_error is the argument check the device entry point shares (periods_error, then the candidates)
 const char *resolve_error(int min_period, int max_period, int penalty, uint32_t min_score, int candidates);
